@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mweights/s quantized (GPTQ 3-bit, 4096 x 4096 layers) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--no-configs]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--no-configs] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...; started WITHOUT a launcher
      -- no WORLD_SIZE in the environment -- `bench.py --gpus N` starts that command itself as a child process, before it touches
      the GPU, relays rank 0's line and exits with the child's code)
@@ -50,7 +50,9 @@ Fields besides the contract's:
                  hash differs from the reference's, each a proven near-tie in tests/test_gpu_parity.py);
   rccl          (N > 1) what the collective did: world size, backend, bytes a rank receives per step, the exchange's
                  duration measured by events on the comm stream, and whether every rank's copy of the payloads carried its
-                 root's checksum (sleekit_amd.dist.verify_exchange).
+                 root's checksum (sleekit_amd.dist.verify_exchange);
+  dump_outputs  (--dump-outputs DIR) where the headline leg's last timed step went and how many bytes (dump_outputs():
+                 at most 64 MB; the inputs are made from fixed seeds, so two builds can be compared file for file).
 """
 
 import argparse
@@ -66,13 +68,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import numpy as np
-# HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES in-order hardware queues (4 by default): with 3 factor
-# streams, a comm stream, loop streams and RCCL's own, some share a queue and stop overlapping -- a loop stream behind a
-# factor chain, the next round's factorisation behind this round's loops.  With 8 queues every stream has its own:
-# one rank's step at N = 8 takes 4.5 ms instead of 4.9 ... 7.0 (depending on how the streams fell), and on one rank
-# three factor streams + ONE loop stream reach 4720 Mweights/s against 4450 for the best pairing found on 4 queues.
-# Small layers are the exception: chains of launches of a few microseconds, where 4 queues and more streams measured
-# better (768 x 768: 0.34 ms per layer against 0.43).  Set in main(), before HIP initialises.
+# HIP multiplexes a process's streams onto a few in-order hardware queues: with 3 factor streams, a comm stream, loop
+# streams and RCCL's own, some share a queue and stop overlapping -- a loop stream behind a factor chain, the next round's
+# factorisation behind this round's loops ("Hardware queues").  The queue count is the environment's: the GPU
+# is shared, and bench.py does not raise it.
 
 import torch
 import torch.distributed as dist
@@ -122,9 +121,14 @@ def parse():
     ap.add_argument("--configs", type=str, default="", help="comma-separated subset of the config legs (default: all four)")
     ap.add_argument("--streams", type=str, default="", help="factor,loop stream counts of the headline leg (default 3,1; 3,3 for small-layer models)")
     ap.add_argument("--stages", action="store_true", help="also print per-kernel timing table to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no GPU: the ranks only form a gloo group, all-reduce their ranks and rank 0 prints a line (tests the self-launch)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Env:
@@ -136,8 +140,7 @@ class Env:
         self.local_rank = int(os.environ.get("LOCAL_RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
 
-    def start(self, launch_bound):
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "4" if launch_bound else "8")
+    def start(self):
         assert torch.cuda.is_available(), "bench.py needs the MI355X"
         dev_index = self.local_rank % torch.cuda.device_count()  # (a rehearsal may put several ranks on one GPU)
         torch.cuda.set_device(dev_index)
@@ -581,6 +584,52 @@ class Leg:
         torch.cuda.empty_cache()
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, shapes, shards, layer_errors, rank=0, world=1, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float32 / float64 .npy files.
+
+    Per layer i: layer<i>_row_err (every row), and for a fixed sample of rows -- the same rows every run, drawn from a
+    generator seeded with the layer's position, the same fraction of every layer, so that the whole dump stays under
+    `limit` bytes -- layer<i>_rows (the row numbers), layer<i>_Q and layer<i>_idx (codebook indices as float32, exact).
+    Besides: layer_errors (the mean of each layer) and info (each layer's factorisation status).  On N > 1 ranks every
+    rank contributes the sampled rows of its own shard and rank 0 writes.  Returns the bytes written (0 off rank 0)."""
+    elems = sum(R * n for R, n in shapes)
+    # Q and idx: 8 bytes an element; row errors, row numbers and the per-layer scalars: 8 bytes each at most; a .npy
+    # header per file (128 bytes; 256 kept for each)
+    room = limit - 8 * sum(2 * R + 2 for R, _ in shapes) - 256 * (4 * len(shapes) + 2)
+    frac = min(1.0, room / (8.0 * elems))
+    arrays = {"layer_errors": np.asarray(layer_errors, dtype=np.float64)}
+    info = []
+    for i, ((R, n), sh) in enumerate(zip(shapes, shards)):
+        rows = np.sort(np.random.default_rng([0x5EED, i]).choice(R, max(1, int(frac * R)), replace=False))
+        lo, hi = sh["rows"]
+        mine = rows[(rows >= lo) & (rows < hi)]
+        pick = torch.as_tensor(mine - lo, dtype=torch.long, device=sh["Q"].device)
+        part = {"rows": mine.astype(np.float64), "row_err": sh["row_err"].float().cpu().numpy(), "Q": sh["Q"][pick].float().cpu().numpy()}
+        if sh.get("idx") is not None:
+            part["idx"] = sh["idx"][pick].float().cpu().numpy()
+        parts = [part]
+        if world > 1:  # row shards in rank order: concatenated, they are the layer's rows in order
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+        for key in parts[0]:
+            arrays[f"layer{i:03d}_{key}"] = np.concatenate([p[key] for p in parts])
+        info.append(float(sh["info"].item()) if isinstance(sh.get("info"), torch.Tensor) else float("nan"))
+    arrays["info"] = np.asarray(info, dtype=np.float64)
+    if rank != 0:
+        return 0
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    assert total <= limit, f"--dump-outputs wrote {total} bytes, more than {limit}"
+    return total
+
+
 def distinct_shape_sample(shapes):
     """[(index of the first layer of each distinct shape, how many layers have it)] in order of appearance."""
     first, count = {}, {}
@@ -708,8 +757,7 @@ def main():
         levels, moves, strip = args.levels, args.moves, False
     widest = max(n for _, n in shapes)
     run_configs = not args.config and not args.no_configs
-    # small shapes alone (see the note on hardware queues at the top); with the config legs in the same process: 8 queues
-    env.start(launch_bound=widest <= 1024 and env.world == 1 and not run_configs)
+    env.start()
     rank, world, device = env.rank, env.world, env.device
 
     from sleekit_amd import _device as dev
@@ -737,6 +785,9 @@ def main():
     layer_errors = {"layers": len(errs), "all_finite": True, "min": min(errs), "max": max(errs)}
     if len(errs) <= 16:
         layer_errors["values"] = errs
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, shapes, shards, errs, rank, world)
     golden = head.golden(shards)
 
     roofline, exchange = None, None
@@ -898,13 +949,15 @@ def main():
             "device_mallocs_while_timed": head_mallocs, "allocator_settle_steps": head_settle, "timed_region_repeats": head_repeats,
             "peak_hbm_gb": round(peak_hbm / 2**30, 2),
             "streams": {"factor": head.streams[0], "loop": head.streams[1]},
-            "gpu_max_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+            "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),  # (None: the HIP runtime's default)
         },
         "roofline": roofline, "cpu_baseline": cpu, "layer_error": errs[0], "layer_errors": layer_errors, "latency_ms_single_layer": latency,
         "asymmetric_H": asym, "hessian_accumulate": hess, "local_search": search, "golden": golden,
     }
     if rccl:
         line["rccl"] = rccl
+    if args.dump_outputs:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
 
     # ---- the other BASELINE configs, a short leg each.  The headline above is complete: whatever happens in a leg (an
     #      exception, or on N > 1 ranks a collective that never returns) the line is printed -- a watchdog prints it and

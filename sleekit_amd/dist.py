@@ -119,9 +119,9 @@ class HipBackend:
             return None, None, None
         if not hasattr(self, "_streams"):
             nf, nl = (self.overlap if isinstance(self.overlap, tuple) else (3, 1))  # best on 8 hardware queues
-            # ONE set of side streams per device and process, shared by every backend: with 8 hardware queues
-            # (GPU_MAX_HW_QUEUES, sleekit_amd/__init__.py) the first seven streams a process makes -- and the default stream --
-            # have a queue each, later ones double up with them and stop overlapping.  A second backend with streams of its own
+            # ONE set of side streams per device and process, shared by every backend: the first streams a process makes --
+            # as many as it has hardware queues, the default stream included -- have a queue each, later ones double up
+            # with them and stop overlapping.  A second backend with streams of its own
             # ran like a different program (bench.py: OPT-350M 69.8 ms per step after the headline's backend, 61.2 on its streams).
             dev_index = torch.cuda.current_device()
             pool = _stream_pool.setdefault(dev_index, [])
@@ -783,11 +783,10 @@ def _quantize_stream(layers, backend, comm_device=None, join=True, _local=True):
             own = [l for l in members if l in stream_of]
             if side and own and getattr(backend, "rounds_on_factor_streams", True):
                 # The round runs on the stream that factored this rank's layer of it: one stream fewer to pair badly.
-                # HIP multiplexes all streams of a process onto GPU_MAX_HW_QUEUES (4 by default) in-order hardware queues;
-                # a loop stream that shares its queue with the factor stream of the NEXT round puts that factorisation
-                # behind this round's loops and the pipeline collapses into factor -> loop -> factor (4.4 ... 7.0 ms per
-                # step at N = 8 depending on how the streams fell).  Multi-rank runs should raise GPU_MAX_HW_QUEUES to 8
-                # before HIP starts (bench.py does): every stream, RCCL's included, then has a queue of its own.
+                # HIP multiplexes all streams of a process onto a few in-order hardware queues; a loop stream that shares
+                # its queue with the factor stream of the NEXT round puts that factorisation behind this round's loops and
+                # the pipeline collapses into factor -> loop -> factor (4.4 ... 7.0 ms per step at N = 8 depending on how
+                # the streams fell).
                 ls = stream_of[own[0]]
             batched_rounds += 1
             if side:

@@ -45,7 +45,7 @@ def bench_env():
     import bench
 
     env = bench.Env(argparse.Namespace(gpus=1))
-    env.start(launch_bound=False)
+    env.start()
     return bench, env
 
 

@@ -13,8 +13,6 @@ rate N such ranks would reach if the exchange hid completely behind the loops --
 """
 
 import os
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # as bench.py
 import sys
 
 import torch
