@@ -75,7 +75,9 @@ typedef void *slk_stream_t;
  * 8: no new entry point -- the factorisation's default form is the CHAIN (an outer block's panels in one launch of workgroups that
  * hand the panels on through flags in memory: option "panel_split" 0 / 3; 1 / 2 = round 3's panel kernels), whose status word can
  * read SLK_INFO_HANDOFF_TIMEOUT; the factorisation's workspace holds its flags (slk_factor_workspace_bytes_batch grew by
- * 8 * (ld / 64) bytes per matrix); new options "tall_error", "rows_below_wide".   */
+ * 8 * (ld / 64) bytes per matrix); new options "tall_error", "rows_below_wide".  Still 8, with entries added alongside: the
+ * group-scale forms slk_gptq_quantize_grouped, slk_column_miss_grouped, slk_scale_search_grouped and slk_dequantize_grouped
+ * (one scale per row and per group of columns; nothing existing changed).   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -266,6 +268,31 @@ int slk_gptq_quantize_batch(const float *W, const float *scale, const long long 
                             const float *table, int min_block, int num_blocks, int flags, float *Q,
                             uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream);
 size_t slk_workspace_bytes_batch(int batch, int rows_per_layer, int n);
+
+/* Group scales.  gscale: R x G float32, positive, G = n / group_size (group_size >= 1 must divide n); element (r, c)
+ * belongs to group c / group_size.  The group quantizer maps x in column c of row r to
+ *     codebook(x / s) / (1 / s),   s = gscale[r][c / group_size]   (float32 IEEE divides, as scaling.py:73, 80).
+ * slk_gptq_quantize_grouped: quantize_opt(W, H, group quantizer, ...) (sleekit/obq.py:169-217) without local search: the
+ *     loop of slk_gptq_quantize on the UNSCALED W, only its leaves scale.  Q: de-scaled values, original column order;
+ *     idx (may be NULL, levels <= 256): the codebook indices of Q / s; E_out (may be NULL): errors in processing order.
+ *     flags: SLK_LOOP_LATENCY only (accepted; the grouped loop runs 16 rows per window workgroup either way).
+ *     Workspace: slk_workspace_bytes(R, n).
+ * slk_column_miss_grouped: slk_column_miss with the group quantizer (the err / sqerr keys of the grouped loop).
+ * slk_scale_search_grouped: slk_scale_search on every group at once: row r G + k of the (R G, group_size) view of W is
+ *     group k of row r, with base[r G + k] and, hdiag given (length n), the slice hdiag[k group_size : (k + 1) group_size];
+ *     out: R x G.
+ * slk_dequantize_grouped: Q[r][c] = value(idx[r][c]) / (1 / s), bit for bit the Q that slk_gptq_quantize_grouped returned. */
+int slk_gptq_quantize_grouped(const float *W, const float *gscale, int group_size, const long long *order, const double *U,
+                              int R, int n, int levels, double lo, double hi, const float *table, int min_block,
+                              int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace,
+                              size_t ws_bytes, slk_stream_t stream);
+int slk_column_miss_grouped(const float *W, const float *gscale, int group_size, int R, int n, int levels, double lo,
+                            double hi, const float *table, int squared, float *miss, slk_stream_t stream);
+int slk_scale_search_grouped(const float *W, const float *base, const float *factors, int n_factors, const float *hdiag,
+                             int group_size, int R, int n, int levels, double lo, double hi, const float *table, float *out,
+                             slk_stream_t stream);
+int slk_dequantize_grouped(const uint8_t *idx, const float *gscale, int group_size, int R, int n, int levels, double lo,
+                           double hi, const float *table, float *Q, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -71,6 +71,13 @@ PROTOTYPES = {
         [P, P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],
     ),
     "slk_workspace_bytes_batch": (c_size_t, [c_int, c_int, c_int]),
+    "slk_gptq_quantize_grouped": (
+        c_int,
+        [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],
+    ),
+    "slk_column_miss_grouped": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P, P]),
+    "slk_scale_search_grouped": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),
+    "slk_dequantize_grouped": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

@@ -112,8 +112,11 @@ __global__ __launch_bounds__(256) void k_zero_dead(float *__restrict__ W, int R,
 // took 1.4 ms for a 4096 x 4096 layer: 4096 dependent trips to memory.)
 typedef float float4v_t __attribute__((ext_vector_type(4)));
 constexpr int CM_COLS = 32, CM_ROWS = 256;
+// GROUPED: q = codebook(w / s) / rs with the element's group scale s = S[r][j / gsize], rs = RN(1 / s) (slk_column_miss_grouped)
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W, int R, int n, Grid g,
-                                                     int squared, float *__restrict__ miss, int vec_ok) {
+                                                     int squared, float *__restrict__ miss, int vec_ok,
+                                                     const float *__restrict__ S, int gsize) {
     __shared__ float term[CM_ROWS][CM_COLS + 1];
     const int t = threadIdx.x;
     const int j0 = blockIdx.x * CM_COLS;
@@ -141,7 +144,15 @@ __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float w = cur[p][e];
-                const float d = cb_value(w, g) - w;
+                float qv;
+                if constexpr (GROUPED) {
+                    // (clamped like the loads: a row beyond R or a column beyond n is never added)
+                    const float sv = S[(size_t)min(base + p * 32 + lr, R - 1) * (n / gsize) + min(j0 + c4 + e, n - 1) / gsize];
+                    qv = cb_value(w / sv, g) / (1.0f / sv);
+                } else {
+                    qv = cb_value(w, g);
+                }
+                const float d = qv - w;
                 term[p * 32 + lr][c4 + e] = squared ? d * d : fabsf(d);
             }
         __syncthreads();
@@ -154,6 +165,18 @@ __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W
         for (int p = 0; p < 8; ++p) cur[p] = nxt[p];
     }
     if (t < CM_COLS && j0 + t < n) miss[j0 + t] = acc;
+}
+// Q[r][c] = value(idx[r][c]) / RN(1 / S[r][c / gsize]): the grouped loop's result rebuilt from its compact form.  The value
+// of index t is formed like the quantizer's (t * step + zero in float32, codebook.py:58-63) or read from the table.
+__global__ __launch_bounds__(256) void k_dequantize_grouped(const uint8_t *__restrict__ idx, const float *__restrict__ S, int gsize,
+                                                            int R, int n, Grid g, float *__restrict__ Q) {
+    const size_t total = (size_t)R * n;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = e / n, c = e % n;
+        const int k = min((int)idx[e], g.n - 1);
+        const float v = g.table ? g.table[k] : grid_val((float)k, g);
+        Q[e] = v / (1.0f / S[r * (n / gsize) + c / gsize]);
+    }
 }
 
 }  // namespace slk
@@ -253,8 +276,32 @@ int slk_column_miss(const float *W, int R, int n, int levels, double lo, double 
     SLK_REQUIRE(R >= 0 && n > 0 && W && miss, "bad arguments");
     hipStream_t s = as_stream(stream);
     SLK_RUN("column_miss", 0, 4.0 * R * n, s,
-            k_column_miss<<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
-                                                                      n % 4 == 0 && (uintptr_t)W % 16 == 0));
+            k_column_miss<false><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
+                                                                             n % 4 == 0 && (uintptr_t)W % 16 == 0, nullptr, 1));
+    return SLK_OK;
+}
+
+int slk_column_miss_grouped(const float *W, const float *gscale, int group_size, int R, int n, int levels, double lo, double hi,
+                            const float *table, int squared, float *miss, slk_stream_t stream) {
+    SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
+    SLK_REQUIRE(R > 0 && n > 0 && W && gscale && miss, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    SLK_RUN("column_miss_grouped", 0, 4.0 * R * n, s,
+            k_column_miss<true><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
+                                                                            n % 4 == 0 && (uintptr_t)W % 16 == 0, gscale, group_size));
+    return SLK_OK;
+}
+
+int slk_dequantize_grouped(const uint8_t *idx, const float *gscale, int group_size, int R, int n, int levels, double lo, double hi,
+                           const float *table, float *Q, slk_stream_t stream) {
+    SLK_REQUIRE(levels >= 2 && levels <= 256 && (table || lo < hi), "codebook needs 2 <= levels <= 256 and lo < hi");
+    SLK_REQUIRE(R > 0 && n > 0 && idx && gscale && Q, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    SLK_RUN("dequantize_grouped", 0, 9.0 * R * n, s,
+            k_dequantize_grouped<<<stream_blocks((size_t)R * n, 256 * 4), 256, 0, s>>>(idx, gscale, group_size, R, n,
+                                                                                     make_grid(levels, lo, hi, table), Q));
     return SLK_OK;
 }
 

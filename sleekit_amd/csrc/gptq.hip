@@ -137,6 +137,30 @@ __global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict
     }
 }
 
+// ------------------------------------------------------------------ group scales (slk_gptq_quantize_grouped)
+// S (R x G, G = n / gsize) holds one scale per row and per group of gsize ORIGINAL columns; the loop runs on the
+// unscaled weights and only its leaves scale (see leaf_registers_grouped).  pg[c] = group of processing column c.
+__global__ __launch_bounds__(256) void k_group_of_column(const long long *__restrict__ order, int n, int gsize, int *__restrict__ pg) {
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) pg[c] = (int)((order ? order[c] : c) / gsize);
+}
+
+// Q[r][j] = Qp[r][inv[j]] (already de-scaled by the leaves);  idx[r][j] = codebook index of Q[r][j] / S[r][j / gsize].
+// Q = value / rs with rs = RN(1 / s), so Q / s is the codebook value to within a few ulps: far closer than half a step
+// (uniform) or than the nearest bin limit (table), and the index comes back exactly (dequantize_grouped checks it).
+__global__ __launch_bounds__(256) void k_permute_out_grouped(const float *__restrict__ Qp, const int *__restrict__ inv_order,
+                                                             int R, int n, Grid g, const float *__restrict__ S, int gsize,
+                                                             float *__restrict__ Q, uint8_t *__restrict__ idx) {
+    const int G = n / gsize;
+    for (int r = blockIdx.x; r < R; r += gridDim.x) {
+        const float *src = Qp + (size_t)r * n;
+        for (int j = threadIdx.x; j < n; j += blockDim.x) {
+            const float v = src[inv_order[j]];
+            Q[(size_t)r * n + j] = v;
+            if (idx) idx[(size_t)r * n + j] = (uint8_t)cb_index(v / S[(size_t)r * G + j / gsize], g);
+        }
+    }
+}
+
 // ------------------------------------------------------------------ window kernel
 struct LeafTables {
     double u[ULEAF][ULEAF + 1];  // leaf block of U, STRICTLY upper part (zero on/below the diagonal and beyond the width)
@@ -256,6 +280,70 @@ __device__ __forceinline__ void leaf_registers(WindowSmem &sm, const LeafTables 
     }
 }
 
+// The window's scales in the grouped loop, beside WindowSmem: s[r][c] = S[row][group of column c], rs = RN(1 / s).
+// The pitch leaves room for the steps a leaf runs past its width (up to 31 columns beyond the window), which read 1.0.
+constexpr int GPITCH = WMAX + 32;
+struct GroupTile {
+    float s[RB][GPITCH];
+    float rs[RB][GPITCH];
+};
+
+// leaf_registers with the group quantizer: x is unscaled, q = codebook(x / s) / rs with this row's scale of column i
+// (two true divides; the codebook step keeps the exact-division sequence).  The scales of step i + 1 are read from
+// LDS before step i, like the U row.
+template <int NSTEP>
+__device__ __forceinline__ void leaf_registers_grouped(WindowSmem &sm, const GroupTile &gt, const LeafTables &lt, int wave, int lane,
+                                                       int a_rel, int w, const Grid g, float inv_step) {
+    const int c16 = lane & 15, rg = lane >> 4;
+    const int row = 4 * wave + rg;
+    const bool m0 = c16 < w, m1 = c16 + 16 < w;
+    float x0 = m0 ? sm.q[row][a_rel + c16] : 0.0f, x1 = m1 ? sm.q[row][a_rel + 16 + c16] : 0.0f;
+    float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
+    // steps beyond the width read the tile's padding, 1.0: a finite error that meets a zero U row
+    double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
+    float sn = gt.s[row][a_rel], rsn = gt.rs[row][a_rel];
+    static_for<0, NSTEP>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
+        const float sc = sn, rsc = rsn;
+        if constexpr (i + 1 < NSTEP) {
+            u0n = lt.u[i + 1][c16];
+            u1n = lt.u[i + 1][c16 + 16];
+            uiin = lt.udr[i + 1][0];
+            riin = lt.udr[i + 1][1];
+            sn = gt.s[row][a_rel + i + 1];
+            rsn = gt.rs[row][a_rel + i + 1];
+        }
+        asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
+        constexpr int src = i & 15;
+        const float xi = row_bcast<src>(i < 16 ? x0 : x1);
+        const float q = grid_value_fast(xi / sc, g, inv_step) / rsc;
+        const double d = (double)(xi - q);
+        const double qq = d * rii;
+        const double rem = __builtin_fma(-uii, qq, d);
+        const double err = __builtin_fma(rem, rii, qq);
+        const float ef = (float)err;
+        const bool here = c16 == src;
+        if (i < 16) {
+            q0 = here ? q : q0;
+            e0 = here ? ef : e0;
+        } else {
+            q1 = here ? q : q1;
+            e1 = here ? ef : e1;
+        }
+        if (i < 15) x0 = (float)((double)x0 - err * u0);
+        if (NSTEP > 16) x1 = (float)((double)x1 - err * u1);
+    });
+    if (m0) {
+        sm.q[row][a_rel + c16] = q0;
+        sm.e[row][a_rel + c16] = e0;
+    }
+    if (m1) {
+        sm.q[row][a_rel + 16 + c16] = q1;
+        sm.e[row][a_rel + 16 + c16] = e1;
+    }
+}
+
 // cycle counters of workgroup 0 (SLK_WIN_DBG bit 3), read back by slk_probe_window_cycles
 __device__ long long g_win_cycles[16];
 __device__ long long g_win_trace[64];  // window2: busy cycles per period, chain wave 0 / helper wave 2 (+32)
@@ -272,12 +360,17 @@ __device__ long long g_win_trace[64];  // window2: busy cycles per period, chain
 // each rounded to float32 once, so the result is the reference's bit for bit.
 // UPDATE: the target columns are cut in 16-wide MFMA blocks (M = the 16 rows of the tile), dealt
 // round-robin to the participating waves, K in chunks of 64.
-template <bool IN_LDS>
+// GROUPED: the leaves quantize with the group scales S (R x G) of the unscaled weights, pg[c] =
+// group of processing column c; in LDS the window's scales sit in a GroupTile behind WindowSmem.  Everything else --
+// updates, deferral, staging -- is the same code.
+template <bool IN_LDS, bool GROUPED>
 __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, float *__restrict__ Eg,
                                                      const double *__restrict__ U, int R, int n, int w0, int w1,
-                                                     Grid g, float inv_step, int fast_ok, int dbg, OpTable tab, int rpl) {
+                                                     Grid g, float inv_step, int fast_ok, int dbg, OpTable tab, int rpl,
+                                                     const float *__restrict__ Sg, const int *__restrict__ pg, int G) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     WindowSmem &sm = *reinterpret_cast<WindowSmem *>(smem_raw);
+    GroupTile &gt = *reinterpret_cast<GroupTile *>(smem_raw + sizeof(WindowSmem));  // (GROUPED && IN_LDS only)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const bool helper = wave >= 4;
     const int ht = t - 256;  // helper thread index
@@ -361,6 +454,15 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
         const bool any = __builtin_amdgcn_ballot_w64(odd) != 0;
         if (lane == 0) sm.odd[buf][wave - 4] = any ? 1 : 0;
     };
+
+    if constexpr (GROUPED && IN_LDS) {  // the window's scales (1.0 on the padding and on rows beyond R), read after the barrier below
+        for (int e = t; e < RB * GPITCH; e += 512) {
+            const int r = e / GPITCH, c = e % GPITCH;
+            const float sv = (c < width && r0 + r < R) ? Sg[(size_t)(r0 + r) * G + pg[w0 + c]] : 1.0f;
+            gt.s[r][c] = sv;
+            gt.rs[r][c] = 1.0f / sv;
+        }
+    }
 
     // Warm this XCD's L2 with the window's block of U (workgroup i runs on XCD i % 8; the
     // workgroups of an XCD share the lines, one 4-byte touch per 128-byte line).
@@ -497,7 +599,13 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             double err = 0.0;
             if (live) {
                 x = qld(myrow, i);
-                q = cb_value(x, g);
+                if constexpr (GROUPED) {
+                    const float sv = IN_LDS ? gt.s[myrow][i - w0] : Sg[(size_t)(r0 + myrow) * G + pg[i]];
+                    const float rsv = IN_LDS ? gt.rs[myrow][i - w0] : 1.0f / sv;
+                    q = cb_value(x / sv, g) / rsv;
+                } else {
+                    q = cb_value(x, g);
+                }
                 const double uii = staged ? lt.udr[i - a][0] : U[(size_t)i * n + i];
                 err = (double)(x - q) / uii;
             }
@@ -597,8 +705,13 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             if (use_fast) {
                 if (!helper && !no_leaf_regs) {
                     const int w = op.b - op.a;
-                    if (w <= 16) leaf_registers<16>(sm, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                    else leaf_registers<32>(sm, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                    if constexpr (GROUPED) {
+                        if (w <= 16) leaf_registers_grouped<16>(sm, gt, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        else leaf_registers_grouped<32>(sm, gt, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                    } else {
+                        if (w <= 16) leaf_registers<16>(sm, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        else leaf_registers<32>(sm, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                    }
                 }
                 lap(0, 0);
                 lap(5, 4);
@@ -882,12 +995,12 @@ extern "C" int slk_gptq_quantize(const float *W, const float *scale, const long 
 // `batch` layers of one shape stacked by rows: every launch of the loop covers all of them, each row tile
 // reading its own layer's factor.  What a row shard of a multi-GPU run needs: R / G rows alone leave most of
 // the chip idle (the window kernel runs one workgroup per 16 rows), G layers' shards together fill it.
-extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const long long *order, const double *U,
-                                       int batch, int rows_per_layer, int n, int levels, double lo, double hi,
-                                       const float *table, int min_block, int num_blocks, int flags, float *Q, uint8_t *idx,
-                                       float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream) {
-    SLK_REQUIRE(W && U && Q, "null pointer");
-    SLK_REQUIRE((flags & ~(SLK_LOOP_UNSCALE | SLK_LOOP_LATENCY)) == 0, "unknown flags");
+// gscale != nullptr: the grouped loop (slk_gptq_quantize_grouped), batch 1, no row scale.
+static int gptq_loop(const float *W, const float *scale, const long long *order, const double *U, int batch, int rows_per_layer,
+                     int n, int levels, double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
+                     float *Q, uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream,
+                     const float *gscale, int group_size) {
+    const bool grouped = gscale != nullptr;
     const int unscale = flags & SLK_LOOP_UNSCALE;
     SLK_REQUIRE(!unscale || scale, "unscale needs the row scales");
     SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
@@ -904,7 +1017,8 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
     float *Qp = ws.take<float>((size_t)R * n);
     float *Eg = ws.take<float>((size_t)R * n);
     int *inv_order = ws.take<int>((size_t)batch * n);
-    if (!Qp || !Eg || !inv_order) {
+    int *pg = grouped ? ws.take<int>((size_t)n) : nullptr;
+    if (!Qp || !Eg || !inv_order || (grouped && !pg)) {
         set_error("workspace too small for a %d x %d layer", R, n);
         return SLK_E_WS;
     }
@@ -922,7 +1036,8 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
     const int dbg = opt(OPT_WIN_DBG) & (8 | 16 | 32 | 64 | 128);  // cycle counters, no L2 warm-up, whole tile loaded up front: same results
 #endif
     const bool no_defer = opt(OPT_NO_DEFER) != 0;
-    SLK_LDS_OPT_IN(k_gptq_window<true>, sizeof(WindowSmem));
+    SLK_LDS_OPT_IN((k_gptq_window<true, false>), sizeof(WindowSmem));
+    if (grouped) SLK_LDS_OPT_IN((k_gptq_window<true, true>), sizeof(WindowSmem) + sizeof(GroupTile));
     SLK_LDS_OPT_IN(k_gptq_window2<1>, sizeof(Window2SmemT<1>));
     SLK_LDS_OPT_IN(k_gptq_window2<2>, sizeof(Window2SmemT<2>));
     // 32 rows per workgroup (eight rows per chain wave, ONE quantizer instruction stream for them: leaf_chain8) halve the CUs
@@ -935,7 +1050,8 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
     // counts then is the length of the launch chain, 16 rows again: one rank of 8 on OPT-125M 14.0 -> 12.6 ms per step)
     const int window_rows = opt(OPT_WINDOW_ROWS) == 16 || opt(OPT_WINDOW_ROWS) == 32 ? opt(OPT_WINDOW_ROWS)
                                                                                      : (((flags & SLK_LOOP_LATENCY) || R < 2048) ? 16 : 32);
-    const bool periods_ok = n % 2 == 0 && n <= 16384 && (uintptr_t)U % 16 == 0 && !opt(OPT_NO_WINDOW2) && (dbg & ~(24 | 64 | 128)) == 0;
+    // the grouped loop runs on k_gptq_window alone (16 rows per workgroup whatever window_rows / SLK_LOOP_LATENCY ask)
+    const bool periods_ok = !grouped && n % 2 == 0 && n <= 16384 && (uintptr_t)U % 16 == 0 && !opt(OPT_NO_WINDOW2) && (dbg & ~(24 | 64 | 128)) == 0;
 
     // rows staged through LDS when they fit and 16-byte accesses line up
     const bool perm_lds = order && n % 4 == 0 && n <= PERM_MAX && ((uintptr_t)W | (uintptr_t)Q | (uintptr_t)workspace) % 16 == 0 &&
@@ -948,6 +1064,10 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
         SLK_RUN("permute_in", 0, 8.0 * R * n, s, k_permute_in_lds<<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(W, scale, order, R, n, Qp, inv_order, rpl));
     else
         SLK_RUN("permute_in", 0, 8.0 * R * n, s, k_permute_in<<<R < 2048 ? R : 2048, 256, 0, s>>>(W, scale, order, R, n, Qp, inv_order, rpl));
+
+    const int G = grouped ? n / group_size : 0;
+    if (grouped)
+        SLK_RUN("group_of_column", 0, 12.0 * n, s, k_group_of_column<<<(n + 255) / 256, 256, 0, s>>>(order, n, group_size, pg));
 
     Plan p;
     plan(0, n, min_block, num_blocks, p);
@@ -1002,14 +1122,22 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
                                   k_gptq_window2<1><<<row_tiles, 512, sizeof(Window2SmemT<1>), s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step,
                                                                                                  fast_ok, dbg & 24, pt, rpl));
                 }
+                else if (grouped && in_lds)
+                    SLK_RUN("gptq_window_grouped", fl * R, wbytes, s,
+                            k_gptq_window<true, true><<<row_tiles, 512, sizeof(WindowSmem) + sizeof(GroupTile), s>>>(
+                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, R, gscale, pg, G));
+                else if (grouped)
+                    SLK_RUN("gptq_window_wide_grouped", fl * R, wbytes, s,
+                            k_gptq_window<false, true><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
+                                                                             dbg, tab, R, gscale, pg, G));
                 else if (in_lds)
                     SLK_RUN("gptq_window", fl * R, wbytes, s,
-                            k_gptq_window<true><<<row_tiles, 512, sizeof(WindowSmem), s>>>(Qp, Eg, U, R, n, st.a, st.b, g,
-                                                                                        inv_step, fast_ok, dbg, tab, rpl));
+                            k_gptq_window<true, false><<<row_tiles, 512, sizeof(WindowSmem), s>>>(Qp, Eg, U, R, n, st.a, st.b, g,
+                                                                                        inv_step, fast_ok, dbg, tab, rpl, nullptr, nullptr, 0));
                 else
                     SLK_RUN("gptq_window_wide", fl * R, wbytes, s,
-                            k_gptq_window<false><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
-                                                                           dbg, tab, rpl));
+                            k_gptq_window<false, false><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
+                                                                           dbg, tab, rpl, nullptr, nullptr, 0));
             }
         } else {
             const double K = st.b - st.a, N = st.c - st.b;
@@ -1021,10 +1149,37 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
             }
         }
     }
-    if (perm_lds)
+    if (grouped)
+        SLK_RUN("permute_out_grouped", 0, (idx ? 13.0 : 8.0) * R * n, s,
+                k_permute_out_grouped<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx));
+    else if (perm_lds)
         SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out_lds<<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl));
     else
         SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl));
     if (E_out) copy_async(E_out, Eg, sizeof(float) * (size_t)R * n, s);
     return SLK_OK;
+}
+
+extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const long long *order, const double *U,
+                                       int batch, int rows_per_layer, int n, int levels, double lo, double hi,
+                                       const float *table, int min_block, int num_blocks, int flags, float *Q, uint8_t *idx,
+                                       float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    SLK_REQUIRE(W && U && Q, "null pointer");
+    SLK_REQUIRE((flags & ~(SLK_LOOP_UNSCALE | SLK_LOOP_LATENCY)) == 0, "unknown flags");
+    return gptq_loop(W, scale, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
+                     workspace, ws_bytes, stream, nullptr, 0);
+}
+
+// One layer with one scale per row and per group of `group_size` original columns (gscale: R x n / group_size, positive).
+extern "C" int slk_gptq_quantize_grouped(const float *W, const float *gscale, int group_size, const long long *order, const double *U,
+                                         int R, int n, int levels, double lo, double hi, const float *table, int min_block,
+                                         int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace,
+                                         size_t ws_bytes, slk_stream_t stream) {
+    SLK_REQUIRE(W && gscale && U && Q, "null pointer");
+    SLK_REQUIRE((flags & ~SLK_LOOP_LATENCY) == 0, "the grouped loop takes SLK_LOOP_LATENCY only");
+    SLK_REQUIRE(R > 0 && n > 0, "empty layer");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
+                group_size);
+    return gptq_loop(W, nullptr, order, U, 1, R, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out, workspace,
+                     ws_bytes, stream, gscale, group_size);
 }

@@ -75,16 +75,21 @@ __device__ __forceinline__ bool divisor_ok(float b) {
 // ------------------------------------------------------------------ grid search
 // mode 0: error = sum E^2;  mode 1: error = sum hdiag_j * E_j^2   (scaling.py:84-95)
 // E = quantize_with_scaling(w, s * base) - w with round-to-nearest quantization (scaling.py:73, 79-80)
-template <int EPT>
+// GROUPED (slk_scale_search_grouped): the rows are the (R G, gsize) view of an (R, n) layer, and row r weighs its terms
+// with group r % G's slice of the diagonal, hdiag[(r % G) gsize : (r % G + 1) gsize] (`n` is gsize here).
+template <int EPT, bool GROUPED>
 __global__ __launch_bounds__(256) void k_scale_search(const float *__restrict__ W, const float *__restrict__ base,
                                                       const float *__restrict__ factors, int n_factors,
                                                       const float *__restrict__ hdiag, int R, int n, Grid g,
-                                                      float *__restrict__ out, int fast_div) {
+                                                      float *__restrict__ out, int fast_div, int G) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     SumTree *trees = reinterpret_cast<SumTree *>(smem_raw);
     float *terms = reinterpret_cast<float *>(smem_raw + 2 * sizeof(SumTree));
     const int r = blockIdx.x, t = threadIdx.x;
     const float *w = W + (size_t)r * n;
+    if constexpr (GROUPED) {
+        if (hdiag) hdiag += (size_t)(r % G) * n;
+    }
     prepare_trees(trees, n);
     const float b = base[r];
     float best_err = __builtin_huge_valf(), best_f = __builtin_huge_valf();
@@ -119,7 +124,6 @@ __global__ __launch_bounds__(256) void k_scale_search(const float *__restrict__ 
     }
     if (t == 0) out[r] = b * best_f;  // scaling.py:134
 }
-
 // The same search for rows whose NumPy summation tree is REGULAR: n = L * m with L = 2^k leaves of m <= 128
 // elements, m a multiple of 8 (4096 = 32 x 128, 3072 = 32 x 96, 1024 = 8 x 128, 768 = 8 x 96, ...).  NumPy's leaf is
 // eight running sums r[a] += x[8 i + a] combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), and its tree a
@@ -295,7 +299,26 @@ int slk_scale_search(const float *W, const float *base, const float *factors, in
 #undef SLK_SEARCH_CASE
     }
     SLK_RUN("scale_search", 0, 4.0 * R * n, s,
-            k_scale_search<1><<<R, 256, search_smem(n), s>>>(W, base, factors, n_factors, hdiag, R, n, g, out, fast_div));
+            k_scale_search<1, false><<<R, 256, search_smem(n), s>>>(W, base, factors, n_factors, hdiag, R, n, g, out, fast_div, 1));
+    return SLK_OK;
+}
+
+// All groups of an (R, n) layer in one launch: row r G + k of the (R G, group_size) view is group k of row r.  base and
+// out: R x G.  hdiag: diag(H) of length n (or NULL: unweighted, as in slk_scale_search).  Always the staged-sum kernel,
+// which sums every row length in NumPy's order (the regular one only serves rows of 576 and more).
+int slk_scale_search_grouped(const float *W, const float *base, const float *factors, int n_factors, const float *hdiag, int group_size,
+                             int R, int n, int levels, double lo, double hi, const float *table, float *out, slk_stream_t stream) {
+    SLK_REQUIRE(W && base && factors && out && R > 0 && n > 0 && n_factors > 0, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
+    const int G = n / group_size;
+    SLK_REQUIRE((long long)R * G <= 0x7fffffffLL, "too many groups");
+    hipStream_t s = as_stream(stream);
+    const Grid g = make_grid(levels, lo, hi, table);
+    const int fast_div = !opt(OPT_NO_FAST_SEARCH_DIV);
+    SLK_RUN("scale_search_grouped", 0, 4.0 * R * n, s,
+            k_scale_search<1, true><<<R * G, 256, search_smem(group_size), s>>>(W, base, factors, n_factors, hdiag, R * G, group_size, g,
+                                                                             out, fast_div, G));
     return SLK_OK;
 }
 

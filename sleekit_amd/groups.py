@@ -1,0 +1,187 @@
+"""Group-wise scales: one scale per row and per group of `g` columns, from the scale search through the GPTQ loop.
+
+    S = compute_group_scaling(W, cb, g, H, mode="diag")        # (R, n / g) float32
+    Q = quantize_grouped(W, S, cb, H, g, act_order="sqerr")     # de-scaled values, like W
+    Q, idx = quantize_grouped(..., return_indices=True)         # idx uint8: (idx, S) is the compact form of the layer
+    Q == dequantize_grouped(idx, S, cb, g)                      # bit for bit
+
+Element (r, c) belongs to group c // g.  The GROUP QUANTIZER maps x in column c of row r to
+
+    codebook.quantize_value(x / s) / (np.float32(1) / s),   s = S[r, c // g]
+
+(float32 IEEE divides: the arithmetic of sleekit/scaling.py:73, 80).  `quantize_grouped` returns what the reference's
+own `quantize_opt(W, H, Z, act_order, damp, 0, min_block_size, num_blocks)` (sleekit/obq.py:169-217) returns for a
+callable Z that applies the group quantizer by column: the loop runs on the UNSCALED weights with the reference's rank-1
+and block updates, only the leaves scale, and the err / sqerr keys come from Z(W) - W in original units.
+`compute_group_scaling` gives column k of S as the reference's `compute_scaling` of the k-th column block of W with
+the k-th diagonal block of H.
+
+Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out, and
+every step runs on the GPU (no CPU fallback).
+"""
+
+import numpy as np
+import torch
+
+from . import _device as dev
+from . import _lib
+from . import engine
+from . import scaling
+
+_MODES = ("max", "mse", "diag", "hessian")  # and diagN / hessianN
+
+
+def _groups(n, g):
+    g = int(g)
+    if g < 1 or n % g != 0:
+        raise ValueError(f"group_size must be >= 1 and divide the {n} columns (got {g})")
+    return g, n // g
+
+
+def _diag_mean(Hb):
+    """float32 mean of the diagonal of a square device matrix, summed in NumPy's order (slk_diag_mean)."""
+    out = torch.empty(1, dtype=torch.float32, device=Hb.device)
+    ws, ws_bytes = dev.workspace(0, Hb.shape[0])
+    _lib.check(_lib.lib.slk_diag_mean(dev.ptr(Hb), Hb.shape[0], dev.ptr(out), dev.ptr(ws), ws_bytes, dev.stream_handle()))
+    return out
+
+
+def compute_group_scaling(W, codebook, group_size, H=None, mode="mse", min_factor=0.05, max_factor=1.0, grid_size=100):
+    """S (R, n / group_size) float32: column k is the reference's compute_scaling(W[:, k g : (k + 1) g], codebook,
+    H[k g : (k + 1) g, k g : (k + 1) g], mode) (sleekit/scaling.py:193-238).
+
+    Modes max, mse, diag[N], hessian[N]; "obq" and "norm" raise NotImplementedError.  mse and diag search every group
+    of every row in one launch; hessian runs the stacked search of sleekit_amd.scaling group by group (with that
+    search's known deviation: near-tied grid points may fall the other way, see sleekit_amd.scaling).
+    """
+    assert W.ndim == 2
+    cb_abi = engine.require_uniform(codebook)
+    if mode in ("obq", "norm"):
+        raise NotImplementedError(f'group scales support modes {", ".join(_MODES)} (and diagN / hessianN), not "{mode}"')
+    if not (mode in ("max", "mse") or mode.startswith("diag") or mode.startswith("hessian")):
+        raise RuntimeError(f"Unknown scaling mode {mode}")
+    if mode not in ("max", "mse") and H is None:
+        raise ValueError(f'scaling mode "{mode}" needs the Hessian H')
+    Wd = dev.to_device(W)
+    R, n = Wd.shape
+    g, G = _groups(n, group_size)
+    view = Wd.view(R * G, g)  # row r G + k = group k of row r: the reference's per-group problem, row for row
+    if mode == "max":
+        return dev.like_input(scaling._no_clip_scale(view, codebook).view(R, G), W)
+    Hd = None if H is None else dev.to_device(H)
+    if Hd is not None:
+        assert Hd.shape == (n, n)
+    kw = dict(min_factor=min_factor, max_factor=max_factor, grid_size=grid_size)
+    if mode.startswith("hessian"):
+        cols = []
+        for k in range(G):
+            Hk = Hd[k * g:(k + 1) * g, k * g:(k + 1) * g].contiguous()
+            if len(mode) > 7:  # scaling.py:222-225 on the group's block
+                Hk.diagonal().add_(np.float32(0.01 * float(mode[7:])) * Hk.diagonal().mean())
+            cols.append(scaling.compute_min_mse_scaling(Wd[:, k * g:(k + 1) * g].contiguous(), codebook, H=Hk, **kw))
+        return dev.like_input(torch.stack(cols, dim=1).contiguous(), W)
+    hd = None
+    if mode.startswith("diag"):
+        hd = Hd.diagonal().contiguous()
+        if len(mode) > 4:  # scaling.py:226-229: each group's penalty is from its own block's mean diagonal
+            pen = np.float32(0.01 * float(mode[4:]))
+            parts = []
+            for k in range(G):
+                mean = _diag_mean(Hd[k * g:(k + 1) * g, k * g:(k + 1) * g].contiguous())
+                parts.append(hd[k * g:(k + 1) * g] + mean * float(pen))  # float32(pen) * mean, rounded once
+            hd = torch.cat(parts).contiguous()
+    base = scaling._no_clip_scale(view, codebook)
+    factors = torch.from_numpy(np.linspace(min_factor, max_factor, grid_size, dtype=np.float32)).to(Wd.device)
+    out = torch.empty(R * G, dtype=torch.float32, device=Wd.device)
+    levels, lo, hi, table = cb_abi
+    _lib.check(
+        _lib.lib.slk_scale_search_grouped(
+            dev.ptr(Wd), dev.ptr(base), dev.ptr(factors), grid_size, dev.ptr(hd), g, R, n, levels, lo, hi, dev.ptr(table),
+            dev.ptr(out), dev.stream_handle(),
+        )
+    )
+    return dev.like_input(out.view(R, G), W)
+
+
+def column_miss_grouped(W, S, group_size, cb_abi, squared):
+    """Column sums of |Z(W) - W| (or squared) with the group quantizer Z, in NumPy's row-after-row order (device tensors)."""
+    R, n = W.shape
+    levels, lo, hi, table = cb_abi
+    out = torch.empty(n, dtype=torch.float32, device=W.device)
+    _lib.check(
+        _lib.lib.slk_column_miss_grouped(
+            dev.ptr(W), dev.ptr(S), int(group_size), R, n, levels, lo, hi, dev.ptr(table), 1 if squared else 0, dev.ptr(out),
+            dev.stream_handle(),
+        )
+    )
+    return out
+
+
+def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
+                           want_idx=True):
+    """The grouped layer on device tensors: W (R, n), S (R, n / group_size), H (n, n), all float32.  Returns an
+    engine.LayerResult (Q de-scaled, idx uint8 or None, order, U, info); raises LinAlgError if H + damping is not
+    positive definite."""
+    assert W.ndim == 2 and H.ndim == 2 and H.shape[0] == H.shape[1] == W.shape[1]
+    assert min_block_size >= 1
+    cb_abi = engine.require_uniform(quantizer)
+    R, n = W.shape
+    g, G = _groups(n, group_size)
+    if tuple(S.shape) != (R, G):
+        raise ValueError(f"group scales must be ({R}, {G}) for a ({R}, {n}) layer with group_size {g}; got {tuple(S.shape)}")
+    if want_idx and cb_abi[0] > 256:
+        raise ValueError("uint8 indices need a codebook of at most 256 entries")
+    mode = engine.order_mode_code(act_order)
+    if mode == _lib.ORDER_KEYS:
+        miss = engine.order_keys(H, n, damp, act_order)
+    elif mode >= _lib.ORDER_ERR:
+        miss = column_miss_grouped(W, S, g, cb_abi, mode == _lib.ORDER_SQERR)
+    else:
+        miss = None
+    res = engine.LayerResult()
+    res.order, res.U, res.info = engine.factorize(H, n, damp, mode, miss, lookahead=True)
+    levels, lo, hi, table = cb_abi
+    ws, ws_bytes = dev.workspace(R, n)
+    res.Q = torch.empty((R, n), dtype=torch.float32, device=W.device)
+    res.idx = torch.empty((R, n), dtype=torch.uint8, device=W.device) if want_idx else None
+    _lib.check(
+        _lib.lib.slk_gptq_quantize_grouped(
+            dev.ptr(W), dev.ptr(S), g, dev.ptr(res.order), dev.ptr(res.U), R, n, levels, lo, hi, dev.ptr(table), int(min_block_size),
+            int(num_blocks), 2, dev.ptr(res.Q), dev.ptr(res.idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
+        )
+    )
+    # read back behind the loop, as engine.quantize_layer does
+    dev.note_info(res.info, "compute_hessian_chol")
+    return res
+
+
+def quantize_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
+                     return_indices=False):
+    """GPTQ-style quantization of one layer with group scales S (R, n / group_size).
+
+    Returns the de-scaled values Q (float32, shaped like W): what sleekit/obq.py:169-217 returns for the group quantizer
+    (module docstring).  return_indices: (Q, idx) with idx the uint8 codebook indices of Q / S.
+    """
+    assert W.ndim == 2 and H.ndim == 2
+    res = quantize_layer_grouped(dev.to_device(W), dev.to_device(S), quantizer, dev.to_device(H), group_size, act_order, damp,
+                                 min_block_size, num_blocks, want_idx=return_indices)
+    Q = dev.like_input(res.Q, W)
+    return (Q, dev.like_input(res.idx, W)) if return_indices else Q
+
+
+def dequantize_grouped(idx, S, codebook, group_size):
+    """Q[r, c] = value(idx[r, c]) / (1 / S[r, c // group_size]): bit for bit the Q of quantize_grouped."""
+    assert idx.ndim == 2
+    levels, lo, hi, table = engine.require_uniform(codebook)
+    idx_d = dev.to_device(idx, torch.uint8)
+    Sd = dev.to_device(S)
+    R, n = idx_d.shape
+    g, G = _groups(n, group_size)
+    if tuple(Sd.shape) != (R, G):
+        raise ValueError(f"group scales must be ({R}, {G}); got {tuple(Sd.shape)}")
+    Q = torch.empty((R, n), dtype=torch.float32, device=Sd.device)
+    _lib.check(
+        _lib.lib.slk_dequantize_grouped(dev.ptr(idx_d), dev.ptr(Sd), g, R, n, levels, lo, hi, dev.ptr(table), dev.ptr(Q),
+                                        dev.stream_handle())
+    )
+    return dev.like_input(Q, idx)

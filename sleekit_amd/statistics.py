@@ -119,12 +119,18 @@ class Sleekit:
     quantize_sleekit_heavy = _preset_method("sleekit_heavy")
 
     def quantize(self, nbits, scaling_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0,
-                 grid_size=100, min_factor=0.05, max_factor=1.0, scale=None):
+                 grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, group_size=None):
         """The layer's weight replaced by its `nbits` quantization, in place (statistics.py:146-190).
 
         bias_correction: quantize against H - mean mean^T and move the expected output shift into the bias.
         `scale` (optional, (out,) float32): this per-row scale instead of the scale search.
+        group_size (optional): one scale per row and per group of `group_size` input features (sleekit_amd.groups):
+        compute_group_scaling, then quantize_grouped; `scale`, if given, is then the (out, features / group_size) group
+        scales.  Local search and the "obq" scaling mode are not available with group scales.
         """
+        if group_size is not None:
+            return self._quantize_grouped(nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
+                                          max_factor, scale, group_size)
         codebook = UniformCodebook(2**nbits, -1, 1)
         weight = self.layer.weight.data.flatten(1).float().contiguous()
         H = self.hessian
@@ -136,6 +142,32 @@ class Sleekit:
             scale = compute_scaling(weight, codebook, H=H, mode=scaling_mode, grid_size=grid_size, min_factor=min_factor,
                                     max_factor=max_factor)
         result = engine.quantize_layer(weight, H, codebook, dev.to_device(scale), order_mode, damp, nb_ls_moves)
+        target = self.layer.weight
+        target.data = result.Q.reshape(target.shape).to(target.dtype)
+        if bias_correction:
+            shift = ((weight - result.Q) * self.mean).sum(dim=1)
+            self.layer.bias.data += shift.to(self.layer.bias.dtype)
+        return result
+
+    def _quantize_grouped(self, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
+                          max_factor, scale, group_size):
+        from . import groups
+
+        if nb_ls_moves > 0:
+            raise NotImplementedError("local search with group scales is not supported (nb_ls_moves must be 0)")
+        if scaling_mode == "obq":
+            raise NotImplementedError('the "obq" scaling mode is not supported with group scales')
+        codebook = UniformCodebook(2**nbits, -1, 1)
+        weight = self.layer.weight.data.flatten(1).float().contiguous()
+        H = self.hessian
+        if bias_correction:
+            centred = torch.empty_like(H)
+            _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
+            H = centred
+        if scale is None:
+            scale = groups.compute_group_scaling(weight, codebook, group_size, H=H, mode=scaling_mode, grid_size=grid_size,
+                                                 min_factor=min_factor, max_factor=max_factor)
+        result = groups.quantize_layer_grouped(weight, dev.to_device(scale), codebook, H, group_size, order_mode, damp)
         target = self.layer.weight
         target.data = result.Q.reshape(target.shape).to(target.dtype)
         if bias_correction:
