@@ -73,7 +73,8 @@ typedef void *slk_stream_t;
  * and turns the loop's `unscale` argument into `flags` (SLK_LOOP_UNSCALE = 1 as before, SLK_LOOP_LATENCY = 2); slk_local_search(_batch)
  * gain `row_err` (the rows' errors after the moves), slk_probe_panel_cycles is new; 7 adds slk_stack_rows and the option "panel_split";
  * 8: no new entry point -- the factorisation's default form is the CHAIN (an outer block's panels in one launch of workgroups that
- * hand the panels on through flags in memory: option "panel_split" 0 / 3; 1 / 2 = round 3's panel kernels), whose status word can
+ * hand the panels on through flags in memory: option "panel_split" 0 / 3; 1 / 2 = round 3's panel kernels; past 4 GiB of one
+ * float64 factor, ld * ld * 8 > 2^32, always the panel kernels, whose pointers are 64-bit), whose status word can
  * read SLK_INFO_HANDOFF_TIMEOUT; the factorisation's workspace holds its flags (slk_factor_workspace_bytes_batch grew by
  * 8 * (ld / 64) bytes per matrix); new options "tall_error", "rows_below_wide".  Still 8, with entries added alongside: the
  * group-scale forms slk_gptq_quantize_grouped, slk_column_miss_grouped, slk_scale_search_grouped and slk_dequantize_grouped

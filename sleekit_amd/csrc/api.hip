@@ -112,7 +112,7 @@ size_t slk_workspace_bytes(int R, int n) {
     if (R < 0 || n <= 0) return 0;
     const size_t ld = (size_t)slk_factor_ld(n);
     const size_t rn = (size_t)(R > 0 ? R : 1) * (size_t)n;
-    size_t factor = 2 * ld * ld * sizeof(double);                      // X and S of slk_chol_inverse_upper
+    size_t factor = 2 * ld * ld * sizeof(double) + 2 * (ld / 64) * sizeof(int);  // X and S of slk_chol_inverse_upper, the chain's flags
     size_t loop = 2 * rn * sizeof(float) + (size_t)n * sizeof(int);    // permuted Q and E, inverse order
     size_t search = rn * sizeof(float) + (size_t)(R + n) * sizeof(float) + (size_t)R * ((n + 127) / 128) * sizeof(float) + 4096;
     // layer error on the bfloat16 MFMA: three 2-byte planes of W - Q and of H, the per-tile partial sums

@@ -539,6 +539,8 @@ __global__ __launch_bounds__(256) void k_panel_below(double *__restrict__ A, int
 //   (SLK_INFO_HANDOFF_TIMEOUT) instead of hanging the GPU.
 // Same blocks, same products in the same order, one rounding per panel update: U is the panel kernels' bit for bit.
 constexpr int INFO_HANDOFF_TIMEOUT = 0x7fffffff;
+// GBuf's offsets (elem * 8u) stay below 2^32 for every element of an ld x ld matrix
+constexpr bool slk_chain_addressable(int ld) { return (size_t)ld * (size_t)ld * sizeof(double) <= 0xffffffffull; }
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -1186,8 +1188,11 @@ static int chol_inverse_impl(double *A, int batch, int n, double *U, int *info, 
     // Since round 4 the default is neither: an outer block's panels are ONE launch of a chain of workgroups that hand the
     // panels on through flags (k_chol_chain), plus one wide launch for the rows below (k_chol_rows_below) -- same U bit for
     // bit; panel_split = 1 | 2 still force the panel kernels (3 = the chain, explicitly).
+    // The chain addresses A and X through buffer resources at 32-bit byte offsets (GBuf): past 4 GiB of one matrix
+    // (ld * ld * 8 > 2^32, that is from ld = 23232 on) its offsets would wrap.  Such factorisations take the panel kernels,
+    // whose pointers are 64-bit -- the same U bit for bit, with or without panel_split.
     const int sp = opt(OPT_PANEL_SPLIT);
-    const bool chain = sp == 0 || sp == 3;
+    const bool chain = (sp == 0 || sp == 3) && slk_chain_addressable(ld);
     const bool split = !chain && !want_lookahead && sp != 2 && (sp == 1 || batch > 1 || n >= 8192);
     if (split) SLK_LDS_OPT_IN(k_panel_below, sizeof(BelowSmem));
     if (chain) {

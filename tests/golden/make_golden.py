@@ -3,7 +3,7 @@
 
 Run only in the build container, where the reference is mounted read-only:
 
-    python tests/golden/make_golden.py [--large]
+    python tests/golden/make_golden.py [--large] [--wide]
 
 It imports `sleekit` from /root/reference, feeds it layers from the build's own
 integer-hash generator (sleekit_amd/synth.py) and stores inputs' hashes and the
@@ -12,6 +12,11 @@ reference's outputs:
     small_cases.npz   full outputs (u8 indices, order, row errors, ...) of small layers
     pieces.npz        known-answer vectors of the helper functions on the path
     large_cases.json  SHA-256 of indices + float32 errors of BASELINE-sized layers
+    wide_cases.json   the same records for layers wider than 16384 columns (--wide; kept apart so that no test of
+                      large_cases.json runs them): 64 x 16512 (diag, sqerr) and 64 x 24576 (diag), 4 bit, T = 2 n.
+                      Measured on an 8-core box (NumPy 2.2.6, OpenBLAS), generator + reference: 64 x 16512 diag
+                      97 + 51 s, sqerr 108 + 62 s, 64 x 24576 diag 437 + 198 s -- 16 minutes in all,
+                      29 GB peak resident memory.
     codebook_fit.npz  known answers of the codebook training functions (equiprobable start, Lloyd-Max rounds, final
                       codebooks with and without the entropy term, drawn starts, empty bins)
     ls_traces.npz     for every case with local-search moves: the reference's sequence of moves and how close each
@@ -359,9 +364,18 @@ LARGE = [
 ]
 
 
-def large_cases(selected=None):
+WIDE = [
+    # (R, n, seed, levels, order, damp, moves, strip_mean): past the window2, PERM_MAX and local-search limits (16384),
+    # and past 4 GiB of float64 factor (ld * ld * 8 > 2^32 from ld = 23232 on)
+    (64, 16512, 1100, 16, "diag", 0.01, 0, False),
+    (64, 16512, 1101, 16, "sqerr", 0.01, 0, False),
+    (64, 24576, 1102, 16, "diag", 0.01, 0, False),
+]
+
+
+def large_cases(selected=None, specs=LARGE, timed=True):
     out = []
-    for spec in LARGE:
+    for spec in specs:
         R, n, seed, levels, order, damp, moves, strip = spec
         if selected and f"{R}x{n}" not in selected and f"{R}x{n}s{seed}" not in selected:
             continue
@@ -375,8 +389,12 @@ def large_cases(selected=None):
             sha_W=sha(L["W"]), sha_H=sha(L["H"]), sha_mean=sha(L["mean"]), sha_scale=sha(L["scale"]),
             sha_idx=sha(r["idx"]), err_f32_hex=np.float32(r["err"]).tobytes().hex(), err=float(r["err"]),
             idx_histogram=np.bincount(r["idx"].ravel(), minlength=levels).tolist(),
-            gen_seconds=round(t1 - t0, 2), reference_seconds=round(t2 - t1, 2),
         )
+        if timed:
+            rec.update(gen_seconds=round(t1 - t0, 2), reference_seconds=round(t2 - t1, 2))
+        else:  # (a file that must regenerate byte for byte: the times go to the console only)
+            rec.update(T=int(L["T"]))
+            print(f"{R}x{n} {order}: generator {t1 - t0:.0f} s, reference {t2 - t1:.0f} s", flush=True)
         print(rec, flush=True)
         out.append(rec)
     return out
@@ -491,6 +509,7 @@ def inverse_diag_orders():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--large", action="store_true", help="also (re)generate large_cases.json (minutes)")
+    ap.add_argument("--wide", action="store_true", help="(re)generate wide_cases.json (layers past 16384 columns; long)")
     ap.add_argument("--only", nargs="*", help="large shapes to run, e.g. 768x768 (or 4096x4096s1011 for one seed)")
     ap.add_argument("--skip-small", action="store_true", help="leave small_cases.npz and pieces.npz as they are")
     ap.add_argument("--ls-traces", action="store_true", help="(re)generate ls_traces.npz (a minute: runs the large LS cases too)")
@@ -519,6 +538,9 @@ def main():
         np.savez_compressed(os.path.join(HERE, "codebook_fit.npz"), **codebook_fit())
     if args.ls_traces:
         np.savez_compressed(os.path.join(HERE, "ls_traces.npz"), **ls_traces())
+    if args.wide:
+        with open(os.path.join(HERE, "wide_cases.json"), "w") as f:
+            json.dump(dict(environment=env, cases=large_cases(None, WIDE, timed=False)), f, indent=1)
     if args.large:
         path = os.path.join(HERE, "large_cases.json")
         recs = large_cases(args.only)

@@ -40,6 +40,10 @@ def test_abi_version_and_sizes():
     # 4096 x 4096: two float64 n x n scratch matrices dominate
     assert _lib.lib.slk_workspace_bytes(4096, 4096) >= 2 * 4096 * 4096 * 8
     assert _lib.lib.slk_workspace_bytes(512, 11008) >= 2 * 11008 * 11008 * 8
+    # the factorisation alone (R = 0): X and S, and the chain's 2 x (ld / 64) hand-off flags -- up to 405B-class widths
+    for n in (1, 4096, 23232, 28672, 53248):
+        ld = _lib.lib.slk_factor_ld(n)
+        assert _lib.lib.slk_workspace_bytes(0, n) >= 2 * ld * ld * 8 + 2 * (ld // 64) * 4, n
 
 
 def test_options_are_read_once_and_set_through_the_abi():
