@@ -78,7 +78,8 @@ typedef void *slk_stream_t;
  * read SLK_INFO_HANDOFF_TIMEOUT; the factorisation's workspace holds its flags (slk_factor_workspace_bytes_batch grew by
  * 8 * (ld / 64) bytes per matrix); new options "tall_error", "rows_below_wide".  Still 8, with entries added alongside: the
  * group-scale forms slk_gptq_quantize_grouped, slk_column_miss_grouped, slk_scale_search_grouped and slk_dequantize_grouped
- * (one scale per row and per group of columns; nothing existing changed).   */
+ * (one scale per row and per group of columns; nothing existing changed), then slk_gptq_quantize_grouped_batch (the grouped
+ * loop over a batch of layers stacked by rows; slk_gptq_quantize_grouped is its batch of one).   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -278,6 +279,11 @@ size_t slk_workspace_bytes_batch(int batch, int rows_per_layer, int n);
  *     idx (may be NULL, levels <= 256): the codebook indices of Q / s; E_out (may be NULL): errors in processing order.
  *     flags: SLK_LOOP_LATENCY only (accepted; the grouped loop runs 16 rows per window workgroup either way).
  *     Workspace: slk_workspace_bytes(R, n).
+ * slk_gptq_quantize_grouped_batch: the same loop over `batch` layers of one shape stacked by rows, as slk_gptq_quantize_batch:
+ *     W, Q, idx, E_out are (batch * rows_per_layer) x n, gscale (batch * rows_per_layer) x G, order batch x n, U
+ *     batch x n x n.  Results are those of `batch` separate slk_gptq_quantize_grouped calls, bit for bit.  batch in 1..64;
+ *     batch > 1 needs rows_per_layer % 64 == 0 and the orders.  Workspace: slk_workspace_bytes_batch(batch, rows_per_layer, n)
+ *     (it covers the loop's 2 R n floats and 2 batch n ints with room to spare, R = batch * rows_per_layer).
  * slk_column_miss_grouped: slk_column_miss with the group quantizer (the err / sqerr keys of the grouped loop).
  * slk_scale_search_grouped: slk_scale_search on every group at once: row r G + k of the (R G, group_size) view of W is
  *     group k of row r, with base[r G + k] and, hdiag given (length n), the slice hdiag[k group_size : (k + 1) group_size];
@@ -287,6 +293,10 @@ int slk_gptq_quantize_grouped(const float *W, const float *gscale, int group_siz
                               int R, int n, int levels, double lo, double hi, const float *table, int min_block,
                               int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace,
                               size_t ws_bytes, slk_stream_t stream);
+int slk_gptq_quantize_grouped_batch(const float *W, const float *gscale, int group_size, const long long *order, const double *U,
+                                    int batch, int rows_per_layer, int n, int levels, double lo, double hi, const float *table,
+                                    int min_block, int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out,
+                                    void *workspace, size_t ws_bytes, slk_stream_t stream);
 int slk_column_miss_grouped(const float *W, const float *gscale, int group_size, int R, int n, int levels, double lo,
                             double hi, const float *table, int squared, float *miss, slk_stream_t stream);
 int slk_scale_search_grouped(const float *W, const float *base, const float *factors, int n_factors, const float *hdiag,

@@ -68,10 +68,11 @@ def ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
-def workspace(R, n, batch=1):
-    """(tensor, bytes): grow-only scratch per (device, stream) sized by slk_workspace_bytes(_batch)."""
+def workspace(R, n, batch=1, grouped=False):
+    """(tensor, bytes): grow-only scratch per (device, stream) sized by slk_workspace_bytes(_batch); `grouped`: for the
+    grouped batch loop, whose workspace is slk_workspace_bytes_batch at every batch size."""
     dev = require_gpu()
-    if batch > 1:
+    if batch > 1 or grouped:
         need = int(_lib.lib.slk_workspace_bytes_batch(int(batch), int(R), int(n)))
     else:
         need = int(_lib.lib.slk_workspace_bytes(int(R), int(n)))

@@ -75,6 +75,10 @@ PROTOTYPES = {
         c_int,
         [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],
     ),
+    "slk_gptq_quantize_grouped_batch": (
+        c_int,
+        [P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],
+    ),
     "slk_column_miss_grouped": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P, P]),
     "slk_scale_search_grouped": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),
     "slk_dequantize_grouped": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),

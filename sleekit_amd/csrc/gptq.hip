@@ -137,11 +137,15 @@ __global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict
     }
 }
 
-// ------------------------------------------------------------------ group scales (slk_gptq_quantize_grouped)
+// ------------------------------------------------------------------ group scales (slk_gptq_quantize_grouped_batch)
 // S (R x G, G = n / gsize) holds one scale per row and per group of gsize ORIGINAL columns; the loop runs on the
-// unscaled weights and only its leaves scale (see leaf_registers_grouped).  pg[c] = group of processing column c.
-__global__ __launch_bounds__(256) void k_group_of_column(const long long *__restrict__ order, int n, int gsize, int *__restrict__ pg) {
-    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) pg[c] = (int)((order ? order[c] : c) / gsize);
+// unscaled weights and only its leaves scale (see leaf_registers_grouped).  pg[b n + c] = group of processing column c
+// of layer b (a batch of layers stacked by rows, `batch` rows of order; no order: batch 1, the identity).
+__global__ __launch_bounds__(256) void k_group_of_column(const long long *__restrict__ order, int batch, int n, int gsize,
+                                                         int *__restrict__ pg) {
+    const size_t total = (size_t)batch * n;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x)
+        pg[e] = (int)((order ? order[e] : (long long)e) / gsize);
 }
 
 // Q[r][j] = Qp[r][inv[j]] (already de-scaled by the leaves);  idx[r][j] = codebook index of Q[r][j] / S[r][j / gsize].
@@ -149,12 +153,13 @@ __global__ __launch_bounds__(256) void k_group_of_column(const long long *__rest
 // (uniform) or than the nearest bin limit (table), and the index comes back exactly (dequantize_grouped checks it).
 __global__ __launch_bounds__(256) void k_permute_out_grouped(const float *__restrict__ Qp, const int *__restrict__ inv_order,
                                                              int R, int n, Grid g, const float *__restrict__ S, int gsize,
-                                                             float *__restrict__ Q, uint8_t *__restrict__ idx) {
+                                                             float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl) {
     const int G = n / gsize;
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
         const float *src = Qp + (size_t)r * n;
+        const int *inv_o = inv_order + (size_t)(r / rpl) * n;
         for (int j = threadIdx.x; j < n; j += blockDim.x) {
-            const float v = src[inv_order[j]];
+            const float v = src[inv_o[j]];
             Q[(size_t)r * n + j] = v;
             if (idx) idx[(size_t)r * n + j] = (uint8_t)cb_index(v / S[(size_t)r * G + j / gsize], g);
         }
@@ -376,6 +381,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
     const int ht = t - 256;  // helper thread index
     const int r0 = blockIdx.x * RB;
     U += (size_t)(r0 / rpl) * n * n;  // a batch of layers stacked by rows: rows [b rpl, (b + 1) rpl) use factor b
+    if constexpr (GROUPED) pg += (size_t)(r0 / rpl) * n;  // ... and group table b (a tile never straddles two layers)
     if (IN_LDS && g.table) {  // the leaves search the codebook once per column: keep it next to them
         for (int i = t; i < 2 * g.n - 1; i += 512) sm.cbt[i] = g.table[i];
         g.table = sm.cbt;  // visible after the first barrier below
@@ -995,7 +1001,8 @@ extern "C" int slk_gptq_quantize(const float *W, const float *scale, const long 
 // `batch` layers of one shape stacked by rows: every launch of the loop covers all of them, each row tile
 // reading its own layer's factor.  What a row shard of a multi-GPU run needs: R / G rows alone leave most of
 // the chip idle (the window kernel runs one workgroup per 16 rows), G layers' shards together fill it.
-// gscale != nullptr: the grouped loop (slk_gptq_quantize_grouped), batch 1, no row scale.
+// gscale != nullptr: the grouped loop (slk_gptq_quantize_grouped_batch), no row scale.  Arena: Qp and Eg (R n floats
+// each), the inverse orders (batch n ints) and, grouped, the group tables (batch n ints): four 256-byte-aligned takes.
 static int gptq_loop(const float *W, const float *scale, const long long *order, const double *U, int batch, int rows_per_layer,
                      int n, int levels, double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
                      float *Q, uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream,
@@ -1017,7 +1024,7 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     float *Qp = ws.take<float>((size_t)R * n);
     float *Eg = ws.take<float>((size_t)R * n);
     int *inv_order = ws.take<int>((size_t)batch * n);
-    int *pg = grouped ? ws.take<int>((size_t)n) : nullptr;
+    int *pg = grouped ? ws.take<int>((size_t)batch * n) : nullptr;  // group of every processing column, per layer
     if (!Qp || !Eg || !inv_order || (grouped && !pg)) {
         set_error("workspace too small for a %d x %d layer", R, n);
         return SLK_E_WS;
@@ -1067,7 +1074,8 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
 
     const int G = grouped ? n / group_size : 0;
     if (grouped)
-        SLK_RUN("group_of_column", 0, 12.0 * n, s, k_group_of_column<<<(n + 255) / 256, 256, 0, s>>>(order, n, group_size, pg));
+        SLK_RUN("group_of_column", 0, 12.0 * batch * n, s,
+                k_group_of_column<<<(batch * n + 255) / 256, 256, 0, s>>>(order, batch, n, group_size, pg));
 
     Plan p;
     plan(0, n, min_block, num_blocks, p);
@@ -1125,11 +1133,11 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
                 else if (grouped && in_lds)
                     SLK_RUN("gptq_window_grouped", fl * R, wbytes, s,
                             k_gptq_window<true, true><<<row_tiles, 512, sizeof(WindowSmem) + sizeof(GroupTile), s>>>(
-                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, R, gscale, pg, G));
+                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G));
                 else if (grouped)
                     SLK_RUN("gptq_window_wide_grouped", fl * R, wbytes, s,
                             k_gptq_window<false, true><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
-                                                                             dbg, tab, R, gscale, pg, G));
+                                                                             dbg, tab, rpl, gscale, pg, G));
                 else if (in_lds)
                     SLK_RUN("gptq_window", fl * R, wbytes, s,
                             k_gptq_window<true, false><<<row_tiles, 512, sizeof(WindowSmem), s>>>(Qp, Eg, U, R, n, st.a, st.b, g,
@@ -1151,7 +1159,7 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     }
     if (grouped)
         SLK_RUN("permute_out_grouped", 0, (idx ? 13.0 : 8.0) * R * n, s,
-                k_permute_out_grouped<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx));
+                k_permute_out_grouped<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx, rpl));
     else if (perm_lds)
         SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out_lds<<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl));
     else
@@ -1170,16 +1178,26 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
                      workspace, ws_bytes, stream, nullptr, 0);
 }
 
-// One layer with one scale per row and per group of `group_size` original columns (gscale: R x n / group_size, positive).
+// `batch` layers with one scale per row and per group of `group_size` original columns (gscale: (batch rows_per_layer) x
+// n / group_size, positive), stacked by rows like slk_gptq_quantize_batch.
+extern "C" int slk_gptq_quantize_grouped_batch(const float *W, const float *gscale, int group_size, const long long *order,
+                                               const double *U, int batch, int rows_per_layer, int n, int levels, double lo,
+                                               double hi, const float *table, int min_block, int num_blocks, int flags, float *Q,
+                                               uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    SLK_REQUIRE(W && gscale && U && Q, "null pointer");
+    SLK_REQUIRE((flags & ~SLK_LOOP_LATENCY) == 0, "the grouped loop takes SLK_LOOP_LATENCY only");
+    SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
+                group_size);
+    return gptq_loop(W, nullptr, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
+                     workspace, ws_bytes, stream, gscale, group_size);
+}
+
+// One layer with group scales: the batch of one.
 extern "C" int slk_gptq_quantize_grouped(const float *W, const float *gscale, int group_size, const long long *order, const double *U,
                                          int R, int n, int levels, double lo, double hi, const float *table, int min_block,
                                          int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace,
                                          size_t ws_bytes, slk_stream_t stream) {
-    SLK_REQUIRE(W && gscale && U && Q, "null pointer");
-    SLK_REQUIRE((flags & ~SLK_LOOP_LATENCY) == 0, "the grouped loop takes SLK_LOOP_LATENCY only");
-    SLK_REQUIRE(R > 0 && n > 0, "empty layer");
-    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
-                group_size);
-    return gptq_loop(W, nullptr, order, U, 1, R, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out, workspace,
-                     ws_bytes, stream, gscale, group_size);
+    return slk_gptq_quantize_grouped_batch(W, gscale, group_size, order, U, 1, R, n, levels, lo, hi, table, min_block, num_blocks,
+                                           flags, Q, idx, E_out, workspace, ws_bytes, stream);
 }

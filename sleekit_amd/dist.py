@@ -16,6 +16,7 @@ The module is engine-agnostic: `backend` supplies factorize / run_rows, which le
 test-suite drive the same scheduling code over gloo with a stand-in backend.
 """
 
+import operator
 import os
 
 import torch
@@ -67,12 +68,50 @@ def factor_root(position, size):
     return position % size
 
 
+def _layer_kind(layer):
+    """What a layer's scales make of its loop: "unscaled", "row" (one scale per row, `scale`) or ("group", g) (one per row
+    and per group of g columns, `gscale` / `group_size`).  Every bucketing decision -- rounds, short rounds, groups of
+    rounds, loop batches -- keys on (shape, kind): layers of different kinds never share a loop."""
+    if layer.get("gscale") is not None:
+        return ("group", int(layer["group_size"]))
+    return "row" if layer.get("scale") is not None else "unscaled"
+
+
+def check_layers(layers, moves=0):
+    """The group-scale keys of a stream, checked before anything runs -- on every rank alike, since every rank holds every
+    layer's inputs -- so that a refusal leaves no rank waiting in a collective.  `gscale` (R, n / group_size) float32 and
+    `group_size` (an int that divides n) come together and exclude `scale`.  Grouped layers have no local search
+    (NotImplementedError when moves > 0)."""
+    grouped = False
+    for l, lay in enumerate(layers):
+        S, g = lay.get("gscale"), lay.get("group_size")
+        if S is None and g is None:
+            continue
+        R, n = lay["W"].shape
+        if S is None or g is None:
+            raise ValueError(f"layer {l}: group scales need both `gscale` and `group_size`")
+        if lay.get("scale") is not None:
+            raise ValueError(f"layer {l}: `gscale` and `scale` are exclusive (one scale per row, or per row and group)")
+        try:
+            g = operator.index(g) if not isinstance(g, bool) else 0
+        except TypeError:
+            g = 0
+        if g < 1 or n % g != 0:
+            raise ValueError(f"layer {l}: group_size must be an int >= 1 that divides the {n} columns (got {lay['group_size']!r})")
+        if tuple(S.shape) != (R, n // g) or S.dtype != torch.float32:
+            raise ValueError(f"layer {l}: gscale must be float32 ({R}, {n // g}) for a ({R}, {n}) layer with group_size {g}; "
+                             f"got {S.dtype} {tuple(S.shape)}")
+        grouped = True
+    if grouped and moves > 0:
+        raise NotImplementedError("quantize_stream: local search (nb_ls_moves > 0) is not available with group scales")
+
+
 def plan_rounds(layers, size, bucket=True):
     """Rounds of at most `size` layers, each of ONE shape, and every layer's factor root.
 
     A model's layers come in an order that mixes shapes (an OPT / BLOOM block is {d x d ..., 4d x d, d x 4d};
     reference: experiments/compare.py:37-53 walks one directory per layer), but they are independent
-    (compare.py:50-131), so the stream is bucketed by (rows, columns, scaled?) and each bucket cut into rounds: the
+    (compare.py:50-131), so the stream is bucketed by (rows, columns, _layer_kind) and each bucket cut into rounds: the
     row shards of a round's layers then go through the kernels as one batch (HipBackend.run_round).  Roots follow
     the position in this processing order, so a bucket's partial last round does not leave the same ranks idle
     every time.  Returns (rounds, root): rounds = lists of layer indices, root[l] = the rank that factors layer l.
@@ -83,7 +122,7 @@ def plan_rounds(layers, size, bucket=True):
     else:
         by_shape = {}
         for l, lay in enumerate(layers):
-            key = (tuple(lay["W"].shape), tuple(lay["H"].shape), lay.get("scale") is not None)
+            key = (tuple(lay["W"].shape), tuple(lay["H"].shape), _layer_kind(lay))
             by_shape.setdefault(key, []).append(l)
         groups = list(by_shape.values())  # in order of first appearance
     rounds, root, position = [], [None] * n_layers, 0
@@ -176,8 +215,13 @@ class HipBackend:
             miss = eng.order_keys(H, n, self.damp, self.act_order)
         elif mode >= 2:  # err / sqerr need the statistics of ALL rows, before sharding
             cb = eng.require_uniform(self.quantizer)
-            Ws = eng.rows_divide(W, layer["scale"]) if layer.get("scale") is not None else W
-            miss = eng.column_miss(Ws, cb, mode == 3)
+            if layer.get("gscale") is not None:  # (with the group quantizer, in original units)
+                from . import groups
+
+                miss = groups.column_miss_grouped(W, layer["gscale"], layer["group_size"], cb, mode == 3)
+            else:
+                Ws = eng.rows_divide(W, layer["scale"]) if layer.get("scale") is not None else W
+                miss = eng.column_miss(Ws, cb, mode == 3)
         factor = eng.factorize(H, n, self.damp, mode, miss)
         if self.with_error:  # the layer error wants to know whether H is symmetric: decided here, once per layer
             factor = factor + (self._symmetry(layer),)
@@ -271,10 +315,17 @@ class HipBackend:
                         row_err=torch.empty(0, dtype=torch.float32, device=device) if self.with_error else None, rows=(lo, hi))
         W = layer["W"][lo:hi].contiguous()
         sc = layer["scale"][lo:hi].contiguous() if layer.get("scale") is not None else None
-        # (lookahead = "alone on the GPU": with overlapping streams the loop takes the window kernel's least-chip-time form)
-        res = eng.quantize_layer(W, layer["H"], self.quantizer, sc, self.act_order, self.damp, self.moves, factor=factor[:3],
-                                 lookahead=not self.overlap,
-                                 want_ls_error=self.with_error and self.moves > 0 and layer.get("symmetric") is True)
+        if layer.get("gscale") is not None:  # the grouped loop on the shard, from the factor it was handed (no search)
+            from . import groups
+
+            res = groups.quantize_layer_grouped(W, layer["gscale"][lo:hi].contiguous(), self.quantizer, layer["H"], layer["group_size"],
+                                                self.act_order, self.damp, want_idx=eng.require_uniform(self.quantizer)[0] <= 256,
+                                                factor=factor[:3])
+        else:
+            # (lookahead = "alone on the GPU": with overlapping streams the loop takes the window kernel's least-chip-time form)
+            res = eng.quantize_layer(W, layer["H"], self.quantizer, sc, self.act_order, self.damp, self.moves, factor=factor[:3],
+                                     lookahead=not self.overlap,
+                                     want_ls_error=self.with_error and self.moves > 0 and layer.get("symmetric") is True)
         err = None
         if res.ls_error is not None:  # carried through the search (scaled domain: times scale^2)
             err = res.ls_error if sc is None else (res.ls_error * sc) * sc
@@ -292,9 +343,9 @@ class HipBackend:
         if len(round_layers) < self.min_batch or len(round_layers) > 64 or hi == lo:
             return False
         first = round_layers[0]
-        scaled = first.get("scale") is not None
+        kind = _layer_kind(first)
         return all(lay["W"].shape == first["W"].shape and lay["H"].shape == first["H"].shape
-                   and (lay.get("scale") is not None) == scaled for lay in round_layers)
+                   and _layer_kind(lay) == kind for lay in round_layers)
 
     def run_round(self, round_layers, lo, hi, payloads):
         """Shards of the round's layers from their packed factors: unpack into one stacked factor, ONE loop and
@@ -375,6 +426,7 @@ class HipBackend:
         rows = hi - lo
         Rp = (rows + 127) // 128 * 128  # the batch entry points want whole 128-row tiles per layer (96 rows at 768 / 8)
         scaled = round_layers[0].get("scale") is not None
+        grouped = round_layers[0].get("gscale") is not None
         # ragged shard: every layer's rows padded to whole tiles (zero weights, unit scale); rows never interact, so the
         # padding rows are wasted work and nothing else -- they are cut off below.  One launch for the stack either way
         # (engine.stack_rows: a copy per layer was 120 small launches per step for one rank of 8 on OPT-125M).
@@ -382,7 +434,15 @@ class HipBackend:
         sc = eng.stack_rows([lay["scale"][lo:hi] for lay in round_layers], Rp, 1.0) if scaled else None
         cb = eng.require_uniform(self.quantizer)
         want_idx = cb[0] <= 256  # (the kernels emit uint8 indices)
-        if self.moves > 0:
+        if grouped:
+            # group scales: padding rows get unit scales; the loop runs on the unscaled weights and Q comes back de-scaled, so
+            # the layer error is the unscaled layers' (quantize_stream refuses a local search here)
+            from . import groups
+
+            S = eng.stack_rows([lay["gscale"][lo:hi] for lay in round_layers], Rp, 1.0)
+            Q, idx = groups.run_loop_batch_grouped(W, S, order, U, cb, round_layers[0]["group_size"], 32, 8, want_idx=want_idx)
+            err = eng.row_errors_batch(W, Q, [lay["H"] for lay in round_layers], known) if self.with_error else None
+        elif self.moves > 0:
             # local search works in the scaled domain (engine.quantize_layer): scaled copy in, ONE search over the stack
             # (engine.local_search_batch: a search per layer is ten small launches, and the shards of a round on several
             # ranks are a few hundred rows each), de-scale on the way out.  (Padding rows of a ragged shard search too:
@@ -411,13 +471,13 @@ class HipBackend:
 
 
 def _guard_inputs(layers, stream):
-    """The caller's tensors of `layers` (W, H, scale, mean) are read on the side stream `stream`: tell the caching allocator,
+    """The caller's tensors of `layers` (W, H, scale, gscale, mean) are read on the side stream `stream`: tell the caching allocator,
     so that a caller who drops them right after a join=False call does not hand memory the side streams still read back for
     reuse (the allocator then holds the block until `stream` has passed this point)."""
     if stream is None:
         return
     for lay in layers:
-        for key in ("W", "H", "scale", "mean"):
+        for key in ("W", "H", "scale", "gscale", "mean"):
             t = lay.get(key)
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 t.record_stream(stream)
@@ -560,7 +620,7 @@ def _short_rounds(layers, short, backend):
     """Rounds of same-shaped `short` layers whose stacked rows come to about a full layer's worth (4096)."""
     by_shape = {}
     for l in short:
-        by_shape.setdefault((tuple(layers[l]["W"].shape), layers[l].get("scale") is not None), []).append(l)
+        by_shape.setdefault((tuple(layers[l]["W"].shape), _layer_kind(layers[l])), []).append(l)
     rounds = []
     for (shape, _), members in by_shape.items():
         per = max(2, min(backend.local_batch, int(getattr(backend, "short_rows", 4096)) // max(shape[0], 1)))
@@ -581,7 +641,12 @@ def quantize_stream(layers, backend, comm_device=None, join=True):
     join=True ends in ONE blocking device -> host read of the status words (a host synchronisation per call).  join=False
     blocks nowhere: `_device.raise_pending()` is then REQUIRED, after synchronising, to see the statuses (the list it reads is
     bounded: _device.PENDING_LIMIT); the inputs may be dropped at once (_guard_inputs).
+
+    Group scales: a layer dict may carry `gscale` (R, n / group_size) float32 and `group_size` instead of `scale`; its shards
+    are then those of sleekit_amd.groups (Q de-scaled, idx the codebook indices of Q / s).  check_layers refuses bad keys
+    (ValueError) and grouped layers under a local search (NotImplementedError) before anything runs.
     """
+    check_layers(layers, getattr(backend, "moves", 0))
     out = _quantize_stream(layers, backend, comm_device, join, True)
     note = getattr(backend, "note_statuses", None)
     if note is not None:
@@ -597,8 +662,8 @@ def _group_rounds(rounds, layers, backend, rank, size):
     groups, key_now, count, limit = [], None, 0, 0
     for g, members in enumerate(rounds):
         first = layers[members[0]]
-        same = len({(tuple(layers[l]["W"].shape), layers[l].get("scale") is not None) for l in members}) == 1
-        key = (tuple(first["W"].shape), first.get("scale") is not None) if same else None
+        same = len({(tuple(layers[l]["W"].shape), _layer_kind(layers[l])) for l in members}) == 1
+        key = (tuple(first["W"].shape), _layer_kind(first)) if same else None
         if limit_of is not None and key is not None and key == key_now and count + len(members) <= limit:
             groups[-1].append(g)
             count += len(members)
@@ -614,7 +679,7 @@ def _group_rounds(rounds, layers, backend, rank, size):
 
 
 def _quantize_stream(layers, backend, comm_device=None, join=True, _local=True):
-    """Quantize `layers` (list of dicts with W (R, n), H (n, n), optional scale (R,)) across the ranks.
+    """Quantize `layers` (list of dicts with W (R, n), H (n, n), optional scale (R,) or gscale / group_size) across the ranks.
 
     Returns, per layer, this rank's shard: dict(Q, idx, row_err, rows=(lo, hi), info).
     Every rank holds every layer's inputs (W, H are inputs of the path and resident before

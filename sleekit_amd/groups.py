@@ -117,11 +117,47 @@ def column_miss_grouped(W, S, group_size, cb_abi, squared):
     return out
 
 
+def grouped_keys(W, S, group_size, cb_abi, act_order, H, damp):
+    """The sort keys (`miss`) of act_order for a grouped layer: the err / sqerr statistics of the group quantizer over all
+    rows, the kernel-made keys of inv_diag / combined_diag / pivot, None for the rest."""
+    mode = engine.order_mode_code(act_order)
+    if mode == _lib.ORDER_KEYS:
+        return engine.order_keys(H, H.shape[0], damp, act_order)
+    if mode >= _lib.ORDER_ERR:
+        return column_miss_grouped(W, S, group_size, cb_abi, mode == _lib.ORDER_SQERR)
+    return None
+
+
+def run_loop_batch_grouped(W, S, order, U, cb_abi, group_size, min_block, num_blocks, want_idx=True):
+    """The grouped loop over a batch of layers stacked by rows (slk_gptq_quantize_grouped_batch).
+
+    W (B, R, n) float32, S (B, R, n / group_size) float32, order (B, n) int64, U (B, n, n) float64, all contiguous.
+    Returns (Q, idx) shaped (B, R, n), Q de-scaled: what B single-layer grouped loops return, in launches that cover all B.
+    """
+    B, R, n = W.shape
+    g, G = _groups(n, group_size)
+    assert S.shape == (B, R, G) and order.shape == (B, n) and U.shape == (B, n, n)
+    assert W.is_contiguous() and S.is_contiguous() and order.is_contiguous() and U.is_contiguous()
+    levels, lo, hi, table = cb_abi
+    ws, ws_bytes = dev.workspace(R, n, batch=B, grouped=True)
+    Q = torch.empty((B, R, n), dtype=torch.float32, device=W.device)
+    idx = torch.empty((B, R, n), dtype=torch.uint8, device=W.device) if want_idx else None
+    _lib.check(
+        _lib.lib.slk_gptq_quantize_grouped_batch(
+            dev.ptr(W), dev.ptr(S), g, dev.ptr(order), dev.ptr(U), B, R, n, levels, lo, hi, dev.ptr(table), int(min_block),
+            int(num_blocks), 0, dev.ptr(Q), dev.ptr(idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
+        )
+    )
+    return Q, idx
+
+
 def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
-                           want_idx=True):
+                           want_idx=True, factor=None, lookahead=True):
     """The grouped layer on device tensors: W (R, n), S (R, n / group_size), H (n, n), all float32.  Returns an
     engine.LayerResult (Q de-scaled, idx uint8 or None, order, U, info); raises LinAlgError if H + damping is not
-    positive definite."""
+    positive definite.  `factor` = (order, U, info) re-uses a factor made elsewhere (sleekit_amd.dist: a row shard), as
+    engine.quantize_layer does; its status is then the caller's to check.  lookahead: this layer is alone on the GPU
+    (engine.factorize)."""
     assert W.ndim == 2 and H.ndim == 2 and H.shape[0] == H.shape[1] == W.shape[1]
     assert min_block_size >= 1
     cb_abi = engine.require_uniform(quantizer)
@@ -131,15 +167,12 @@ def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", dam
         raise ValueError(f"group scales must be ({R}, {G}) for a ({R}, {n}) layer with group_size {g}; got {tuple(S.shape)}")
     if want_idx and cb_abi[0] > 256:
         raise ValueError("uint8 indices need a codebook of at most 256 entries")
-    mode = engine.order_mode_code(act_order)
-    if mode == _lib.ORDER_KEYS:
-        miss = engine.order_keys(H, n, damp, act_order)
-    elif mode >= _lib.ORDER_ERR:
-        miss = column_miss_grouped(W, S, g, cb_abi, mode == _lib.ORDER_SQERR)
-    else:
-        miss = None
     res = engine.LayerResult()
-    res.order, res.U, res.info = engine.factorize(H, n, damp, mode, miss, lookahead=True)
+    check_factor = factor is None
+    if factor is None:
+        miss = grouped_keys(W, S, g, cb_abi, act_order, H, damp)
+        factor = engine.factorize(H, n, damp, engine.order_mode_code(act_order), miss, lookahead=lookahead)
+    res.order, res.U, res.info = factor[:3]
     levels, lo, hi, table = cb_abi
     ws, ws_bytes = dev.workspace(R, n)
     res.Q = torch.empty((R, n), dtype=torch.float32, device=W.device)
@@ -151,7 +184,8 @@ def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", dam
         )
     )
     # read back behind the loop, as engine.quantize_layer does
-    dev.note_info(res.info, "compute_hessian_chol")
+    if check_factor:
+        dev.note_info(res.info, "compute_hessian_chol")
     return res
 
 
