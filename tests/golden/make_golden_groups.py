@@ -4,6 +4,7 @@
 Run only where the reference is available (same pattern as make_golden.py; SLEEKIT_REF overrides its location):
 
     python tests/golden/make_golden_groups.py [--no-large]
+    python tests/golden/make_golden_groups.py --edges      # tests/golden/groups_edges.npz only
 
 Inputs come from the build's own generator (sleekit_amd.synth, keyed by the seeds stored here); only outputs are
 written.  For every small case:
@@ -18,6 +19,12 @@ Stored: S (float32) and the SHA-256 of Q for every case; for the cases of at mos
 codebook indices of Q / S, from which Q = value(idx) / (1 / S) is rebuilt bit for bit (checked here before writing).
 Q itself is not stored: as float32 it is most of the bytes and compresses poorly.  The large case (4096 x 4096,
 g = 128, 8 levels, diag order, mse group scales) is stored as the SHA-256 of S and of Q.
+
+--edges writes tests/golden/groups_edges.npz in the same format from EDGE_CASES: the shapes where kernels break (ragged
+row tiles, odd group sizes, widths that are not a multiple of 4, leaves of 1 to 48 and of 550 columns), every act_order,
+codebooks of 2 to 256 levels and nf4, and layers with one whole group of zero weights (their scales sit at the floor).
+Those cases have no exactly tied order keys (checked here), so the reference's unstable argsort and the device's
+stable-tie order agree on them.
 
 No reference source text is copied.
 """
@@ -139,13 +146,79 @@ CASES = [
     (96, 192, 32, "4", "diag", "max", 0.01, 32, 8, 5130),
 ]
 
+# (R, n, g, codebook, act_order, scale mode, damp, min_block_size, num_blocks, seed, zero group or None)
+EDGE_CASES = [
+    (1, 96, 1, "3", "none", "max", 0.01, 32, 8, 5201, None),
+    (5, 96, 3, "16", "diag", "mse", 0.01, 48, 4, 5202, None),
+    (17, 192, 24, "2", "err", "diag", 0.01, 32, 8, 5203, None),
+    (33, 172, 4, "256", "sqerr", "diag3", 0.03, 1, 2, 5204, None),
+    (17, 172, 43, "nf4", "pivot", "mse", 0.01, 32, 8, 5205, None),
+    (1, 100, 25, "8", "inv_diag", "max", 0.01, 48, 4, 5206, None),
+    (109, 105, 7, "3", "combined_diag", "diag", 0.1, 32, 8, 5207, None),
+    (33, 258, 43, "16", "sqerr", "mse", 0.01, 48, 4, 5208, None),
+    (70, 1100, 100, "8", "diag", "mse", 0.01, 32, 8, 5209, None),
+    (5, 1100, 55, "nf4", "err", "diag2", 0.01, 640, 2, 5210, None),     # two 550-column leaves (global-memory window)
+    (17, 1376, 43, "4", "inv_diag", "mse", 0.01, 32, 8, 5211, None),
+    (70, 172, 43, "8", "sqerr", "max", 0.01, 32, 8, 5212, 2),           # a zero group: its scale is the floor, 1e-16
+    (33, 96, 3, "3", "diag", "mse", 0.01, 1, 2, 5213, 5),               # a zero group: 5e-18 after the search
+    (5, 105, 7, "2", "pivot", "diag", 0.01, 48, 4, 5214, None),
+    (70, 1100, 55, "256", "combined_diag", "max", 0.01, 640, 2, 5215, None),
+    (17, 100, 25, "16", "none", "diag5", 0.03, 1, 2, 5216, None),
+    (109, 192, 24, "nf4", "err", "mse", 0.01, 48, 4, 5217, None),
+]
+
+
+def edge_layer(R, n, g, seed, zero):
+    L = synth.make_layer(R, n, seed)
+    if zero is not None:
+        L["W"][:, zero * g:(zero + 1) * g] = 0
+    return L
+
+
+def assert_no_tied_keys(W, S, H, g, cbn, act_order, damp):
+    """The order with NumPy's tie-breaking equals the stable-tie order: no two order keys are exactly equal."""
+    from groups_model import GroupGrid, oracle_grid
+    from oracle import obq_ref
+
+    Hd = H + damp * H.diagonal().mean() * np.eye(H.shape[0])
+    Z = GroupGrid(oracle_grid(cbn), S, g, None)
+    a = obq_ref.column_order(W, Hd, Z, act_order, "numpy")
+    b = obq_ref.column_order(W, Hd, Z, act_order, "stable")
+    assert np.array_equal(a, b), "tied order keys: the reference's order is not the device's"
+
+
+def edges():
+    sys.path.insert(0, os.path.dirname(HERE))  # tests/, for groups_model
+    out = {}
+    meta = []
+    for i, (R, n, g, cbn, order, mode, damp, mb, nb, seed, zero) in enumerate(EDGE_CASES):
+        t0 = time.time()
+        L = edge_layer(R, n, g, seed, zero)
+        cb = make_codebook(cbn)
+        S = group_scales(L["W"], cb, L["H"], g, mode)
+        assert_no_tied_keys(L["W"], S, L["H"], g, cbn, order, damp)
+        Q = quantize_grouped_ref(L["W"], S, cb, L["H"], g, order, damp, mb, nb)
+        out[f"S_{i}"] = S
+        idx = indices(cb, Q, S, g)
+        if R * n <= SMALL_IDX:
+            out[f"idx_{i}"] = idx
+        meta.append(dict(R=R, n=n, g=g, codebook=cbn, act_order=order, mode=mode, damp=damp, min_block_size=mb, num_blocks=nb,
+                         seed=seed, zero_group=zero, sha256_Q=sha(Q)))
+        print(f"edge {i}: {R}x{n} g={g} cb={cbn} {order} {mode}: {time.time() - t0:.1f} s", flush=True)
+    out["meta"] = np.array(json.dumps(dict(cases=meta, numpy=np.__version__)))
+    np.savez_compressed(os.path.join(HERE, "groups_edges.npz"), **out)
+
+
 LARGE = dict(R=4096, n=4096, g=128, codebook="8", act_order="diag", mode="mse", damp=0.01, seed=5199)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-large", action="store_true")
+    ap.add_argument("--edges", action="store_true", help="write groups_edges.npz only")
     args = ap.parse_args()
+    if args.edges:
+        return edges()
     out = {}
     meta = []
     for i, (R, n, g, cbn, order, mode, damp, mb, nb, seed) in enumerate(CASES):

@@ -44,6 +44,12 @@ def test_abi_version_and_sizes():
     for n in (1, 4096, 23232, 28672, 53248):
         ld = _lib.lib.slk_factor_ld(n)
         assert _lib.lib.slk_workspace_bytes(0, n) >= 2 * ld * ld * 8 + 2 * (ld // 64) * 4, n
+    # the single grouped call's arena, without the 64 KB slack: permuted Q and E (2 R n floats), the inverse order and the
+    # group table (2 n ints), four 256-byte alignments
+    for R in (1, 16, 4096, 65536):
+        for n in (1, 7, 96, 1100, 4096, 16512, 23232, 53248):
+            need = 2 * R * n * 4 + 2 * n * 4 + 4 * 256
+            assert _lib.lib.slk_workspace_bytes(R, n) - (1 << 16) >= need, (R, n)
 
 
 def test_options_are_read_once_and_set_through_the_abi():

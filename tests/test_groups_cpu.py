@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from groups_model import model_grouped, oracle_grid, rebuild
 
 GROUPED = ("slk_gptq_quantize_grouped", "slk_column_miss_grouped", "slk_scale_search_grouped", "slk_dequantize_grouped")
 
@@ -81,55 +82,6 @@ def test_grouped_calls_have_no_cpu_path():
             call()
 
 
-class GroupGrid:
-    """The group quantizer over an oracle grid: whole matrices by column, leaf columns in processing order."""
-
-    def __init__(self, grid, S, g, order):
-        self.grid, self.S, self.g, self.order, self.i = grid, S, g, order, 0
-
-    def __call__(self, x):
-        if x.ndim == 2:
-            s = np.repeat(self.S, self.g, axis=1)
-        else:
-            s = self.S[:, self.order[self.i] // self.g]
-            self.i += 1
-        return (self.grid.value(x / s) / (np.float32(1) / s)).astype(np.float32)
-
-
-def model_grouped(W, S, grd, H, g, act_order, damp, mb, nb):
-    """quantize_grouped as NumPy, from oracle.obq_ref's pieces."""
-    from oracle import obq_ref
-
-    n = W.shape[1]
-    H_damped = H + damp * H.diagonal().mean() * np.eye(n)
-    order = obq_ref.column_order(W, H_damped, GroupGrid(grd, S, g, None), act_order)
-    Q = W[:, order].copy()
-    U = obq_ref.inverse_factor_upper(H_damped[order][:, order])
-    E = np.zeros_like(Q)
-    Z = GroupGrid(grd, S, g, order)
-    obq_ref.run_schedule(Q, E, U, Z, obq_ref.block_schedule(n, mb, nb))
-    assert Z.i == n
-    return Q[:, np.argsort(order)]
-
-
-def oracle_grid(name):
-    from oracle import grid
-
-    return grid.TableGrid.nf4() if name == "nf4" else grid.UniformGrid(int(name), -1, 1)
-
-
-def rebuild(idx, S, name, g):
-    """Q = value(idx) / (1 / s): the codebook value formed like quantize_value (t * step + zero in float32, or the table)."""
-    from oracle import grid
-
-    if name == "nf4":
-        vals = np.asarray(grid.TableGrid.nf4().values, np.float32)[idx]
-    else:
-        levels = int(name)
-        vals = idx.astype(np.float32) * np.float32(2 / (levels - 1)) + np.float32(-1)
-    return (vals / (np.float32(1) / np.repeat(S, g, axis=1))).astype(np.float32)
-
-
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
@@ -153,3 +105,56 @@ def test_numpy_model_reproduces_the_reference_fixtures():
             back = rebuild(data[f"idx_{i}"], S, c["codebook"], c["g"])
             assert np.array_equal(back.view(np.uint32), Q.view(np.uint32)), f"case {i}: indices"
     assert kept >= 8
+
+
+def load_edges():
+    data = np.load(os.path.join(GOLDEN, "groups_edges.npz"))
+    return data, json.loads(str(data["meta"]))
+
+
+def edge_layer(c):
+    """The layer of an edge case: the synthetic generator's, with one group of weights zeroed where the case says so."""
+    from sleekit_amd import synth
+
+    L = synth.make_layer(c["R"], c["n"], c["seed"])
+    if c["zero_group"] is not None:
+        k, g = c["zero_group"], c["g"]
+        L["W"][:, k * g:(k + 1) * g] = 0
+    return L
+
+
+def test_numpy_model_reproduces_the_edge_fixtures():
+    """groups_edges.npz (ragged rows, odd and tiny groups, widths off a multiple of 4, leaves of 1 to 550 columns, every
+    order, 2 to 256 levels and nf4, zero groups): the model's Q to the reference's SHA-256, its indices to the reference's
+    where kept, and the per-group pick_scale to the reference's S bit for bit."""
+    from groups_model import group_scales_model, indices
+
+    data, meta = load_edges()
+    cases = meta["cases"]
+    assert len(cases) >= 16
+    assert {c["act_order"] for c in cases} >= {"none", "diag", "err", "sqerr", "pivot", "inv_diag", "combined_diag"}
+    assert {c["codebook"] for c in cases} >= {"2", "3", "16", "256", "nf4"}
+    assert sum(c["zero_group"] is not None for c in cases) >= 2
+    kept = 0
+    for i, c in enumerate(cases):
+        L = edge_layer(c)
+        grd = oracle_grid(c["codebook"])
+        S = data[f"S_{i}"]
+        assert S.shape == (c["R"], c["n"] // c["g"]) and S.dtype == np.float32 and (S > 0).all()
+        if c["zero_group"] is not None:  # the floor of the scale search: 1e-16, times the smallest factor after a search
+            floor = np.float32(1e-16) if c["mode"] == "max" else np.float32(1e-16) * np.float32(0.05)
+            assert (S[:, c["zero_group"]] == floor).all(), f"case {i}"
+        want_S = group_scales_model(L["W"], grd, L["H"], c["g"], c["mode"])
+        assert np.array_equal(want_S.view(np.uint32), S.view(np.uint32)), f"case {i}: scales"
+        Q = model_grouped(L["W"], S, grd, L["H"], c["g"], c["act_order"], c["damp"], c["min_block_size"], c["num_blocks"])
+        assert sha(Q) == c["sha256_Q"], f"case {i}: {c}"
+        # no exact key ties: the stable-tie order (the device's) gives the same Q
+        Qs = model_grouped(L["W"], S, grd, L["H"], c["g"], c["act_order"], c["damp"], c["min_block_size"], c["num_blocks"],
+                           ties="stable")
+        assert sha(Qs) == c["sha256_Q"], f"case {i}: stable ties"
+        if f"idx_{i}" in data.files:
+            kept += 1
+            assert np.array_equal(indices(Q, S, grd, c["g"]), data[f"idx_{i}"]), f"case {i}: indices"
+            back = rebuild(data[f"idx_{i}"], S, c["codebook"], c["g"])
+            assert np.array_equal(back.view(np.uint32), Q.view(np.uint32)), f"case {i}: rebuild"
+    assert kept >= 10
