@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mweights/s quantized (GPTQ 3-bit, 4096 x 4096 layers) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--no-configs] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full [--no-configs]]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...; started WITHOUT a launcher
      -- no WORLD_SIZE in the environment -- `bench.py --gpus N` starts that command itself as a child process, before it touches
      the GPU, relays rank 0's line and exits with the child's code)
@@ -21,16 +21,23 @@ with W, H and the row scales resident in HBM before the clock starts.  N > 1 sha
 rows of every layer across the ranks (sleekit_amd/dist.py); the factors are made by the ranks in turn and cross
 xGMI once, in one RCCL all-gather per round of N same-shaped layers.  Total work is the same at every N ("strong").
 
-The ONE JSON line carries the headline run and, unless --no-configs / --config is given, every other BASELINE config
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+ONE JSON line with the headline and the layer errors of the last timed step.  Everything else it can measure or check runs
+only with --full: the roofline, the golden-hash checks, the RCCL exchange check, the single-layer latency, the asymmetric-H,
+local-search and Hessian-accumulation legs, the CPU baseline and the other BASELINE configs.  All of it comes after the
+timed steps, so --full does not change the headline's measurement; --no-profile / --no-cpu-baseline / --no-extras /
+--no-configs / --configs / --stages trim or extend a --full run.
+
+With --full the line carries the headline run and, unless --no-configs / --config is given, every other BASELINE config
 as a short leg of its own under "configs" (compact: value, ms_per_step, layer_errors {min, max, max_rel_diff_vs_cpu},
 roofline {dominant kernel, its frac timed and alone, loop_frac {alone, timed, timed_chip_time}, top four kernels as [name, chip
 share, frac]}, cpu_baseline) (cfg2: 20 steps, cfg3, cfg4: 8; cfg5: 2 steps of all 32 layers), each with its own roofline and CPU
-baseline, so that one driver run backs every number of DESIGN.md's table.  The line ENDS with "summary": every config's
+baseline, so that one --full run backs every number of DESIGN.md's table.  The line ENDS with "summary": every config's
 [Mweights/s, ms per step], the loop's roofline fractions, the single-layer latency, the Hessian accumulation's fraction and the
 golden-hash checks in under 600 characters -- what a 2 kB tail of the output still holds.  Before a leg's clock starts its pipeline
 runs until the caching allocator has stopped growing (`allocator_settle_steps`, untimed, BEFORE the W warm-up steps): a hipMalloc
 inside the timed steps costs tens of ms; a timed region that still saw one is repeated (`timed_region_repeats`).
-Fields besides the contract's:
+Fields besides the contract's (all but layer_errors and dump_outputs come with --full only):
   roofline      for the kernel with the largest share of the chip's time IN THE TIMED CONFIGURATION (HIP events
                  around every launch, on the launch stream: slk_profile_* in the C ABI; a launch of fewer than 256
                  workgroups counts for that share of its duration); achieved = ALGORITHMIC flops or bytes of its
@@ -114,13 +121,16 @@ def parse():
     ap.add_argument("--levels", type=int, default=8, help="codebook size (8 = 3 bit)")
     ap.add_argument("--moves", type=int, default=0, help="local-search moves")
     ap.add_argument("--distinct", type=int, default=0, help="distinct synthetic layers cycled through the batch (0 = every layer its own)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-layer latency, asymmetric-H and Hessian-accumulation legs")
-    ap.add_argument("--no-configs", action="store_true", help="skip the legs of the other BASELINE configs (cfg2 ... cfg5)")
-    ap.add_argument("--configs", type=str, default="", help="comma-separated subset of the config legs (default: all four)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything besides the headline (roofline, golden hashes, "
+                         "extra legs, CPU baseline, the other BASELINE configs); a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="(--full) skip the roofline's profiled steps")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the single-layer latency, asymmetric-H and Hessian-accumulation legs")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip the legs of the other BASELINE configs (cfg2 ... cfg5)")
+    ap.add_argument("--configs", type=str, default="", help="(--full) comma-separated subset of the config legs (default: all four)")
     ap.add_argument("--streams", type=str, default="", help="factor,loop stream counts of the headline leg (default 3,1; 3,3 for small-layer models)")
-    ap.add_argument("--stages", action="store_true", help="also print per-kernel timing table to stderr")
+    ap.add_argument("--stages", action="store_true", help="(--full) also print per-kernel timing table to stderr")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last timed step to DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--launcher-selftest", action="store_true",
@@ -128,6 +138,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.stages and not args.full:
+        ap.error("--stages prints the profiled pass of --full: give --full as well")
     return args
 
 
@@ -756,7 +768,8 @@ def main():
         shapes = [(args.rows, args.cols)] * args.layers
         levels, moves, strip = args.levels, args.moves, False
     widest = max(n for _, n in shapes)
-    run_configs = not args.config and not args.no_configs
+    full = args.full
+    run_configs = full and not args.config and not args.no_configs
     env.start()
     rank, world, device = env.rank, env.world, env.device
 
@@ -788,16 +801,18 @@ def main():
     dumped = None
     if args.dump_outputs:
         dumped = dump_outputs(args.dump_outputs, shapes, shards, errs, rank, world)
-    golden = head.golden(shards)
+
+    # ---- --full only from here to the line: everything the headline figure does not need
+    golden = head.golden(shards) if full else None
 
     roofline, exchange = None, None
-    if not args.no_profile:
+    if full and not args.no_profile:
         roofline, exchange, _ = head.profile(args.steps, full=True)
         dev.raise_pending()
 
     # ---- N > 1: what the collective did, and that every rank received its roots' bytes
     rccl = None
-    if world > 1:
+    if full and world > 1:
         check = sdist.verify_exchange(head.layers if not strip else [head.strip_mean(lay) for lay in head.layers], head.backend)
         env.fence()
         rccl = {"world_size": check["world_size"], "backend": check["backend"], "payload_bytes": check["payload_bytes"],
@@ -809,7 +824,7 @@ def main():
                              "stream, in the pass repeated with events (it overlaps the loops of the round before)")
         assert check["agree"], "a rank's copy of a packed factor differs from its root's"
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = full and rank == 0 and world == 1 and not args.no_extras
     # ---- one isolated layer, start to finish ("report the single-layer number separately")
     latency = None
     if extras:
@@ -921,7 +936,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores, one layer of the same workload (best of 3), or one per shape
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sample = distinct_shape_sample(shapes) if args.config else [(0, 1)]
         cpu, checks = head.cpu_baseline(shards, sample, 1 if args.config else 3)
         layer_errors["against_cpu"] = checks
@@ -940,7 +955,7 @@ def main():
         "metric": metric, "value": round(value, 2), "unit": "Mweights/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic",
+        "data": "synthetic", "full": full,
         "config": {
             "workload": workload, "layers_per_step": L, "distinct_inputs": len(head.made),
             "shapes": sorted({f"{R}x{n}" for R, n in shapes}), "row_sharding": f"{world} ranks",
@@ -976,7 +991,7 @@ def main():
         s["hessian_frac"] = hess["frac"] if hess else None
         s["ls_us"] = [(search.get(f"moves_{m}") or {}).get("us") for m in (10, 100)] if search else None
         gold = list(golden or []) + [g for leg in (line.get("configs") or {}).values() if isinstance(leg, dict) for g in (leg.get("golden") or [])]
-        s["golden_ok"] = [sum(1 for g in gold if g["idx_sha_ok"] or g.get("all_recorded_near_ties")), len(gold)]
+        s["golden_ok"] = [sum(1 for g in gold if g["idx_sha_ok"] or g.get("all_recorded_near_ties")), len(gold)] if full else None
         s["mallocs_timed"] = [head_mallocs] + [leg.get("device_mallocs_while_timed") for leg in (line.get("configs") or {}).values() if isinstance(leg, dict)]
         if "error" in (line.get("configs") or {}):
             s["error"] = line["configs"]["error"][:80]

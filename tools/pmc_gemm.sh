@@ -1,19 +1,22 @@
 #!/bin/bash
 # PMC pass (GPU box): is a GEMM kernel MFMA-pipe-bound or clock-bound?  GRBM_GUI_ACTIVE / 8 / duration = clock.
+#   usage: bash tools/pmc_gemm.sh <output dir>
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out/pmc
+OUT=${1:?usage: bash tools/pmc_gemm.sh <output dir>}
+mkdir -p "$OUT"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
-  --output-format csv -d gpurun_out/pmc/gemm -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile --streams 1,1 > gpurun_out/pmc/gemm_stdout.log 2>&1
-python3 - <<'PY'
-import csv, glob, collections
+  --output-format csv -d "$OUT/gemm" -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-profile --streams 1,1 > "$OUT/gemm_stdout.log" 2>&1
+python3 - "$OUT" <<'PY'
+import csv, glob, collections, sys
+out = sys.argv[1]
 cnt = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
-for path in glob.glob("gpurun_out/pmc/gemm/*/*counter_collection.csv"):
+for path in glob.glob(f"{out}/gemm/*/*counter_collection.csv"):
     for row in csv.DictReader(open(path)):
         k = row["Kernel_Name"].split("(")[0][-28:]
         cnt[k][row["Counter_Name"]] += float(row["Counter_Value"])
         if row["Counter_Name"] == "GRBM_GUI_ACTIVE": n[k] += 1
 dur = collections.defaultdict(float)
-for path in glob.glob("gpurun_out/pmc/gemm/*/*kernel_trace.csv"):
+for path in glob.glob(f"{out}/gemm/*/*kernel_trace.csv"):
     for row in csv.DictReader(open(path)):
         dur[row["Kernel_Name"].split("(")[0][-28:]] += float(row["End_Timestamp"]) - float(row["Start_Timestamp"])
 for k, c in sorted(cnt.items(), key=lambda kv: -dur[kv[0]]):

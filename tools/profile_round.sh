@@ -9,9 +9,9 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/profiles_$TAG
 rm -rf $OUT
 mkdir -p $OUT
-# 1. per-kernel time of the command the driver runs: its headline leg (--no-configs: the config legs get a CSV each below,
+# 1. per-kernel time of the driver's command with --full: its headline leg and passes (--no-configs: the config legs get a CSV each below,
 #    so that a kernel's average is over launches of ONE workload)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-configs > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-configs > $OUT/bench_under_rocprof.log 2>&1
 cp $OUT/stats/*/*kernel_stats.csv $OUT/${TAG}_kernel_stats_default_bench.csv
 grep '"metric"' $OUT/bench_under_rocprof.log > $OUT/${TAG}_bench_line_under_rocprof.json
 echo "stats pass done"
@@ -19,7 +19,7 @@ echo "stats pass done"
 for CFG in cfg2 cfg3 cfg4 cfg5; do
   BLK=""; STEPS=3
   if [ $CFG = cfg5 ]; then BLK="--blocks 16"; STEPS=2; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$CFG -- python3 bench.py --gpus 1 --config $CFG $BLK --steps $STEPS --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_${CFG}_under_rocprof.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$CFG -- python3 bench.py --gpus 1 --config $CFG $BLK --steps $STEPS --warmup 1 --full --no-cpu-baseline --no-extras > $OUT/bench_${CFG}_under_rocprof.log 2>&1
   cp $OUT/stats_$CFG/*/*kernel_stats.csv $OUT/${TAG}_kernel_stats_${CFG}.csv
   grep '"metric"' $OUT/bench_${CFG}_under_rocprof.log > $OUT/${TAG}_bench_line_${CFG}_under_rocprof.json
   rm -rf $OUT/stats_$CFG
