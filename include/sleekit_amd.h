@@ -79,7 +79,8 @@ typedef void *slk_stream_t;
  * 8 * (ld / 64) bytes per matrix); new options "tall_error", "rows_below_wide".  Still 8, with entries added alongside: the
  * group-scale forms slk_gptq_quantize_grouped, slk_column_miss_grouped, slk_scale_search_grouped and slk_dequantize_grouped
  * (one scale per row and per group of columns; nothing existing changed), then slk_gptq_quantize_grouped_batch (the grouped
- * loop over a batch of layers stacked by rows; slk_gptq_quantize_grouped is its batch of one).   */
+ * loop over a batch of layers stacked by rows; slk_gptq_quantize_grouped is its batch of one), then slk_local_search_grouped (the
+ * best-first search with the group quantizer's candidates).   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -353,6 +354,14 @@ int slk_local_search(const float *W, float *Q, const float *H, int R, int n, int
 int slk_local_search_batch(const float *W, float *Q, const float *const *H, int batch, int rows_per_layer, int n,
                            int levels, double lo, double hi, const float *table, int moves, uint8_t *idx,
                            const int *symmetric, float *row_err, void *workspace, size_t ws_bytes, slk_stream_t stream);
+/* slk_local_search with the GROUP QUANTIZER of gscale (R x n / group_size float32, positive; group_size >= 1 divides n): the
+ * candidates of element (r, c) are codebook.quantize_up / quantize_down(x / s) / (1 / s) with s = gscale[r][c / group_size],
+ * float32 IEEE divides (sleekit/obq.py:234-346 with that quantizer, on W unscaled, Q de-scaled and H undamped in original column
+ * order).  Gains, moves, `trace`, `row_err`, the refusals and the workspace are slk_local_search's; there are no carried gains.
+ * idx (may be NULL; levels <= 256): the codebook indices of Q / s, from which slk_dequantize_grouped rebuilds Q bit for bit.  */
+int slk_local_search_grouped(const float *W, float *Q, const float *H, const float *gscale, int group_size, int R, int n,
+                             int levels, double lo, double hi, const float *table, int moves, uint8_t *idx, int *trace,
+                             float *row_err, void *workspace, size_t ws_bytes, slk_stream_t stream);
 
 /* Scale selection: the callers' pre-step -------------------------- */
 /* compute_non_saturating_scaling (sleekit/scaling.py:44-55): scale[r] = max(max_r / hi_code,

@@ -87,6 +87,9 @@ PROTOTYPES = {
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),
     "slk_local_search": (c_int, [P, P, P, c_int, c_int, c_int, c_double, c_double, P, c_int, P, P, P, c_int, P, P, c_size_t, P]),
     "slk_local_search_batch": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P, P, P, P, c_size_t, P]),
+    "slk_local_search_grouped": (
+        c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P, P, P, P, c_size_t, P],
+    ),
     "slk_scale_minmax": (c_int, [P, c_int, c_int, c_double, c_double, P, P]),
     "slk_scale_norm": (c_int, [P, c_int, c_int, P, P]),
     "slk_scale_search": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_double, c_double, P, P, P]),

@@ -19,6 +19,10 @@ namespace slk {
 
 __device__ __forceinline__ float cand_up(float q, const Grid g) { return cb_up(q, g); }
 __device__ __forceinline__ float cand_down(float q, const Grid g) { return cb_down(q, g); }
+// The group quantizer's candidates (sleekit_amd/groups.py): codebook(x / s) / (1 / s) with s the scale of x's column, both
+// float32 IEEE divides like the reference's quantizer callable
+__device__ __forceinline__ float gcand_up(float q, const Grid g, float s) { return cb_up(q / s, g) / (1.0f / s); }
+__device__ __forceinline__ float gcand_down(float q, const Grid g, float s) { return cb_down(q / s, g) / (1.0f / s); }
 
 struct Best {
     float v;
@@ -138,6 +142,12 @@ struct Steps {
             if (CAND == 1) du[E] = su, dd[E] = sd;
         }
     }
+    // the same with the group quantizer of scale s (CAND == 1 only: the grouped search keeps its steps as floats)
+    __device__ __forceinline__ void set_scaled(int E, float qv, const Grid g, float s, float &su, float &sd) {
+        su = gcand_up(qv, g, s) - qv;
+        sd = gcand_down(qv, g, s) - qv;
+        if (CAND == 1) du[E] = su, dd[E] = sd;
+    }
     // slot E takes what `one` keeps for its slot 0
     __device__ __forceinline__ void put(int E, const Steps<1, CAND> &one) {
         if (CAND == 2) {
@@ -166,12 +176,18 @@ struct Steps {
 // first move on at which the row had nothing left to gain (or only a "move" onto the value it already has).
 // TABLE: a general codebook (binary searches); false: the uniform grid alone -- as one kernel every one of a move's candidate
 // computations sat between two jumps on g.table.
-template <int EPT, bool TABLE, int CAND>
+// GS: the group quantizer (gscale: R x n / gsz, the row's scale of column j at gscale[row G + j / gsz]).  Its steps are kept as
+// floats (CAND == 1): a step from packed levels or recomputed would take a true division per slot and move; so a slot's scale
+// is read once (the steps' initial values), the moved column's once per move (its new candidates), and once more on output.
+// The per-row search is GS = false (gscale and gsz unused): the grouped arguments come last, so its code is what it was.
+template <int EPT, bool TABLE, int CAND, bool GS>
 __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ W, float *__restrict__ Q,
                                                       PtrTable hs, int rpl, const float *__restrict__ G,
                                                       const float *__restrict__ hdiag, int R, int n, Grid g,
                                                       int moves, uint8_t *__restrict__ idx, int *__restrict__ trace,
-                                                      float *__restrict__ gains, int gains_mode, float *__restrict__ row_err) {
+                                                      float *__restrict__ gains, int gains_mode, float *__restrict__ row_err,
+                                                      const float *__restrict__ gscale, int gsz) {
+    static_assert(!GS || CAND == 1, "the grouped search keeps its steps as floats");
     if (!TABLE) g.table = nullptr;
     // (a stack of layers by rows: rows [b rpl, (b + 1) rpl) search against Hessian b)
     const float *__restrict__ H = hs.p[blockIdx.x / rpl];
@@ -186,6 +202,7 @@ __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const size_t base = (size_t)row * n;
     const float NEG = -__builtin_huge_valf();
+    const float *__restrict__ srow = GS ? gscale + (size_t)row * (n / gsz) : nullptr;  // the row's group scales
 
     heap_sum_plan(plan, n);
 
@@ -199,7 +216,8 @@ __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ 
             wl[256 * e] = W[base + j];
             q[e] = Q[base + j];
             float su, sd;
-            st.set(e, q[e], g, su, sd);
+            if (GS) st.set_scaled(e, q[e], g, srow[j / gsz], su, sd);
+            else st.set(e, q[e], g, su, sd);
             if (gains_mode == 2) {
                 // carried over from an earlier call (the stateful LocalSearchQuantizer, obq.py:234-346): the gains as
                 // the reference holds them between two do_move() calls, incrementally updated, not rebuilt
@@ -268,8 +286,10 @@ __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ 
 #pragma unroll
         for (int k = 0; k < CHUNK; ++k) h[k] = hrow[min(tz + 256 * k, n - 1)];
         const float hd = hdiag[c];
+        const float sc = GS ? srow[c / gsz] : 1.0f;  // the moved column's scale
         asm volatile("" ::: "memory");
-        const float q_new = go_up ? cand_up(q_old, g) : cand_down(q_old, g);
+        const float q_new = GS ? (go_up ? gcand_up(q_old, g, sc) : gcand_down(q_old, g, sc))
+                               : (go_up ? cand_up(q_old, g) : cand_down(q_old, g));
         // A "move" onto the value the weight already has (the up-candidate of the top level is the top level; a
         // rounding residue can leave such a candidate a positive gain): the reference carries it out, and every
         // term of its gain update (obq.py:322-334) is then a product with a zero difference -- Q and the gains stay as
@@ -284,11 +304,13 @@ __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ 
         //      off the moved column
         const float two_dq = 2.0f * (q_old - q_new);
         // the moved column's candidates before and after the move (obq.py:322-334)
-        const float d1u = cand_up(q_old, g) - q_old, d1d = cand_down(q_old, g) - q_old;
+        const float d1u = (GS ? gcand_up(q_old, g, sc) : cand_up(q_old, g)) - q_old;
+        const float d1d = (GS ? gcand_down(q_old, g, sc) : cand_down(q_old, g)) - q_old;
         Steps<1, CAND> moved;
         moved.clear();
         float d2u, d2d;
-        moved.set(0, q_new, g, d2u, d2d);
+        if (GS) moved.set_scaled(0, q_new, g, sc, d2u, d2d);
+        else moved.set(0, q_new, g, d2u, d2d);
         const float sq_u = d1u * d1u - d2u * d2u, sq_d = d1d * d1d - d2d * d2d;
         const float df_u = d1u - d2u, df_d = d1d - d2d;
 
@@ -352,7 +374,7 @@ __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ 
         const int j = t + 256 * e;
         if (j < n) {
             Q[base + j] = q[e];
-            if (idx) idx[base + j] = (uint8_t)cb_index(q[e], g);
+            if (idx) idx[base + j] = (uint8_t)cb_index(GS ? q[e] / srow[j / gsz] : q[e], g);  // (groups.py: indices of Q / S)
             if (gains_mode) {
                 gains[2 * base + j] = gu[e];
                 gains[2 * base + n + j] = gd[e];
@@ -381,12 +403,15 @@ __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ 
 #ifndef SLK_LS_WAVES_PER_SIMD
 #define SLK_LS_WAVES_PER_SIMD 4  // rows of 3072 / 4096 columns a CU keeps in flight (register cap 128)
 #endif
-template <int M8, int S, int WAVES, bool TABLE, int CAND>
+// GS: the group quantizer, as in k_local_search (steps as floats, CAND == 1; the grouped arguments last)
+template <int M8, int S, int WAVES, bool TABLE, int CAND, bool GS>
 __global__ __launch_bounds__(256, (WAVES == 4 && S == 1 && CAND == 2 ? SLK_LS_WAVES_PER_SIMD : 1)) void k_local_search_wave(const float *__restrict__ W, float *__restrict__ Q,
                                                            PtrTable hs, int rpl, const float *__restrict__ G,
                                                            const float *__restrict__ hdiag, int R, int n, Grid g, int moves,
                                                            uint8_t *__restrict__ idx, int *__restrict__ trace,
-                                                           float *__restrict__ gains, int gains_mode, float *__restrict__ row_err) {
+                                                           float *__restrict__ gains, int gains_mode, float *__restrict__ row_err,
+                                                           const float *__restrict__ gscale, int gsz) {
+    static_assert(!GS || CAND == 1, "the grouped search keeps its steps as floats");
     if (!TABLE) g.table = nullptr;
     constexpr int EPT = M8 * S;
     __shared__ Best red_up[4], red_dn[4];
@@ -403,6 +428,7 @@ __global__ __launch_bounds__(256, (WAVES == 4 && S == 1 && CAND == 2 ? SLK_LS_WA
     const int tr = WAVES == 1 ? lane : threadIdx.x;  // thread within the row
     const size_t base = (size_t)row * n;
     const float NEG = -__builtin_huge_valf();
+    const float *__restrict__ srow = GS ? gscale + (size_t)row * (n / gsz) : nullptr;  // the row's group scales
     // slot e = s2 * M8 + i of this thread: column col0 + 8 WAVES m s2 + 8 i, increasing with e (one register and constant
     // offsets: as an array of EPT columns they cost EPT registers, and the row's loads a register each for their address)
     const int col0 = (tr >> 3) * m + (tr & 7);
@@ -416,7 +442,8 @@ __global__ __launch_bounds__(256, (WAVES == 4 && S == 1 && CAND == 2 ? SLK_LS_WA
         wl[e][threadIdx.x] = W[base + j];
         q[e] = Q[base + j];
         float su, sd;
-        st.set(e, q[e], g, su, sd);
+        if (GS) st.set_scaled(e, q[e], g, srow[j / gsz], su, sd);
+        else st.set(e, q[e], g, su, sd);
         if (gains_mode == 2) {
             gu[e] = gains[2 * base + j];
             gd[e] = gains[2 * base + n + j];
@@ -465,18 +492,22 @@ __global__ __launch_bounds__(256, (WAVES == 4 && S == 1 && CAND == 2 ? SLK_LS_WA
 #pragma unroll
         for (int i = 0; i < M8; ++i) h[i] = hrow[col(i)];
         const float hd = hdiag[c];
+        const float sc = GS ? srow[c / gsz] : 1.0f;  // the moved column's scale
         asm volatile("" ::: "memory");
-        const float q_new = go_up ? cand_up(q_old, g) : cand_down(q_old, g);
+        const float q_new = GS ? (go_up ? gcand_up(q_old, g, sc) : gcand_down(q_old, g, sc))
+                               : (go_up ? cand_up(q_old, g) : cand_down(q_old, g));
         if (q_new == q_old) break;  // a "move" onto the same value: see k_local_search
         if (trace && tr == 0) trace[(size_t)row * moves + mv] = 2 * c + (go_up ? 1 : 0);
         e_run = e_run - (go_up ? bu.v : bd.v);
         const float two_dq = 2.0f * (q_old - q_new);
         // the moved column's candidates before and after the move (obq.py:322-334)
-        const float d1u = cand_up(q_old, g) - q_old, d1d = cand_down(q_old, g) - q_old;
+        const float d1u = (GS ? gcand_up(q_old, g, sc) : cand_up(q_old, g)) - q_old;
+        const float d1d = (GS ? gcand_down(q_old, g, sc) : cand_down(q_old, g)) - q_old;
         Steps<1, CAND> moved;
         moved.clear();
         float d2u, d2d;
-        moved.set(0, q_new, g, d2u, d2d);
+        if (GS) moved.set_scaled(0, q_new, g, sc, d2u, d2d);
+        else moved.set(0, q_new, g, d2u, d2d);
         const float sq_u = d1u * d1u - d2u * d2u, sq_d = d1d * d1d - d2d * d2d;
         const float df_u = d1u - d2u, df_d = d1d - d2d;
 
@@ -552,7 +583,7 @@ __global__ __launch_bounds__(256, (WAVES == 4 && S == 1 && CAND == 2 ? SLK_LS_WA
     for (int e = 0; e < EPT; ++e) {
         const int j = col(e);
         Q[base + j] = q[e];
-        if (idx) idx[base + j] = (uint8_t)cb_index(q[e], g);
+        if (idx) idx[base + j] = (uint8_t)cb_index(GS ? q[e] / srow[j / gsz] : q[e], g);
         if (gains_mode) {
             gains[2 * base + j] = gu[e];
             gains[2 * base + n + j] = gd[e];
@@ -571,7 +602,7 @@ using namespace slk;
 static int local_search_impl(const float *W, float *Q, const float *const *Hs, int batch, int rpl, int n, int levels, double lo,
                              double hi, const float *table, int moves, uint8_t *idx, int *trace, float *gains,
                              int gains_mode, const int *sym_known, float *row_err_out, void *workspace, size_t ws_bytes,
-                             slk_stream_t stream) {
+                             slk_stream_t stream, const float *gscale = nullptr, int group_size = 1) {
     const int R = batch * rpl;
     SLK_REQUIRE(row_err_out == nullptr || gains_mode != 2, "the carried error needs the initial product (gains_mode 0 or 1)");
     Arena ws(workspace, ws_bytes);
@@ -600,13 +631,22 @@ static int local_search_impl(const float *W, float *Q, const float *const *Hs, i
     const bool small_grid = !g.table && levels <= 256;
 #define SLK_LS_T(E, T, C)                                                                                           \
     do {                                                                                                            \
-        SLK_LDS_OPT_IN((k_local_search<E, T, C>), lds);                                                             \
+        SLK_LDS_OPT_IN((k_local_search<E, T, C, false>), lds);                                                             \
         SLK_RUN("local_search", 10.0 * n * R * moves, 4.0 * n * R * moves + 13.0 * R * n, s,                       \
-                (k_local_search<E, T, C><<<R, 256, lds, s>>>(W, Q, hs, rpl, G, hdiag, R, n, g, moves, idx, trace, gains, gains_mode, row_err_out))); \
+                (k_local_search<E, T, C, false><<<R, 256, lds, s>>>(W, Q, hs, rpl, G, hdiag, R, n, g, moves, idx, trace, gains, gains_mode, row_err_out, nullptr, 1))); \
+    } while (0)
+#define SLK_LSG_T(E, T)                                                                                             \
+    do {                                                                                                            \
+        SLK_LDS_OPT_IN((k_local_search<E, T, 1, true>), lds);                                                        \
+        SLK_RUN("local_search_grouped", 10.0 * n * R * moves, 4.0 * n * R * moves + 17.0 * R * n, s,               \
+                (k_local_search<E, T, 1, true><<<R, 256, lds, s>>>(W, Q, hs, rpl, G, hdiag, R, n, g, moves, idx, trace, nullptr, 0, row_err_out, gscale, group_size))); \
     } while (0)
 #define SLK_LS(E)                                                                                                   \
     do {                                                                                                            \
-        if constexpr (E <= 8) { /* short rows: the steps as floats */                                               \
+        if (gscale) { /* the group quantizer: steps as floats at every length */                                    \
+            if (g.table) SLK_LSG_T(E, true);                                                                        \
+            else SLK_LSG_T(E, false);                                                                               \
+        } else if constexpr (E <= 8) { /* short rows: the steps as floats */                                        \
             if (g.table) SLK_LS_T(E, true, 1);                                                                      \
             else SLK_LS_T(E, false, 1);                                                                             \
         } else {                                                                                                    \
@@ -632,12 +672,19 @@ static int local_search_impl(const float *W, float *Q, const float *const *Hs, i
         const int m8 = m / 8;
 #define SLK_LSW_T(M8, S, WAVES, T, C)                                                                                   \
     SLK_RUN("local_search", 10.0 * n * R * moves, 4.0 * n * R * moves + 13.0 * R * n, s,                               \
-            (k_local_search_wave<M8, S, WAVES, T, C><<<WAVES == 1 ? (R + 3) / 4 : R, 256, 0, s>>>(                      \
-                W, Q, hs, rpl, G, hdiag, R, n, g, moves, idx, trace, gains, gains_mode, row_err_out)))
+            (k_local_search_wave<M8, S, WAVES, T, C, false><<<WAVES == 1 ? (R + 3) / 4 : R, 256, 0, s>>>(               \
+                W, Q, hs, rpl, G, hdiag, R, n, g, moves, idx, trace, gains, gains_mode, row_err_out, nullptr, 1)))
+#define SLK_LSWG_T(M8, S, WAVES, T)                                                                                     \
+    SLK_RUN("local_search_grouped", 10.0 * n * R * moves, 4.0 * n * R * moves + 17.0 * R * n, s,                       \
+            (k_local_search_wave<M8, S, WAVES, T, 1, true><<<WAVES == 1 ? (R + 3) / 4 : R, 256, 0, s>>>(                \
+                W, Q, hs, rpl, G, hdiag, R, n, g, moves, idx, trace, nullptr, 0, row_err_out, gscale, group_size)))
 #define SLK_LSW(M8, S, WAVES, LEAVES)                                                                                   \
     if (regular && m8 == M8 && leaves == LEAVES) {                                                                      \
         constexpr bool keep = WAVES == 1 && S == 1;                                                                     \
-        if (g.table) SLK_LSW_T(M8, S, WAVES, true, (keep ? 1 : 0));                                                     \
+        if (gscale) {                                                                                                   \
+            if (g.table) SLK_LSWG_T(M8, S, WAVES, true);                                                                \
+            else SLK_LSWG_T(M8, S, WAVES, false);                                                                       \
+        } else if (g.table) SLK_LSW_T(M8, S, WAVES, true, (keep ? 1 : 0));                                              \
         else SLK_LSW_T(M8, S, WAVES, false, (keep ? 1 : 2));                                                            \
         return SLK_OK;                                                                                                  \
     }
@@ -653,6 +700,7 @@ static int local_search_impl(const float *W, float *Q, const float *const *Hs, i
         SLK_LSW(16, 2, 4, 64)  // n = 8192
         SLK_LSW(12, 2, 4, 64)  // n = 6144
 #undef SLK_LSW
+#undef SLK_LSWG_T
 #undef SLK_LSW_T
     }
     if (ept <= 4) SLK_LS(4);
@@ -662,6 +710,7 @@ static int local_search_impl(const float *W, float *Q, const float *const *Hs, i
     else if (ept <= 48) SLK_LS(48);
     else SLK_LS(64);
 #undef SLK_LS
+#undef SLK_LSG_T
 #undef SLK_LS_T
     return SLK_OK;
 }
@@ -693,3 +742,17 @@ extern "C" int slk_local_search_batch(const float *W, float *Q, const float *con
                              workspace, ws_bytes, stream);
 }
 
+// The search with the group quantizer (gscale: R x n / group_size, positive): every candidate is codebook(x / s) / (1 / s)
+// with its own column's scale s.  No carried gains.
+extern "C" int slk_local_search_grouped(const float *W, float *Q, const float *H, const float *gscale, int group_size, int R, int n,
+                                        int levels, double lo, double hi, const float *table, int moves, uint8_t *idx, int *trace,
+                                        float *row_err, void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    SLK_REQUIRE(W && Q && H && gscale && R > 0 && n > 0 && moves >= 0, "bad arguments");
+    SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
+    SLK_REQUIRE(idx == nullptr || levels <= 256, "uint8 indices need levels <= 256");
+    SLK_REQUIRE(n <= 256 * 64, "local search supports n <= 16384");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
+                group_size);
+    return local_search_impl(W, Q, &H, 1, R, n, levels, lo, hi, table, moves, idx, trace, nullptr, 0, nullptr, row_err, workspace,
+                             ws_bytes, stream, gscale, group_size);
+}

@@ -4,6 +4,8 @@
     Q = quantize_grouped(W, S, cb, H, g, act_order="sqerr")     # de-scaled values, like W
     Q, idx = quantize_grouped(..., return_indices=True)         # idx uint8: (idx, S) is the compact form of the layer
     Q == dequantize_grouped(idx, S, cb, g)                      # bit for bit
+    Q = quantize_grouped(..., nb_ls_moves=100)                  # then the best-first local search, group quantizer's candidates
+    Q = local_search_grouped(W, Q, S, cb, H, g, 100)            # the search alone
 
 Element (r, c) belongs to group c // g.  The GROUP QUANTIZER maps x in column c of row r to
 
@@ -13,6 +15,9 @@ Element (r, c) belongs to group c // g.  The GROUP QUANTIZER maps x in column c 
 own `quantize_opt(W, H, Z, act_order, damp, 0, min_block_size, num_blocks)` (sleekit/obq.py:169-217) returns for a
 callable Z that applies the group quantizer by column: the loop runs on the UNSCALED weights with the reference's rank-1
 and block updates, only the leaves scale, and the err / sqerr keys come from Z(W) - W in original units.
+`local_search_grouped` is the reference's `quantize_local_search(W, Q, H, quantizer, nb_moves)` (sleekit/obq.py:234-358)
+with that quantizer's up / down neighbours as candidates: codebook.quantize_up(x / s) / (np.float32(1) / s) for x in column
+c, s = S[r, c // g], with the reference's gains, decisions and incremental updates.
 `compute_group_scaling` gives column k of S as the reference's `compute_scaling` of the k-th column block of W with
 the k-th diagonal block of H.
 
@@ -151,13 +156,60 @@ def run_loop_batch_grouped(W, S, order, U, cb_abi, group_size, min_block, num_bl
     return Q, idx
 
 
+def run_search_grouped(W, Q, S, H, cb_abi, group_size, moves, idx=None, want_trace=False, row_err=None):
+    """slk_local_search_grouped in place on Q (and idx) (device tensors): W, Q (R, n), S (R, n / group_size), H (n, n).
+    want_trace: returns the (R, moves) int32 record of the moves (engine.local_search); row_err (R,) float32: receives the
+    rows' errors after the moves."""
+    R, n = W.shape
+    levels, lo, hi, table = cb_abi
+    ws, ws_bytes = dev.workspace(R, n)
+    trace = torch.empty((R, int(moves)), dtype=torch.int32, device=W.device) if want_trace else None
+    _lib.check(
+        _lib.lib.slk_local_search_grouped(
+            dev.ptr(W), dev.ptr(Q), dev.ptr(H), dev.ptr(S), int(group_size), R, n, levels, lo, hi, dev.ptr(table), int(moves),
+            dev.ptr(idx), dev.ptr(trace), dev.ptr(row_err), dev.ptr(ws), ws_bytes, dev.stream_handle(),
+        )
+    )
+    return trace
+
+
+def _check_scales(S, R, n, g):
+    g, G = _groups(n, g)
+    if tuple(S.shape) != (R, G):
+        raise ValueError(f"group scales must be ({R}, {G}) for a ({R}, {n}) layer with group_size {g}; got {tuple(S.shape)}")
+    return g
+
+
+def local_search_grouped(W, Q, S, quantizer, H, group_size, nb_moves, return_indices=False):
+    """Best-first local search with the group quantizer's candidates (module docstring): the grouped counterpart of
+    obq.quantize_local_search.  W unscaled, Q de-scaled (what quantize_grouped returns), S (R, n / group_size), H the
+    undamped Hessian in original column order.  Returns Q itself when nb_moves == 0.  return_indices: (Q, idx) with idx the
+    uint8 codebook indices of Q / S (dequantize_grouped(idx, S, quantizer, group_size) == Q bit for bit)."""
+    assert W.ndim == 2 and H.ndim == 2 and Q.shape == W.shape and H.shape[0] == H.shape[1] == W.shape[1]
+    cb_abi = engine.require_uniform(quantizer)
+    if return_indices and cb_abi[0] > 256:
+        raise ValueError("uint8 indices need a codebook of at most 256 entries")
+    R, n = W.shape
+    g = _check_scales(S, R, n, group_size)
+    if nb_moves == 0 and not return_indices:
+        return Q
+    Wd, Sd, Hd = dev.to_device(W), dev.to_device(S), dev.to_device(H)
+    Qd = dev.to_device(Q).clone()
+    idx = torch.empty((R, n), dtype=torch.uint8, device=Wd.device) if return_indices else None
+    run_search_grouped(Wd, Qd, Sd, Hd, cb_abi, g, nb_moves, idx)
+    Qo = Q if nb_moves == 0 else dev.like_input(Qd, W)
+    return (Qo, dev.like_input(idx, W)) if return_indices else Qo
+
+
 def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
-                           want_idx=True, factor=None, lookahead=True):
+                           want_idx=True, factor=None, lookahead=True, nb_ls_moves=0, want_ls_trace=False):
     """The grouped layer on device tensors: W (R, n), S (R, n / group_size), H (n, n), all float32.  Returns an
     engine.LayerResult (Q de-scaled, idx uint8 or None, order, U, info); raises LinAlgError if H + damping is not
     positive definite.  `factor` = (order, U, info) re-uses a factor made elsewhere (sleekit_amd.dist: a row shard), as
     engine.quantize_layer does; its status is then the caller's to check.  lookahead: this layer is alone on the GPU
-    (engine.factorize)."""
+    (engine.factorize).  nb_ls_moves > 0: the local search (local_search_grouped) runs after the loop, on Q and idx in
+    place; res.ls_error holds the rows' errors after the moves (carried through the search) and, with want_ls_trace,
+    res.ls_trace the moves taken."""
     assert W.ndim == 2 and H.ndim == 2 and H.shape[0] == H.shape[1] == W.shape[1]
     assert min_block_size >= 1
     cb_abi = engine.require_uniform(quantizer)
@@ -183,22 +235,27 @@ def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", dam
             int(num_blocks), 2, dev.ptr(res.Q), dev.ptr(res.idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
         )
     )
-    # read back behind the loop, as engine.quantize_layer does
+    if nb_ls_moves > 0:
+        res.ls_error = torch.empty(R, dtype=torch.float32, device=W.device)
+        res.ls_trace = run_search_grouped(W, res.Q, S, H, cb_abi, g, nb_ls_moves, res.idx, want_trace=want_ls_trace,
+                                          row_err=res.ls_error)
+    # read back behind the loop (and the search), as engine.quantize_layer does
     if check_factor:
         dev.note_info(res.info, "compute_hessian_chol")
     return res
 
 
 def quantize_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
-                     return_indices=False):
+                     return_indices=False, nb_ls_moves=0):
     """GPTQ-style quantization of one layer with group scales S (R, n / group_size).
 
     Returns the de-scaled values Q (float32, shaped like W): what sleekit/obq.py:169-217 returns for the group quantizer
-    (module docstring).  return_indices: (Q, idx) with idx the uint8 codebook indices of Q / S.
+    (module docstring), with nb_ls_moves of its local search after the loop.  return_indices: (Q, idx) with idx the uint8
+    codebook indices of Q / S.
     """
     assert W.ndim == 2 and H.ndim == 2
     res = quantize_layer_grouped(dev.to_device(W), dev.to_device(S), quantizer, dev.to_device(H), group_size, act_order, damp,
-                                 min_block_size, num_blocks, want_idx=return_indices)
+                                 min_block_size, num_blocks, want_idx=return_indices, nb_ls_moves=nb_ls_moves)
     Q = dev.like_input(res.Q, W)
     return (Q, dev.like_input(res.idx, W)) if return_indices else Q
 
