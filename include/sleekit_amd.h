@@ -80,7 +80,9 @@ typedef void *slk_stream_t;
  * group-scale forms slk_gptq_quantize_grouped, slk_column_miss_grouped, slk_scale_search_grouped and slk_dequantize_grouped
  * (one scale per row and per group of columns; nothing existing changed), then slk_gptq_quantize_grouped_batch (the grouped
  * loop over a batch of layers stacked by rows; slk_gptq_quantize_grouped is its batch of one), then slk_local_search_grouped (the
- * best-first search with the group quantizer's candidates).   */
+ * best-first search with the group quantizer's candidates), then the asymmetric group quantizer (an offset per row and group
+ * beside the scale): slk_gptq_quantize_grouped_asym, slk_gptq_quantize_grouped_asym_batch, slk_column_miss_grouped_asym,
+ * slk_dequantize_grouped_asym, slk_group_midpoints and slk_group_center.   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -305,6 +307,35 @@ int slk_scale_search_grouped(const float *W, const float *base, const float *fac
                              slk_stream_t stream);
 int slk_dequantize_grouped(const uint8_t *idx, const float *gscale, int group_size, int R, int n, int levels, double lo,
                            double hi, const float *table, float *Q, slk_stream_t stream);
+
+/* Group scales with offsets (asymmetric).  goffset: R x G float32 beside gscale, element (r, c) has s = gscale[r][k] and
+ * o = goffset[r][k], k = c / group_size.  The ASYMMETRIC group quantizer maps x to
+ *     codebook((x - o) / s) / (1 / s) + o     (float32 IEEE, in this order: subtract, divide, codebook, divide, add);
+ * with goffset all zero it is the group quantizer above.
+ * slk_gptq_quantize_grouped_asym(_batch): slk_gptq_quantize_grouped(_batch) with that quantizer in the leaves; the loop runs
+ *     on the unscaled, uncentred W.  idx (may be NULL): codebook indices from which slk_dequantize_grouped_asym rebuilds Q
+ *     bit for bit.  Same flags, shapes and workspace as the symmetric forms; the batch gives the results of separate calls.
+ * slk_column_miss_grouped_asym: slk_column_miss with the asymmetric group quantizer.
+ * slk_dequantize_grouped_asym: Q[r][c] = value(idx[r][c]) / (1 / s) + o.
+ * slk_group_midpoints: goffset[r][k] = 0.5f * (min + max) of group k of row r; Wc (may be NULL): the centred weights
+ *     W - goffset by element (R x n).
+ * slk_group_center: Wc = W - goffset by element, goffset given. */
+int slk_gptq_quantize_grouped_asym(const float *W, const float *gscale, const float *goffset, int group_size, const long long *order,
+                                   const double *U, int R, int n, int levels, double lo, double hi, const float *table,
+                                   int min_block, int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out,
+                                   void *workspace, size_t ws_bytes, slk_stream_t stream);
+int slk_gptq_quantize_grouped_asym_batch(const float *W, const float *gscale, const float *goffset, int group_size,
+                                         const long long *order, const double *U, int batch, int rows_per_layer, int n,
+                                         int levels, double lo, double hi, const float *table, int min_block, int num_blocks,
+                                         int flags, float *Q, uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes,
+                                         slk_stream_t stream);
+int slk_column_miss_grouped_asym(const float *W, const float *gscale, const float *goffset, int group_size, int R, int n,
+                                 int levels, double lo, double hi, const float *table, int squared, float *miss,
+                                 slk_stream_t stream);
+int slk_dequantize_grouped_asym(const uint8_t *idx, const float *gscale, const float *goffset, int group_size, int R, int n,
+                                int levels, double lo, double hi, const float *table, float *Q, slk_stream_t stream);
+int slk_group_midpoints(const float *W, int group_size, int R, int n, float *goffset, float *Wc, slk_stream_t stream);
+int slk_group_center(const float *W, const float *goffset, int group_size, int R, int n, float *Wc, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -82,6 +82,18 @@ PROTOTYPES = {
     "slk_column_miss_grouped": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P, P]),
     "slk_scale_search_grouped": (c_int, [P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),
     "slk_dequantize_grouped": (c_int, [P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),
+    "slk_gptq_quantize_grouped_asym": (
+        c_int,
+        [P, P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],
+    ),
+    "slk_gptq_quantize_grouped_asym_batch": (
+        c_int,
+        [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],
+    ),
+    "slk_column_miss_grouped_asym": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, P, P]),
+    "slk_dequantize_grouped_asym": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, P, P]),
+    "slk_group_midpoints": (c_int, [P, c_int, c_int, c_int, P, P, P]),
+    "slk_group_center": (c_int, [P, P, c_int, c_int, c_int, P, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

@@ -113,10 +113,11 @@ __global__ __launch_bounds__(256) void k_zero_dead(float *__restrict__ W, int R,
 typedef float float4v_t __attribute__((ext_vector_type(4)));
 constexpr int CM_COLS = 32, CM_ROWS = 256;
 // GROUPED: q = codebook(w / s) / rs with the element's group scale s = S[r][j / gsize], rs = RN(1 / s) (slk_column_miss_grouped)
-template <bool GROUPED>
+// OFFSET (with GROUPED): q = codebook((w - o) / s) / rs + o, o = O[r][j / gsize] (slk_column_miss_grouped_asym)
+template <bool GROUPED, bool OFFSET = false>
 __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W, int R, int n, Grid g,
                                                      int squared, float *__restrict__ miss, int vec_ok,
-                                                     const float *__restrict__ S, int gsize) {
+                                                     const float *__restrict__ S, int gsize, const float *__restrict__ O) {
     __shared__ float term[CM_ROWS][CM_COLS + 1];
     const int t = threadIdx.x;
     const int j0 = blockIdx.x * CM_COLS;
@@ -145,7 +146,11 @@ __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W
             for (int e = 0; e < 4; ++e) {
                 const float w = cur[p][e];
                 float qv;
-                if constexpr (GROUPED) {
+                if constexpr (OFFSET) {
+                    const size_t k = (size_t)min(base + p * 32 + lr, R - 1) * (n / gsize) + min(j0 + c4 + e, n - 1) / gsize;
+                    const float sv = S[k], ov = O[k];
+                    qv = cb_value((w - ov) / sv, g) / (1.0f / sv) + ov;
+                } else if constexpr (GROUPED) {
                     // (clamped like the loads: a row beyond R or a column beyond n is never added)
                     const float sv = S[(size_t)min(base + p * 32 + lr, R - 1) * (n / gsize) + min(j0 + c4 + e, n - 1) / gsize];
                     qv = cb_value(w / sv, g) / (1.0f / sv);
@@ -168,14 +173,64 @@ __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W
 }
 // Q[r][c] = value(idx[r][c]) / RN(1 / S[r][c / gsize]): the grouped loop's result rebuilt from its compact form.  The value
 // of index t is formed like the quantizer's (t * step + zero in float32, codebook.py:58-63) or read from the table.
+// OFFSET: Q[r][c] = value / RN(1 / s) + o, o = O[r][c / gsize] (slk_dequantize_grouped_asym).
+template <bool OFFSET = false>
 __global__ __launch_bounds__(256) void k_dequantize_grouped(const uint8_t *__restrict__ idx, const float *__restrict__ S, int gsize,
-                                                            int R, int n, Grid g, float *__restrict__ Q) {
+                                                            int R, int n, Grid g, float *__restrict__ Q, const float *__restrict__ O) {
     const size_t total = (size_t)R * n;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const size_t r = e / n, c = e % n;
         const int k = min((int)idx[e], g.n - 1);
         const float v = g.table ? g.table[k] : grid_val((float)k, g);
-        Q[e] = v / (1.0f / S[r * (n / gsize) + c / gsize]);
+        if constexpr (OFFSET)
+            Q[e] = v / (1.0f / S[r * (n / gsize) + c / gsize]) + O[r * (n / gsize) + c / gsize];
+        else
+            Q[e] = v / (1.0f / S[r * (n / gsize) + c / gsize]);
+    }
+}
+
+// ---------------------------------------------------------------- group offsets
+// MIDPOINTS: O[r][k] = 0.5f * (min + max) of group k of row r (float32, as NumPy forms it), then, Wc given, the centred
+// weights Wc = W - O by element (what the scale search of an asymmetric layer reads).  !MIDPOINTS: O is given, Wc only.
+// One workgroup per row: the row is read from memory once for O and again, from the cache, for Wc.  Groups of at least
+// 64 columns take a wave each (lanes stride the group, then a butterfly), smaller ones a thread each.
+template <bool MIDPOINTS>
+__global__ __launch_bounds__(256) void k_group_offsets(const float *__restrict__ W, int R, int n, int gsize, float *__restrict__ O,
+                                                       float *__restrict__ Wc) {
+    const int G = n / gsize, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    for (int r = blockIdx.x; r < R; r += gridDim.x) {
+        const float *w = W + (size_t)r * n;
+        if constexpr (MIDPOINTS) {
+            if (gsize >= 64) {
+                for (int k = wave; k < G; k += 4) {
+                    float mn = w[(size_t)k * gsize], mx = mn;
+                    for (int c = lane; c < gsize; c += 64) {
+                        const float v = w[(size_t)k * gsize + c];
+                        mn = fminf(mn, v);
+                        mx = fmaxf(mx, v);
+                    }
+                    for (int off = 32; off > 0; off >>= 1) {
+                        mn = fminf(mn, __shfl_xor(mn, off));
+                        mx = fmaxf(mx, __shfl_xor(mx, off));
+                    }
+                    if (lane == 0) O[(size_t)r * G + k] = 0.5f * (mn + mx);
+                }
+            } else {
+                for (int k = t; k < G; k += 256) {
+                    float mn = w[(size_t)k * gsize], mx = mn;
+                    for (int c = 1; c < gsize; ++c) {
+                        const float v = w[(size_t)k * gsize + c];
+                        mn = fminf(mn, v);
+                        mx = fmaxf(mx, v);
+                    }
+                    O[(size_t)r * G + k] = 0.5f * (mn + mx);
+                }
+            }
+            __syncthreads();  // (global writes of this workgroup, read back below)
+        }
+        if (Wc)
+            for (int c = t; c < n; c += 256) Wc[(size_t)r * n + c] = w[c] - O[(size_t)r * G + c / gsize];
+        if constexpr (MIDPOINTS) __syncthreads();
     }
 }
 
@@ -277,7 +332,7 @@ int slk_column_miss(const float *W, int R, int n, int levels, double lo, double 
     hipStream_t s = as_stream(stream);
     SLK_RUN("column_miss", 0, 4.0 * R * n, s,
             k_column_miss<false><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
-                                                                             n % 4 == 0 && (uintptr_t)W % 16 == 0, nullptr, 1));
+                                                                             n % 4 == 0 && (uintptr_t)W % 16 == 0, nullptr, 1, nullptr));
     return SLK_OK;
 }
 
@@ -289,7 +344,7 @@ int slk_column_miss_grouped(const float *W, const float *gscale, int group_size,
     hipStream_t s = as_stream(stream);
     SLK_RUN("column_miss_grouped", 0, 4.0 * R * n, s,
             k_column_miss<true><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
-                                                                            n % 4 == 0 && (uintptr_t)W % 16 == 0, gscale, group_size));
+                                                                            n % 4 == 0 && (uintptr_t)W % 16 == 0, gscale, group_size, nullptr));
     return SLK_OK;
 }
 
@@ -301,7 +356,50 @@ int slk_dequantize_grouped(const uint8_t *idx, const float *gscale, int group_si
     hipStream_t s = as_stream(stream);
     SLK_RUN("dequantize_grouped", 0, 9.0 * R * n, s,
             k_dequantize_grouped<<<stream_blocks((size_t)R * n, 256 * 4), 256, 0, s>>>(idx, gscale, group_size, R, n,
-                                                                                     make_grid(levels, lo, hi, table), Q));
+                                                                                     make_grid(levels, lo, hi, table), Q, nullptr));
+    return SLK_OK;
+}
+
+int slk_column_miss_grouped_asym(const float *W, const float *gscale, const float *goffset, int group_size, int R, int n, int levels,
+                                 double lo, double hi, const float *table, int squared, float *miss, slk_stream_t stream) {
+    SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
+    SLK_REQUIRE(R > 0 && n > 0 && W && gscale && goffset && miss, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    SLK_RUN("column_miss_grouped_asym", 0, 4.0 * R * n, s,
+            k_column_miss<true, true><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
+                                                                                  n % 4 == 0 && (uintptr_t)W % 16 == 0, gscale, group_size,
+                                                                                  goffset));
+    return SLK_OK;
+}
+
+int slk_dequantize_grouped_asym(const uint8_t *idx, const float *gscale, const float *goffset, int group_size, int R, int n, int levels,
+                                double lo, double hi, const float *table, float *Q, slk_stream_t stream) {
+    SLK_REQUIRE(levels >= 2 && levels <= 256 && (table || lo < hi), "codebook needs 2 <= levels <= 256 and lo < hi");
+    SLK_REQUIRE(R > 0 && n > 0 && idx && gscale && goffset && Q, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    SLK_RUN("dequantize_grouped_asym", 0, 13.0 * R * n, s,
+            k_dequantize_grouped<true><<<stream_blocks((size_t)R * n, 256 * 4), 256, 0, s>>>(idx, gscale, group_size, R, n,
+                                                                                           make_grid(levels, lo, hi, table), Q, goffset));
+    return SLK_OK;
+}
+
+int slk_group_midpoints(const float *W, int group_size, int R, int n, float *goffset, float *Wc, slk_stream_t stream) {
+    SLK_REQUIRE(R > 0 && n > 0 && W && goffset, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    SLK_RUN("group_midpoints", 0, (Wc ? 8.0 : 4.0) * R * n, s,
+            k_group_offsets<true><<<R < 4096 ? R : 4096, 256, 0, s>>>(W, R, n, group_size, goffset, Wc));
+    return SLK_OK;
+}
+
+int slk_group_center(const float *W, const float *goffset, int group_size, int R, int n, float *Wc, slk_stream_t stream) {
+    SLK_REQUIRE(R > 0 && n > 0 && W && goffset && Wc, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    SLK_RUN("group_center", 0, 8.0 * R * n, s,
+            k_group_offsets<false><<<R < 4096 ? R : 4096, 256, 0, s>>>(W, R, n, group_size, const_cast<float *>(goffset), Wc));
     return SLK_OK;
 }
 

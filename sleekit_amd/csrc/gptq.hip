@@ -151,9 +151,14 @@ __global__ __launch_bounds__(256) void k_group_of_column(const long long *__rest
 // Q[r][j] = Qp[r][inv[j]] (already de-scaled by the leaves);  idx[r][j] = codebook index of Q[r][j] / S[r][j / gsize].
 // Q = value / rs with rs = RN(1 / s), so Q / s is the codebook value to within a few ulps: far closer than half a step
 // (uniform) or than the nearest bin limit (table), and the index comes back exactly (dequantize_grouped checks it).
+// OFFSET (slk_gptq_quantize_grouped_asym): Q = value / rs + o, o = O[r][j / gsize], and the index is that of (Q - o) / s,
+// checked to rebuild Q bit for bit; where `+ o` has absorbed part of the codebook term (|o| / s large, s at its floor)
+// that index may not, and the codebook is searched for one that does (the leaf's own always does).
+template <bool OFFSET = false>
 __global__ __launch_bounds__(256) void k_permute_out_grouped(const float *__restrict__ Qp, const int *__restrict__ inv_order,
                                                              int R, int n, Grid g, const float *__restrict__ S, int gsize,
-                                                             float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl) {
+                                                             float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl,
+                                                             const float *__restrict__ O) {
     const int G = n / gsize;
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
         const float *src = Qp + (size_t)r * n;
@@ -161,7 +166,26 @@ __global__ __launch_bounds__(256) void k_permute_out_grouped(const float *__rest
         for (int j = threadIdx.x; j < n; j += blockDim.x) {
             const float v = src[inv_o[j]];
             Q[(size_t)r * n + j] = v;
-            if (idx) idx[(size_t)r * n + j] = (uint8_t)cb_index(v / S[(size_t)r * G + j / gsize], g);
+            if constexpr (OFFSET) {
+                if (idx) {
+                    const float sv = S[(size_t)r * G + j / gsize], ov = O[(size_t)r * G + j / gsize];
+                    const float rs = 1.0f / sv;
+                    auto back = [&](int k) {
+                        const float val = g.table ? g.table[k] : grid_val((float)k, g);
+                        return __float_as_uint(val / rs + ov);
+                    };
+                    int k = cb_index((v - ov) / sv, g);
+                    if (back(k) != __float_as_uint(v))
+                        for (int t = 0; t < g.n; ++t)
+                            if (back(t) == __float_as_uint(v)) {
+                                k = t;
+                                break;
+                            }
+                    idx[(size_t)r * n + j] = (uint8_t)k;
+                }
+            } else {
+                if (idx) idx[(size_t)r * n + j] = (uint8_t)cb_index(v / S[(size_t)r * G + j / gsize], g);
+            }
         }
     }
 }
@@ -349,6 +373,76 @@ __device__ __forceinline__ void leaf_registers_grouped(WindowSmem &sm, const Gro
     }
 }
 
+// The asymmetric grouped loop (OFFSET) needs a third value per step, the offset o.  A third per-column plane beside the
+// GroupTile does not fit in LDS, so this tile holds s, rs and o per ROW AND GROUP instead -- all G groups of the tile's
+// rows when G <= GSLOTS -- and a column -> group map of the window (its padding points at slot GSLOTS: s = 1, o = 0).
+// Beyond GSLOTS groups the leaves read S and O from memory (the generic leaf).
+constexpr int GSLOTS = 384;
+struct GroupSlots {
+    float s[RB][GSLOTS + 1];
+    float rs[RB][GSLOTS + 1];
+    float o[RB][GSLOTS + 1];
+    int slot[GPITCH];
+};
+static_assert(sizeof(WindowSmem) + sizeof(GroupSlots) <= 160 * 1024, "the asymmetric window's LDS exceeds a CU's 160 KiB");
+
+// leaf_registers_grouped with the asymmetric group quantizer: q = codebook((x - o) / s) / rs + o.  The map entry and the
+// three values of step i + 1 are read before step i.
+template <int NSTEP>
+__device__ __forceinline__ void leaf_registers_offset(WindowSmem &sm, const GroupSlots &gs, const LeafTables &lt, int wave, int lane,
+                                                      int a_rel, int w, const Grid g, float inv_step) {
+    const int c16 = lane & 15, rg = lane >> 4;
+    const int row = 4 * wave + rg;
+    const bool m0 = c16 < w, m1 = c16 + 16 < w;
+    float x0 = m0 ? sm.q[row][a_rel + c16] : 0.0f, x1 = m1 ? sm.q[row][a_rel + 16 + c16] : 0.0f;
+    float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
+    double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
+    int kn = gs.slot[a_rel];
+    float sn = gs.s[row][kn], rsn = gs.rs[row][kn], on = gs.o[row][kn];
+    static_for<0, NSTEP>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
+        const float sc = sn, rsc = rsn, oc = on;
+        if constexpr (i + 1 < NSTEP) {
+            u0n = lt.u[i + 1][c16];
+            u1n = lt.u[i + 1][c16 + 16];
+            uiin = lt.udr[i + 1][0];
+            riin = lt.udr[i + 1][1];
+            kn = gs.slot[a_rel + i + 1];
+            sn = gs.s[row][kn];
+            rsn = gs.rs[row][kn];
+            on = gs.o[row][kn];
+        }
+        asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
+        constexpr int src = i & 15;
+        const float xi = row_bcast<src>(i < 16 ? x0 : x1);
+        const float q = grid_value_fast((xi - oc) / sc, g, inv_step) / rsc + oc;
+        const double d = (double)(xi - q);
+        const double qq = d * rii;
+        const double rem = __builtin_fma(-uii, qq, d);
+        const double err = __builtin_fma(rem, rii, qq);
+        const float ef = (float)err;
+        const bool here = c16 == src;
+        if (i < 16) {
+            q0 = here ? q : q0;
+            e0 = here ? ef : e0;
+        } else {
+            q1 = here ? q : q1;
+            e1 = here ? ef : e1;
+        }
+        if (i < 15) x0 = (float)((double)x0 - err * u0);
+        if (NSTEP > 16) x1 = (float)((double)x1 - err * u1);
+    });
+    if (m0) {
+        sm.q[row][a_rel + c16] = q0;
+        sm.e[row][a_rel + c16] = e0;
+    }
+    if (m1) {
+        sm.q[row][a_rel + 16 + c16] = q1;
+        sm.e[row][a_rel + 16 + c16] = e1;
+    }
+}
+
 // cycle counters of workgroup 0 (SLK_WIN_DBG bit 3), read back by slk_probe_window_cycles
 __device__ long long g_win_cycles[16];
 __device__ long long g_win_trace[64];  // window2: busy cycles per period, chain wave 0 / helper wave 2 (+32)
@@ -368,14 +462,20 @@ __device__ long long g_win_trace[64];  // window2: busy cycles per period, chain
 // GROUPED: the leaves quantize with the group scales S (R x G) of the unscaled weights, pg[c] =
 // group of processing column c; in LDS the window's scales sit in a GroupTile behind WindowSmem.  Everything else --
 // updates, deferral, staging -- is the same code.
-template <bool IN_LDS, bool GROUPED>
+// OFFSET (with GROUPED): the asymmetric group quantizer, offsets O (R x G) beside S; in LDS a GroupSlots behind WindowSmem
+// when G <= GSLOTS, otherwise every leaf is the generic one and reads S and O from memory.
+template <bool IN_LDS, bool GROUPED, bool OFFSET = false>
 __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, float *__restrict__ Eg,
                                                      const double *__restrict__ U, int R, int n, int w0, int w1,
                                                      Grid g, float inv_step, int fast_ok, int dbg, OpTable tab, int rpl,
-                                                     const float *__restrict__ Sg, const int *__restrict__ pg, int G) {
+                                                     const float *__restrict__ Sg, const int *__restrict__ pg, int G,
+                                                     const float *__restrict__ Og) {
+    static_assert(GROUPED || !OFFSET, "offsets come with group scales");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     WindowSmem &sm = *reinterpret_cast<WindowSmem *>(smem_raw);
     GroupTile &gt = *reinterpret_cast<GroupTile *>(smem_raw + sizeof(WindowSmem));  // (GROUPED && IN_LDS only)
+    GroupSlots &gs = *reinterpret_cast<GroupSlots *>(smem_raw + sizeof(WindowSmem));  // (OFFSET && IN_LDS only)
+    const bool slots = OFFSET && IN_LDS && G <= GSLOTS;  // the leaves' s, rs, o in LDS
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const bool helper = wave >= 4;
     const int ht = t - 256;  // helper thread index
@@ -461,7 +561,20 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
         if (lane == 0) sm.odd[buf][wave - 4] = any ? 1 : 0;
     };
 
-    if constexpr (GROUPED && IN_LDS) {  // the window's scales (1.0 on the padding and on rows beyond R), read after the barrier below
+    if constexpr (OFFSET && IN_LDS) {  // every group of the tile's rows (s = 1, o = 0 beyond G and R), read after the barrier below
+        if (slots) {
+            for (int e = t; e < RB * (GSLOTS + 1); e += 512) {
+                const int r = e / (GSLOTS + 1), k = e % (GSLOTS + 1);
+                const bool in = k < G && r0 + r < R;
+                const float sv = in ? Sg[(size_t)(r0 + r) * G + k] : 1.0f;
+                gs.s[r][k] = sv;
+                gs.rs[r][k] = 1.0f / sv;
+                gs.o[r][k] = in ? Og[(size_t)(r0 + r) * G + k] : 0.0f;
+            }
+            for (int c = t; c < GPITCH; c += 512) gs.slot[c] = c < width ? pg[w0 + c] : GSLOTS;
+        }
+    }
+    if constexpr (GROUPED && !OFFSET && IN_LDS) {  // the window's scales (1.0 on the padding and on rows beyond R), read after the barrier below
         for (int e = t; e < RB * GPITCH; e += 512) {
             const int r = e / GPITCH, c = e % GPITCH;
             const float sv = (c < width && r0 + r < R) ? Sg[(size_t)(r0 + r) * G + pg[w0 + c]] : 1.0f;
@@ -605,7 +718,19 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             double err = 0.0;
             if (live) {
                 x = qld(myrow, i);
-                if constexpr (GROUPED) {
+                if constexpr (OFFSET) {
+                    float sv, rsv, ov;
+                    if (slots) {
+                        const int k = gs.slot[i - w0];
+                        sv = gs.s[myrow][k], rsv = gs.rs[myrow][k], ov = gs.o[myrow][k];
+                    } else if (r0 + myrow < R) {
+                        const size_t k = (size_t)(r0 + myrow) * G + pg[i];
+                        sv = Sg[k], rsv = 1.0f / sv, ov = Og[k];
+                    } else {  // the in-LDS tile's padding rows (x = 0) past R: nothing of S or O to read there
+                        sv = 1.0f, rsv = 1.0f, ov = 0.0f;
+                    }
+                    q = cb_value((x - ov) / sv, g) / rsv + ov;
+                } else if constexpr (GROUPED) {
                     const float sv = IN_LDS ? gt.s[myrow][i - w0] : Sg[(size_t)(r0 + myrow) * G + pg[i]];
                     const float rsv = IN_LDS ? gt.rs[myrow][i - w0] : 1.0f / sv;
                     q = cb_value(x / sv, g) / rsv;
@@ -658,6 +783,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             staged = IN_LDS && w <= ULEAF;
             use_fast = staged && fast_ok;
             if (use_fast) use_fast = (sm.odd[sbuf][0] | sm.odd[sbuf][1] | sm.odd[sbuf][2] | sm.odd[sbuf][3]) == 0;
+            if constexpr (OFFSET) use_fast = use_fast && slots;
             lap(1, 0);
             if (use_fast) {
                 // this leaf's share of the pending blocks, in whole turns of the four helpers
@@ -711,7 +837,10 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             if (use_fast) {
                 if (!helper && !no_leaf_regs) {
                     const int w = op.b - op.a;
-                    if constexpr (GROUPED) {
+                    if constexpr (OFFSET) {
+                        if (w <= 16) leaf_registers_offset<16>(sm, gs, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        else leaf_registers_offset<32>(sm, gs, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                    } else if constexpr (GROUPED) {
                         if (w <= 16) leaf_registers_grouped<16>(sm, gt, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
                         else leaf_registers_grouped<32>(sm, gt, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
                     } else {
@@ -1006,8 +1135,8 @@ extern "C" int slk_gptq_quantize(const float *W, const float *scale, const long 
 static int gptq_loop(const float *W, const float *scale, const long long *order, const double *U, int batch, int rows_per_layer,
                      int n, int levels, double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
                      float *Q, uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream,
-                     const float *gscale, int group_size) {
-    const bool grouped = gscale != nullptr;
+                     const float *gscale, int group_size, const float *goffset) {
+    const bool grouped = gscale != nullptr, asym = goffset != nullptr;
     const int unscale = flags & SLK_LOOP_UNSCALE;
     SLK_REQUIRE(!unscale || scale, "unscale needs the row scales");
     SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
@@ -1044,7 +1173,8 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
 #endif
     const bool no_defer = opt(OPT_NO_DEFER) != 0;
     SLK_LDS_OPT_IN((k_gptq_window<true, false>), sizeof(WindowSmem));
-    if (grouped) SLK_LDS_OPT_IN((k_gptq_window<true, true>), sizeof(WindowSmem) + sizeof(GroupTile));
+    if (grouped && !asym) SLK_LDS_OPT_IN((k_gptq_window<true, true>), sizeof(WindowSmem) + sizeof(GroupTile));
+    if (asym) SLK_LDS_OPT_IN((k_gptq_window<true, true, true>), sizeof(WindowSmem) + sizeof(GroupSlots));
     SLK_LDS_OPT_IN(k_gptq_window2<1>, sizeof(Window2SmemT<1>));
     SLK_LDS_OPT_IN(k_gptq_window2<2>, sizeof(Window2SmemT<2>));
     // 32 rows per workgroup (eight rows per chain wave, ONE quantizer instruction stream for them: leaf_chain8) halve the CUs
@@ -1130,22 +1260,30 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
                                   k_gptq_window2<1><<<row_tiles, 512, sizeof(Window2SmemT<1>), s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step,
                                                                                                  fast_ok, dbg & 24, pt, rpl));
                 }
+                else if (asym && in_lds)
+                    SLK_RUN("gptq_window_grouped_asym", fl * R, wbytes, s,
+                            k_gptq_window<true, true, true><<<row_tiles, 512, sizeof(WindowSmem) + sizeof(GroupSlots), s>>>(
+                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G, goffset));
+                else if (asym)
+                    SLK_RUN("gptq_window_wide_grouped_asym", fl * R, wbytes, s,
+                            k_gptq_window<false, true, true><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
+                                                                                   dbg, tab, rpl, gscale, pg, G, goffset));
                 else if (grouped && in_lds)
                     SLK_RUN("gptq_window_grouped", fl * R, wbytes, s,
                             k_gptq_window<true, true><<<row_tiles, 512, sizeof(WindowSmem) + sizeof(GroupTile), s>>>(
-                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G));
+                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G, nullptr));
                 else if (grouped)
                     SLK_RUN("gptq_window_wide_grouped", fl * R, wbytes, s,
                             k_gptq_window<false, true><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
-                                                                             dbg, tab, rpl, gscale, pg, G));
+                                                                             dbg, tab, rpl, gscale, pg, G, nullptr));
                 else if (in_lds)
                     SLK_RUN("gptq_window", fl * R, wbytes, s,
                             k_gptq_window<true, false><<<row_tiles, 512, sizeof(WindowSmem), s>>>(Qp, Eg, U, R, n, st.a, st.b, g,
-                                                                                        inv_step, fast_ok, dbg, tab, rpl, nullptr, nullptr, 0));
+                                                                                        inv_step, fast_ok, dbg, tab, rpl, nullptr, nullptr, 0, nullptr));
                 else
                     SLK_RUN("gptq_window_wide", fl * R, wbytes, s,
                             k_gptq_window<false, false><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
-                                                                           dbg, tab, rpl, nullptr, nullptr, 0));
+                                                                           dbg, tab, rpl, nullptr, nullptr, 0, nullptr));
             }
         } else {
             const double K = st.b - st.a, N = st.c - st.b;
@@ -1157,9 +1295,14 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
             }
         }
     }
-    if (grouped)
+    if (asym)
+        SLK_RUN("permute_out_grouped_asym", 0, (idx ? 17.0 : 8.0) * R * n, s,
+                k_permute_out_grouped<true><<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx, rpl,
+                                                                               goffset));
+    else if (grouped)
         SLK_RUN("permute_out_grouped", 0, (idx ? 13.0 : 8.0) * R * n, s,
-                k_permute_out_grouped<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx, rpl));
+                k_permute_out_grouped<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx, rpl,
+                                                                         nullptr));
     else if (perm_lds)
         SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out_lds<<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl));
     else
@@ -1175,7 +1318,7 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
     SLK_REQUIRE(W && U && Q, "null pointer");
     SLK_REQUIRE((flags & ~(SLK_LOOP_UNSCALE | SLK_LOOP_LATENCY)) == 0, "unknown flags");
     return gptq_loop(W, scale, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
-                     workspace, ws_bytes, stream, nullptr, 0);
+                     workspace, ws_bytes, stream, nullptr, 0, nullptr);
 }
 
 // `batch` layers with one scale per row and per group of `group_size` original columns (gscale: (batch rows_per_layer) x
@@ -1190,7 +1333,7 @@ extern "C" int slk_gptq_quantize_grouped_batch(const float *W, const float *gsca
     SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
                 group_size);
     return gptq_loop(W, nullptr, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
-                     workspace, ws_bytes, stream, gscale, group_size);
+                     workspace, ws_bytes, stream, gscale, group_size, nullptr);
 }
 
 // One layer with group scales: the batch of one.
@@ -1200,4 +1343,29 @@ extern "C" int slk_gptq_quantize_grouped(const float *W, const float *gscale, in
                                          size_t ws_bytes, slk_stream_t stream) {
     return slk_gptq_quantize_grouped_batch(W, gscale, group_size, order, U, 1, R, n, levels, lo, hi, table, min_block, num_blocks,
                                            flags, Q, idx, E_out, workspace, ws_bytes, stream);
+}
+
+// The asymmetric group quantizer: goffset (batch rows_per_layer) x n / group_size beside gscale, stacked by rows like
+// slk_gptq_quantize_grouped_batch.
+extern "C" int slk_gptq_quantize_grouped_asym_batch(const float *W, const float *gscale, const float *goffset, int group_size,
+                                                    const long long *order, const double *U, int batch, int rows_per_layer, int n,
+                                                    int levels, double lo, double hi, const float *table, int min_block,
+                                                    int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace,
+                                                    size_t ws_bytes, slk_stream_t stream) {
+    SLK_REQUIRE(W && gscale && goffset && U && Q, "null pointer");
+    SLK_REQUIRE((flags & ~SLK_LOOP_LATENCY) == 0, "the grouped loop takes SLK_LOOP_LATENCY only");
+    SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
+                group_size);
+    return gptq_loop(W, nullptr, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
+                     workspace, ws_bytes, stream, gscale, group_size, goffset);
+}
+
+// One layer with group scales and offsets: the batch of one.
+extern "C" int slk_gptq_quantize_grouped_asym(const float *W, const float *gscale, const float *goffset, int group_size,
+                                              const long long *order, const double *U, int R, int n, int levels, double lo, double hi,
+                                              const float *table, int min_block, int num_blocks, int flags, float *Q, uint8_t *idx,
+                                              float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    return slk_gptq_quantize_grouped_asym_batch(W, gscale, goffset, group_size, order, U, 1, R, n, levels, lo, hi, table, min_block,
+                                                num_blocks, flags, Q, idx, E_out, workspace, ws_bytes, stream);
 }

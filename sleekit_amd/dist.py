@@ -81,9 +81,11 @@ def check_layers(layers, moves=0):
     """The group-scale keys of a stream, checked before anything runs -- on every rank alike, since every rank holds every
     layer's inputs -- so that a refusal leaves no rank waiting in a collective.  `gscale` (R, n / group_size) float32 and
     `group_size` (an int that divides n) come together and exclude `scale`.  Grouped layers have no local search
-    (NotImplementedError when moves > 0)."""
+    (NotImplementedError when moves > 0).  Group offsets (`goffset`) are not supported in the stream: NotImplementedError."""
     grouped = False
     for l, lay in enumerate(layers):
+        if "goffset" in lay:
+            raise NotImplementedError(f"layer {l}: group offsets (`goffset`) are not supported in quantize_stream")
         S, g = lay.get("gscale"), lay.get("group_size")
         if S is None and g is None:
             continue

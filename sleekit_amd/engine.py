@@ -75,10 +75,11 @@ def require_uniform(quantizer):
 class LayerResult:
     """Device tensors produced for one layer."""
 
-    __slots__ = ("Q", "idx", "order", "U", "info", "E", "ls_trace", "ls_error")
+    __slots__ = ("Q", "idx", "order", "U", "info", "E", "ls_trace", "ls_error", "S", "O")
 
     def __init__(self):
         self.Q = self.idx = self.order = self.U = self.info = self.E = self.ls_trace = self.ls_error = None
+        self.S = self.O = None  # group scales and offsets (Sleekit.quantize with offsets)
 
 
 def factorize(H, n, damp, mode, miss=None, keep=None, lookahead=False):

@@ -6,6 +6,10 @@
     Q == dequantize_grouped(idx, S, cb, g)                      # bit for bit
     Q = quantize_grouped(..., nb_ls_moves=100)                  # then the best-first local search, group quantizer's candidates
     Q = local_search_grouped(W, Q, S, cb, H, g, 100)            # the search alone
+    O = compute_group_offsets(W, g)                             # (R, n / g) float32: each group's midpoint
+    S = compute_group_scaling(W, cb, g, H, mode="mse", offsets=O)   # the scales of the centred weights W - O
+    Q, idx = quantize_grouped_asym(W, S, O, cb, H, g, return_indices=True)
+    Q == dequantize_grouped(idx, S, cb, g, offsets=O)           # bit for bit: (idx, S, O) is the compact form
 
 Element (r, c) belongs to group c // g.  The GROUP QUANTIZER maps x in column c of row r to
 
@@ -20,6 +24,17 @@ with that quantizer's up / down neighbours as candidates: codebook.quantize_up(x
 c, s = S[r, c // g], with the reference's gains, decisions and incremental updates.
 `compute_group_scaling` gives column k of S as the reference's `compute_scaling` of the k-th column block of W with
 the k-th diagonal block of H.
+
+ASYMMETRIC groups: an offset o = O[r, c // g] per group beside the scale, and the quantizer
+
+    codebook.quantize_value((x - o) / s) / (np.float32(1) / s) + o
+
+(float32 IEEE in exactly this order: subtract, divide, codebook, divide, add; O = 0 gives the group quantizer).  With
+offsets O, quantize_grouped_asym (and quantize_layer_grouped(..., offsets=O)) is quantize_opt with that quantizer (the loop still runs on the unscaled, uncentred W; the
+err / sqerr keys come from Z(W) - W), compute_group_scaling is the symmetric search on the centred weights W - O (O
+repeated over each group, a float32 subtract), and dequantize_grouped rebuilds Q from (idx, S, O) bit for bit.
+`compute_group_offsets` gives each group's midpoint, np.float32(0.5) * (min + max).  Offsets have no local search yet
+(NotImplementedError with nb_ls_moves > 0).
 
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out, and
 every step runs on the GPU (no CPU fallback).
@@ -51,9 +66,42 @@ def _diag_mean(Hb):
     return out
 
 
-def compute_group_scaling(W, codebook, group_size, H=None, mode="mse", min_factor=0.05, max_factor=1.0, grid_size=100):
+def _check_offsets(O, R, n, g):
+    """The device copy of the (R, n / g) float32 offsets."""
+    Od = dev.to_device(O)
+    if tuple(Od.shape) != (R, n // g) or Od.dtype != torch.float32:
+        raise ValueError(f"group offsets must be float32 ({R}, {n // g}) for a ({R}, {n}) layer with group_size {g}; "
+                         f"got {Od.dtype} {tuple(Od.shape)}")
+    return Od.contiguous()
+
+
+def compute_group_offsets(W, group_size, centred=False):
+    """O (R, n / group_size) float32: the midpoint of each group's range, np.float32(0.5) * (min + max), in one pass over W.
+    centred: (O, Wc), Wc = W - O (O repeated over each group, a float32 subtract) from the same pass -- what
+    compute_group_scaling(W, ..., offsets=O) searches on, so compute_group_scaling(Wc, ...) gives the same S."""
+    assert W.ndim == 2
+    Wd = dev.to_device(W).contiguous()
+    R, n = Wd.shape
+    g, G = _groups(n, group_size)
+    O = torch.empty((R, G), dtype=torch.float32, device=Wd.device)
+    Wc = torch.empty_like(Wd) if centred else None
+    _lib.check(_lib.lib.slk_group_midpoints(dev.ptr(Wd), g, R, n, dev.ptr(O), dev.ptr(Wc), dev.stream_handle()))
+    return (dev.like_input(O, W), dev.like_input(Wc, W)) if centred else dev.like_input(O, W)
+
+
+def center_groups(Wd, Od, group_size):
+    """W - O by element, O repeated over each group (float32 subtract; device tensors)."""
+    R, n = Wd.shape
+    Wc = torch.empty_like(Wd)
+    _lib.check(_lib.lib.slk_group_center(dev.ptr(Wd), dev.ptr(Od), int(group_size), R, n, dev.ptr(Wc), dev.stream_handle()))
+    return Wc
+
+
+def compute_group_scaling(W, codebook, group_size, H=None, mode="mse", min_factor=0.05, max_factor=1.0, grid_size=100,
+                          offsets=None):
     """S (R, n / group_size) float32: column k is the reference's compute_scaling(W[:, k g : (k + 1) g], codebook,
-    H[k g : (k + 1) g, k g : (k + 1) g], mode) (sleekit/scaling.py:193-238).
+    H[k g : (k + 1) g, k g : (k + 1) g], mode) (sleekit/scaling.py:193-238).  offsets (R, n / group_size): the same on the
+    centred weights W - O.
 
     Modes max, mse, diag[N], hessian[N]; "obq" and "norm" raise NotImplementedError.  mse and diag search every group
     of every row in one launch; hessian runs the stacked search of sleekit_amd.scaling group by group (with that
@@ -70,6 +118,8 @@ def compute_group_scaling(W, codebook, group_size, H=None, mode="mse", min_facto
     Wd = dev.to_device(W)
     R, n = Wd.shape
     g, G = _groups(n, group_size)
+    if offsets is not None:
+        Wd = center_groups(Wd.contiguous(), _check_offsets(offsets, R, n, g), g)
     view = Wd.view(R * G, g)  # row r G + k = group k of row r: the reference's per-group problem, row for row
     if mode == "max":
         return dev.like_input(scaling._no_clip_scale(view, codebook).view(R, G), W)
@@ -108,11 +158,20 @@ def compute_group_scaling(W, codebook, group_size, H=None, mode="mse", min_facto
     return dev.like_input(out.view(R, G), W)
 
 
-def column_miss_grouped(W, S, group_size, cb_abi, squared):
-    """Column sums of |Z(W) - W| (or squared) with the group quantizer Z, in NumPy's row-after-row order (device tensors)."""
+def column_miss_grouped(W, S, group_size, cb_abi, squared, O=None):
+    """Column sums of |Z(W) - W| (or squared) with the group quantizer Z, in NumPy's row-after-row order (device tensors);
+    O given: the asymmetric group quantizer."""
     R, n = W.shape
     levels, lo, hi, table = cb_abi
     out = torch.empty(n, dtype=torch.float32, device=W.device)
+    if O is not None:
+        _lib.check(
+            _lib.lib.slk_column_miss_grouped_asym(
+                dev.ptr(W), dev.ptr(S), dev.ptr(O), int(group_size), R, n, levels, lo, hi, dev.ptr(table), 1 if squared else 0,
+                dev.ptr(out), dev.stream_handle(),
+            )
+        )
+        return out
     _lib.check(
         _lib.lib.slk_column_miss_grouped(
             dev.ptr(W), dev.ptr(S), int(group_size), R, n, levels, lo, hi, dev.ptr(table), 1 if squared else 0, dev.ptr(out),
@@ -122,22 +181,23 @@ def column_miss_grouped(W, S, group_size, cb_abi, squared):
     return out
 
 
-def grouped_keys(W, S, group_size, cb_abi, act_order, H, damp):
-    """The sort keys (`miss`) of act_order for a grouped layer: the err / sqerr statistics of the group quantizer over all
-    rows, the kernel-made keys of inv_diag / combined_diag / pivot, None for the rest."""
+def grouped_keys(W, S, group_size, cb_abi, act_order, H, damp, O=None):
+    """The sort keys (`miss`) of act_order for a grouped layer: the err / sqerr statistics of the group quantizer (with
+    offsets O, the asymmetric one) over all rows, the kernel-made keys of inv_diag / combined_diag / pivot, None for the rest."""
     mode = engine.order_mode_code(act_order)
     if mode == _lib.ORDER_KEYS:
         return engine.order_keys(H, H.shape[0], damp, act_order)
     if mode >= _lib.ORDER_ERR:
-        return column_miss_grouped(W, S, group_size, cb_abi, mode == _lib.ORDER_SQERR)
+        return column_miss_grouped(W, S, group_size, cb_abi, mode == _lib.ORDER_SQERR, O)
     return None
 
 
-def run_loop_batch_grouped(W, S, order, U, cb_abi, group_size, min_block, num_blocks, want_idx=True):
+def run_loop_batch_grouped(W, S, order, U, cb_abi, group_size, min_block, num_blocks, want_idx=True, offsets=None):
     """The grouped loop over a batch of layers stacked by rows (slk_gptq_quantize_grouped_batch).
 
     W (B, R, n) float32, S (B, R, n / group_size) float32, order (B, n) int64, U (B, n, n) float64, all contiguous.
     Returns (Q, idx) shaped (B, R, n), Q de-scaled: what B single-layer grouped loops return, in launches that cover all B.
+    offsets (B, R, n / group_size) float32, contiguous: the asymmetric loop (slk_gptq_quantize_grouped_asym_batch).
     """
     B, R, n = W.shape
     g, G = _groups(n, group_size)
@@ -147,6 +207,15 @@ def run_loop_batch_grouped(W, S, order, U, cb_abi, group_size, min_block, num_bl
     ws, ws_bytes = dev.workspace(R, n, batch=B, grouped=True)
     Q = torch.empty((B, R, n), dtype=torch.float32, device=W.device)
     idx = torch.empty((B, R, n), dtype=torch.uint8, device=W.device) if want_idx else None
+    if offsets is not None:
+        assert offsets.shape == (B, R, G) and offsets.is_contiguous() and offsets.dtype == torch.float32
+        _lib.check(
+            _lib.lib.slk_gptq_quantize_grouped_asym_batch(
+                dev.ptr(W), dev.ptr(S), dev.ptr(offsets), g, dev.ptr(order), dev.ptr(U), B, R, n, levels, lo, hi, dev.ptr(table),
+                int(min_block), int(num_blocks), 0, dev.ptr(Q), dev.ptr(idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
+            )
+        )
+        return Q, idx
     _lib.check(
         _lib.lib.slk_gptq_quantize_grouped_batch(
             dev.ptr(W), dev.ptr(S), g, dev.ptr(order), dev.ptr(U), B, R, n, levels, lo, hi, dev.ptr(table), int(min_block),
@@ -202,14 +271,14 @@ def local_search_grouped(W, Q, S, quantizer, H, group_size, nb_moves, return_ind
 
 
 def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
-                           want_idx=True, factor=None, lookahead=True, nb_ls_moves=0, want_ls_trace=False):
+                           want_idx=True, factor=None, lookahead=True, nb_ls_moves=0, want_ls_trace=False, offsets=None):
     """The grouped layer on device tensors: W (R, n), S (R, n / group_size), H (n, n), all float32.  Returns an
     engine.LayerResult (Q de-scaled, idx uint8 or None, order, U, info); raises LinAlgError if H + damping is not
     positive definite.  `factor` = (order, U, info) re-uses a factor made elsewhere (sleekit_amd.dist: a row shard), as
     engine.quantize_layer does; its status is then the caller's to check.  lookahead: this layer is alone on the GPU
     (engine.factorize).  nb_ls_moves > 0: the local search (local_search_grouped) runs after the loop, on Q and idx in
     place; res.ls_error holds the rows' errors after the moves (carried through the search) and, with want_ls_trace,
-    res.ls_trace the moves taken."""
+    res.ls_trace the moves taken.  offsets (R, n / group_size): the asymmetric group quantizer (no local search)."""
     assert W.ndim == 2 and H.ndim == 2 and H.shape[0] == H.shape[1] == W.shape[1]
     assert min_block_size >= 1
     cb_abi = engine.require_uniform(quantizer)
@@ -219,16 +288,32 @@ def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", dam
         raise ValueError(f"group scales must be ({R}, {G}) for a ({R}, {n}) layer with group_size {g}; got {tuple(S.shape)}")
     if want_idx and cb_abi[0] > 256:
         raise ValueError("uint8 indices need a codebook of at most 256 entries")
+    O = None
+    if offsets is not None:
+        if nb_ls_moves > 0:
+            raise NotImplementedError("local search with group offsets is not supported (nb_ls_moves must be 0)")
+        O = _check_offsets(offsets, R, n, g)
     res = engine.LayerResult()
     check_factor = factor is None
     if factor is None:
-        miss = grouped_keys(W, S, g, cb_abi, act_order, H, damp)
+        miss = grouped_keys(W, S, g, cb_abi, act_order, H, damp, O)
         factor = engine.factorize(H, n, damp, engine.order_mode_code(act_order), miss, lookahead=lookahead)
     res.order, res.U, res.info = factor[:3]
     levels, lo, hi, table = cb_abi
     ws, ws_bytes = dev.workspace(R, n)
     res.Q = torch.empty((R, n), dtype=torch.float32, device=W.device)
     res.idx = torch.empty((R, n), dtype=torch.uint8, device=W.device) if want_idx else None
+    if O is not None:
+        _lib.check(
+            _lib.lib.slk_gptq_quantize_grouped_asym(
+                dev.ptr(W), dev.ptr(S), dev.ptr(O), g, dev.ptr(res.order), dev.ptr(res.U), R, n, levels, lo, hi, dev.ptr(table),
+                int(min_block_size), int(num_blocks), 2, dev.ptr(res.Q), dev.ptr(res.idx), None, dev.ptr(ws), ws_bytes,
+                dev.stream_handle(),
+            )
+        )
+        if check_factor:
+            dev.note_info(res.info, "compute_hessian_chol")
+        return res
     _lib.check(
         _lib.lib.slk_gptq_quantize_grouped(
             dev.ptr(W), dev.ptr(S), g, dev.ptr(res.order), dev.ptr(res.U), R, n, levels, lo, hi, dev.ptr(table), int(min_block_size),
@@ -251,7 +336,7 @@ def quantize_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01
 
     Returns the de-scaled values Q (float32, shaped like W): what sleekit/obq.py:169-217 returns for the group quantizer
     (module docstring), with nb_ls_moves of its local search after the loop.  return_indices: (Q, idx) with idx the uint8
-    codebook indices of Q / S.
+    codebook indices of Q / S.  (The asymmetric form, with offsets, is quantize_grouped_asym.)
     """
     assert W.ndim == 2 and H.ndim == 2
     res = quantize_layer_grouped(dev.to_device(W), dev.to_device(S), quantizer, dev.to_device(H), group_size, act_order, damp,
@@ -260,8 +345,22 @@ def quantize_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01
     return (Q, dev.like_input(res.idx, W)) if return_indices else Q
 
 
-def dequantize_grouped(idx, S, codebook, group_size):
-    """Q[r, c] = value(idx[r, c]) / (1 / S[r, c // group_size]): bit for bit the Q of quantize_grouped."""
+def quantize_grouped_asym(W, S, O, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
+                          return_indices=False):
+    """quantize_grouped with offsets O (R, n / group_size) beside the scales: the asymmetric group quantizer (module
+    docstring).  return_indices: (Q, idx), from which dequantize_grouped(idx, S, quantizer, group_size, offsets=O) rebuilds
+    Q bit for bit.  No local search with offsets yet.  (quantize_grouped keeps its parameter list, return_indices and
+    nb_ls_moves included, as it was; the offset form is this sibling.)"""
+    assert W.ndim == 2 and H.ndim == 2
+    res = quantize_layer_grouped(dev.to_device(W), dev.to_device(S), quantizer, dev.to_device(H), group_size, act_order, damp,
+                                 min_block_size, num_blocks, want_idx=return_indices, offsets=O)
+    Q = dev.like_input(res.Q, W)
+    return (Q, dev.like_input(res.idx, W)) if return_indices else Q
+
+
+def dequantize_grouped(idx, S, codebook, group_size, offsets=None):
+    """Q[r, c] = value(idx[r, c]) / (1 / S[r, c // group_size]) (+ offsets[r, c // group_size]): bit for bit the Q of
+    quantize_grouped."""
     assert idx.ndim == 2
     levels, lo, hi, table = engine.require_uniform(codebook)
     idx_d = dev.to_device(idx, torch.uint8)
@@ -271,6 +370,13 @@ def dequantize_grouped(idx, S, codebook, group_size):
     if tuple(Sd.shape) != (R, G):
         raise ValueError(f"group scales must be ({R}, {G}); got {tuple(Sd.shape)}")
     Q = torch.empty((R, n), dtype=torch.float32, device=Sd.device)
+    if offsets is not None:
+        Od = _check_offsets(offsets, R, n, g)
+        _lib.check(
+            _lib.lib.slk_dequantize_grouped_asym(dev.ptr(idx_d), dev.ptr(Sd), dev.ptr(Od), g, R, n, levels, lo, hi, dev.ptr(table),
+                                                 dev.ptr(Q), dev.stream_handle())
+        )
+        return dev.like_input(Q, idx)
     _lib.check(
         _lib.lib.slk_dequantize_grouped(dev.ptr(idx_d), dev.ptr(Sd), g, R, n, levels, lo, hi, dev.ptr(table), dev.ptr(Q),
                                         dev.stream_handle())

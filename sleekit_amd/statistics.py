@@ -119,7 +119,7 @@ class Sleekit:
     quantize_sleekit_heavy = _preset_method("sleekit_heavy")
 
     def quantize(self, nbits, scaling_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0,
-                 grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, group_size=None):
+                 grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, offsets=None, group_size=None):
         """The layer's weight replaced by its `nbits` quantization, in place (statistics.py:146-190).
 
         bias_correction: quantize against H - mean mean^T and move the expected output shift into the bias.
@@ -127,10 +127,15 @@ class Sleekit:
         group_size (optional): one scale per row and per group of `group_size` input features (sleekit_amd.groups):
         compute_group_scaling, then quantize_grouped; `scale`, if given, is then the (out, features / group_size) group
         scales.  Local search and the "obq" scaling mode are not available with group scales.
+        offsets (optional, with group_size): an offset per row and group beside the scale (the asymmetric group quantizer
+        of sleekit_amd.groups): "mid" for each group's midpoint, or an (out, features / group_size) array used as given;
+        the scale search then runs on the centred weight.  The result carries S and O (result.S, result.O) beside idx.
         """
+        if offsets is not None and group_size is None:
+            raise ValueError("offsets need group_size: an offset per row and group of input features")
         if group_size is not None:
             return self._quantize_grouped(nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                                          max_factor, scale, group_size)
+                                          max_factor, scale, group_size, offsets)
         codebook = UniformCodebook(2**nbits, -1, 1)
         weight = self.layer.weight.data.flatten(1).float().contiguous()
         H = self.hessian
@@ -150,7 +155,7 @@ class Sleekit:
         return result
 
     def _quantize_grouped(self, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                          max_factor, scale, group_size):
+                          max_factor, scale, group_size, offsets=None):
         from . import groups
 
         if nb_ls_moves > 0:
@@ -164,10 +169,23 @@ class Sleekit:
             centred = torch.empty_like(H)
             _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
             H = centred
+        search = dict(H=H, mode=scaling_mode, grid_size=grid_size, min_factor=min_factor, max_factor=max_factor)
+        if isinstance(offsets, str):
+            if offsets != "mid":
+                raise ValueError(f'offsets must be "mid" or an (out, features / group_size) array, not "{offsets}"')
+            # the midpoints and the centred weight in one pass; the scale search of the centred weight is the search with offsets
+            offsets, centred = groups.compute_group_offsets(weight, group_size, centred=True)
+            if scale is None:
+                scale = groups.compute_group_scaling(centred, codebook, group_size, **search)
+            del centred
+        elif offsets is not None:
+            offsets = dev.to_device(offsets)
         if scale is None:
-            scale = groups.compute_group_scaling(weight, codebook, group_size, H=H, mode=scaling_mode, grid_size=grid_size,
-                                                 min_factor=min_factor, max_factor=max_factor)
-        result = groups.quantize_layer_grouped(weight, dev.to_device(scale), codebook, H, group_size, order_mode, damp)
+            scale = groups.compute_group_scaling(weight, codebook, group_size, offsets=offsets, **search)
+        scale = dev.to_device(scale)
+        result = groups.quantize_layer_grouped(weight, scale, codebook, H, group_size, order_mode, damp, offsets=offsets)
+        if offsets is not None:
+            result.S, result.O = scale, offsets
         target = self.layer.weight
         target.data = result.Q.reshape(target.shape).to(target.dtype)
         if bias_correction:
