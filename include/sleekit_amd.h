@@ -82,7 +82,8 @@ typedef void *slk_stream_t;
  * loop over a batch of layers stacked by rows; slk_gptq_quantize_grouped is its batch of one), then slk_local_search_grouped (the
  * best-first search with the group quantizer's candidates), then the asymmetric group quantizer (an offset per row and group
  * beside the scale): slk_gptq_quantize_grouped_asym, slk_gptq_quantize_grouped_asym_batch, slk_column_miss_grouped_asym,
- * slk_dequantize_grouped_asym, slk_group_midpoints and slk_group_center.   */
+ * slk_dequantize_grouped_asym, slk_group_midpoints and slk_group_center, then bit-packed indices: slk_pack_indices,
+ * slk_unpack_indices and slk_dequantize_packed.   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -336,6 +337,31 @@ int slk_dequantize_grouped_asym(const uint8_t *idx, const float *gscale, const f
                                 int levels, double lo, double hi, const float *table, float *Q, slk_stream_t stream);
 int slk_group_midpoints(const float *W, int group_size, int R, int n, float *goffset, float *Wc, slk_stream_t stream);
 int slk_group_center(const float *W, const float *goffset, int group_size, int R, int n, float *Wc, slk_stream_t stream);
+
+/* Packed indices: uint8 codebook indices at `bits` = b bits each (1 <= b <= 8), the compact form of (idx, S[, O]).
+ *   - each row is cut into chunks of 32 consecutive indices; the last one is padded with zero indices.  A row takes
+ *     b * ceil(n / 32) 32-bit words and starts on a word boundary: `words` is R x (b * ceil(n / 32)).
+ *   - chunk k of row r is words [b k, b k + b) of that row, read as ONE little-endian integer of 32 b bits (word j holds
+ *     bits [32 j, 32 j + 32)); index 32 k + i sits in its bits [i b, i b + b).
+ *   - only the low b bits of an index are stored: an index >= 2^b is a caller error and comes back masked.
+ *   - b = 8 is the idx bytes read as little-endian words, each row padded to a multiple of 32 bytes.
+ *   A stack of B layers of one width, (B, R, n), is B R rows: no batch form is needed.
+ * slk_pack_indices: idx (R x n uint8) -> words.
+ * slk_unpack_indices: words -> idx (R x n uint8).
+ * slk_dequantize_packed: out[r][c] = value(k), k = min(index, levels - 1), de-scaled by at most one of
+ *     scale (R float32):               value(k) / (1 / scale[r])            (the loop's per-row de-scale)
+ *     gscale (R x n / group_size):     value(k) / (1 / gscale[r][c / group_size])   (slk_dequantize_grouped)
+ *     gscale and goffset:              value(k) / (1 / s) + goffset[r][c / group_size]  (slk_dequantize_grouped_asym)
+ *   in float32 (bit for bit the paths named), or that float32 value rounded to nearest even as bfloat16 / float16
+ *   (`out_dtype`).  scale and gscale are exclusive; goffset needs gscale; group_size is read only with gscale. */
+#define SLK_DTYPE_F32 0
+#define SLK_DTYPE_BF16 1
+#define SLK_DTYPE_F16 2
+int slk_pack_indices(const uint8_t *idx, int R, int n, int bits, uint32_t *words, slk_stream_t stream);
+int slk_unpack_indices(const uint32_t *words, int R, int n, int bits, uint8_t *idx, slk_stream_t stream);
+int slk_dequantize_packed(const uint32_t *words, int R, int n, int bits, int levels, double lo, double hi, const float *table,
+                          const float *scale, const float *gscale, const float *goffset, int group_size, int out_dtype, void *out,
+                          slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */
