@@ -193,6 +193,38 @@ __device__ __forceinline__ float cb_up(float x, const Grid g) {
 __device__ __forceinline__ float cb_down(float x, const Grid g) {
     return g.table ? g.table[max(table_index(x, g) - 1, 0)] : grid_val(grid_pos(x, g, -1.0f, 0.0f, g.top - 1.0f), g);
 }
+// the value of codebook entry k (codebook.py:58-63: k * step + zero in float32, or the table's)
+__device__ __forceinline__ float cb_entry(int k, const Grid g) { return g.table ? g.table[k] : grid_val((float)k, g); }
+
+// The group quantizer of one element (sleekit_amd/groups.py): its group's scale s, rs = RN(1 / s) and, OFFSET, offset o.
+//   value   codebook(x / s) / rs             OFFSET: codebook((x - o) / s) / rs + o
+//   index   cb_index(x / s)                  OFFSET: cb_index((x - o) / s)
+// Float32 IEEE divides in this order are what make the indices the reference's bit for bit.  The symmetric form is not
+// the asymmetric one with o = 0: -0.0f + 0.0f is +0.0f, and the leaf chain would pay an instruction for it.
+template <bool OFFSET>
+struct GroupQ {
+    float s, rs, o;  // (o: OFFSET only)
+    __device__ __forceinline__ static GroupQ of(float s, float o = 0.0f) { return {s, 1.0f / s, o}; }
+    // group k of the scales S (and offsets O) in memory
+    __device__ __forceinline__ static GroupQ at(const float *S, const float *O, size_t k) {
+        GroupQ e = of(S[k]);
+        if constexpr (OFFSET) e.o = O[k];
+        return e;
+    }
+    // x in codebook units, and back: the dequantised value of codebook value v
+    __device__ __forceinline__ float scaled(float x) const {
+        if constexpr (OFFSET) return (x - o) / s;
+        else return x / s;
+    }
+    __device__ __forceinline__ float dequant(float v) const {
+        if constexpr (OFFSET) return v / rs + o;
+        else return v / rs;
+    }
+    __device__ __forceinline__ float value(float x, const Grid g) const { return dequant(cb_value(scaled(x), g)); }
+    __device__ __forceinline__ int index(float x, const Grid g) const { return cb_index(scaled(x), g); }
+    __device__ __forceinline__ float up(float x, const Grid g) const { return dequant(cb_up(scaled(x), g)); }
+    __device__ __forceinline__ float down(float x, const Grid g) const { return dequant(cb_down(scaled(x), g)); }
+};
 
 // Broadcast lane `src` (wave-uniform index) of a double to the whole wave through SGPRs.
 __device__ __forceinline__ double readlane_f64(double v, int src) {

@@ -146,14 +146,10 @@ __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W
             for (int e = 0; e < 4; ++e) {
                 const float w = cur[p][e];
                 float qv;
-                if constexpr (OFFSET) {
-                    const size_t k = (size_t)min(base + p * 32 + lr, R - 1) * (n / gsize) + min(j0 + c4 + e, n - 1) / gsize;
-                    const float sv = S[k], ov = O[k];
-                    qv = cb_value((w - ov) / sv, g) / (1.0f / sv) + ov;
-                } else if constexpr (GROUPED) {
+                if constexpr (GROUPED) {
                     // (clamped like the loads: a row beyond R or a column beyond n is never added)
-                    const float sv = S[(size_t)min(base + p * 32 + lr, R - 1) * (n / gsize) + min(j0 + c4 + e, n - 1) / gsize];
-                    qv = cb_value(w / sv, g) / (1.0f / sv);
+                    const size_t k = (size_t)min(base + p * 32 + lr, R - 1) * (n / gsize) + min(j0 + c4 + e, n - 1) / gsize;
+                    qv = GroupQ<OFFSET>::at(S, O, k).value(w, g);
                 } else {
                     qv = cb_value(w, g);
                 }
@@ -180,12 +176,8 @@ __global__ __launch_bounds__(256) void k_dequantize_grouped(const uint8_t *__res
     const size_t total = (size_t)R * n;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const size_t r = e / n, c = e % n;
-        const int k = min((int)idx[e], g.n - 1);
-        const float v = g.table ? g.table[k] : grid_val((float)k, g);
-        if constexpr (OFFSET)
-            Q[e] = v / (1.0f / S[r * (n / gsize) + c / gsize]) + O[r * (n / gsize) + c / gsize];
-        else
-            Q[e] = v / (1.0f / S[r * (n / gsize) + c / gsize]);
+        const float v = cb_entry(min((int)idx[e], g.n - 1), g);
+        Q[e] = GroupQ<OFFSET>::at(S, O, r * (n / gsize) + c / gsize).dequant(v);
     }
 }
 
@@ -232,6 +224,41 @@ __global__ __launch_bounds__(256) void k_group_offsets(const float *__restrict__
             for (int c = t; c < n; c += 256) Wc[(size_t)r * n + c] = w[c] - O[(size_t)r * G + c / gsize];
         if constexpr (MIDPOINTS) __syncthreads();
     }
+}
+
+// slk_column_miss_grouped[_asym] and slk_dequantize_grouped[_asym]: goffset == nullptr is the symmetric quantizer
+static int column_miss_grouped(const float *W, const float *gscale, const float *goffset, int group_size, int R, int n, int levels,
+                               double lo, double hi, const float *table, int squared, float *miss, slk_stream_t stream) {
+    SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
+    SLK_REQUIRE(R > 0 && n > 0 && W && gscale && miss, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    const Grid g = make_grid(levels, lo, hi, table);
+    const int blocks = (n + CM_COLS - 1) / CM_COLS, vec_ok = n % 4 == 0 && (uintptr_t)W % 16 == 0;
+    if (goffset)
+        SLK_RUN("column_miss_grouped_asym", 0, 4.0 * R * n, s,
+                k_column_miss<true, true><<<blocks, 256, 0, s>>>(W, R, n, g, squared, miss, vec_ok, gscale, group_size, goffset));
+    else
+        SLK_RUN("column_miss_grouped", 0, 4.0 * R * n, s,
+                k_column_miss<true><<<blocks, 256, 0, s>>>(W, R, n, g, squared, miss, vec_ok, gscale, group_size, nullptr));
+    return SLK_OK;
+}
+
+static int dequantize_grouped(const uint8_t *idx, const float *gscale, const float *goffset, int group_size, int R, int n, int levels,
+                              double lo, double hi, const float *table, float *Q, slk_stream_t stream) {
+    SLK_REQUIRE(levels >= 2 && levels <= 256 && (table || lo < hi), "codebook needs 2 <= levels <= 256 and lo < hi");
+    SLK_REQUIRE(R > 0 && n > 0 && idx && gscale && Q, "bad arguments");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
+    hipStream_t s = as_stream(stream);
+    const Grid g = make_grid(levels, lo, hi, table);
+    const int blocks = stream_blocks((size_t)R * n, 256 * 4);
+    if (goffset)
+        SLK_RUN("dequantize_grouped_asym", 0, 13.0 * R * n, s,
+                k_dequantize_grouped<true><<<blocks, 256, 0, s>>>(idx, gscale, group_size, R, n, g, Q, goffset));
+    else
+        SLK_RUN("dequantize_grouped", 0, 9.0 * R * n, s,
+                k_dequantize_grouped<<<blocks, 256, 0, s>>>(idx, gscale, group_size, R, n, g, Q, nullptr));
+    return SLK_OK;
 }
 
 }  // namespace slk
@@ -338,51 +365,24 @@ int slk_column_miss(const float *W, int R, int n, int levels, double lo, double 
 
 int slk_column_miss_grouped(const float *W, const float *gscale, int group_size, int R, int n, int levels, double lo, double hi,
                             const float *table, int squared, float *miss, slk_stream_t stream) {
-    SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
-    SLK_REQUIRE(R > 0 && n > 0 && W && gscale && miss, "bad arguments");
-    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
-    hipStream_t s = as_stream(stream);
-    SLK_RUN("column_miss_grouped", 0, 4.0 * R * n, s,
-            k_column_miss<true><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
-                                                                            n % 4 == 0 && (uintptr_t)W % 16 == 0, gscale, group_size, nullptr));
-    return SLK_OK;
+    return column_miss_grouped(W, gscale, nullptr, group_size, R, n, levels, lo, hi, table, squared, miss, stream);
 }
 
 int slk_dequantize_grouped(const uint8_t *idx, const float *gscale, int group_size, int R, int n, int levels, double lo, double hi,
                            const float *table, float *Q, slk_stream_t stream) {
-    SLK_REQUIRE(levels >= 2 && levels <= 256 && (table || lo < hi), "codebook needs 2 <= levels <= 256 and lo < hi");
-    SLK_REQUIRE(R > 0 && n > 0 && idx && gscale && Q, "bad arguments");
-    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
-    hipStream_t s = as_stream(stream);
-    SLK_RUN("dequantize_grouped", 0, 9.0 * R * n, s,
-            k_dequantize_grouped<<<stream_blocks((size_t)R * n, 256 * 4), 256, 0, s>>>(idx, gscale, group_size, R, n,
-                                                                                     make_grid(levels, lo, hi, table), Q, nullptr));
-    return SLK_OK;
+    return dequantize_grouped(idx, gscale, nullptr, group_size, R, n, levels, lo, hi, table, Q, stream);
 }
 
 int slk_column_miss_grouped_asym(const float *W, const float *gscale, const float *goffset, int group_size, int R, int n, int levels,
                                  double lo, double hi, const float *table, int squared, float *miss, slk_stream_t stream) {
-    SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
-    SLK_REQUIRE(R > 0 && n > 0 && W && gscale && goffset && miss, "bad arguments");
-    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
-    hipStream_t s = as_stream(stream);
-    SLK_RUN("column_miss_grouped_asym", 0, 4.0 * R * n, s,
-            k_column_miss<true, true><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
-                                                                                  n % 4 == 0 && (uintptr_t)W % 16 == 0, gscale, group_size,
-                                                                                  goffset));
-    return SLK_OK;
+    SLK_REQUIRE(goffset, "bad arguments");
+    return column_miss_grouped(W, gscale, goffset, group_size, R, n, levels, lo, hi, table, squared, miss, stream);
 }
 
 int slk_dequantize_grouped_asym(const uint8_t *idx, const float *gscale, const float *goffset, int group_size, int R, int n, int levels,
                                 double lo, double hi, const float *table, float *Q, slk_stream_t stream) {
-    SLK_REQUIRE(levels >= 2 && levels <= 256 && (table || lo < hi), "codebook needs 2 <= levels <= 256 and lo < hi");
-    SLK_REQUIRE(R > 0 && n > 0 && idx && gscale && goffset && Q, "bad arguments");
-    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n");
-    hipStream_t s = as_stream(stream);
-    SLK_RUN("dequantize_grouped_asym", 0, 13.0 * R * n, s,
-            k_dequantize_grouped<true><<<stream_blocks((size_t)R * n, 256 * 4), 256, 0, s>>>(idx, gscale, group_size, R, n,
-                                                                                           make_grid(levels, lo, hi, table), Q, goffset));
-    return SLK_OK;
+    SLK_REQUIRE(goffset, "bad arguments");
+    return dequantize_grouped(idx, gscale, goffset, group_size, R, n, levels, lo, hi, table, Q, stream);
 }
 
 int slk_group_midpoints(const float *W, int group_size, int R, int n, float *goffset, float *Wc, slk_stream_t stream) {

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict
 
 // ------------------------------------------------------------------ group scales (slk_gptq_quantize_grouped_batch)
 // S (R x G, G = n / gsize) holds one scale per row and per group of gsize ORIGINAL columns; the loop runs on the
-// unscaled weights and only its leaves scale (see leaf_registers_grouped).  pg[b n + c] = group of processing column c
+// unscaled weights and only its leaves scale (see leaf_registers and LeafTile).  pg[b n + c] = group of processing column c
 // of layer b (a batch of layers stacked by rows, `batch` rows of order; no order: batch 1, the identity).
 __global__ __launch_bounds__(256) void k_group_of_column(const long long *__restrict__ order, int batch, int n, int gsize,
                                                          int *__restrict__ pg) {
@@ -166,25 +166,19 @@ __global__ __launch_bounds__(256) void k_permute_out_grouped(const float *__rest
         for (int j = threadIdx.x; j < n; j += blockDim.x) {
             const float v = src[inv_o[j]];
             Q[(size_t)r * n + j] = v;
-            if constexpr (OFFSET) {
-                if (idx) {
-                    const float sv = S[(size_t)r * G + j / gsize], ov = O[(size_t)r * G + j / gsize];
-                    const float rs = 1.0f / sv;
-                    auto back = [&](int k) {
-                        const float val = g.table ? g.table[k] : grid_val((float)k, g);
-                        return __float_as_uint(val / rs + ov);
-                    };
-                    int k = cb_index((v - ov) / sv, g);
+            if (idx) {
+                const GroupQ<OFFSET> gq = GroupQ<OFFSET>::at(S, O, (size_t)r * G + j / gsize);
+                int k = gq.index(v, g);
+                if constexpr (OFFSET) {
+                    auto back = [&](int t) { return __float_as_uint(gq.dequant(cb_entry(t, g))); };
                     if (back(k) != __float_as_uint(v))
                         for (int t = 0; t < g.n; ++t)
                             if (back(t) == __float_as_uint(v)) {
                                 k = t;
                                 break;
                             }
-                    idx[(size_t)r * n + j] = (uint8_t)k;
                 }
-            } else {
-                if (idx) idx[(size_t)r * n + j] = (uint8_t)cb_index(v / S[(size_t)r * G + j / gsize], g);
+                idx[(size_t)r * n + j] = (uint8_t)k;
             }
         }
     }
@@ -255,33 +249,40 @@ __device__ __forceinline__ float grid_value_fast_med3(float x, const Grid g, flo
 // taken once per leaf by a true division.  The loop is issue-bound (~35 instructions a step),
 // which is why four rows share a wave and the other four waves of the workgroup stay parked
 // at the barrier: two waves per SIMD would just take turns (measured 430 -> ~230 cycles/step).
-template <int NSTEP>
-__device__ __forceinline__ void leaf_registers(WindowSmem &sm, const LeafTables &lt, int wave, int lane, int a_rel, int w,
-                                               const Grid g, float inv_step) {
+// The policy P is the quantizer: P::Step is what a step reads from LDS besides U (read one step
+// ahead, like the U row), P.at(row, a, k) reads it for column a + k, and P::q(x, step, g, inv_step)
+// forms q.  (The tile's reads take a and k apart: one base address for s and rs, k in the offsets.)
+template <int NSTEP, class P>
+__device__ __forceinline__ void leaf_registers(WindowSmem &sm, const P &pol, const LeafTables &lt, int wave, int lane, int a_rel,
+                                               int w, const Grid g, float inv_step) {
     const int c16 = lane & 15, rg = lane >> 4;
     const int row = 4 * wave + rg;
     const bool m0 = c16 < w, m1 = c16 + 16 < w;
     float x0 = m0 ? sm.q[row][a_rel + c16] : 0.0f, x1 = m1 ? sm.q[row][a_rel + 16 + c16] : 0.0f;
     float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
-    // Steps beyond the width run on the padding (x = 0, U row = 0, diagonal = 1) and change
-    // nothing: no per-step branch, so the whole leaf is one basic block and the LDS reads of
-    // step i + 1 (U row, diagonal, reciprocal) are issued before the arithmetic of step i.
+    // Steps beyond the width run on the padding (x = 0, U row = 0, diagonal = 1; the group tables
+    // read 1.0 there: a finite error that meets a zero U row) and change nothing: no per-step branch,
+    // so the whole leaf is one basic block and the LDS reads of step i + 1 (U row, diagonal,
+    // reciprocal, the policy's step) are issued before the arithmetic of step i.
     double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
+    typename P::Step sn = pol.at(row, a_rel, 0);
     static_for<0, NSTEP>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
+        const typename P::Step sc = sn;
         if constexpr (i + 1 < NSTEP) {
             u0n = lt.u[i + 1][c16];
             u1n = lt.u[i + 1][c16 + 16];
             uiin = lt.udr[i + 1][0];
             riin = lt.udr[i + 1][1];
+            sn = pol.at(row, a_rel, i + 1);
         }
         // the chain values pass through this point: the reads above are issued before step i starts
         asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
         constexpr int src = i & 15;
         // column i of each of the wave's four rows, broadcast inside its 16-lane DPP row
         const float xi = row_bcast<src>(i < 16 ? x0 : x1);
-        const float q = grid_value_fast(xi, g, inv_step);
+        const float q = P::q(xi, sc, g, inv_step);
         const double d = (double)(xi - q);
         const double qq = d * rii;
         const double rem = __builtin_fma(-uii, qq, d);
@@ -309,6 +310,20 @@ __device__ __forceinline__ void leaf_registers(WindowSmem &sm, const LeafTables 
     }
 }
 
+// the per-row quantizer: nothing to read per step
+struct LeafRows {
+    struct Step {};
+    __device__ __forceinline__ Step at(int, int, int) const { return {}; }
+    __device__ __forceinline__ static float q(float x, Step, const Grid g, float inv_step) { return grid_value_fast(x, g, inv_step); }
+};
+
+// the group quantizers: q = codebook(x / s) / rs (two true divides; the codebook step keeps the exact-division sequence),
+// OFFSET codebook((x - o) / s) / rs + o
+template <bool OFFSET>
+__device__ __forceinline__ float leaf_group_q(float x, const GroupQ<OFFSET> e, const Grid g, float inv_step) {
+    return e.dequant(grid_value_fast(e.scaled(x), g, inv_step));
+}
+
 // The window's scales in the grouped loop, beside WindowSmem: s[r][c] = S[row][group of column c], rs = RN(1 / s).
 // The pitch leaves room for the steps a leaf runs past its width (up to 31 columns beyond the window), which read 1.0.
 constexpr int GPITCH = WMAX + 32;
@@ -316,62 +331,13 @@ struct GroupTile {
     float s[RB][GPITCH];
     float rs[RB][GPITCH];
 };
-
-// leaf_registers with the group quantizer: x is unscaled, q = codebook(x / s) / rs with this row's scale of column i
-// (two true divides; the codebook step keeps the exact-division sequence).  The scales of step i + 1 are read from
-// LDS before step i, like the U row.
-template <int NSTEP>
-__device__ __forceinline__ void leaf_registers_grouped(WindowSmem &sm, const GroupTile &gt, const LeafTables &lt, int wave, int lane,
-                                                       int a_rel, int w, const Grid g, float inv_step) {
-    const int c16 = lane & 15, rg = lane >> 4;
-    const int row = 4 * wave + rg;
-    const bool m0 = c16 < w, m1 = c16 + 16 < w;
-    float x0 = m0 ? sm.q[row][a_rel + c16] : 0.0f, x1 = m1 ? sm.q[row][a_rel + 16 + c16] : 0.0f;
-    float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
-    // steps beyond the width read the tile's padding, 1.0: a finite error that meets a zero U row
-    double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
-    float sn = gt.s[row][a_rel], rsn = gt.rs[row][a_rel];
-    static_for<0, NSTEP>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
-        const float sc = sn, rsc = rsn;
-        if constexpr (i + 1 < NSTEP) {
-            u0n = lt.u[i + 1][c16];
-            u1n = lt.u[i + 1][c16 + 16];
-            uiin = lt.udr[i + 1][0];
-            riin = lt.udr[i + 1][1];
-            sn = gt.s[row][a_rel + i + 1];
-            rsn = gt.rs[row][a_rel + i + 1];
-        }
-        asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
-        constexpr int src = i & 15;
-        const float xi = row_bcast<src>(i < 16 ? x0 : x1);
-        const float q = grid_value_fast(xi / sc, g, inv_step) / rsc;
-        const double d = (double)(xi - q);
-        const double qq = d * rii;
-        const double rem = __builtin_fma(-uii, qq, d);
-        const double err = __builtin_fma(rem, rii, qq);
-        const float ef = (float)err;
-        const bool here = c16 == src;
-        if (i < 16) {
-            q0 = here ? q : q0;
-            e0 = here ? ef : e0;
-        } else {
-            q1 = here ? q : q1;
-            e1 = here ? ef : e1;
-        }
-        if (i < 15) x0 = (float)((double)x0 - err * u0);
-        if (NSTEP > 16) x1 = (float)((double)x1 - err * u1);
-    });
-    if (m0) {
-        sm.q[row][a_rel + c16] = q0;
-        sm.e[row][a_rel + c16] = e0;
-    }
-    if (m1) {
-        sm.q[row][a_rel + 16 + c16] = q1;
-        sm.e[row][a_rel + 16 + c16] = e1;
-    }
-}
+// the symmetric group quantizer with s, rs of every (row, column) from the GroupTile
+struct LeafTile {
+    const GroupTile &gt;
+    typedef GroupQ<false> Step;
+    __device__ __forceinline__ Step at(int row, int a, int k) const { return {(&gt.s[row][a])[k], (&gt.rs[row][a])[k]}; }
+    __device__ __forceinline__ static float q(float x, Step e, const Grid g, float inv_step) { return leaf_group_q(x, e, g, inv_step); }
+};
 
 // The asymmetric grouped loop (OFFSET) needs a third value per step, the offset o.  A third per-column plane beside the
 // GroupTile does not fit in LDS, so this tile holds s, rs and o per ROW AND GROUP instead -- all G groups of the tile's
@@ -385,63 +351,16 @@ struct GroupSlots {
     int slot[GPITCH];
 };
 static_assert(sizeof(WindowSmem) + sizeof(GroupSlots) <= 160 * 1024, "the asymmetric window's LDS exceeds a CU's 160 KiB");
-
-// leaf_registers_grouped with the asymmetric group quantizer: q = codebook((x - o) / s) / rs + o.  The map entry and the
-// three values of step i + 1 are read before step i.
-template <int NSTEP>
-__device__ __forceinline__ void leaf_registers_offset(WindowSmem &sm, const GroupSlots &gs, const LeafTables &lt, int wave, int lane,
-                                                      int a_rel, int w, const Grid g, float inv_step) {
-    const int c16 = lane & 15, rg = lane >> 4;
-    const int row = 4 * wave + rg;
-    const bool m0 = c16 < w, m1 = c16 + 16 < w;
-    float x0 = m0 ? sm.q[row][a_rel + c16] : 0.0f, x1 = m1 ? sm.q[row][a_rel + 16 + c16] : 0.0f;
-    float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
-    double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
-    int kn = gs.slot[a_rel];
-    float sn = gs.s[row][kn], rsn = gs.rs[row][kn], on = gs.o[row][kn];
-    static_for<0, NSTEP>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
-        const float sc = sn, rsc = rsn, oc = on;
-        if constexpr (i + 1 < NSTEP) {
-            u0n = lt.u[i + 1][c16];
-            u1n = lt.u[i + 1][c16 + 16];
-            uiin = lt.udr[i + 1][0];
-            riin = lt.udr[i + 1][1];
-            kn = gs.slot[a_rel + i + 1];
-            sn = gs.s[row][kn];
-            rsn = gs.rs[row][kn];
-            on = gs.o[row][kn];
-        }
-        asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
-        constexpr int src = i & 15;
-        const float xi = row_bcast<src>(i < 16 ? x0 : x1);
-        const float q = grid_value_fast((xi - oc) / sc, g, inv_step) / rsc + oc;
-        const double d = (double)(xi - q);
-        const double qq = d * rii;
-        const double rem = __builtin_fma(-uii, qq, d);
-        const double err = __builtin_fma(rem, rii, qq);
-        const float ef = (float)err;
-        const bool here = c16 == src;
-        if (i < 16) {
-            q0 = here ? q : q0;
-            e0 = here ? ef : e0;
-        } else {
-            q1 = here ? q : q1;
-            e1 = here ? ef : e1;
-        }
-        if (i < 15) x0 = (float)((double)x0 - err * u0);
-        if (NSTEP > 16) x1 = (float)((double)x1 - err * u1);
-    });
-    if (m0) {
-        sm.q[row][a_rel + c16] = q0;
-        sm.e[row][a_rel + c16] = e0;
+// the asymmetric group quantizer: the map entry of column a + k, then that group's s, rs and o
+struct LeafSlots {
+    const GroupSlots &gs;
+    typedef GroupQ<true> Step;
+    __device__ __forceinline__ Step at(int row, int a, int k) const {
+        const int slot = gs.slot[a + k];
+        return {gs.s[row][slot], gs.rs[row][slot], gs.o[row][slot]};
     }
-    if (m1) {
-        sm.q[row][a_rel + 16 + c16] = q1;
-        sm.e[row][a_rel + 16 + c16] = e1;
-    }
-}
+    __device__ __forceinline__ static float q(float x, Step e, const Grid g, float inv_step) { return leaf_group_q(x, e, g, inv_step); }
+};
 
 // cycle counters of workgroup 0 (SLK_WIN_DBG bit 3), read back by slk_probe_window_cycles
 __device__ long long g_win_cycles[16];
@@ -719,21 +638,17 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             if (live) {
                 x = qld(myrow, i);
                 if constexpr (OFFSET) {
-                    float sv, rsv, ov;
+                    GroupQ<true> gq = {1.0f, 1.0f, 0.0f};  // the in-LDS tile's padding rows (x = 0) past R: nothing of S or O to read
                     if (slots) {
                         const int k = gs.slot[i - w0];
-                        sv = gs.s[myrow][k], rsv = gs.rs[myrow][k], ov = gs.o[myrow][k];
+                        gq = {gs.s[myrow][k], gs.rs[myrow][k], gs.o[myrow][k]};
                     } else if (r0 + myrow < R) {
-                        const size_t k = (size_t)(r0 + myrow) * G + pg[i];
-                        sv = Sg[k], rsv = 1.0f / sv, ov = Og[k];
-                    } else {  // the in-LDS tile's padding rows (x = 0) past R: nothing of S or O to read there
-                        sv = 1.0f, rsv = 1.0f, ov = 0.0f;
+                        gq = GroupQ<true>::at(Sg, Og, (size_t)(r0 + myrow) * G + pg[i]);
                     }
-                    q = cb_value((x - ov) / sv, g) / rsv + ov;
+                    q = gq.value(x, g);
                 } else if constexpr (GROUPED) {
                     const float sv = IN_LDS ? gt.s[myrow][i - w0] : Sg[(size_t)(r0 + myrow) * G + pg[i]];
-                    const float rsv = IN_LDS ? gt.rs[myrow][i - w0] : 1.0f / sv;
-                    q = cb_value(x / sv, g) / rsv;
+                    q = GroupQ<false>{sv, IN_LDS ? gt.rs[myrow][i - w0] : 1.0f / sv}.value(x, g);
                 } else {
                     q = cb_value(x, g);
                 }
@@ -838,14 +753,14 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
                 if (!helper && !no_leaf_regs) {
                     const int w = op.b - op.a;
                     if constexpr (OFFSET) {
-                        if (w <= 16) leaf_registers_offset<16>(sm, gs, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                        else leaf_registers_offset<32>(sm, gs, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        if (w <= 16) leaf_registers<16>(sm, LeafSlots{gs}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        else leaf_registers<32>(sm, LeafSlots{gs}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
                     } else if constexpr (GROUPED) {
-                        if (w <= 16) leaf_registers_grouped<16>(sm, gt, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                        else leaf_registers_grouped<32>(sm, gt, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        if (w <= 16) leaf_registers<16>(sm, LeafTile{gt}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        else leaf_registers<32>(sm, LeafTile{gt}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
                     } else {
-                        if (w <= 16) leaf_registers<16>(sm, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                        else leaf_registers<32>(sm, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        if (w <= 16) leaf_registers<16>(sm, LeafRows{}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                        else leaf_registers<32>(sm, LeafRows{}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
                     }
                 }
                 lap(0, 0);
@@ -1057,7 +972,7 @@ __global__ void k_probe_leaf(double *out, int iters, int mode, Grid g, float inv
     if (t == 0) out[2] = (double)__builtin_amdgcn_s_getreg((4 << 11) | (0 << 6) | 4);  // HW_ID, 32 bits... low 16 here
     if (leafer || mode == 0) {
         // (with more than two leaf waves per SIMD several waves run the same four rows: garbage values, honest timing)
-        for (int it = 0; it < iters; ++it) leaf_registers<32>(sm, sm.lt[0], ((wave & 1) + ((wave >> 2) << 1)) & 3, lane, (it & 1) * 32, 32, g, inv_step);
+        for (int it = 0; it < iters; ++it) leaf_registers<32>(sm, LeafRows{}, sm.lt[0], ((wave & 1) + ((wave >> 2) << 1)) & 3, lane, (it & 1) * 32, 32, g, inv_step);
     } else if (mode == 5) {
         // companion wave on the same SIMD: back-to-back bfloat16 MFMAs (what the layer-error kernel issues)
         typedef __bf16 probe_bf16x8_t __attribute__((ext_vector_type(8)));

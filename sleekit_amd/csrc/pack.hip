@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void k_dequantize_packed(const unsigned *__res
     typedef typename PkOut<OUT>::T T;
     typedef typename PkOut<OUT>::V V;
     __shared__ float lut[256];
-    for (int k = threadIdx.x; k < g.n; k += blockDim.x) lut[k] = g.table ? g.table[k] : grid_val((float)k, g);
+    for (int k = threadIdx.x; k < g.n; k += blockDim.x) lut[k] = cb_entry(k, g);
     __syncthreads();
     const int lane = threadIdx.x & 63, l = lane & 7, top = g.n - 1;
     const int C = (n + 31) >> 5, spr = (C + 7) >> 3, G = SCALE >= 2 ? n / gsize : 1;
@@ -199,9 +199,7 @@ __global__ __launch_bounds__(256) void k_dequantize_packed(const unsigned *__res
                 if constexpr (SCALE == 1) x = x / inv;
                 if constexpr (SCALE >= 2) {
                     const int c = min(col + (quad ? 0 : e), n - 1);
-                    const size_t gi = r * G + c / gsize;
-                    x = x / (1.0f / scale[gi]);
-                    if constexpr (SCALE == 3) x = x + O[gi];
+                    x = GroupQ<SCALE == 3>::at(scale, O, r * G + c / gsize).dequant(x);
                 }
                 v[e] = PkOut<OUT>::cvt(x);
             }

@@ -19,10 +19,9 @@ namespace slk {
 
 __device__ __forceinline__ float cand_up(float q, const Grid g) { return cb_up(q, g); }
 __device__ __forceinline__ float cand_down(float q, const Grid g) { return cb_down(q, g); }
-// The group quantizer's candidates (sleekit_amd/groups.py): codebook(x / s) / (1 / s) with s the scale of x's column, both
-// float32 IEEE divides like the reference's quantizer callable
-__device__ __forceinline__ float gcand_up(float q, const Grid g, float s) { return cb_up(q / s, g) / (1.0f / s); }
-__device__ __forceinline__ float gcand_down(float q, const Grid g, float s) { return cb_down(q / s, g) / (1.0f / s); }
+// the group quantizer's candidates with s the scale of q's column (common.h, GroupQ)
+__device__ __forceinline__ float gcand_up(float q, const Grid g, float s) { return GroupQ<false>::of(s).up(q, g); }
+__device__ __forceinline__ float gcand_down(float q, const Grid g, float s) { return GroupQ<false>::of(s).down(q, g); }
 
 struct Best {
     float v;
@@ -374,7 +373,7 @@ __global__ __launch_bounds__(256) void k_local_search(const float *__restrict__ 
         const int j = t + 256 * e;
         if (j < n) {
             Q[base + j] = q[e];
-            if (idx) idx[base + j] = (uint8_t)cb_index(GS ? q[e] / srow[j / gsz] : q[e], g);  // (groups.py: indices of Q / S)
+            if (idx) idx[base + j] = (uint8_t)(GS ? GroupQ<false>::of(srow[j / gsz]).index(q[e], g) : cb_index(q[e], g));  // (groups.py: indices of Q / S)
             if (gains_mode) {
                 gains[2 * base + j] = gu[e];
                 gains[2 * base + n + j] = gd[e];
@@ -583,7 +582,7 @@ __global__ __launch_bounds__(256, (WAVES == 4 && S == 1 && CAND == 2 ? SLK_LS_WA
     for (int e = 0; e < EPT; ++e) {
         const int j = col(e);
         Q[base + j] = q[e];
-        if (idx) idx[base + j] = (uint8_t)cb_index(GS ? q[e] / srow[j / gsz] : q[e], g);
+        if (idx) idx[base + j] = (uint8_t)(GS ? GroupQ<false>::of(srow[j / gsz]).index(q[e], g) : cb_index(q[e], g));
         if (gains_mode) {
             gains[2 * base + j] = gu[e];
             gains[2 * base + n + j] = gd[e];

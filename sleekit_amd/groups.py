@@ -283,9 +283,7 @@ def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", dam
     assert min_block_size >= 1
     cb_abi = engine.require_uniform(quantizer)
     R, n = W.shape
-    g, G = _groups(n, group_size)
-    if tuple(S.shape) != (R, G):
-        raise ValueError(f"group scales must be ({R}, {G}) for a ({R}, {n}) layer with group_size {g}; got {tuple(S.shape)}")
+    g = _check_scales(S, R, n, group_size)
     if want_idx and cb_abi[0] > 256:
         raise ValueError("uint8 indices need a codebook of at most 256 entries")
     O = None
@@ -366,9 +364,7 @@ def dequantize_grouped(idx, S, codebook, group_size, offsets=None):
     idx_d = dev.to_device(idx, torch.uint8)
     Sd = dev.to_device(S)
     R, n = idx_d.shape
-    g, G = _groups(n, group_size)
-    if tuple(Sd.shape) != (R, G):
-        raise ValueError(f"group scales must be ({R}, {G}); got {tuple(Sd.shape)}")
+    g = _check_scales(Sd, R, n, group_size)
     Q = torch.empty((R, n), dtype=torch.float32, device=Sd.device)
     if offsets is not None:
         Od = _check_offsets(offsets, R, n, g)
