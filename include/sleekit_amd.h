@@ -76,7 +76,7 @@ typedef void *slk_stream_t;
  * hand the panels on through flags in memory: option "panel_split" 0 / 3; 1 / 2 = round 3's panel kernels; past 4 GiB of one
  * float64 factor, ld * ld * 8 > 2^32, always the panel kernels, whose pointers are 64-bit), whose status word can
  * read SLK_INFO_HANDOFF_TIMEOUT; the factorisation's workspace holds its flags (slk_factor_workspace_bytes_batch grew by
- * 8 * (ld / 64) bytes per matrix); new options "tall_error", "rows_below_wide".  Still 8, with entries added alongside: the
+ * 8 * (ld / 64) bytes per matrix); new option "rows_below_wide" ("tall_error" was one of ABI 8 too and is gone).  Still 8, with entries added alongside: the
  * group-scale forms slk_gptq_quantize_grouped, slk_column_miss_grouped, slk_scale_search_grouped and slk_dequantize_grouped
  * (one scale per row and per group of columns; nothing existing changed), then slk_gptq_quantize_grouped_batch (the grouped
  * loop over a batch of layers stacked by rows; slk_gptq_quantize_grouped is its batch of one), then slk_local_search_grouped (the

@@ -607,87 +607,51 @@ def test_integration_stub_runs(amd):
     assert np.array_equal(got.cpu().numpy(), amd.obq.quantize_opt(Ws, L["H"], cb))
 
 
-def test_layer_error_on_tall_tiles_is_the_square_tile_kernel(amd, slkopt):
-    """Whole layers (>= 2048 rows) CAN take 256 x 128 tiles on the bfloat16 MFMA (option tall_error; k_error_tiles_bf16_tall: two
-    images of a round in LDS, half the workgroups); the default, smaller ones and K-chunked shards are 128 x 128.  Same slabs, same six products per element,
-    same rounds: the row errors and the product G = (W - Q) H are the square-tile kernel's BIT FOR BIT -- symmetric H (half
-    the products), an H that is not symmetric (averaged planes), the full product for the local search, and a stack of layers."""
-    rng = np.random.default_rng(23)
-    R, n = 2304, 1024  # nine row tiles of 256: the XCD-aware order leaves a last partial group
-    W = torch.from_numpy(rng.standard_normal((R, n)).astype(np.float32)).cuda()
-    Q = W + 0.2 * torch.from_numpy(rng.standard_normal((R, n)).astype(np.float32)).cuda()
-    X = rng.standard_normal((2 * n, n)).astype(np.float32)
-    H = (X.T @ X / (2 * n)).astype(np.float32)
-    H = ((H + H.T) * np.float32(0.5)).astype(np.float32)
-    Ha = (H + np.float32(0.05) * np.triu(rng.standard_normal((n, n)).astype(np.float32), 1)).astype(np.float32)
-    Hs, Has = torch.from_numpy(H).cuda(), torch.from_numpy(Ha).cuda()
-
-    def both(fn):
-        square = fn()
-        slkopt.setenv("SLK_TALL_ERROR", "1")
-        tall = fn()
-        slkopt.delenv("SLK_TALL_ERROR")
-        return tall, square
-
-    for Hx in (Hs, Has):
-        tall, square = both(lambda: amd.engine.row_errors(W, Q, Hx))
-        assert torch.equal(tall, square)
-        (e1, G1), (e2, G2) = both(lambda: amd.engine.row_errors(W, Q, Hx, want_G=True))
-        assert torch.equal(e1, e2) and torch.equal(G1, G2)
-    D = (W - Q).double().cpu().numpy()
-    want = ((D @ H.astype(np.float64)) * D).sum(axis=1)
-    np.testing.assert_allclose(amd.engine.row_errors(W, Q, Hs).cpu().numpy(), want, rtol=1e-5)
-    # a stack of three layers of 768 rows (a multiple of 256) with Hessians of their own
-    H2 = torch.from_numpy(((H * np.float32(1.25)) + np.float32(0.01) * np.eye(n, dtype=np.float32))).cuda()
-    Wb, Qb = W.view(3, 768, n).contiguous(), Q.view(3, 768, n).contiguous()
-    tall, square = both(lambda: amd.engine.row_errors_batch(Wb, Qb, [Hs, H2, Has]))
-    assert torch.equal(tall, square)
-    one = amd.engine.row_errors(Wb[1].contiguous(), Qb[1].contiguous(), H2)
-    np.testing.assert_allclose(tall[1].cpu().numpy(), one.cpu().numpy(), rtol=2e-6)
-
-
-def test_layer_error_on_256_tiles(amd, slkopt):
-    """Whole layers CAN take 256 x 256 tiles (option tall_error = 2; k_error_tiles_bf16_big: K in steps of 16 through a ring of
-    three LDS images filled by global_load_lds, planes in the K16 layout).  Same six products per element and 16-k step in
-    the same order: the product G = (W - Q) H is the square-tile kernel's BIT FOR BIT; a row's partial sums are added in
-    another order (256 columns and two k blocks per slot), so the row errors agree to rounding.  Symmetric H, an H that is
-    not symmetric (averaged planes without G, the float32 kernel with it), and a stack of layers."""
-    rng = np.random.default_rng(29)
-    for R, n in ((2304, 1024), (2048, 2304)):  # nine row tiles / nine column tiles: partial patches and XCDs without a row tile
-        W = torch.from_numpy(rng.standard_normal((R, n)).astype(np.float32)).cuda()
-        Q = W + 0.2 * torch.from_numpy(rng.standard_normal((R, n)).astype(np.float32)).cuda()
-        X = rng.standard_normal((2 * n, n)).astype(np.float32)
-        H = (X.T @ X / (2 * n)).astype(np.float32)
-        H = ((H + H.T) * np.float32(0.5)).astype(np.float32)
-        Ha = (H + np.float32(0.05) * np.triu(rng.standard_normal((n, n)).astype(np.float32), 1)).astype(np.float32)
-        Hs, Has = torch.from_numpy(H).cuda(), torch.from_numpy(Ha).cuda()
-
-        def both(fn):
-            square = fn()
-            slkopt.setenv("SLK_TALL_ERROR", "2")
-            big = fn()
-            slkopt.delenv("SLK_TALL_ERROR")
-            return big, square
-
-        for Hx in (Hs, Has):
-            big, square = both(lambda: amd.engine.row_errors(W, Q, Hx))
-            np.testing.assert_allclose(big.cpu().numpy(), square.cpu().numpy(), rtol=2e-6)
-            (e1, G1), (e2, G2) = both(lambda: amd.engine.row_errors(W, Q, Hx, want_G=True))
-            if Hx is Hs:
-                assert torch.equal(G1, G2)
-            else:  # (not symmetric, G wanted: the float32 kernel here, transposed planes on the square tiles)
-                np.testing.assert_allclose(G1.cpu().numpy(), G2.cpu().numpy(), rtol=0, atol=2e-5)
-            np.testing.assert_allclose(e1.cpu().numpy(), e2.cpu().numpy(), rtol=2e-6)
-        D = (W - Q).double().cpu().numpy()
-        want = ((D @ H.astype(np.float64)) * D).sum(axis=1)
-        slkopt.setenv("SLK_TALL_ERROR", "2")
-        np.testing.assert_allclose(amd.engine.row_errors(W, Q, Hs).cpu().numpy(), want, rtol=1e-5)
-        slkopt.delenv("SLK_TALL_ERROR")
-        if R % 768 == 0:
-            H2 = torch.from_numpy(((H * np.float32(1.25)) + np.float32(0.01) * np.eye(n, dtype=np.float32))).cuda()
-            Wb, Qb = W.view(3, 768, n).contiguous(), Q.view(3, 768, n).contiguous()
-            big, square = both(lambda: amd.engine.row_errors_batch(Wb, Qb, [Hs, H2, Has]))
-            np.testing.assert_allclose(big.cpu().numpy(), square.cpu().numpy(), rtol=2e-6)
+def test_layer_error_of_whole_layers(amd, slkopt):
+    """Whole layers on the bfloat16 kernel's XCD-aware tile order: nine row tiles of 256 rows (2304 x 1024) and nine column
+    tiles of 256 (2048 x 2304), partial groups of XCDs and of column ranks, which no other error test reaches.  A symmetric H
+    (half the products) and an H that is not symmetric (averaged planes without G, planes of H^T with it): every row error
+    within 1e-5 of the float64 value, with and without the product G = (W - Q) H to 2e-6 of each other, and a stack of three
+    768-row layers to 2e-6 of the single layers.
+    G itself against the float64 product rounded to float32, as max |difference| / max |G|: the float32-MFMA kernel
+    (SLK_NO_BF16_ERROR, the form the bfloat16 kernel replaced) is measured on the same input and the default path is
+    allowed twice its figure.  Measured on an MI355X (float32 kernel / default path; the test prints them):
+        seed 23, 2304 x 1024: symmetric 2.007e-06 / 1.386e-06, not symmetric 1.416e-06 / 1.048e-06
+        seed 29, 2304 x 1024: symmetric 1.636e-06 / 1.273e-06, not symmetric 1.614e-06 / 1.162e-06
+        seed 29, 2048 x 2304: symmetric 2.437e-06 / 2.156e-06, not symmetric 2.124e-06 / 1.858e-06"""
+    for seed, shapes in ((23, ((2304, 1024),)), (29, ((2304, 1024), (2048, 2304)))):
+        rng = np.random.default_rng(seed)
+        for R, n in shapes:
+            W = torch.from_numpy(rng.standard_normal((R, n)).astype(np.float32)).cuda()
+            Q = W + 0.2 * torch.from_numpy(rng.standard_normal((R, n)).astype(np.float32)).cuda()
+            X = rng.standard_normal((2 * n, n)).astype(np.float32)
+            H = (X.T @ X / (2 * n)).astype(np.float32)
+            H = ((H + H.T) * np.float32(0.5)).astype(np.float32)
+            Ha = (H + np.float32(0.05) * np.triu(rng.standard_normal((n, n)).astype(np.float32), 1)).astype(np.float32)
+            Hs, Has = torch.from_numpy(H).cuda(), torch.from_numpy(Ha).cuda()
+            D = (W - Q).double().cpu().numpy()
+            for Hx, H64 in ((Hs, H.astype(np.float64)), (Has, Ha.astype(np.float64))):
+                G64 = D @ H64
+                want, want_G = (G64 * D).sum(axis=1), G64.astype(np.float32)
+                err = amd.engine.row_errors(W, Q, Hx)
+                np.testing.assert_allclose(err.cpu().numpy(), want, rtol=1e-5)
+                err_g, G = amd.engine.row_errors(W, Q, Hx, want_G=True)
+                np.testing.assert_allclose(err_g.cpu().numpy(), err.cpu().numpy(), rtol=2e-6)
+                slkopt.setenv("SLK_NO_BF16_ERROR", "1")
+                G32 = amd.engine.row_errors(W, Q, Hx, want_G=True)[1]
+                slkopt.delenv("SLK_NO_BF16_ERROR")
+                scale = np.abs(want_G).max()
+                f32_figure = np.abs(G32.cpu().numpy() - want_G).max() / scale
+                figure = np.abs(G.cpu().numpy() - want_G).max() / scale
+                print(f"seed {seed} {R} x {n} {'symmetric' if Hx is Hs else 'not symmetric'}: "
+                      f"G against float64, float32 kernel {f32_figure:.3e}, default path {figure:.3e}")
+                assert figure <= 2 * f32_figure, (seed, R, n, figure, f32_figure)
+            if R % 768 == 0:  # a stack of three layers of 768 rows with Hessians of their own
+                H2 = torch.from_numpy(((H * np.float32(1.25)) + np.float32(0.01) * np.eye(n, dtype=np.float32))).cuda()
+                Wb, Qb = W.view(3, 768, n).contiguous(), Q.view(3, 768, n).contiguous()
+                stack = amd.engine.row_errors_batch(Wb, Qb, [Hs, H2, Has])
+                one = amd.engine.row_errors(Wb[1].contiguous(), Qb[1].contiguous(), H2)
+                np.testing.assert_allclose(stack[1].cpu().numpy(), one.cpu().numpy(), rtol=2e-6)
 
 
 def test_layer_error_bf16_path(amd, slkopt):
