@@ -83,13 +83,14 @@ typedef void *slk_stream_t;
  * best-first search with the group quantizer's candidates), then the asymmetric group quantizer (an offset per row and group
  * beside the scale): slk_gptq_quantize_grouped_asym, slk_gptq_quantize_grouped_asym_batch, slk_column_miss_grouped_asym,
  * slk_dequantize_grouped_asym, slk_group_midpoints and slk_group_center, then bit-packed indices: slk_pack_indices,
- * slk_unpack_indices and slk_dequantize_packed.   */
+ * slk_unpack_indices and slk_dequantize_packed, then slk_gptq_quantize_batch_error (the loop that carries the layer error)
+ * and the option "no_loop_error".   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
  * measurement: "no_window2", "no_fast_leaf", "no_defer", "win_dbg", "no_regular_search", "no_fast_search_div",
  * "no_error_splitk", "error_cb", "no_sym_error", "no_bf16_error", "no_bf16_dma", "no_bf16_hessian", "no_bf16_asym", "no_sym_average",
- * "error_f32_below", "no_wave_search", "lookahead" (EVERY factorisation forks the bulk of its outer updates onto a helper stream: a measurement
+ * "error_f32_below", "no_wave_search", "no_loop_error" (see slk_gptq_quantize_batch_error), "lookahead" (EVERY factorisation forks the bulk of its outer updates onto a helper stream: a measurement
  * switch; one call at a time asks for it through slk_chol_inverse_upper_lookahead instead), "window_rows" (16 or 32 rows per
  * window workgroup, forced; 0 = 32, or 16 under SLK_LOOP_LATENCY), "panel_split" (the factorisation's panel step: 1 = two launches, diagonal tile then
  * the rest, 2 = one launch in which every workgroup below the diagonal tile repeats its pivot chain; 0 = two for batches and from 8192
@@ -274,6 +275,34 @@ int slk_gptq_quantize_batch(const float *W, const float *scale, const long long 
                             const float *table, int min_block, int num_blocks, int flags, float *Q,
                             uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream);
 size_t slk_workspace_bytes_batch(int batch, int rows_per_layer, int n);
+
+/* (e') slk_gptq_quantize_batch that also returns the layer error, carried by the loop instead of a product of its own:
+ *     row_err ((batch * rows_per_layer) float32) = (W - Q) H_b (W - Q)^T per row (obq.py:89-95 before the mean), Q being
+ *     the values this call stores, from the scaled errors E the loop keeps for its trailing updates (obq.py:115).  With
+ *     Hd = H + lambda I the damped Hessian the factor was made from, U^T U = Hd[order][:, order]^-1, error propagation gives
+ *         row_err[r] = float32(scale_r^2 * sum_j E[r][j]^2 - lambda_b * sum_j (W[r][j] - Q[r][j])^2),
+ *     lambda_b = float32(damp) * mean(diag H_b) formed as slk_hessian_prepare forms it, the differences in float32, squares
+ *     and sums in float64, scale_r = 1 without scales: one pass over E and W in the loop's last kernel (16 R n bytes
+ *     where the plain loop's moves 8 R n), no atomics -- the same inputs give the same bits on every run and stream.
+ *     H: HOST array of `batch` device pointers (as slk_row_errors_batch takes them), b = r / rows_per_layer; damp: the
+ *     damping the factor was made with.
+ *     WHEN it is the reference's error: H bit-wise symmetric (the factor reads one triangle of H, the product all of it)
+ *     and U the factor of THIS H with THIS damp in this order; nothing here checks either -- a caller that cannot vouch
+ *     for them calls slk_row_errors_batch.  HOW CLOSE: the identity is exact up to the loop's own roundings (float64
+ *     updates, float32 stores); against the float64 product the worst row is below 1e-6 relative on well-conditioned
+ *     Hessians (the reference's own float32 product: 2e-7 ... 1e-6), a few 1e-5 on a steeply decaying spectrum where the
+ *     reference's float32 product is 1e-3 off: at least as close to float64 as the reference's float32 result, and not
+ *     bit-equal to slk_row_errors_batch.
+ *     scale given: flags must hold SLK_LOOP_UNSCALE (the error is that of the de-scaled Q); SLK_E_ARG otherwise.
+ *     Everything else as slk_gptq_quantize_batch; batch = 1 serves a single layer.  Workspace:
+ *     slk_workspace_bytes_batch(batch, rows_per_layer, n) (slk_workspace_bytes(R, n) for batch = 1).
+ *     Option "no_loop_error": sleekit_amd's callers (engine.loop_error_route) then never take this entry and compute the
+ *     product as before -- an A/B switch inside one build, and a way out.                                      */
+int slk_gptq_quantize_batch_error(const float *W, const float *scale, const long long *order, const double *U,
+                                  const float *const *H, float damp, int batch, int rows_per_layer, int n, int levels,
+                                  double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
+                                  float *Q, uint8_t *idx, float *E_out, float *row_err, void *workspace, size_t ws_bytes,
+                                  slk_stream_t stream);
 
 /* Group scales.  gscale: R x G float32, positive, G = n / group_size (group_size >= 1 must divide n); element (r, c)
  * belongs to group c / group_size.  The group quantizer maps x in column c of row r to

@@ -72,6 +72,10 @@ PROTOTYPES = {
         [P, P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],
     ),
     "slk_workspace_bytes_batch": (c_size_t, [c_int, c_int, c_int]),
+    "slk_gptq_quantize_batch_error": (
+        c_int,
+        [P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P],
+    ),
     "slk_gptq_quantize_grouped": (
         c_int,
         [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],

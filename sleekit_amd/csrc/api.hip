@@ -113,7 +113,7 @@ size_t slk_workspace_bytes(int R, int n) {
     const size_t ld = (size_t)slk_factor_ld(n);
     const size_t rn = (size_t)(R > 0 ? R : 1) * (size_t)n;
     size_t factor = 2 * ld * ld * sizeof(double) + 2 * (ld / 64) * sizeof(int);  // X and S of slk_chol_inverse_upper, the chain's flags
-    size_t loop = 2 * rn * sizeof(float) + (size_t)n * sizeof(int);    // permuted Q and E, inverse order
+    size_t loop = 2 * rn * sizeof(float) + (size_t)n * sizeof(int) + 64 * sizeof(float) + 5 * 256;  // permuted Q and E, inverse order, the diagonal mean of the carried error; five aligned takes
     size_t search = rn * sizeof(float) + (size_t)(R + n) * sizeof(float) + (size_t)R * ((n + 127) / 128) * sizeof(float) + 4096;
     // layer error on the bfloat16 MFMA: three 2-byte planes of W - Q and of H, the per-tile partial sums
     size_t error = 6 * (rn + 128 * (size_t)n) + 6 * (size_t)n * n + 4 * (size_t)R * ((n + 127) / 128) * sizeof(float) + 8192;
@@ -131,7 +131,8 @@ size_t slk_workspace_bytes_batch(int batch, int rows_per_layer, int n) {
     if (batch < 1 || batch > 64 || rows_per_layer < 0 || n <= 0 || (long long)batch * rows_per_layer > 0x7fffffffLL) return 0;
     // the stacked rows as one layer, plus the operand planes of the other Hessians and the other inverse orders
     return slk_workspace_bytes(batch * rows_per_layer, n) + (size_t)(batch - 1) * 6 * (size_t)n * n +
-           (size_t)batch * n * (sizeof(int) + sizeof(float)) + 4096;  // (+ every layer's diagonal for a batched local search)
+           (size_t)batch * n * (sizeof(int) + sizeof(float)) + (size_t)(batch - 1) * 64 * sizeof(float) +
+           4096;  // (+ every layer's diagonal for a batched local search, and its mean for the loop's carried error)
 }
 
 int slk_probe_mfma_f64(double *sink, int blocks, int iters, slk_stream_t stream) {
@@ -180,6 +181,7 @@ const char *const kOptNames[OPT_COUNT] = {
     "NO_FAST_LEAF", "NO_DEFER", "NO_WINDOW2", "WIN_DBG", "NO_REGULAR_SEARCH", "NO_FAST_SEARCH_DIV",
     "NO_ERROR_SPLITK", "ERROR_CB", "NO_SYM_ERROR", "NO_BF16_ERROR", "NO_BF16_DMA", "NO_BF16_HESSIAN",
     "ERROR_F32_BELOW", "NO_BF16_ASYM", "NO_SYM_AVERAGE", "NO_WAVE_SEARCH", "LOOKAHEAD", "WINDOW_ROWS", "PANEL_SPLIT", "ROWS_BELOW_WIDE",
+    "NO_LOOP_ERROR",
 };
 std::atomic<int> g_opts[OPT_COUNT];
 std::once_flag g_opts_once;

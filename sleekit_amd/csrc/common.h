@@ -86,6 +86,7 @@ enum Opt {
     OPT_WINDOW_ROWS,           // window kernel: rows per workgroup forced to 16 or 32 (0: 32, or 16 where the caller asks for latency)
     OPT_PANEL_SPLIT,           // factorisation: 0 / 3: an outer block's panels as a chain of workgroups in one launch; 1 / 2: the panel kernel, two launches / one per panel
     OPT_ROWS_BELOW_WIDE,       // factorisation: the rows below a diagonal block 64 rows per workgroup (1) or 16 (2) whatever the batch (0: 64 from 1024 strips per launch up)
+    OPT_NO_LOOP_ERROR,         // layer error: sleekit_amd's callers never take the error the loop carries (slk_gptq_quantize_batch_error); the product instead
     OPT_COUNT
 };
 int opt(Opt o);
@@ -118,6 +119,10 @@ struct PtrTable {
 // the local search starts from (sgemm.hip; the public entries are slk_row_errors / slk_row_errors_batch)
 int row_errors_products(const float *W, const float *Q, const float *const *Hs, int batch, int rpl, int n, const int *sym_known,
                         float *row_err, float *G, void *workspace, size_t ws_bytes, slk_stream_t stream);
+
+// mean(diag Hs[b]) in float32, NumPy's order, at out[64 b] for b < batch: the means slk_hessian_prepare damps with, by the
+// kernels it forms them with (prepare.hip); what the loop's carried error takes its damping term from
+int loop_error_means(const float *const *Hs, int batch, int n, float *out, hipStream_t s);
 
 static inline hipStream_t as_stream(slk_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 

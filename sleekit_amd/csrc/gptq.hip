@@ -93,24 +93,71 @@ __global__ __launch_bounds__(256) void k_permute_in_lds(const float *__restrict_
 }
 
 // Q[r][j] = Qp[r][inv[j]];  idx[r][j] = grid index of that value (codebook.py:43-54).
+// ERR (slk_gptq_quantize_batch_error): the workgroup that writes row r of Q also reads row r of W and of the loop's scaled
+// errors E and leaves the row's error (W - Qw) H (W - Qw)^T, carried by the loop instead of a product of its own:
+//     row_err[r] = float32(scale_r^2 * sum_j E[r][j]^2 - lambda_b * sum_j (W[r][j] - Qw[r][j])^2)
+// with Qw the value STORED to Q, float32 differences, float64 squares and sums, lambda_b = damp * mean(diag H_b) the float32
+// damping term the factor was made with (hmean[64 b]: loop_error_means).  E is in processing order, W and Q in the
+// original one: the sums do not care.  One fixed-order workgroup reduction and one store per row: the same bits every run.
+struct RowErrArgs {
+    const float *W, *E, *scale, *hmean;  // scale: nullptr = 1
+    float damp;
+    float *row_err;
+};
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;  // lane 0 holds the sum
+}
+// the row's two sums over the workgroup's 256 threads, then the store (red: 8 doubles of LDS)
+__device__ __forceinline__ void row_error_store(double se, double sd, double *red, const RowErrArgs &a, int r, int rpl) {
+    se = wave_sum_f64(se);
+    sd = wave_sum_f64(sd);
+    const int t = threadIdx.x;
+    if ((t & 63) == 0) {
+        red[t >> 6] = se;
+        red[4 + (t >> 6)] = sd;
+    }
+    __syncthreads();
+    if (t == 0) {
+        const double SE = ((red[0] + red[1]) + red[2]) + red[3], SD = ((red[4] + red[5]) + red[6]) + red[7];
+        const double s = a.scale ? (double)a.scale[r] : 1.0;
+        const float lambda = a.damp * a.hmean[64 * (r / rpl)];  // float32 product, as k_diag_prepare forms it
+        a.row_err[r] = (float)((s * s) * SE - (double)lambda * SD);
+    }
+    __syncthreads();  // red is free again
+}
+
+template <bool ERR = false>
 __global__ __launch_bounds__(256) void k_permute_out(const float *__restrict__ Qp, const int *__restrict__ inv_order,
                                                      int R, int n, Grid g, const float *__restrict__ unscale,
-                                                     float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl) {
+                                                     float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl, RowErrArgs ea) {
+    __shared__ double red[ERR ? 8 : 1];
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
         const float *src = Qp + (size_t)r * n;
         const int *inv_o = inv_order + (size_t)(r / rpl) * n;
         const float inv = unscale ? 1.0f / unscale[r] : 1.0f;  // scaling.py:80: a division by the reciprocal
+        double se = 0.0, sd = 0.0;
         for (int j = threadIdx.x; j < n; j += blockDim.x) {
             const float v = src[inv_o[j]];
-            Q[(size_t)r * n + j] = unscale ? v / inv : v;
+            const float qw = unscale ? v / inv : v;
+            Q[(size_t)r * n + j] = qw;
             if (idx) idx[(size_t)r * n + j] = (uint8_t)cb_index(v, g);
+            if constexpr (ERR) {
+                const float d = ea.W[(size_t)r * n + j] - qw, e = ea.E[(size_t)r * n + j];
+                sd += (double)d * (double)d;
+                se += (double)e * (double)e;
+            }
         }
+        if constexpr (ERR) row_error_store(se, sd, red, ea, r, rpl);
     }
 }
+template <bool ERR = false>
 __global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict__ Qp, const int *__restrict__ inv_order,
                                                          int R, int n, Grid g, const float *__restrict__ unscale,
-                                                         float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl) {
+                                                         float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl, RowErrArgs ea) {
     extern __shared__ __attribute__((aligned(16))) float row[];
+    __shared__ double red[ERR ? 8 : 1];
     const int t = threadIdx.x, n4 = n >> 2;
     const int *inv_all = inv_order;
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
@@ -122,6 +169,9 @@ __global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict
         float4v_t *dst = reinterpret_cast<float4v_t *>(Q + (size_t)r * n);
         unsigned *di = idx ? reinterpret_cast<unsigned *>(idx + (size_t)r * n) : nullptr;
         const float inv = unscale ? 1.0f / unscale[r] : 1.0f;  // scaling.py:80: a division by the reciprocal
+        const float4v_t *w4 = ERR ? reinterpret_cast<const float4v_t *>(ea.W + (size_t)r * n) : nullptr;
+        const float4v_t *e4 = ERR ? reinterpret_cast<const float4v_t *>(ea.E + (size_t)r * n) : nullptr;
+        double se = 0.0, sd = 0.0;
         for (int c = t; c < n4; c += 256) {
             float4v_t v;
             unsigned packed = 0;
@@ -133,7 +183,17 @@ __global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict
             }
             dst[c] = v;
             if (idx) di[c] = packed;
+            if constexpr (ERR) {
+                const float4v_t w = w4[c], ev = e4[c];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float d = w[e] - v[e];
+                    sd += (double)d * (double)d;
+                    se += (double)ev[e] * (double)ev[e];
+                }
+            }
         }
+        if constexpr (ERR) row_error_store(se, sd, red, ea, r, rpl);
     }
 }
 
@@ -1047,10 +1107,13 @@ extern "C" int slk_gptq_quantize(const float *W, const float *scale, const long 
 // the chip idle (the window kernel runs one workgroup per 16 rows), G layers' shards together fill it.
 // gscale != nullptr: the grouped loop (slk_gptq_quantize_grouped_batch), no row scale.  Arena: Qp and Eg (R n floats
 // each), the inverse orders (batch n ints) and, grouped, the group tables (batch n ints): four 256-byte-aligned takes.
+// row_err != nullptr (slk_gptq_quantize_batch_error; Hs: host array of the layers' Hessians): the last kernel also leaves the
+// rows' errors (k_permute_out<true>), from the diagonal means of a fifth take (64 floats per layer).
 static int gptq_loop(const float *W, const float *scale, const long long *order, const double *U, int batch, int rows_per_layer,
                      int n, int levels, double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
                      float *Q, uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream,
-                     const float *gscale, int group_size, const float *goffset) {
+                     const float *gscale, int group_size, const float *goffset, const float *const *Hs = nullptr, float damp = 0.0f,
+                     float *row_err = nullptr) {
     const bool grouped = gscale != nullptr, asym = goffset != nullptr;
     const int unscale = flags & SLK_LOOP_UNSCALE;
     SLK_REQUIRE(!unscale || scale, "unscale needs the row scales");
@@ -1069,7 +1132,8 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     float *Eg = ws.take<float>((size_t)R * n);
     int *inv_order = ws.take<int>((size_t)batch * n);
     int *pg = grouped ? ws.take<int>((size_t)batch * n) : nullptr;  // group of every processing column, per layer
-    if (!Qp || !Eg || !inv_order || (grouped && !pg)) {
+    float *hmean = row_err ? ws.take<float>(64 * (size_t)batch) : nullptr;  // mean(diag H_b) at [64 b]
+    if (!Qp || !Eg || !inv_order || (grouped && !pg) || (row_err && !hmean)) {
         set_error("workspace too small for a %d x %d layer", R, n);
         return SLK_E_WS;
     }
@@ -1110,7 +1174,8 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
                           (idx == nullptr || (uintptr_t)idx % 4 == 0);
     if (perm_lds) {
         SLK_LDS_OPT_IN(k_permute_in_lds, PERM_MAX * 4);
-        SLK_LDS_OPT_IN(k_permute_out_lds, PERM_MAX * 4);
+        SLK_LDS_OPT_IN(k_permute_out_lds<false>, PERM_MAX * 4);
+        if (row_err) SLK_LDS_OPT_IN(k_permute_out_lds<true>, PERM_MAX * 4);
     }
     if (perm_lds)
         SLK_RUN("permute_in", 0, 8.0 * R * n, s, k_permute_in_lds<<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(W, scale, order, R, n, Qp, inv_order, rpl));
@@ -1218,10 +1283,21 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
         SLK_RUN("permute_out_grouped", 0, (idx ? 13.0 : 8.0) * R * n, s,
                 k_permute_out_grouped<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx, rpl,
                                                                          nullptr));
-    else if (perm_lds)
-        SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out_lds<<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl));
+    else if (row_err) {
+        // the rows' errors ride on the last kernel: 8 R n bytes more (the rows of W and E) instead of a product of its own
+        const int rc = loop_error_means(Hs, batch, n, hmean, s);
+        if (rc != SLK_OK) return rc;
+        const RowErrArgs ea{W, Eg, unscale ? scale : nullptr, hmean, damp, row_err};
+        if (perm_lds)
+            SLK_RUN("permute_out_error", 4.0 * R * n, (idx ? 17.0 : 16.0) * R * n, s,
+                    k_permute_out_lds<true><<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, ea));
+        else
+            SLK_RUN("permute_out_error", 4.0 * R * n, (idx ? 17.0 : 16.0) * R * n, s,
+                    k_permute_out<true><<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, ea));
+    } else if (perm_lds)
+        SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out_lds<false><<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, RowErrArgs{}));
     else
-        SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl));
+        SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out<false><<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, RowErrArgs{}));
     if (E_out) copy_async(E_out, Eg, sizeof(float) * (size_t)R * n, s);
     return SLK_OK;
 }
@@ -1234,6 +1310,22 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
     SLK_REQUIRE((flags & ~(SLK_LOOP_UNSCALE | SLK_LOOP_LATENCY)) == 0, "unknown flags");
     return gptq_loop(W, scale, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
                      workspace, ws_bytes, stream, nullptr, 0, nullptr);
+}
+
+// slk_gptq_quantize_batch that also leaves the rows' errors (W - Qw) H (W - Qw)^T, carried by the loop (k_permute_out<true>).
+extern "C" int slk_gptq_quantize_batch_error(const float *W, const float *scale, const long long *order, const double *U,
+                                             const float *const *H, float damp, int batch, int rows_per_layer, int n, int levels,
+                                             double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
+                                             float *Q, uint8_t *idx, float *E_out, float *row_err, void *workspace, size_t ws_bytes,
+                                             slk_stream_t stream) {
+    SLK_REQUIRE(W && U && Q && H && row_err, "null pointer");
+    SLK_REQUIRE((flags & ~(SLK_LOOP_UNSCALE | SLK_LOOP_LATENCY)) == 0, "unknown flags");
+    SLK_REQUIRE(batch >= 1 && batch <= 64, "batch must be 1..64");
+    for (int b = 0; b < batch; ++b) SLK_REQUIRE(H[b] != nullptr, "null Hessian (layer %d)", b);
+    SLK_REQUIRE(scale == nullptr || (flags & SLK_LOOP_UNSCALE),
+                "the carried error is that of the de-scaled Q: row scales need SLK_LOOP_UNSCALE");
+    return gptq_loop(W, scale, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
+                     workspace, ws_bytes, stream, nullptr, 0, nullptr, H, damp, row_err);
 }
 
 // `batch` layers with one scale per row and per group of `group_size` original columns (gscale: (batch rows_per_layer) x

@@ -567,3 +567,20 @@ int slk_hessian_prepare_batch(const float *const *H, int batch, int n, float dam
 }
 
 }  // extern "C"
+
+// The diagonal means hessian_prepare_impl damps with, alone: the same kernels at the same widths, one workgroup per layer.
+int slk::loop_error_means(const float *const *Hs, int batch, int n, float *out, hipStream_t s) {
+    SLK_REQUIRE(Hs && out && n > 0 && batch >= 1 && batch <= 64, "bad arguments");
+    PtrTable hs;
+    for (int b = 0; b < 64; ++b) hs.p[b] = b < batch ? Hs[b] : nullptr;
+    const unsigned B = (unsigned)batch;
+    if (n <= 16384) {
+        const size_t lds = (size_t)(n + 8 * (n / 128) + 8) * sizeof(float);  // heap_sum_floats(n)
+        SLK_LDS_OPT_IN(k_diag_prepare, lds);
+        SLK_RUN_W("loop_error_mean", 0, 4.0 * n * batch, batch, s,
+                  k_diag_prepare<<<dim3(1, 1, B), 256, lds, s>>>(hs, n, 0.0f, nullptr, out, nullptr, nullptr, 0));
+    } else {
+        SLK_RUN_W("loop_error_mean", 0, 4.0 * n * batch, batch, s, k_diag_mean<<<dim3(1, 1, B), 256, 0, s>>>(hs, n, n, out));
+    }
+    return SLK_OK;
+}

@@ -231,8 +231,8 @@ class HipBackend:
 
     def _symmetry(self, layer):
         """int32[1] on the device: 1 iff H is bit-wise symmetric.  A layer dict may VOUCH for it (`symmetric=True`: the caller
-        has checked, e.g. once when the statistics were loaded): no check per call then, and a searched layer's error can be
-        the one the search carries (see _run_stacked)."""
+        has checked, e.g. once when the statistics were loaded): no check per call then, and the layer's error can be the one
+        the loop or the search carries instead of a product of its own (see run_rows, _run_stacked)."""
         if layer.get("symmetric") is True:
             dev_ = layer["H"].device
             if getattr(self, "_yes", None) is None or self._yes.device != dev_:
@@ -324,13 +324,18 @@ class HipBackend:
                                                 self.act_order, self.damp, want_idx=eng.require_uniform(self.quantizer)[0] <= 256,
                                                 factor=factor[:3])
         else:
+            # a Hessian the caller vouches to be symmetric: the error comes with the search, or with the loop itself (the
+            # factor is this H's at self.damp on every rank) -- no product of its own
+            vouched = self.with_error and layer.get("symmetric") is True
             # (lookahead = "alone on the GPU": with overlapping streams the loop takes the window kernel's least-chip-time form)
             res = eng.quantize_layer(W, layer["H"], self.quantizer, sc, self.act_order, self.damp, self.moves, factor=factor[:3],
-                                     lookahead=not self.overlap,
-                                     want_ls_error=self.with_error and self.moves > 0 and layer.get("symmetric") is True)
+                                     lookahead=not self.overlap, want_ls_error=vouched and self.moves > 0,
+                                     want_loop_error=vouched and self.moves == 0 and eng.loop_error_route())
         err = None
         if res.ls_error is not None:  # carried through the search (scaled domain: times scale^2)
             err = res.ls_error if sc is None else (res.ls_error * sc) * sc
+        elif res.loop_error is not None:  # carried through the loop (of the de-scaled Q already)
+            err = res.loop_error
         elif self.with_error and len(factor) > 3:  # the verdict on H's symmetry came with the factor
             err = eng.row_errors_batch(W[None], res.Q[None], [layer["H"]], factor[3])[0]
         elif self.with_error:
@@ -465,6 +470,11 @@ class HipBackend:
                     err = (err * sc) * sc
             if self.with_error and err is None:
                 err = eng.row_errors_batch(W, Q, [lay["H"] for lay in round_layers], known)
+        elif self.with_error and all(lay.get("symmetric") is True for lay in round_layers) and eng.loop_error_route():
+            # vouched Hessians, no search: the loop carries every row's error (engine.run_loop_batch with Hs; the loop de-scales
+            # itself here whatever the order, so the error is that of the Q returned); `known` is not needed
+            Q, idx, err = eng.run_loop_batch(W, sc, order, U, cb, 32, 8, want_idx=want_idx, unscale=sc is not None,
+                                             Hs=[lay["H"] for lay in round_layers], damp=self.damp)
         else:
             Q, idx = eng.run_loop_batch(W, sc, order, U, cb, 32, 8, want_idx=want_idx, unscale=sc is not None)
             err = eng.row_errors_batch(W, Q, [lay["H"] for lay in round_layers], known) if self.with_error else None

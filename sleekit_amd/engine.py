@@ -75,10 +75,10 @@ def require_uniform(quantizer):
 class LayerResult:
     """Device tensors produced for one layer."""
 
-    __slots__ = ("Q", "idx", "order", "U", "info", "E", "ls_trace", "ls_error", "S", "O")
+    __slots__ = ("Q", "idx", "order", "U", "info", "E", "ls_trace", "ls_error", "loop_error", "S", "O")
 
     def __init__(self):
-        self.Q = self.idx = self.order = self.U = self.info = self.E = self.ls_trace = self.ls_error = None
+        self.Q = self.idx = self.order = self.U = self.info = self.E = self.ls_trace = self.ls_error = self.loop_error = None
         self.S = self.O = None  # group scales and offsets (Sleekit.quantize with offsets)
 
 
@@ -139,15 +139,37 @@ def factorize_order_only(H, n, mode, miss=None):
     return order, None, None
 
 
-def run_loop(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=True, want_E=False, unscale=False, latency=False):
+def loop_error_route():
+    """Whether callers may take the layer error the loop carries (slk_gptq_quantize_batch_error) instead of the product
+    (slk_row_errors_batch): yes unless slk_set_option("no_loop_error", 1).  The caller still has to vouch for the rest: H
+    bit-wise symmetric, the factor made from this H with this damp, the loop itself de-scaling (or no scales)."""
+    return _lib.lib.slk_get_option(b"no_loop_error") == 0
+
+
+def run_loop(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=True, want_E=False, unscale=False, latency=False,
+             H=None, damp=None):
     """The column-sequential loop on device tensors. Returns (Q, idx, E); `unscale`: Q comes back de-scaled; `latency`:
-    this layer is alone on the GPU (SLK_LOOP_LATENCY: 16-row window workgroups; same results)."""
+    this layer is alone on the GPU (SLK_LOOP_LATENCY: 16-row window workgroups; same results).
+    H (n, n) float32 and damp given: returns (Q, idx, E, row_err), row_err (R,) the rows' errors (W - Q) H (W - Q)^T carried
+    by the loop (slk_gptq_quantize_batch_error: H symmetric, U its factor at this damp; with `scale`, `unscale` is required)."""
     R, n = W.shape
     levels, lo, hi, table = cb_abi
     ws, ws_bytes = dev.workspace(R, n)
     Q = torch.empty((R, n), dtype=torch.float32, device=W.device)
     idx = torch.empty((R, n), dtype=torch.uint8, device=W.device) if want_idx else None
     E = torch.empty((R, n), dtype=torch.float32, device=W.device) if want_E else None
+    if H is not None:
+        assert H.shape == (n, n) and H.dtype == torch.float32 and H.is_contiguous() and damp is not None
+        row_err = torch.empty(R, dtype=torch.float32, device=W.device)
+        ptrs = (ctypes.c_void_p * 1)(dev.ptr(H))
+        _lib.check(
+            _lib.lib.slk_gptq_quantize_batch_error(
+                dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), ptrs, float(damp), 1, R, n, levels, lo, hi, dev.ptr(table),
+                int(min_block), int(num_blocks), (1 if unscale else 0) | (2 if latency else 0), dev.ptr(Q), dev.ptr(idx), dev.ptr(E),
+                dev.ptr(row_err), dev.ptr(ws), ws_bytes, dev.stream_handle(),
+            )
+        )
+        return Q, idx, E, row_err
     _lib.check(
         _lib.lib.slk_gptq_quantize(
             dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), R, n, levels, lo, hi, dev.ptr(table), int(min_block),
@@ -158,11 +180,13 @@ def run_loop(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=True, w
     return Q, idx, E
 
 
-def run_loop_batch(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=True, unscale=False):
+def run_loop_batch(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=True, unscale=False, Hs=None, damp=None):
     """The loop over a batch of layers stacked by rows (slk_gptq_quantize_batch).
 
     W (B, R, n) float32, scale (B, R) or None, order (B, n) int64, U (B, n, n) float64, all contiguous.
     Returns (Q, idx) shaped (B, R, n): what B calls of run_loop return, in launches that cover all B layers.
+    Hs (a list of B (n, n) float32 Hessians) and damp given: returns (Q, idx, row_err), row_err (B, R) the rows' errors carried
+    by the loop (slk_gptq_quantize_batch_error; see run_loop).
     """
     B, R, n = W.shape
     assert order.shape == (B, n) and U.shape == (B, n, n) and (scale is None or scale.shape == (B, R))
@@ -171,6 +195,19 @@ def run_loop_batch(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=T
     ws, ws_bytes = dev.workspace(R, n, batch=B)
     Q = torch.empty((B, R, n), dtype=torch.float32, device=W.device)
     idx = torch.empty((B, R, n), dtype=torch.uint8, device=W.device) if want_idx else None
+    if Hs is not None:
+        assert len(Hs) == B and damp is not None
+        assert all(H.shape == (n, n) and H.dtype == torch.float32 and H.is_contiguous() for H in Hs)
+        row_err = torch.empty((B, R), dtype=torch.float32, device=W.device)
+        ptrs = (ctypes.c_void_p * B)(*[dev.ptr(H) for H in Hs])
+        _lib.check(
+            _lib.lib.slk_gptq_quantize_batch_error(
+                dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), ptrs, float(damp), B, R, n, levels, lo, hi, dev.ptr(table),
+                int(min_block), int(num_blocks), 1 if unscale else 0, dev.ptr(Q), dev.ptr(idx), None, dev.ptr(row_err), dev.ptr(ws),
+                ws_bytes, dev.stream_handle(),
+            )
+        )
+        return Q, idx, row_err
     _lib.check(
         _lib.lib.slk_gptq_quantize_batch(
             dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), B, R, n, levels, lo, hi, dev.ptr(table), int(min_block),
@@ -287,7 +324,7 @@ def row_errors(W, Q, H, want_G=False):
 
 def quantize_layer(
     W, H, quantizer, scale=None, act_order="diag", damp=0.01, nb_ls_moves=0, min_block_size=32, num_blocks=8,
-    factor=None, unscale=True, want_idx=True, want_ls_trace=False, lookahead=True, want_ls_error=False,
+    factor=None, unscale=True, want_idx=True, want_ls_trace=False, lookahead=True, want_ls_error=False, want_loop_error=False,
 ):
     """One layer through the whole path, on device tensors.
 
@@ -298,6 +335,10 @@ def quantize_layer(
     (sleekit/obq.py:169-217).  want_ls_trace: res.ls_trace = the local search's moves (slk_local_search).
     lookahead: this layer is alone on the GPU (the default of this single-layer API; sleekit_amd.dist passes False): the
     factorisation looks ahead (see factorize) and the loop's window kernel takes 16-row workgroups (SLK_LOOP_LATENCY).
+    want_loop_error: the caller vouches that H is bit-wise symmetric (and that `factor`, if given, is H's at this damp):
+    res.loop_error = the rows' errors (W - Q) H (W - Q)^T carried by the loop (run_loop with H) -- when there is no local
+    search and the loop itself de-scales (or there are no scales); None otherwise (err / sqerr orders with scales run the loop on a
+    pre-divided copy, in the scaled domain): the caller then computes the product.
     """
     assert W.ndim == 2
     assert H.ndim == 2
@@ -327,7 +368,12 @@ def quantize_layer(
 
     # without local search the loop's last kernel de-scales on the way out (one pass over Q less)
     fused = scale is not None and unscale and nb_ls_moves == 0 and loop_scale is not None
-    res.Q, res.idx, _ = run_loop(Ws, loop_scale, res.order, res.U, cb_abi, min_block_size, num_blocks, want_idx, unscale=fused, latency=lookahead)
+    if want_loop_error and nb_ls_moves == 0 and (scale is None or fused):
+        res.Q, res.idx, _, res.loop_error = run_loop(Ws, loop_scale, res.order, res.U, cb_abi, min_block_size, num_blocks, want_idx,
+                                                     unscale=fused, latency=lookahead, H=H, damp=damp)
+    else:
+        res.Q, res.idx, _ = run_loop(Ws, loop_scale, res.order, res.U, cb_abi, min_block_size, num_blocks, want_idx, unscale=fused,
+                                     latency=lookahead)
     if nb_ls_moves > 0:
         if want_ls_error:  # the rows' errors after the moves, in the scaled domain (res.ls_error)
             res.ls_error = torch.empty(R, dtype=torch.float32, device=W.device)
