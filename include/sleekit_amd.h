@@ -392,6 +392,44 @@ int slk_dequantize_packed(const uint32_t *words, int R, int n, int bits, int lev
                           const float *scale, const float *gscale, const float *goffset, int group_size, int out_dtype, void *out,
                           slk_stream_t stream);
 
+/* MXFP4: the OCP MX block format the MI355X computes in.  A BLOCK is 32 consecutive original columns of one row
+ * (n % 32 == 0, else SLK_E_ARG); it shares one power-of-two scale, and its elements are FP4 E2M1 codes.
+ *   - element: code = sign << 3 | m, 4 bits; magnitudes m = 0 .. 7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6.  The codebook is the
+ *     15-entry table -6, -4, -3, -2, -1.5, -1, -0.5, 0, 0.5, 1, 1.5, 2, 3, 4, 6 with the midpoints as limits (a tie goes
+ *     upward); table index i < 7 is code 8 | (7 - i), otherwise code i - 7.  Code 0x8 (-0) is never written and reads back
+ *     as index 7, value +0.  An index above 14 is a caller error and is stored as code 7.
+ *   - codes: uint8 R x n / 2; byte j of a row holds column 2 j in its low nibble and column 2 j + 1 in its high nibble
+ *     (the bytes of slk_pack_indices at 4 bits applied to the codes).
+ *   - scales: uint8 R x n / 32, E8M0: byte b means 2^(b - 127).  Scales chosen here have b in [71, 253] (2^-56 .. 2^126:
+ *     s and 1 / s are normal float32); byte 255 (NaN) is never written and raises `flag` on input.
+ *   Known answers: indices 0 .. 14 in order are codes f e d c b a 9 0 1 2 3 4 5 6 7; columns with codes 1, 2, 0xf, 0 pack
+ *   to bytes 0x21 0x0f; the scale 0.0078125 is byte 120.
+ *   With such a scale s the group quantizer of slk_gptq_quantize_grouped (group_size 32, that table) is exact in every step:
+ *   Q = value(idx) / (1 / s) = +-magnitude * 2^(b - 127) bit for bit, which is what slk_mx_dequantize rebuilds.
+ * slk_mx_scale_search: per block, b0 = max(max / 6, min / -6, 1e-16) in float32 (sleekit/scaling.py:44-55), base the smallest
+ *   power of two >= b0; SLK_MX_MAX gives base; SLK_MX_MSE and SLK_MX_DIAG run the loop body of compute_min_mse_scaling
+ *   (sleekit/scaling.py:127-134) over the factors 0.125, 0.25, 0.5, 1 in this order: the error sum_j [hdiag_j] E_j^2 of the
+ *   round-to-nearest quantization with scale f * base in NumPy's summation order, the FIRST minimum kept; the result is
+ *   base * best factor (base itself where no error is below +inf).  hdiag: diag(H), n float32, with SLK_MX_DIAG only.
+ *   scales (uint8) and S (the same scales as float32), R x n / 32 each; either may be NULL.  Weights must be finite.
+ * slk_mx_pack: idx (R x n uint8 table indices) -> codes, and S (R x n / 32 float32) -> scales; either pair may be NULL.
+ *   A scale that is not a positive normal power of two sets flag[0] = 1 (DEVICE int, zeroed by the call; may be NULL).
+ * slk_mx_unpack: codes -> idx and scales -> S; either pair may be NULL.  flag[0] = 1 if a scale byte is 255.
+ * slk_mx_dequantize: out[r][c] = value(code) * 2^(b - 127), R x n float32, or that value rounded to nearest even as
+ *   bfloat16 / float16 (`out_dtype`, SLK_DTYPE_*).  flag as in slk_mx_unpack.
+ *   idx, codes and out must be aligned to 16 bytes (SLK_E_ARG otherwise). */
+#define SLK_MX_MAX 0
+#define SLK_MX_MSE 1
+#define SLK_MX_DIAG 2
+int slk_mx_scale_search(const float *W, const float *hdiag, int mode, int R, int n, uint8_t *scales, float *S,
+                        slk_stream_t stream);
+int slk_mx_pack(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag,
+                slk_stream_t stream);
+int slk_mx_unpack(const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag,
+                  slk_stream_t stream);
+int slk_mx_dequantize(const uint8_t *codes, const uint8_t *scales, int R, int n, int out_dtype, void *out, int *flag,
+                      slk_stream_t stream);
+
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */
 int slk_row_errors(const float *W, const float *Q, const float *H, int R, int n, float *row_err,

@@ -1,6 +1,6 @@
 """sleekit_amd: MI355X-native GPTQ/OBQ layer quantization behind the sleekit function surface.
 
-    from sleekit_amd import obq, scaling, codebook, groups, packing, Sleekit
+    from sleekit_amd import obq, scaling, codebook, groups, packing, mx, Sleekit
 
 mirrors `sleekit.obq`, `sleekit.scaling`, `sleekit.codebook` and `sleekit.Sleekit` of
 Coloquinte/sleekit for the hot path.  Submodules are imported lazily
@@ -14,7 +14,7 @@ import importlib
 # queue count to the process environment: the GPU is shared, and more queues per process than the machine allows are not
 # ours to take.)
 
-_SUBMODULES = ("codebook", "obq", "scaling", "statistics", "engine", "dist", "synth", "groups", "packing", "_lib", "_device")
+_SUBMODULES = ("codebook", "obq", "scaling", "statistics", "engine", "dist", "synth", "groups", "packing", "mx", "_lib", "_device")
 
 
 def __getattr__(name):

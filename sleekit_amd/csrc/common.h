@@ -230,6 +230,51 @@ struct GroupQ {
     __device__ __forceinline__ float down(float x, const Grid g) const { return dequant(cb_down(scaled(x), g)); }
 };
 
+// Cross-lane steps on the vector ALU (DPP) instead of the LDS crossbar (__shfl_xor compiles to ds_bpermute_b32: ~150 cycles
+// each, six dependent levels per reduction, three reductions per move -- a third of a move's time).  A butterfly level only
+// needs SOME lane of the partner group once the earlier levels have made the groups uniform:
+//   xor 1, xor 2: quad_perm;  xor 4: row_half_mirror (lane i <-> 7 - i of each 8);  xor 8: row_mirror (i <-> 15 - i of each 16);
+//   across the four 16-lane rows: v_readlane of lanes 0, 16, 32, 48.
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
+}
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int x) {
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true);
+}
+constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140;
+
+// Output element types of the de-quantizers (pack.hip, mx.hip): float32, or that value rounded to nearest even.
+enum { PK_F32 = 0, PK_BF16 = 1, PK_F16 = 2 };
+
+__device__ __forceinline__ unsigned short pk_bf16(float f) {  // round to nearest even, quiet NaN (torch's conversion)
+    const unsigned u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <int OUT>
+struct PkOut;
+template <>
+struct PkOut<PK_F32> {
+    typedef float T;
+    typedef float V __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ float cvt(float v) { return v; }
+};
+template <>
+struct PkOut<PK_BF16> {
+    typedef unsigned short T;
+    typedef unsigned short V __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ unsigned short cvt(float v) { return pk_bf16(v); }
+};
+template <>
+struct PkOut<PK_F16> {
+    typedef _Float16 T;
+    typedef _Float16 V __attribute__((ext_vector_type(4)));
+    static __device__ __forceinline__ _Float16 cvt(float v) { return (_Float16)v; }
+};
+
 // Broadcast lane `src` (wave-uniform index) of a double to the whole wave through SGPRs.
 __device__ __forceinline__ double readlane_f64(double v, int src) {
     const long long b = __double_as_longlong(v);

@@ -131,35 +131,6 @@ __global__ __launch_bounds__(256) void k_unpack_indices(const unsigned *__restri
 // value rounded to nearest even).  The codebook's values sit in LDS: index k reads value min(k, levels - 1), formed like
 // the quantizer's (k * step + zero in float32) or read from the table.  ALIGNED: n % 4 == 0 and an output base aligned
 // to 4 elements, so a lane's four values are one vector store.
-enum { PK_F32 = 0, PK_BF16 = 1, PK_F16 = 2 };
-
-__device__ __forceinline__ unsigned short pk_bf16(float f) {  // round to nearest even, quiet NaN (torch's conversion)
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-template <int OUT>
-struct PkOut;
-template <>
-struct PkOut<PK_F32> {
-    typedef float T;
-    typedef float V __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ float cvt(float v) { return v; }
-};
-template <>
-struct PkOut<PK_BF16> {
-    typedef unsigned short T;
-    typedef unsigned short V __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ unsigned short cvt(float v) { return pk_bf16(v); }
-};
-template <>
-struct PkOut<PK_F16> {
-    typedef _Float16 T;
-    typedef _Float16 V __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ _Float16 cvt(float v) { return (_Float16)v; }
-};
-
 template <int SCALE, int OUT, bool ALIGNED>
 __global__ __launch_bounds__(256) void k_dequantize_packed(const unsigned *__restrict__ words, int R, int n, int b, Grid g,
                                                            const float *__restrict__ scale, int gsize, const float *__restrict__ O,

@@ -45,20 +45,7 @@ __device__ __forceinline__ void pick_first_max(Best &b, float v, int j, float q)
     b.j = take ? j : b.j;
     b.q = take ? q : b.q;
 }
-// Cross-lane steps on the vector ALU (DPP) instead of the LDS crossbar (__shfl_xor compiles to ds_bpermute_b32: ~150 cycles
-// each, six dependent levels per reduction, three reductions per move -- a third of a move's time).  A butterfly level only
-// needs SOME lane of the partner group once the earlier levels have made the groups uniform:
-//   xor 1, xor 2: quad_perm;  xor 4: row_half_mirror (lane i <-> 7 - i of each 8);  xor 8: row_mirror (i <-> 15 - i of each 16);
-//   across the four 16-lane rows: v_readlane of lanes 0, 16, 32, 48.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int x) {
-    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true);
-}
-constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140;
+// (the DPP steps dpp_f / dpp_i and their controls: common.h)
 __device__ __forceinline__ float lane_f(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
 
 // sum over the wave in the order of six xor-butterfly levels (1, 2, 4, 8, 16, 32): every lane ends with

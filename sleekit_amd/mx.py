@@ -1,0 +1,211 @@
+"""MXFP4: the block format the MI355X computes in, as an output of the quantizer.
+
+    S, E = compute_mx_scales(W, H, mode="mse")           # power-of-two scales (R, n / 32): float32, and E8M0 bytes
+    res = quantize_mxfp4(W, H, nb_ls_moves=10)            # MXResult(Q, idx, S, codes, scales)
+    res.Q == dequantize_mxfp4(res.codes, res.scales)      # bit for bit; dtype=torch.bfloat16 / float16: == Q.to(dtype)
+    codes, scales = pack_mxfp4(idx, S);  idx, S = unpack_mxfp4(codes, scales)
+
+FORMAT.  A block is BLOCK = 32 consecutive original columns of one row (n % 32 != 0: ValueError).
+  elements  FP4 E2M1, code = sign << 3 | m, magnitudes m = 0 .. 7: 0, 0.5, 1, 1.5, 2, 3, 4, 6.  The codebook E2M1 is the
+            15-entry table -6 .. 6 whose limits are the midpoints (a tie goes upward); table index i < 7 is code
+            8 | (7 - i), otherwise i - 7.  Code 0x8 (-0) is never written and reads back as index 7, value +0; an index
+            above 14 is a caller error and is stored as code 7.
+  codes     uint8 (R, n / 2): byte j of a row holds column 2 j in its low nibble, column 2 j + 1 in its high nibble --
+            packing.pack_indices(code, 4) viewed as bytes.
+  scales    uint8 (R, n / 32), E8M0: byte b means 2^(b - 127).  Scales chosen here have b in [71, 253] (2^-56 .. 2^126, so s
+            and 1 / s are normal float32); byte 255 (NaN) is never written and is a ValueError on input.
+Known answers: indices 0 .. 14 are codes f e d c b a 9 0 1 2 3 4 5 6 7; columns with codes [1, 2, 0xf, 0] pack to bytes
+[0x21, 0x0f]; the scale 0.0078125 is byte 120.
+
+SCALES.  For every (row, block): b0 = compute_non_saturating_scaling(block, E2M1) (sleekit/scaling.py:44-55), base the
+smallest power of two >= b0; mode "max" gives base, "mse" and "diag" run the reference's loop body (scaling.py:127-134)
+over the factors 0.125, 0.25, 0.5, 1 instead of its linspace -- quantize_with_scaling at f * base, the error with None or
+diag(H) of the block's columns as a float32 row sum in NumPy's order, the first minimum kept -- and give base * best factor.
+(Where no error is below +inf -- squares that overflow float32 -- the reference's answer is not a scale; base is kept.)
+
+THE LOOP is groups.quantize_layer_grouped(W, S, E2M1, H, 32, ...) untouched: with a power-of-two s every step of the group
+quantizer codebook(x / s) / (1 / s) is exact, so Q is +-magnitude * 2^(b - 127) bit for bit and the packed form loses nothing.
+
+Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
+everything runs on the GPU on the current stream, and there is no CPU fallback.
+"""
+
+import collections
+
+import numpy as np
+import torch
+
+from . import _device as dev
+from . import _lib
+from . import groups
+from .codebook import Codebook
+
+BLOCK = 32
+E2M1 = Codebook([-6, -4, -3, -2, -1.5, -1, -0.5, 0, 0.5, 1, 1.5, 2, 3, 4, 6])
+
+MXResult = collections.namedtuple("MXResult", "Q idx S codes scales")
+
+_MODES = {"max": _lib.MX_MAX, "mse": _lib.MX_MSE, "diag": _lib.MX_DIAG}
+_OUT = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def _blocks(n):
+    if n < BLOCK or n % BLOCK != 0:
+        raise ValueError(f"MX blocks are {BLOCK} columns: the column count must be a positive multiple of {BLOCK} (got {n})")
+    return n // BLOCK
+
+
+def _matrix(x, what, dtypes):
+    if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 2:
+        raise ValueError(f"{what} must be a 2-D NumPy array or torch tensor")
+    if x.dtype not in dtypes:
+        raise ValueError(f"{what} must be {dtypes[0]} (got {x.dtype})")
+    if x.shape[0] < 1 or x.shape[0] >= 1 << 31 or x.shape[1] >= 1 << 31:
+        raise ValueError(f"{what} must have 1 <= rows, columns < 2^31 (got {tuple(x.shape)})")
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def _aligned(t):
+    """The kernels move 16 bytes a lane: a contiguous view that starts off such a boundary is copied."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _raise_flag(flag, message):
+    if flag is not None and int(flag.item()):
+        raise ValueError(message)
+
+
+def compute_mx_scales(W, H=None, mode="mse"):
+    """(S, E): the blocks' power-of-two scales as float32 and as E8M0 bytes, (R, n / 32) each (module docstring).
+    mode "max", "mse" or "diag"; "diag" weighs the errors with diag(H) and needs H."""
+    if mode not in _MODES:
+        raise ValueError(f'MX scale modes are "max", "mse" and "diag" (got "{mode}")')
+    if mode == "diag" and H is None:
+        raise ValueError('scale mode "diag" needs the Hessian H')
+    R, n = _matrix(W, "W", (torch.float32, np.float32))
+    G = _blocks(n)
+    Wd = dev.to_device(W)
+    hd = None
+    if mode == "diag":
+        Hd = dev.to_device(H)
+        if tuple(Hd.shape) != (n, n):
+            raise ValueError(f"H must be ({n}, {n}); got {tuple(Hd.shape)}")
+        hd = Hd.diagonal().contiguous()
+    S = torch.empty((R, G), dtype=torch.float32, device=Wd.device)
+    E = torch.empty((R, G), dtype=torch.uint8, device=Wd.device)
+    _lib.check(_lib.lib.slk_mx_scale_search(dev.ptr(Wd), dev.ptr(hd), _MODES[mode], R, n, dev.ptr(E), dev.ptr(S), dev.stream_handle()))
+    return dev.like_input(S, W), dev.like_input(E, W)
+
+
+def _pack(idx_d, S_d, R, n):
+    """(codes, scales) of device idx (R, n) and / or S (R, n / 32); either may be None."""
+    device = (idx_d if idx_d is not None else S_d).device
+    codes = torch.empty((R, n // 2), dtype=torch.uint8, device=device) if idx_d is not None else None
+    scales = torch.empty((R, n // BLOCK), dtype=torch.uint8, device=device) if S_d is not None else None
+    flag = torch.empty(1, dtype=torch.int32, device=device) if S_d is not None else None
+    _lib.check(_lib.lib.slk_mx_pack(dev.ptr(idx_d), dev.ptr(S_d), R, n, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
+    _raise_flag(flag, "MX scales must be positive powers of two in 2^-126 .. 2^127 (E8M0)")
+    return codes, scales
+
+
+def _unpack(codes_d, scales_d, R, n):
+    device = (codes_d if codes_d is not None else scales_d).device
+    idx = torch.empty((R, n), dtype=torch.uint8, device=device) if codes_d is not None else None
+    S = torch.empty((R, n // BLOCK), dtype=torch.float32, device=device) if scales_d is not None else None
+    flag = torch.empty(1, dtype=torch.int32, device=device) if scales_d is not None else None
+    _lib.check(_lib.lib.slk_mx_unpack(dev.ptr(codes_d), dev.ptr(scales_d), R, n, dev.ptr(idx), dev.ptr(S), dev.ptr(flag), dev.stream_handle()))
+    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
+    return idx, S
+
+
+def _check_scale_shape(x, R, n, what):
+    if tuple(x.shape) != (R, n // BLOCK):
+        raise ValueError(f"{what} must be ({R}, {n // BLOCK}) for a ({R}, {n}) layer; got {tuple(x.shape)}")
+
+
+def pack_mxfp4(idx, S):
+    """uint8 table indices (R, n) and float32 power-of-two scales (R, n / 32) -> (codes uint8 (R, n / 2), scales uint8
+    (R, n / 32)).  A scale that is not a power of two E8M0 holds: ValueError."""
+    R, n = _matrix(idx, "indices", (torch.uint8, np.uint8))
+    _blocks(n)
+    _matrix(S, "scales", (torch.float32, np.float32))
+    _check_scale_shape(S, R, n, "scales")
+    codes, scales = _pack(_aligned(dev.to_device(idx, torch.uint8)), dev.to_device(S), R, n)
+    return dev.like_input(codes, idx), dev.like_input(scales, idx)
+
+
+def unpack_mxfp4(codes, scales):
+    """(codes (R, n / 2), scales (R, n / 32)) -> (idx uint8 (R, n), S float32 (R, n / 32))."""
+    R, half = _matrix(codes, "codes", (torch.uint8, np.uint8))
+    n = 2 * half
+    _blocks(n)
+    _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(scales, R, n, "scale bytes")
+    idx, S = _unpack(_aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), R, n)
+    return dev.like_input(idx, codes), dev.like_input(S, codes)
+
+
+def encode_scales(S):
+    """float32 power-of-two scales (R, G) -> E8M0 bytes (R, G); anything E8M0 does not hold: ValueError."""
+    R, G = _matrix(S, "scales", (torch.float32, np.float32))
+    return dev.like_input(_pack(None, dev.to_device(S), R, G * BLOCK)[1], S)
+
+
+def decode_scales(E):
+    """E8M0 bytes (R, G) -> float32 scales 2^(b - 127); byte 255: ValueError."""
+    R, G = _matrix(E, "scale bytes", (torch.uint8, np.uint8))
+    return dev.like_input(_unpack(None, dev.to_device(E, torch.uint8), R, G * BLOCK)[1], E)
+
+
+def dequantize_mxfp4(codes, scales, dtype=torch.float32):
+    """The layer rebuilt from its packed form: (R, n) of `dtype` (float32: bit for bit the Q that was packed; bfloat16 or
+    float16: that value rounded to nearest even, `.to(dtype)`).  NumPy input gives a NumPy array, which has no bfloat16."""
+    if dtype not in _OUT:
+        raise ValueError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16 (got {dtype})")
+    if isinstance(codes, np.ndarray) and dtype == torch.bfloat16:
+        raise ValueError("NumPy has no bfloat16: pass the codes as a device tensor for a bfloat16 result")
+    R, half = _matrix(codes, "codes", (torch.uint8, np.uint8))
+    n = 2 * half
+    _blocks(n)
+    _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(scales, R, n, "scale bytes")
+    cd, sd = _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8)
+    out = torch.empty((R, n), dtype=dtype, device=cd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=cd.device)
+    _lib.check(_lib.lib.slk_mx_dequantize(dev.ptr(cd), dev.ptr(sd), R, n, _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.stream_handle()))
+    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
+    return dev.like_input(out, codes)
+
+
+def quantize_layer_mxfp4(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_moves=0, scales=None, min_block_size=32,
+                         num_blocks=8, want_ls_trace=False):
+    """quantize_mxfp4 on device tensors (W (R, n), H (n, n), float32): (MXResult of device tensors, the grouped loop's
+    engine.LayerResult; want_ls_trace: with the moves taken in its ls_trace)."""
+    R, n = W.shape
+    _blocks(n)
+    if scales is None:
+        S = compute_mx_scales(W, H, scale_mode)[0]
+    else:
+        S = dev.to_device(scales)
+        _check_scale_shape(S, R, n, "scales")
+    res = groups.quantize_layer_grouped(W, S, E2M1, H, BLOCK, act_order, damp, min_block_size, num_blocks, nb_ls_moves=nb_ls_moves,
+                                        want_ls_trace=want_ls_trace)
+    codes, E = _pack(res.idx, S, R, n)  # (scales given by the caller are checked here: not a power of two, ValueError)
+    return MXResult(res.Q, res.idx, S, codes, E), res
+
+
+def quantize_mxfp4(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_moves=0, scales=None, min_block_size=32,
+                   num_blocks=8):
+    """GPTQ-style quantization of one layer to MXFP4: the scales of compute_mx_scales(W, H, scale_mode) (or `scales`,
+    float32 powers of two (R, n / 32)), groups.quantize_layer_grouped with the E2M1 codebook and groups of 32 (nb_ls_moves of
+    its local search after the loop, up to 16384 columns), then the pack.  Returns MXResult(Q, idx, S, codes, scales):
+    Q float32 de-scaled like W, idx the uint8 table indices, S the float32 scales, codes and scales the packed form."""
+    _matrix(W, "W", (torch.float32, np.float32))
+    if H is None or H.ndim != 2 or tuple(H.shape) != (W.shape[1], W.shape[1]):
+        raise ValueError(f"H must be ({W.shape[1]}, {W.shape[1]})")
+    if scale_mode not in _MODES:
+        raise ValueError(f'MX scale modes are "max", "mse" and "diag" (got "{scale_mode}")')
+    _blocks(int(W.shape[1]))
+    out, _ = quantize_layer_mxfp4(dev.to_device(W), dev.to_device(H), act_order, damp, scale_mode, nb_ls_moves, scales,
+                                  min_block_size, num_blocks)
+    return MXResult(*(dev.like_input(t, W) for t in out))

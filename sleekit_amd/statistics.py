@@ -193,6 +193,28 @@ class Sleekit:
             self.layer.bias.data += shift.to(self.layer.bias.dtype)
         return result
 
+    def quantize_mxfp4(self, scale_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0):
+        """The layer's weight replaced by its MXFP4 quantization, in place (sleekit_amd.mx): power-of-two scales per block of
+        32 input features (scale_mode "max", "mse" or "diag"), FP4 E2M1 elements, nb_ls_moves of the local search after the
+        loop.  bias_correction as in `quantize`.  The result (the grouped loop's) carries S, and the packed form as
+        result.codes (uint8 (out, features / 2)) and result.scales (E8M0 bytes (out, features / 32))."""
+        from . import mx
+
+        weight = self.layer.weight.data.flatten(1).float().contiguous()
+        H = self.hessian
+        if bias_correction:
+            centred = torch.empty_like(H)
+            _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
+            H = centred
+        packed, result = mx.quantize_layer_mxfp4(weight, H, order_mode, damp, scale_mode, nb_ls_moves)
+        result.S, result.codes, result.scales = packed.S, packed.codes, packed.scales
+        target = self.layer.weight
+        target.data = result.Q.reshape(target.shape).to(target.dtype)
+        if bias_correction:
+            shift = ((weight - result.Q) * self.mean).sum(dim=1)
+            self.layer.bias.data += shift.to(self.layer.bias.dtype)
+        return result
+
     def free(self):
         self.layer = self.mean = self.hessian = None
         self.count = 0
