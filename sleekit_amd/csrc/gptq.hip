@@ -45,51 +45,61 @@ struct OpTable {
 // the plain kernels.
 constexpr int PERM_MAX = 16384;
 
-// Qp[r][c] = W[r][order[c]] (/ scale[r]);  E is cleared by the window kernels as they go.
+// One body for both forms of a row gather.  LDS: the source row is read from its copy in LDS (rowbuf), four elements an iteration,
+// 16-byte stores; otherwise straight from global memory, one element an iteration.
+template <bool LDS>
+__device__ __forceinline__ void stage_row(float *rowbuf, const float *src, int n) {
+    if constexpr (LDS) {
+        __syncthreads();  // the previous row's gathers are done
+        for (int c = threadIdx.x; c < (n >> 2); c += 256) reinterpret_cast<float4v_t *>(rowbuf)[c] = reinterpret_cast<const float4v_t *>(src)[c];
+        __syncthreads();
+    }
+}
+template <int V>
+__device__ __forceinline__ void load_elems(const float *p, float (&v)[V]) {
+    if constexpr (V == 4) {
+        const float4v_t x = *reinterpret_cast<const float4v_t *>(p);
+        v[0] = x[0], v[1] = x[1], v[2] = x[2], v[3] = x[3];
+    } else {
+        v[0] = *p;
+    }
+}
+template <int V>
+__device__ __forceinline__ void store_elems(float *p, const float (&v)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4v_t *>(p) = (float4v_t){v[0], v[1], v[2], v[3]};
+    else *p = v[0];
+}
+
+// Qp[r][c] = W[r][order[c]] (/ scale[r]);  E is cleared by the window kernels as they go.  order == nullptr (never with LDS):
+// the identity.
+template <bool LDS>
 __global__ __launch_bounds__(256) void k_permute_in(const float *__restrict__ W, const float *__restrict__ scale,
                                                     const long long *__restrict__ order, int R, int n,
                                                     float *__restrict__ Qp, int *__restrict__ inv_order, int rpl) {
+    extern __shared__ __attribute__((aligned(16))) float rowbuf[];  // (LDS only)
+    constexpr int V = LDS ? 4 : 1;
+    const int t = threadIdx.x;
     // (a batch of layers stacked by rows: rows [b rpl, (b + 1) rpl) follow order[b], inv_order[b])
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
         const float *src = W + (size_t)r * n;
-        float *dst = Qp + (size_t)r * n;
-        const long long *ord = order ? order + (size_t)(r / rpl) * n : nullptr;
-        if (scale) {
-            const float s = scale[r];
-            for (int c = threadIdx.x; c < n; c += blockDim.x) dst[c] = src[ord ? ord[c] : c] / s;
-        } else {
-            for (int c = threadIdx.x; c < n; c += blockDim.x) dst[c] = src[ord ? ord[c] : c];
-        }
-    }
-    for (int b = blockIdx.x; b < (R + rpl - 1) / rpl; b += gridDim.x)
-        for (int c = threadIdx.x; c < n; c += blockDim.x) inv_order[(size_t)b * n + (order ? order[(size_t)b * n + c] : c)] = c;
-}
-__global__ __launch_bounds__(256) void k_permute_in_lds(const float *__restrict__ W, const float *__restrict__ scale,
-                                                        const long long *__restrict__ order, int R, int n,
-                                                        float *__restrict__ Qp, int *__restrict__ inv_order, int rpl) {
-    extern __shared__ __attribute__((aligned(16))) float row[];
-    const int t = threadIdx.x, n4 = n >> 2;
-    const long long *order_all = order;
-    for (int r = blockIdx.x; r < R; r += gridDim.x) {
-        order = order_all + (size_t)(r / rpl) * n;
-        const float4v_t *src = reinterpret_cast<const float4v_t *>(W + (size_t)r * n);
-        __syncthreads();  // the previous row's gathers are done
-        for (int c = t; c < n4; c += 256) reinterpret_cast<float4v_t *>(row)[c] = src[c];
-        __syncthreads();
+        const long long *ord = (LDS || order) ? order + (size_t)(r / rpl) * n : nullptr;
+        stage_row<LDS>(rowbuf, src, n);
         const float s = scale ? scale[r] : 1.0f;
-        float4v_t *dst = reinterpret_cast<float4v_t *>(Qp + (size_t)r * n);
-        for (int c = t; c < n4; c += 256) {
-            float4v_t v;
+        for (int c = V * t; c < n; c += V * 256) {
+            long long from[V];  // all of an iteration's order entries first: wide loads, in flight together
+            float v[V];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float x = row[order[4 * c + e]];
+            for (int e = 0; e < V; ++e) from[e] = (LDS || ord) ? ord[c + e] : c + e;
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float x = LDS ? rowbuf[from[e]] : src[from[e]];
                 v[e] = scale ? x / s : x;
             }
-            dst[c] = v;
+            store_elems<V>(Qp + (size_t)r * n + c, v);
         }
     }
     for (int b = blockIdx.x; b < (R + rpl - 1) / rpl; b += gridDim.x)
-        for (int c = t; c < n; c += 256) inv_order[(size_t)b * n + order_all[(size_t)b * n + c]] = c;
+        for (int c = t; c < n; c += 256) inv_order[(size_t)b * n + (order ? order[(size_t)b * n + c] : c)] = c;
 }
 
 // Q[r][j] = Qp[r][inv[j]];  idx[r][j] = grid index of that value (codebook.py:43-54).
@@ -128,66 +138,40 @@ __device__ __forceinline__ void row_error_store(double se, double sd, double *re
     __syncthreads();  // red is free again
 }
 
-template <bool ERR = false>
+template <bool LDS, bool ERR>
 __global__ __launch_bounds__(256) void k_permute_out(const float *__restrict__ Qp, const int *__restrict__ inv_order,
                                                      int R, int n, Grid g, const float *__restrict__ unscale,
                                                      float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl, RowErrArgs ea) {
+    extern __shared__ __attribute__((aligned(16))) float rowbuf[];  // (LDS only)
     __shared__ double red[ERR ? 8 : 1];
+    constexpr int V = LDS ? 4 : 1;
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
         const float *src = Qp + (size_t)r * n;
         const int *inv_o = inv_order + (size_t)(r / rpl) * n;
+        stage_row<LDS>(rowbuf, src, n);
         const float inv = unscale ? 1.0f / unscale[r] : 1.0f;  // scaling.py:80: a division by the reciprocal
         double se = 0.0, sd = 0.0;
-        for (int j = threadIdx.x; j < n; j += blockDim.x) {
-            const float v = src[inv_o[j]];
-            const float qw = unscale ? v / inv : v;
-            Q[(size_t)r * n + j] = qw;
-            if (idx) idx[(size_t)r * n + j] = (uint8_t)cb_index(v, g);
-            if constexpr (ERR) {
-                const float d = ea.W[(size_t)r * n + j] - qw, e = ea.E[(size_t)r * n + j];
-                sd += (double)d * (double)d;
-                se += (double)e * (double)e;
-            }
-        }
-        if constexpr (ERR) row_error_store(se, sd, red, ea, r, rpl);
-    }
-}
-template <bool ERR = false>
-__global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict__ Qp, const int *__restrict__ inv_order,
-                                                         int R, int n, Grid g, const float *__restrict__ unscale,
-                                                         float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl, RowErrArgs ea) {
-    extern __shared__ __attribute__((aligned(16))) float row[];
-    __shared__ double red[ERR ? 8 : 1];
-    const int t = threadIdx.x, n4 = n >> 2;
-    const int *inv_all = inv_order;
-    for (int r = blockIdx.x; r < R; r += gridDim.x) {
-        inv_order = inv_all + (size_t)(r / rpl) * n;
-        const float4v_t *src = reinterpret_cast<const float4v_t *>(Qp + (size_t)r * n);
-        __syncthreads();
-        for (int c = t; c < n4; c += 256) reinterpret_cast<float4v_t *>(row)[c] = src[c];
-        __syncthreads();
-        float4v_t *dst = reinterpret_cast<float4v_t *>(Q + (size_t)r * n);
-        unsigned *di = idx ? reinterpret_cast<unsigned *>(idx + (size_t)r * n) : nullptr;
-        const float inv = unscale ? 1.0f / unscale[r] : 1.0f;  // scaling.py:80: a division by the reciprocal
-        const float4v_t *w4 = ERR ? reinterpret_cast<const float4v_t *>(ea.W + (size_t)r * n) : nullptr;
-        const float4v_t *e4 = ERR ? reinterpret_cast<const float4v_t *>(ea.E + (size_t)r * n) : nullptr;
-        double se = 0.0, sd = 0.0;
-        for (int c = t; c < n4; c += 256) {
-            float4v_t v;
-            unsigned packed = 0;
+        for (int j = V * threadIdx.x; j < n; j += V * 256) {
+            float qw[V];
+            unsigned packed = 0;  // the elements' indices, one byte each
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = row[inv_order[4 * c + e]];
-                if (idx) packed |= (unsigned)(cb_index(v[e], g) & 255) << (8 * e);
-                if (unscale) v[e] = v[e] / inv;
+            for (int e = 0; e < V; ++e) {
+                const float v = LDS ? rowbuf[inv_o[j + e]] : src[inv_o[j + e]];
+                if (idx) packed |= (unsigned)(cb_index(v, g) & 255) << (8 * e);
+                qw[e] = unscale ? v / inv : v;
             }
-            dst[c] = v;
-            if (idx) di[c] = packed;
+            store_elems<V>(Q + (size_t)r * n + j, qw);
+            if (idx) {
+                if constexpr (LDS) *reinterpret_cast<unsigned *>(idx + (size_t)r * n + j) = packed;
+                else idx[(size_t)r * n + j] = (uint8_t)packed;
+            }
             if constexpr (ERR) {
-                const float4v_t w = w4[c], ev = e4[c];
+                float w[V], ev[V];
+                load_elems<V>(ea.W + (size_t)r * n + j, w);
+                load_elems<V>(ea.E + (size_t)r * n + j, ev);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float d = w[e] - v[e];
+                for (int e = 0; e < V; ++e) {
+                    const float d = w[e] - qw[e];
                     sd += (double)d * (double)d;
                     se += (double)ev[e] * (double)ev[e];
                 }
@@ -196,10 +180,17 @@ __global__ __launch_bounds__(256) void k_permute_out_lds(const float *__restrict
         if constexpr (ERR) row_error_store(se, sd, red, ea, r, rpl);
     }
 }
+// one launch of either permute kernel: the LDS form stages a row of n floats
+template <class K, class... A>
+static int launch_permute(const char *name, double flops, double bytes, K kernel, bool lds, int R, int n, hipStream_t s, A... args) {
+    if (lds) SLK_LDS_OPT_IN(kernel, PERM_MAX * 4);
+    SLK_RUN(name, flops, bytes, s, kernel<<<R < 2048 ? R : 2048, 256, lds ? (size_t)n * 4 : 0, s>>>(args...));
+    return SLK_OK;
+}
 
 // ------------------------------------------------------------------ group scales (slk_gptq_quantize_grouped_batch)
 // S (R x G, G = n / gsize) holds one scale per row and per group of gsize ORIGINAL columns; the loop runs on the
-// unscaled weights and only its leaves scale (see leaf_registers and LeafTile).  pg[b n + c] = group of processing column c
+// unscaled weights and only its leaves scale (see leaf_chain16 and LeafTile).  pg[b n + c] = group of processing column c
 // of layer b (a batch of layers stacked by rows, `batch` rows of order; no order: batch 1, the identity).
 __global__ __launch_bounds__(256) void k_group_of_column(const long long *__restrict__ order, int batch, int n, int gsize,
                                                          int *__restrict__ pg) {
@@ -248,6 +239,7 @@ __global__ __launch_bounds__(256) void k_permute_out_grouped(const float *__rest
 struct LeafTables {
     double u[ULEAF][ULEAF + 1];  // leaf block of U, STRICTLY upper part (zero on/below the diagonal and beyond the width)
     double udr[ULEAF][2];        // its diagonal (1 beyond the width) and 1 / diagonal by true division
+    __device__ __forceinline__ static int col(int j) { return j; }  // where column j of a row of u sits
 };
 struct WindowSmem {
     // leaf tables first: their offsets fit the 16-bit immediate of ds_read, so the unrolled leaf
@@ -265,15 +257,29 @@ struct WindowSmem {
 // for every t0 whose quotient neither overflows nor underflows (rint of an underflowing
 // quotient is 0 either way).  Saves ~40 dependent cycles per column on the leaf's critical
 // path.  tests/test_gpu_parity.py::test_fast_quantizer_matches_true_divide sweeps it against
-// the true-divide kernel.
+// the true-divide kernel.  The clamp is one v_med3 (the leaf chain counts instructions).
 __device__ __forceinline__ float grid_value_fast(float x, const Grid g, float inv_step) {
     const float t0 = x - g.zero;
     const float q0 = t0 * inv_step;
     const float r = __builtin_fmaf(-g.step, q0, t0);
     float t = __builtin_fmaf(r, inv_step, q0);
     t = rintf(t);
-    t = fminf(fmaxf(t, 0.0f), g.top);
+    t = __builtin_amdgcn_fmed3f(t, 0.0f, g.top);
     return t * g.step + g.zero;
+}
+
+// A column's error float64(x - q) / uii (obq.py:112).  FAST: the exact-division fma sequence with rii = RN(1 / uii) taken
+// once per leaf by a true division (exact unless uii's significand is all ones, which the caller has excluded).
+template <bool FAST>
+__device__ __forceinline__ double chain_err(float x, float q, double uii, double rii) {
+    const double d = (double)(x - q);
+    if constexpr (FAST) {
+        const double qq = d * rii;
+        const double rem = __builtin_fma(-uii, qq, d);
+        return __builtin_fma(rem, rii, qq);
+    } else {
+        return d / uii;
+    }
 }
 
 template <int I, int N, class F>
@@ -289,43 +295,40 @@ template <int L>
 __device__ __forceinline__ float row_bcast(float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + L, 0xf, 0xf, true));
 }
-// grid_value_fast with the clamp as one v_med3 (the leaf chain counts instructions)
-__device__ __forceinline__ float grid_value_fast_med3(float x, const Grid g, float inv_step) {
-    const float t0 = x - g.zero;
-    const float q0 = t0 * inv_step;
-    const float r = __builtin_fmaf(-g.step, q0, t0);
-    float t = __builtin_fmaf(r, inv_step, q0);
-    t = rintf(t);
-    t = __builtin_amdgcn_fmed3f(t, 0.0f, g.top);
-    return t * g.step + g.zero;
-}
 
-// LEAF, register path (width <= 32, window in LDS), run by waves 0-3 of the workgroup: a wave
-// owns FOUR rows, 16 lanes per row; lane c keeps columns a + c and a + 16 + c of its row in two
-// registers.  Step i: column i's value is read-laned out of the four rows and selected per
-// row group, every lane recomputes q_i and err_i for its own row (no second broadcast), then
+// the per-row quantizer: nothing to read per step
+struct LeafRows {
+    struct Step {};
+    __device__ __forceinline__ Step at(int, int, int) const { return {}; }
+    template <bool FAST>
+    __device__ __forceinline__ static float q(float x, Step, const Grid g, float inv_step) {
+        return FAST ? grid_value_fast(x, g, inv_step) : cb_value(x, g);
+    }
+};
+
+// LEAF, register path (width <= 32, tables in LDS): a chain wave owns FOUR rows, 16 lanes per row; lane c16 keeps
+// columns c16 and 16 + c16 of its row's leaf in x0 and x1.  Step i: column i's value is broadcast inside its
+// 16-lane DPP row, every lane recomputes q_i and err_i for its own row (no second broadcast), then
 // updates its two columns:  x_c <- float32(float64(x_c) - err_i * U[i][c])   (obq.py:114-118)
-// err_i = float64(x_i - q_i) / U[i][i] uses the exact-division fma sequence with reciprocals
-// taken once per leaf by a true division.  The loop is issue-bound (~35 instructions a step),
-// which is why four rows share a wave and the other four waves of the workgroup stay parked
-// at the barrier: two waves per SIMD would just take turns (measured 430 -> ~230 cycles/step).
+// FAST: Markstein divisions (chain_err, grid_value_fast); otherwise true divides / table look-ups.
+// The loop is issue-bound (~35 instructions a step with the per-step selection this chain no longer has), which is why
+// four rows share a wave and, in k_gptq_window, the other four waves of the workgroup stay parked at the barrier: two
+// waves per SIMD would just take turns (measured 430 -> ~230 cycles/step).
+// Steps beyond the width run on the padding (x = 0, U row = 0, diagonal = 1; the group tables
+// read 1.0 / slot GSLOTS there: a finite error that meets a zero U row) and change nothing: no per-step branch,
+// so the whole leaf is one basic block and the LDS reads of step i + 1 (U row, diagonal,
+// reciprocal, the policy's step) are issued before the arithmetic of step i.
 // The policy P is the quantizer: P::Step is what a step reads from LDS besides U (read one step
-// ahead, like the U row), P.at(row, a, k) reads it for column a + k, and P::q(x, step, g, inv_step)
+// ahead, like the U row), pol.at(row, a, k) reads it for column a + k of tile row `row`, and P::q<FAST>(x, step, g, inv_step)
 // forms q.  (The tile's reads take a and k apart: one base address for s and rs, k in the offsets.)
-template <int NSTEP, class P>
-__device__ __forceinline__ void leaf_registers(WindowSmem &sm, const P &pol, const LeafTables &lt, int wave, int lane, int a_rel,
-                                               int w, const Grid g, float inv_step) {
-    const int c16 = lane & 15, rg = lane >> 4;
-    const int row = 4 * wave + rg;
-    const bool m0 = c16 < w, m1 = c16 + 16 < w;
-    float x0 = m0 ? sm.q[row][a_rel + c16] : 0.0f, x1 = m1 ? sm.q[row][a_rel + 16 + c16] : 0.0f;
-    float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
-    // Steps beyond the width run on the padding (x = 0, U row = 0, diagonal = 1; the group tables
-    // read 1.0 there: a finite error that meets a zero U row) and change nothing: no per-step branch,
-    // so the whole leaf is one basic block and the LDS reads of step i + 1 (U row, diagonal,
-    // reciprocal, the policy's step) are issued before the arithmetic of step i.
+// On return q0, e0 (q1, e1) are the quantized value and scaled error of columns c16 (16 + c16); loading x and storing
+// q and e is the caller's.
+template <int NSTEP, bool FAST, class P>
+__device__ __forceinline__ void leaf_chain16(const LeafTables &lt, const P &pol, int row, int a, int c16, float x0, float x1, float &q0,
+                                             float &q1, float &e0, float &e1, const Grid g, float inv_step) {
+    static_assert(FAST || std::is_same<P, LeafRows>::value, "the group quantizers' slow path is the generic leaf");
     double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
-    typename P::Step sn = pol.at(row, a_rel, 0);
+    typename P::Step sn = pol.at(row, a, 0);
     static_for<0, NSTEP>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
@@ -335,47 +338,31 @@ __device__ __forceinline__ void leaf_registers(WindowSmem &sm, const P &pol, con
             u1n = lt.u[i + 1][c16 + 16];
             uiin = lt.udr[i + 1][0];
             riin = lt.udr[i + 1][1];
-            sn = pol.at(row, a_rel, i + 1);
+            sn = pol.at(row, a, i + 1);
         }
         // the chain values pass through this point: the reads above are issued before step i starts
         asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
-        constexpr int src = i & 15;
-        // column i of each of the wave's four rows, broadcast inside its 16-lane DPP row
-        const float xi = row_bcast<src>(i < 16 ? x0 : x1);
-        const float q = P::q(xi, sc, g, inv_step);
-        const double d = (double)(xi - q);
-        const double qq = d * rii;
-        const double rem = __builtin_fma(-uii, qq, d);
-        const double err = __builtin_fma(rem, rii, qq);
-        const float ef = (float)err;
-        const bool here = c16 == src;
-        if (i < 16) {
-            q0 = here ? q : q0;
-            e0 = here ? ef : e0;
-        } else {
-            q1 = here ? q : q1;
-            e1 = here ? ef : e1;
-        }
+        // column i of each of the wave's rows, broadcast inside its 16-lane DPP row; every lane recomputes the
+        // column's error for its own row.  The chain is bound by the ISSUE of these instructions: nothing is kept
+        // per step (the column's own q and e come after the loop, below)
+        const float xi = row_bcast<(i & 15)>(i < 16 ? x0 : x1);
+        const double err = chain_err<FAST>(xi, P::template q<FAST>(xi, sc, g, inv_step), uii, rii);
         // the staged block is zero on and below the diagonal: only later columns move
         if (i < 15) x0 = (float)((double)x0 - err * u0);
         if (NSTEP > 16) x1 = (float)((double)x1 - err * u1);
     });
-    if (m0) {
-        sm.q[row][a_rel + c16] = q0;
-        sm.e[row][a_rel + c16] = e0;
-    }
-    if (m1) {
-        sm.q[row][a_rel + 16 + c16] = q1;
-        sm.e[row][a_rel + 16 + c16] = e1;
+    // A lane's own columns are final once their step has passed: the block of U is zero on and below the diagonal, so
+    // the later steps subtract err * 0 (at most the sign of a zero changes, which no result can see).  Their q and e
+    // are the same expressions on the same value as in the step that broadcast it: computed once here instead of being
+    // selected into place in every step (two v_cndmask and a conversion per step less on the chain).  The policy's step
+    // of a lane's own column is a run-time k into the same tables.
+    q0 = P::template q<FAST>(x0, pol.at(row, a, c16), g, inv_step);
+    e0 = (float)chain_err<FAST>(x0, q0, lt.udr[c16][0], lt.udr[c16][1]);
+    if constexpr (NSTEP > 16) {
+        q1 = P::template q<FAST>(x1, pol.at(row, a, c16 + 16), g, inv_step);
+        e1 = (float)chain_err<FAST>(x1, q1, lt.udr[c16 + 16][0], lt.udr[c16 + 16][1]);
     }
 }
-
-// the per-row quantizer: nothing to read per step
-struct LeafRows {
-    struct Step {};
-    __device__ __forceinline__ Step at(int, int, int) const { return {}; }
-    __device__ __forceinline__ static float q(float x, Step, const Grid g, float inv_step) { return grid_value_fast(x, g, inv_step); }
-};
 
 // the group quantizers: q = codebook(x / s) / rs (two true divides; the codebook step keeps the exact-division sequence),
 // OFFSET codebook((x - o) / s) / rs + o
@@ -396,6 +383,7 @@ struct LeafTile {
     const GroupTile &gt;
     typedef GroupQ<false> Step;
     __device__ __forceinline__ Step at(int row, int a, int k) const { return {(&gt.s[row][a])[k], (&gt.rs[row][a])[k]}; }
+    template <bool FAST>
     __device__ __forceinline__ static float q(float x, Step e, const Grid g, float inv_step) { return leaf_group_q(x, e, g, inv_step); }
 };
 
@@ -419,8 +407,66 @@ struct LeafSlots {
         const int slot = gs.slot[a + k];
         return {gs.s[row][slot], gs.rs[row][slot], gs.o[row][slot]};
     }
+    template <bool FAST>
     __device__ __forceinline__ static float q(float x, Step e, const Grid g, float inv_step) { return leaf_group_q(x, e, g, inv_step); }
 };
+
+// A fast leaf of k_gptq_window's tile, columns [a_rel, a_rel + w) of the window, by chain wave `wave`: x out of sm.q, q and e into
+// sm.q and sm.e.
+template <class P>
+__device__ __forceinline__ void leaf_tile16(WindowSmem &sm, const P &pol, const LeafTables &lt, int wave, int lane, int a_rel, int w,
+                                            const Grid g, float inv_step) {
+    const int c16 = lane & 15, row = 4 * wave + (lane >> 4);
+    const bool m0 = c16 < w, m1 = c16 + 16 < w;
+    const float x0 = m0 ? sm.q[row][a_rel + c16] : 0.0f, x1 = m1 ? sm.q[row][a_rel + 16 + c16] : 0.0f;
+    float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
+    if (w <= 16) leaf_chain16<16, true>(lt, pol, row, a_rel, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
+    else leaf_chain16<32, true>(lt, pol, row, a_rel, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
+    if (m0) {
+        sm.q[row][a_rel + c16] = q0;
+        sm.e[row][a_rel + c16] = e0;
+    }
+    if (m1) {
+        sm.q[row][a_rel + 16 + c16] = q1;
+        sm.e[row][a_rel + 16 + c16] = e1;
+    }
+}
+
+// ---- staging of a leaf's tables by the 256 helper threads (ht = 0 ... 255): thread ht carries the slots e = ht + 256 h,
+// h < 4, of the 32 x 32 block, slot e = (row e >> 5, column e & 31).
+// registers <- U[a : a + w, a : a + w], w >= 1 (clamped, selected when written)
+__device__ __forceinline__ void fetch_leaf_block(const double *__restrict__ U, int n, int a, int w, int ht, double (&pu)[4]) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int e = ht + 256 * h, i = min(e >> 5, w - 1), j = min(e & 31, w - 1);
+        pu[h] = U[(size_t)(a + i) * n + a + j];
+    }
+}
+// table <- registers, all 32 x 32 slots (w = 0: an empty leaf).  Returns whether a diagonal entry met by this WAVE defeats
+// the exact-division shortcut: a significand that is all ones.
+template <class Tables>
+__device__ __forceinline__ bool write_leaf_tables(Tables &lt, const double (&pu)[4], int w, int ht) {
+    // a thread meets at most one diagonal slot (e = 33 i): one division, not four
+    double dgv = 1.0;
+    int di = -1;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int e = ht + 256 * h, i = e >> 5, j = e & 31;
+        const bool in = i < w && j < w;
+        lt.u[i][Tables::col(j)] = (in && j > i) ? pu[h] : 0.0;
+        if (i == j) {
+            dgv = in ? pu[h] : 1.0;
+            di = i;
+        }
+    }
+    bool odd = false;
+    if (di >= 0) {
+        lt.udr[di][0] = dgv;
+        lt.udr[di][1] = 1.0 / dgv;
+        odd = (__double_as_longlong(dgv) & 0xFFFFFFFFFFFFFLL) == 0xFFFFFFFFFFFFFLL;
+    }
+    return __builtin_amdgcn_ballot_w64(odd) != 0;
+}
 
 // cycle counters of workgroup 0 (SLK_WIN_DBG bit 3), read back by slk_probe_window_cycles
 __device__ long long g_win_cycles[16];
@@ -510,33 +556,14 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             const Op nx = tab.op[next_fetch];
             const int w = nx.b - nx.a;
             if (nx.kind != OP_LEAF || w > ULEAF) continue;
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const int e = ht + 256 * h, i = min(e >> 5, w - 1), j = min(e & 31, w - 1);
-                pu[h] = U[(size_t)(nx.a + i) * n + nx.a + j];  // clamped, selected when written
-            }
+            fetch_leaf_block(U, n, nx.a, w, ht, pu);
             fetch_w = w;
             ++next_fetch;
             return;
         }
     };
     auto write_block = [&](int buf) {
-        LeafTables &lt = sm.lt[buf];
-        const int w = fetch_w;
-        bool odd = false;  // exact-division exception: a diagonal entry whose significand is all ones
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int e = ht + 256 * h, i = e >> 5, j = e & 31;  // all 32 x 32 slots
-            const bool in = i < w && j < w;
-            lt.u[i][j] = (in && j > i) ? pu[h] : 0.0;
-            if (i == j) {
-                const double dg = in ? pu[h] : 1.0;
-                lt.udr[i][0] = dg;
-                lt.udr[i][1] = 1.0 / dg;
-                odd = odd || (__double_as_longlong(dg) & 0xFFFFFFFFFFFFFLL) == 0xFFFFFFFFFFFFFLL;
-            }
-        }
-        const bool any = __builtin_amdgcn_ballot_w64(odd) != 0;
+        const bool any = write_leaf_tables(sm.lt[buf], pu, fetch_w, ht);
         if (lane == 0) sm.odd[buf][wave - 4] = any ? 1 : 0;
     };
 
@@ -812,16 +839,9 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             if (use_fast) {
                 if (!helper && !no_leaf_regs) {
                     const int w = op.b - op.a;
-                    if constexpr (OFFSET) {
-                        if (w <= 16) leaf_registers<16>(sm, LeafSlots{gs}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                        else leaf_registers<32>(sm, LeafSlots{gs}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                    } else if constexpr (GROUPED) {
-                        if (w <= 16) leaf_registers<16>(sm, LeafTile{gt}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                        else leaf_registers<32>(sm, LeafTile{gt}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                    } else {
-                        if (w <= 16) leaf_registers<16>(sm, LeafRows{}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                        else leaf_registers<32>(sm, LeafRows{}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
-                    }
+                    if constexpr (OFFSET) leaf_tile16(sm, LeafSlots{gs}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                    else if constexpr (GROUPED) leaf_tile16(sm, LeafTile{gt}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
+                    else leaf_tile16(sm, LeafRows{}, sm.lt[sbuf], wave, lane, op.a - w0, w, g, inv_step);
                 }
                 lap(0, 0);
                 lap(5, 4);
@@ -1032,7 +1052,7 @@ __global__ void k_probe_leaf(double *out, int iters, int mode, Grid g, float inv
     if (t == 0) out[2] = (double)__builtin_amdgcn_s_getreg((4 << 11) | (0 << 6) | 4);  // HW_ID, 32 bits... low 16 here
     if (leafer || mode == 0) {
         // (with more than two leaf waves per SIMD several waves run the same four rows: garbage values, honest timing)
-        for (int it = 0; it < iters; ++it) leaf_registers<32>(sm, LeafRows{}, sm.lt[0], ((wave & 1) + ((wave >> 2) << 1)) & 3, lane, (it & 1) * 32, 32, g, inv_step);
+        for (int it = 0; it < iters; ++it) leaf_tile16(sm, LeafRows{}, sm.lt[0], ((wave & 1) + ((wave >> 2) << 1)) & 3, lane, (it & 1) * 32, 32, g, inv_step);
     } else if (mode == 5) {
         // companion wave on the same SIMD: back-to-back bfloat16 MFMAs (what the layer-error kernel issues)
         typedef __bf16 probe_bf16x8_t __attribute__((ext_vector_type(8)));
@@ -1102,6 +1122,25 @@ extern "C" int slk_gptq_quantize(const float *W, const float *scale, const long 
                                    E_out, workspace, ws_bytes, stream);
 }
 
+// The general window kernel's LDS: the tile, then the group quantizer's tables behind it.
+template <bool IN_LDS, bool GROUPED, bool OFFSET>
+constexpr size_t window_lds() {
+    return !IN_LDS ? 0 : sizeof(WindowSmem) + (OFFSET ? sizeof(GroupSlots) : GROUPED ? sizeof(GroupTile) : 0);
+}
+// One launch of it: the LDS size and the profile name follow from the template arguments (gptq_loop has opted in to the LDS).
+template <bool IN_LDS, bool GROUPED, bool OFFSET>
+static int launch_window(double flops, double bytes, int row_tiles, hipStream_t s, float *Qp, float *Eg, const double *U, int R, int n,
+                         int w0, int w1, Grid g, float inv_step, int fast_ok, int dbg, const OpTable &tab, int rpl, const float *Sg,
+                         const int *pg, int G, const float *Og) {
+    constexpr size_t lds = window_lds<IN_LDS, GROUPED, OFFSET>();
+    const char *name = IN_LDS ? (OFFSET ? "gptq_window_grouped_asym" : GROUPED ? "gptq_window_grouped" : "gptq_window")
+                              : (OFFSET ? "gptq_window_wide_grouped_asym" : GROUPED ? "gptq_window_wide_grouped" : "gptq_window_wide");
+    SLK_RUN(name, flops, bytes, s,
+            k_gptq_window<IN_LDS, GROUPED, OFFSET><<<row_tiles, 512, lds, s>>>(Qp, Eg, U, R, n, w0, w1, g, inv_step, fast_ok, dbg, tab, rpl, Sg, pg, G,
+                                                                             Og));
+    return SLK_OK;
+}
+
 // `batch` layers of one shape stacked by rows: every launch of the loop covers all of them, each row tile
 // reading its own layer's factor.  What a row shard of a multi-GPU run needs: R / G rows alone leave most of
 // the chip idle (the window kernel runs one workgroup per 16 rows), G layers' shards together fill it.
@@ -1151,9 +1190,9 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     const int dbg = opt(OPT_WIN_DBG) & (8 | 16 | 32 | 64 | 128);  // cycle counters, no L2 warm-up, whole tile loaded up front: same results
 #endif
     const bool no_defer = opt(OPT_NO_DEFER) != 0;
-    SLK_LDS_OPT_IN((k_gptq_window<true, false>), sizeof(WindowSmem));
-    if (grouped && !asym) SLK_LDS_OPT_IN((k_gptq_window<true, true>), sizeof(WindowSmem) + sizeof(GroupTile));
-    if (asym) SLK_LDS_OPT_IN((k_gptq_window<true, true, true>), sizeof(WindowSmem) + sizeof(GroupSlots));
+    if (asym) SLK_LDS_OPT_IN((k_gptq_window<true, true, true>), (window_lds<true, true, true>()));
+    else if (grouped) SLK_LDS_OPT_IN((k_gptq_window<true, true, false>), (window_lds<true, true, false>()));
+    else SLK_LDS_OPT_IN((k_gptq_window<true, false, false>), (window_lds<true, false, false>()));
     SLK_LDS_OPT_IN(k_gptq_window2<1>, sizeof(Window2SmemT<1>));
     SLK_LDS_OPT_IN(k_gptq_window2<2>, sizeof(Window2SmemT<2>));
     // 32 rows per workgroup (eight rows per chain wave, ONE quantizer instruction stream for them: leaf_chain8) halve the CUs
@@ -1172,15 +1211,11 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     // rows staged through LDS when they fit and 16-byte accesses line up
     const bool perm_lds = order && n % 4 == 0 && n <= PERM_MAX && ((uintptr_t)W | (uintptr_t)Q | (uintptr_t)workspace) % 16 == 0 &&
                           (idx == nullptr || (uintptr_t)idx % 4 == 0);
-    if (perm_lds) {
-        SLK_LDS_OPT_IN(k_permute_in_lds, PERM_MAX * 4);
-        SLK_LDS_OPT_IN(k_permute_out_lds<false>, PERM_MAX * 4);
-        if (row_err) SLK_LDS_OPT_IN(k_permute_out_lds<true>, PERM_MAX * 4);
+    {
+        const int rc = launch_permute("permute_in", 0, 8.0 * R * n, perm_lds ? k_permute_in<true> : k_permute_in<false>, perm_lds, R, n, s, W, scale,
+                                      order, R, n, Qp, inv_order, rpl);
+        if (rc != SLK_OK) return rc;
     }
-    if (perm_lds)
-        SLK_RUN("permute_in", 0, 8.0 * R * n, s, k_permute_in_lds<<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(W, scale, order, R, n, Qp, inv_order, rpl));
-    else
-        SLK_RUN("permute_in", 0, 8.0 * R * n, s, k_permute_in<<<R < 2048 ? R : 2048, 256, 0, s>>>(W, scale, order, R, n, Qp, inv_order, rpl));
 
     const int G = grouped ? n / group_size : 0;
     if (grouped)
@@ -1240,30 +1275,14 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
                                   k_gptq_window2<1><<<row_tiles, 512, sizeof(Window2SmemT<1>), s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step,
                                                                                                  fast_ok, dbg & 24, pt, rpl));
                 }
-                else if (asym && in_lds)
-                    SLK_RUN("gptq_window_grouped_asym", fl * R, wbytes, s,
-                            k_gptq_window<true, true, true><<<row_tiles, 512, sizeof(WindowSmem) + sizeof(GroupSlots), s>>>(
-                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G, goffset));
-                else if (asym)
-                    SLK_RUN("gptq_window_wide_grouped_asym", fl * R, wbytes, s,
-                            k_gptq_window<false, true, true><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
-                                                                                   dbg, tab, rpl, gscale, pg, G, goffset));
-                else if (grouped && in_lds)
-                    SLK_RUN("gptq_window_grouped", fl * R, wbytes, s,
-                            k_gptq_window<true, true><<<row_tiles, 512, sizeof(WindowSmem) + sizeof(GroupTile), s>>>(
-                                Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G, nullptr));
-                else if (grouped)
-                    SLK_RUN("gptq_window_wide_grouped", fl * R, wbytes, s,
-                            k_gptq_window<false, true><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
-                                                                             dbg, tab, rpl, gscale, pg, G, nullptr));
-                else if (in_lds)
-                    SLK_RUN("gptq_window", fl * R, wbytes, s,
-                            k_gptq_window<true, false><<<row_tiles, 512, sizeof(WindowSmem), s>>>(Qp, Eg, U, R, n, st.a, st.b, g,
-                                                                                        inv_step, fast_ok, dbg, tab, rpl, nullptr, nullptr, 0, nullptr));
-                else
-                    SLK_RUN("gptq_window_wide", fl * R, wbytes, s,
-                            k_gptq_window<false, false><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok,
-                                                                           dbg, tab, rpl, nullptr, nullptr, 0, nullptr));
+                else {
+                    const auto launch = asym      ? (in_lds ? launch_window<true, true, true> : launch_window<false, true, true>)
+                                        : grouped ? (in_lds ? launch_window<true, true, false> : launch_window<false, true, false>)
+                                                  : (in_lds ? launch_window<true, false, false> : launch_window<false, false, false>);
+                    const int rc = launch(fl * R, wbytes, row_tiles, s, Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G,
+                                          goffset);
+                    if (rc != SLK_OK) return rc;
+                }
             }
         } else {
             const double K = st.b - st.a, N = st.c - st.b;
@@ -1283,21 +1302,21 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
         SLK_RUN("permute_out_grouped", 0, (idx ? 13.0 : 8.0) * R * n, s,
                 k_permute_out_grouped<<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, gscale, group_size, Q, idx, rpl,
                                                                          nullptr));
-    else if (row_err) {
+    else {
         // the rows' errors ride on the last kernel: 8 R n bytes more (the rows of W and E) instead of a product of its own
-        const int rc = loop_error_means(Hs, batch, n, hmean, s);
+        RowErrArgs ea{};
+        if (row_err) {
+            const int rc = loop_error_means(Hs, batch, n, hmean, s);
+            if (rc != SLK_OK) return rc;
+            ea = RowErrArgs{W, Eg, unscale ? scale : nullptr, hmean, damp, row_err};
+        }
+        const auto kernel = row_err ? (perm_lds ? k_permute_out<true, true> : k_permute_out<false, true>)
+                                    : (perm_lds ? k_permute_out<true, false> : k_permute_out<false, false>);
+        const int rc = launch_permute(row_err ? "permute_out_error" : "permute_out", row_err ? 4.0 * R * n : 0,
+                                      (row_err ? (idx ? 17.0 : 16.0) : (idx ? 9.0 : 8.0)) * R * n, kernel, perm_lds, R, n, s, Qp, inv_order, R, n, g,
+                                      unscale ? scale : nullptr, Q, idx, rpl, ea);
         if (rc != SLK_OK) return rc;
-        const RowErrArgs ea{W, Eg, unscale ? scale : nullptr, hmean, damp, row_err};
-        if (perm_lds)
-            SLK_RUN("permute_out_error", 4.0 * R * n, (idx ? 17.0 : 16.0) * R * n, s,
-                    k_permute_out_lds<true><<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, ea));
-        else
-            SLK_RUN("permute_out_error", 4.0 * R * n, (idx ? 17.0 : 16.0) * R * n, s,
-                    k_permute_out<true><<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, ea));
-    } else if (perm_lds)
-        SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out_lds<false><<<R < 2048 ? R : 2048, 256, (size_t)n * 4, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, RowErrArgs{}));
-    else
-        SLK_RUN("permute_out", 0, (idx ? 9.0 : 8.0) * R * n, s, k_permute_out<false><<<R < 2048 ? R : 2048, 256, 0, s>>>(Qp, inv_order, R, n, g, unscale ? scale : nullptr, Q, idx, rpl, RowErrArgs{}));
+    }
     if (E_out) copy_async(E_out, Eg, sizeof(float) * (size_t)R * n, s);
     return SLK_OK;
 }

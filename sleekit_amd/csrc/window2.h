@@ -39,6 +39,7 @@ struct PeriodTable {
 struct LeafTables8 {
     double u[ULEAF][ULEAF];  // leaf block of U, strictly upper part, columns permuted: [i][(j & 7) * 4 + (j >> 3)]
     double udr[ULEAF][2];    // its diagonal (1 beyond the width) and 1 / diagonal by true division
+    __device__ __forceinline__ static int col(int j) { return (j & 7) * 4 + (j >> 3); }
 };
 
 template <int SETS>
@@ -63,75 +64,6 @@ __device__ __forceinline__ void lds_wait_ge(int *counter, int target) {
 __device__ __forceinline__ void lds_signal(int *counter, int lane) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's LDS reads / writes are done
     if (lane == 0) __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// The leaf chain on registers (see leaf_registers).  FAST: Markstein divisions (exact unless a
-// significand is all ones, which the caller has excluded); otherwise true divides.
-template <int NSTEP, bool FAST, int SETS>
-__device__ __forceinline__ void leaf_chain(const LeafTables &lt, int c16, float (&x0)[SETS], float (&x1)[SETS], float (&q0)[SETS],
-                                           float (&q1)[SETS], float (&e0)[SETS], float (&e1)[SETS], const Grid g, float inv_step) {
-    double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
-    static_for<0, NSTEP>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
-        if constexpr (i + 1 < NSTEP) {
-            u0n = lt.u[i + 1][c16];
-            u1n = lt.u[i + 1][c16 + 16];
-            uiin = lt.udr[i + 1][0];
-            riin = lt.udr[i + 1][1];
-        }
-        // the reads above are issued before step i starts
-        if constexpr (SETS == 1) asm volatile("" : "+v"(x0[0]), "+v"(x1[0])::"memory");
-        else asm volatile("" : "+v"(x0[0]), "+v"(x1[0]), "+v"(x0[1]), "+v"(x1[1])::"memory");
-        constexpr int src = i & 15;
-#pragma unroll
-        for (int st = 0; st < SETS; ++st) {  // independent chains: the compiler interleaves them
-            // column i of each of the wave's rows, broadcast inside its 16-lane DPP row; every lane recomputes the
-            // column's error for its own row.  The chain is bound by the ISSUE of these instructions: nothing is kept
-            // per step (the column's own q and e come after the loop, below)
-            const float xi = row_bcast<src>(i < 16 ? x0[st] : x1[st]);
-            double err;
-            if (FAST) {
-                const float q = grid_value_fast_med3(xi, g, inv_step);
-                const double d = (double)(xi - q);
-                const double qq = d * rii;
-                const double rem = __builtin_fma(-uii, qq, d);
-                err = __builtin_fma(rem, rii, qq);
-            } else {
-                err = (double)(xi - cb_value(xi, g)) / uii;
-            }
-            if (i < 15) x0[st] = (float)((double)x0[st] - err * u0);
-            if (NSTEP > 16) x1[st] = (float)((double)x1[st] - err * u1);
-        }
-    });
-    // A lane's own columns are final once their step has passed: the block of U is zero on and below the diagonal, so
-    // the later steps subtract err * 0 (at most the sign of a zero changes, which no result can see).  Their q and e
-    // are the same expressions on the same value as in the step that broadcast it: computed once here instead of being
-    // selected into place in every step (two v_cndmask and a conversion per step less on the chain).
-    const double d0 = lt.udr[c16][0], r0 = lt.udr[c16][1];
-    const double d1 = lt.udr[NSTEP > 16 ? c16 + 16 : c16][0], r1 = lt.udr[NSTEP > 16 ? c16 + 16 : c16][1];
-#pragma unroll
-    for (int st = 0; st < SETS; ++st) {
-#pragma unroll
-        for (int half = 0; half < (NSTEP > 16 ? 2 : 1); ++half) {
-            const float xv = half ? x1[st] : x0[st];
-            const double uii = half ? d1 : d0, rii = half ? r1 : r0;
-            float q;
-            double err;
-            if (FAST) {
-                q = grid_value_fast_med3(xv, g, inv_step);
-                const double d = (double)(xv - q);
-                const double qq = d * rii;
-                const double rem = __builtin_fma(-uii, qq, d);
-                err = __builtin_fma(rem, rii, qq);
-            } else {
-                q = cb_value(xv, g);
-                err = (double)(xv - q) / uii;
-            }
-            if (half) q1[st] = q, e1[st] = (float)err;
-            else q0[st] = q, e0[st] = (float)err;
-        }
-    }
 }
 
 // lane S of every 8-lane group, to all lanes of that group: row_newbcast of lane S over the 16-lane DPP row, then lanes
@@ -171,16 +103,7 @@ __device__ __forceinline__ void leaf_chain8(const LeafTables8 &lt, int sub, floa
         // column i of each of the wave's eight rows, broadcast inside its 8-lane group; every lane recomputes the
         // column's error for its own row.  Nothing is kept per step (a lane's own q and e come after the loop).
         const float xi = bcast8<s>(x[kk]);
-        double err;
-        if (FAST) {
-            const float qv = grid_value_fast_med3(xi, g, inv_step);
-            const double d = (double)(xi - qv);
-            const double qq = d * rii;
-            const double rem = __builtin_fma(-uii, qq, d);
-            err = __builtin_fma(rem, rii, qq);
-        } else {
-            err = (double)(xi - cb_value(xi, g)) / uii;
-        }
+        const double err = chain_err<FAST>(xi, LeafRows::q<FAST>(xi, {}, g, inv_step), uii, rii);
 #pragma unroll
         for (int k = kk; k < NK; ++k) {
             if (k == kk && s == 7) continue;  // the last column of register kk: nothing right of it in that register
@@ -193,21 +116,8 @@ __device__ __forceinline__ void leaf_chain8(const LeafTables8 &lt, int sub, floa
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         const double2_t d = *reinterpret_cast<const double2_t *>(&lt.udr[sub + 8 * k][0]);
-        const float xv = x[k];
-        float qv;
-        double err;
-        if (FAST) {
-            qv = grid_value_fast_med3(xv, g, inv_step);
-            const double dd = (double)(xv - qv);
-            const double qq = dd * d[1];
-            const double rem = __builtin_fma(-d[0], qq, dd);
-            err = __builtin_fma(rem, d[1], qq);
-        } else {
-            qv = cb_value(xv, g);
-            err = (double)(xv - qv) / d[0];
-        }
-        q[k] = qv;
-        e[k] = (float)err;
+        q[k] = LeafRows::q<FAST>(x[k], {}, g, inv_step);
+        e[k] = (float)chain_err<FAST>(x[k], q[k], d[0], d[1]);
     }
 }
 
@@ -417,31 +327,24 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
                         }
                     }
                 } else {
-                const auto &lt = sm.lt[par][lf];
-                const bool m0 = c16 < w, m1 = c16 + 16 < w;
-                float x0[SETS], x1[SETS], q0[SETS], q1[SETS], e0[SETS], e1[SETS];
-#pragma unroll
-                for (int st = 0; st < SETS; ++st) {
-                    x0[st] = m0 ? sm.q[row[st]][a - w0 + c16] : 0.0f;
-                    x1[st] = m1 ? sm.q[row[st]][a - w0 + 16 + c16] : 0.0f;
-                    q0[st] = q1[st] = e0[st] = e1[st] = 0.0f;
-                }
-                if (!fast) leaf_chain<32, false, SETS>(lt, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
-                else if (w <= 16) leaf_chain<16, true, SETS>(lt, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
-                else leaf_chain<32, true, SETS>(lt, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
-#pragma unroll
-                for (int st = 0; st < SETS; ++st) {
+                    // four rows per chain wave, 16 lanes x 2 columns per lane (leaf_chain16, gptq.hip)
+                    const auto &lt = sm.lt[par][lf];
+                    const bool m0 = c16 < w, m1 = c16 + 16 < w;
+                    const float x0 = m0 ? sm.q[row[0]][a - w0 + c16] : 0.0f, x1 = m1 ? sm.q[row[0]][a - w0 + 16 + c16] : 0.0f;
+                    float q0 = 0.0f, q1 = 0.0f, e0 = 0.0f, e1 = 0.0f;
+                    if (!fast) leaf_chain16<32, false>(lt, LeafRows{}, 0, 0, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
+                    else if (w <= 16) leaf_chain16<16, true>(lt, LeafRows{}, 0, 0, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
+                    else leaf_chain16<32, true>(lt, LeafRows{}, 0, 0, c16, x0, x1, q0, q1, e0, e1, g, inv_step);
                     if (m0) {
-                        sm.q[row[st]][a - w0 + c16] = q0[st];
-                        sm.e[row[st]][ring(a + c16)] = e0[st];
-                        if (row_live[st]) Eg[(size_t)(r0 + row[st]) * n + a + c16] = e0[st];
+                        sm.q[row[0]][a - w0 + c16] = q0;
+                        sm.e[row[0]][ring(a + c16)] = e0;
+                        if (row_live[0]) Eg[(size_t)(r0 + row[0]) * n + a + c16] = e0;
                     }
                     if (m1) {
-                        sm.q[row[st]][a - w0 + 16 + c16] = q1[st];
-                        sm.e[row[st]][ring(a + 16 + c16)] = e1[st];
-                        if (row_live[st]) Eg[(size_t)(r0 + row[st]) * n + a + 16 + c16] = e1[st];
+                        sm.q[row[0]][a - w0 + 16 + c16] = q1;
+                        sm.e[row[0]][ring(a + 16 + c16)] = e1;
+                        if (row_live[0]) Eg[(size_t)(r0 + row[0]) * n + a + 16 + c16] = e1;
                     }
-                }
                 }
                 lap(1);
             }
@@ -460,43 +363,15 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
         auto fetch_tables = [&](int p) {  // both leaves of period p
             if (p >= np) return;
             const Period P = tab.p[p];
-#pragma unroll
-            for (int lf = 0; lf < 2; ++lf) {
-                const int a = lf ? P.s + P.w1 : P.s, w = max(1, lf ? P.w2 : P.w1);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const int e = ht + 256 * h, i = min(e >> 5, w - 1), j = min(e & 31, w - 1);
-                    pu[lf][h] = U[(size_t)(a + i) * n + a + j];  // clamped, selected when written
-                }
-            }
+            fetch_leaf_block(U, n, P.s, P.w1, ht, pu[0]);
+            fetch_leaf_block(U, n, P.s + P.w1, max(1, P.w2), ht, pu[1]);
         };
         auto write_tables = [&](int p) {
             if (p >= np) return;
             const Period P = tab.p[p];
 #pragma unroll
             for (int lf = 0; lf < 2; ++lf) {
-                auto &lt = sm.lt[p & 1][lf];
-                const int w = lf ? P.w2 : P.w1;
-                // a thread meets at most one diagonal slot (e = 33 i) per leaf: one division, not four
-                double dgv = 1.0;
-                int di = -1;
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const int e = ht + 256 * h, i = e >> 5, j = e & 31;
-                    const bool in = i < w && j < w;
-                    lt.u[i][SETS == 1 ? j : (j & 7) * 4 + (j >> 3)] = (in && j > i) ? pu[lf][h] : 0.0;
-                    if (i == j) {
-                        dgv = in ? pu[lf][h] : 1.0;
-                        di = i;
-                    }
-                }
-                bool odd = false;
-                if (di >= 0) {
-                    lt.udr[di][0] = dgv;
-                    lt.udr[di][1] = 1.0 / dgv;
-                    odd = (__double_as_longlong(dgv) & 0xFFFFFFFFFFFFFLL) == 0xFFFFFFFFFFFFFLL;
-                }
-                const bool any = __builtin_amdgcn_ballot_w64(odd) != 0;
+                const bool any = write_leaf_tables(sm.lt[p & 1][lf], pu[lf], lf ? P.w2 : P.w1, ht);
                 if (lane == 0) sm.odd[p & 1][lf][role_wave] = any ? 1 : 0;
             }
         };

@@ -481,6 +481,84 @@ def test_fast_quantizer_matches_true_divide(amd, levels, lo, hi):
     assert np.array_equal(E, W - want)
 
 
+_permute_cases = {}
+
+
+def permute_case(R, n):
+    """A layer, its order and the factor of its damped, permuted Hessian, with the oracle's indices (made once per shape)."""
+    if (R, n) not in _permute_cases:
+        rng = np.random.default_rng(1000 * R + n)
+        W = (rng.standard_normal((R, n)) * 0.6).astype(np.float32)
+        scale = (0.5 + rng.random(R)).astype(np.float32)
+        order = rng.permutation(n).astype(np.int64)
+        X = rng.standard_normal((2 * n, n)).astype(np.float32)
+        H = (X.T @ X / np.float32(2 * n)).astype(np.float32)
+        H = ((H + H.T) / 2).astype(np.float32)
+        Hp = H.astype(np.float64)[np.ix_(order, order)]
+        U = obq_ref.inverse_factor_upper(Hp + 0.01 * Hp.diagonal().mean() * np.eye(n))
+        Qs = scaling_ref.divide_rows(W, scale, 0)[:, order].copy()
+        obq_ref.run_schedule(Qs, np.zeros_like(Qs), U, grid.UniformGrid(8, -1, 1), obq_ref.block_schedule(n, 32, 8))
+        Qw = np.empty_like(Qs)
+        Qw[:, order] = Qs
+        _permute_cases[(R, n)] = W, scale, order, H, U, grid.UniformGrid(8, -1, 1).index(Qw).reshape(-1)
+    return _permute_cases[(R, n)]
+
+
+@pytest.mark.parametrize("unscale", [False, True])
+@pytest.mark.parametrize("R,n", [(3, 8), (3, 1028), (2064, 8)])
+def test_permute_forms_agree(amd, R, n, unscale):
+    """The two forms of k_permute_in / k_permute_out (a row through LDS, four elements an iteration; straight from global
+    memory, one element an iteration), bit for bit on Q, idx and E, and on the row errors the last kernel carries
+    (slk_gptq_quantize_batch_error): the same layer, order and factor with 16-byte aligned W, Q and idx (LDS form) and with
+    the three one element into larger buffers (plain form).  n = 8: one iteration of a few threads; n = 1028: n / 4 = 257, a
+    second trip of the 256-thread column loop; R = 2064 > 2048 workgroups: the row loop strides.  The two forms are held to
+    each other here and idx to the oracle; Q and E are anchored to the oracle by the loop tests around this one, row_err by
+    test_gpu_loop_error.py."""
+    import ctypes
+
+    from sleekit_amd import _device as dev
+
+    lib = amd.lib.lib
+    W, scale, order, H, U, idx_want = permute_case(R, n)
+    damp = 0.01
+    d_scale, d_order, d_U, d_H = dev.to_device(scale), dev.to_device(order, torch.int64), dev.to_device(U, torch.float64), dev.to_device(H)
+    ws, ws_bytes = dev.workspace(R, n)
+    Hs = (ctypes.c_void_p * 1)(d_H.data_ptr())
+    flags = 1 if unscale else 0
+
+    def run(shift):
+        # W, Q and idx `shift` elements into their buffers: shift 0 is 16-byte aligned, shift 1 is not
+        Wb = torch.zeros(R * n + 8, dtype=torch.float32, device=d_H.device)
+        Wb[shift : shift + R * n] = dev.to_device(W).reshape(-1)
+        out = []
+        for carried in (False, True):
+            Qb = torch.zeros(R * n + 8, dtype=torch.float32, device=d_H.device)
+            ib = torch.zeros(R * n + 8, dtype=torch.uint8, device=d_H.device)
+            E = torch.zeros((R, n), dtype=torch.float32, device=d_H.device)
+            pw, pq, pi = Wb.data_ptr() + 4 * shift, Qb.data_ptr() + 4 * shift, ib.data_ptr() + shift
+            assert ws.data_ptr() % 16 == 0 and all((p % 16 == 0) == (shift == 0) for p in (pw, pq, pi))
+            if carried:  # the carried error is that of the de-scaled Q: row scales only with unscale
+                row_err = torch.zeros(R, dtype=torch.float32, device=d_H.device)
+                amd.lib.check(lib.slk_gptq_quantize_batch_error(
+                    pw, d_scale.data_ptr() if unscale else 0, d_order.data_ptr(), d_U.data_ptr(), Hs, damp, 1, R, n, 8, -1.0, 1.0, 0, 32, 8,
+                    flags, pq, pi, E.data_ptr(), row_err.data_ptr(), ws.data_ptr(), ws_bytes, dev.stream_handle()))
+                out.append(row_err.cpu().numpy())
+            else:
+                amd.lib.check(lib.slk_gptq_quantize_batch(
+                    pw, d_scale.data_ptr(), d_order.data_ptr(), d_U.data_ptr(), 1, R, n, 8, -1.0, 1.0, 0, 32, 8, flags, pq, pi, E.data_ptr(),
+                    ws.data_ptr(), ws_bytes, dev.stream_handle()))
+            out += [Qb[shift : shift + R * n].cpu().numpy(), ib[shift : shift + R * n].cpu().numpy(), E.cpu().numpy()]
+            assert not Qb[:shift].any() and not Qb[shift + R * n :].any() and not ib[:shift].any() and not ib[shift + R * n :].any()
+        return out
+
+    names = ["Q", "idx", "E", "row_err", "Q (carried)", "idx (carried)", "E (carried)"]
+    got = run(0)
+    for name, lds, plain in zip(names, got, run(1)):
+        assert lds.tobytes() == plain.tobytes(), name
+    # and the indices against the oracle's loop on the same factor
+    assert np.array_equal(got[1], idx_want)
+
+
 def test_small_cases_bit_exact(amd, small_cases):
     names = [str(x) for x in small_cases["names"]]
     bad = []
