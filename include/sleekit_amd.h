@@ -430,6 +430,34 @@ int slk_mx_unpack(const uint8_t *codes, const uint8_t *scales, int R, int n, uin
 int slk_mx_dequantize(const uint8_t *codes, const uint8_t *scales, int R, int n, int out_dtype, void *out, int *flag,
                       slk_stream_t stream);
 
+/* A linear layer from the packed form, on the block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4).  The weights are
+ * `codes` / `scales` above (rows are output features, blocks run along K); the activations are quantized to MXFP8:
+ *   - a_scales: uint8 M x K / 32, E8M0.  Per block, b0 = max(amax / 448, 1e-16) in float32 (amax the block's largest |x|
+ *     as float32), the scale the smallest power of two >= b0, the byte its exponent + 127: slk_mx_scale_search's
+ *     SLK_MX_MAX with 448 in place of 6.  A block of zeros gives byte 74.  The scale does not saturate.
+ *   - a_codes: uint8 M x K, OCP E4M3 (e4m3fn: bias 7, subnormals k 2^-9, largest 448 = 0x7e), code = sign << 7 | exp << 3
+ *     | man: x / s (exact) rounded to nearest, ties to even, clamped at +-448.  A zero magnitude is written as 0x00
+ *     (never -0); 0x7f / 0xff (NaN) are never written.
+ *   Known answers: a block whose amax is 1.0 has byte 119 and its elements 1.0, -0.3, 0.001, 0 the codes 78 ea 28 00;
+ *   amax 1.75 gives byte 119 and 1.75, -1.75, 0.01, 1e-5 the codes 7e fe 42 01; after scaling 17 -> 58 (the tie goes to
+ *   16), 19 -> 5a, 2^-10 -> 00, 1.5 * 2^-9 -> 02.
+ * slk_mx_quantize_act: X (M x K row-major, `x_dtype` SLK_DTYPE_*) -> a_codes, a_scales.  flag[0] = 1 (DEVICE int, zeroed
+ *   by the call, required) if X holds a NaN or an infinity; the outputs are then not meaningful.
+ * slk_mx_dequantize_act: out[m][k] = value(code) * 2^(b - 127), float32 or that value rounded to nearest even as
+ *   bfloat16 / float16.  flag (may be NULL): 1 if a scale byte is 255.
+ * slk_mx_gemm: out[m][n] = sum_k A[m][k] W[n][k] (+ bias[n]), A and W the de-quantized operands, the products exact and
+ *   the sum in float32 inside the MFMA, over K in a fixed order (no atomics: a repeated call gives the same bits); out is
+ *   M x N float32, or that value rounded to nearest even as bfloat16 / float16.  bias: N float32, may be NULL.  Any
+ *   M, N >= 1.  Scale byte 255 is not looked for: the hardware reads it as NaN and so does the result.
+ *   K % 32 != 0 or K < 32, M or N < 1, a NULL required pointer, an unknown dtype, or X, a_codes, w_codes or out off
+ *   16-byte alignment: SLK_E_ARG, before any launch. */
+int slk_mx_quantize_act(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag,
+                        slk_stream_t stream);
+int slk_mx_dequantize_act(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
+                          slk_stream_t stream);
+int slk_mx_gemm(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream);
+
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */
 int slk_row_errors(const float *W, const float *Q, const float *H, int R, int n, float *row_err,

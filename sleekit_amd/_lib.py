@@ -107,6 +107,9 @@ PROTOTYPES = {
     "slk_mx_pack": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "slk_mx_unpack": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "slk_mx_dequantize": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
+    "slk_mx_quantize_act": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
+    "slk_mx_dequantize_act": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
+    "slk_mx_gemm": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

@@ -26,6 +26,18 @@ diag(H) of the block's columns as a float32 row sum in NumPy's order, the first 
 THE LOOP is groups.quantize_layer_grouped(W, S, E2M1, H, 32, ...) untouched: with a power-of-two s every step of the group
 quantizer codebook(x / s) / (1 / s) is exact, so Q is +-magnitude * 2^(b - 127) bit for bit and the packed form loses nothing.
 
+LINEAR.  The packed layer runs on the block-scaled MFMA without being de-quantized:
+    y = linear_mxfp4(x, res.codes, res.scales, bias)      # x (..., K) float32 / bfloat16 / float16 -> (..., N)
+    a_codes, a_scales = quantize_mxfp8(X)                  # what it does to x first: MXFP8 E4M3, (M, K) and (M, K / 32)
+    Y = matmul_mx(a_codes, a_scales, res.codes, res.scales)   # sum_k deq(A)[m][k] deq(W)[n][k], float32 sums
+    layer = MXLinear.from_result(nn_linear, res)           # a torch.nn.Module with buffers codes, scales, bias
+  activations  blocks of 32 along K, scale byte = exponent + 127 of the smallest power of two >= max(amax / 448, 1e-16)
+            (float32; compute_mx_scales' "max" with 448 for 6; a block of zeros: byte 74), elements x / s rounded to
+            nearest even onto OCP E4M3 (e4m3fn: bias 7, subnormals k 2^-9, largest 448 = 0x7e), code = sign << 7 |
+            exp << 3 | man; a zero magnitude is 0x00 (never -0) and 0x7f / 0xff are never written.  NaN or inf: ValueError.
+Known answers: amax 1.0 gives byte 119 and 1.0, -0.3, 0.001, 0 the codes 78 ea 28 00; amax 1.75 gives byte 119 and 1.75,
+-1.75, 0.01, 1e-5 the codes 7e fe 42 01.  The product does not look for scale byte 255: it yields NaN, as the hardware does.
+
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
 everything runs on the GPU on the current stream, and there is no CPU fallback.
 """
@@ -209,3 +221,163 @@ def quantize_mxfp4(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_mo
     out, _ = quantize_layer_mxfp4(dev.to_device(W), dev.to_device(H), act_order, damp, scale_mode, nb_ls_moves, scales,
                                   min_block_size, num_blocks)
     return MXResult(*(dev.like_input(t, W) for t in out))
+
+
+# ---------------------------------------------------------------------------------------------------------------- linear
+_ACT = (torch.float32, torch.bfloat16, torch.float16, np.float32, np.float16)
+_NP_OUT = {torch.float32: np.float32, torch.float16: np.float16}
+
+
+def _out_dtype(dtype, template):
+    if dtype not in _OUT:
+        raise ValueError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16 (got {dtype})")
+    if isinstance(template, np.ndarray) and dtype == torch.bfloat16:
+        raise ValueError("NumPy has no bfloat16: pass the input as a device tensor for a bfloat16 result")
+
+
+def _torch_dtype(x):
+    return x.dtype if isinstance(x, torch.Tensor) else {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}[x.dtype]
+
+
+def _quantize_act(Xd, M, K):
+    """(a_codes, a_scales, flag) of a contiguous device X (M, K) of float32, bfloat16 or float16; the caller reads the flag
+    (_raise_finite) once everything that follows has been launched: reading it waits for the stream."""
+    Xd = _aligned(Xd)
+    codes = torch.empty((M, K), dtype=torch.uint8, device=Xd.device)
+    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
+    _lib.check(_lib.lib.slk_mx_quantize_act(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
+    return codes, scales, flag
+
+
+def _raise_finite(flag):
+    _raise_flag(flag, "activations must be finite: X holds a NaN or an infinity")
+
+
+def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype):
+    out = torch.empty((M, N), dtype=dtype, device=ac.device)
+    _lib.check(_lib.lib.slk_mx_gemm(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _OUT[dtype], dev.ptr(out),
+                                    dev.stream_handle()))
+    return out
+
+
+def _weights(codes, scales):
+    """(N, K) of a packed layer, its shapes and dtypes checked."""
+    N, half = _matrix(codes, "codes", (torch.uint8, np.uint8))
+    K = 2 * half
+    _blocks(K)
+    _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(scales, N, K, "scale bytes")
+    return N, K
+
+
+def _check_bias(bias, N):
+    if bias is not None and (not isinstance(bias, (np.ndarray, torch.Tensor)) or tuple(bias.shape) != (N,)):
+        raise ValueError(f"bias must be ({N},); got {tuple(getattr(bias, 'shape', ()))}")
+
+
+def _bias(bias):
+    return None if bias is None else dev.to_device(bias)
+
+
+def quantize_mxfp8(X):
+    """X (M, K) float32, bfloat16 or float16 -> (a_codes uint8 (M, K), a_scales uint8 (M, K / 32)): MXFP8 E4M3 under
+    non-saturating power-of-two block scales (module docstring).  A NaN or an infinity in X: ValueError."""
+    M, K = _matrix(X, "X", _ACT)
+    _blocks(K)
+    codes, scales, flag = _quantize_act(dev.to_device(X, _torch_dtype(X)), M, K)
+    _raise_finite(flag)
+    return dev.like_input(codes, X), dev.like_input(scales, X)
+
+
+def dequantize_mxfp8(a_codes, a_scales, dtype=torch.float32):
+    """value(code) * 2^(b - 127), (M, K) of `dtype` (bfloat16 or float16: the float32 value rounded to nearest even)."""
+    _out_dtype(dtype, a_codes)
+    M, K = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    _blocks(K)
+    _matrix(a_scales, "scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(a_scales, M, K, "scale bytes")
+    cd, sd = _aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8)
+    out = torch.empty((M, K), dtype=dtype, device=cd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=cd.device)
+    _lib.check(_lib.lib.slk_mx_dequantize_act(dev.ptr(cd), dev.ptr(sd), M, K, _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.stream_handle()))
+    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
+    return dev.like_input(out, a_codes)
+
+
+def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32):
+    """Y (M, N) = deq(a_codes, a_scales) @ deq(codes, scales).T + bias on the block-scaled MFMA: MXFP8 activations (M, K)
+    against an MXFP4 layer (N, K), float32 sums in a fixed order, the result rounded once to `dtype`."""
+    _out_dtype(dtype, a_codes)
+    M, K = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    _blocks(K)
+    _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(a_scales, M, K, "activation scale bytes")
+    N, Kw = _weights(codes, scales)
+    if Kw != K:
+        raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
+    _check_bias(bias, N)
+    out = _gemm(_aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), _aligned(dev.to_device(codes, torch.uint8)),
+                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype)
+    return dev.like_input(out, a_codes)
+
+
+def linear_mxfp4(x, codes, scales, bias=None, dtype=None):
+    """torch.nn.functional.linear with a packed MXFP4 weight: x (..., K) float32, bfloat16 or float16 is quantized to MXFP8
+    (quantize_mxfp8), multiplied with the layer (N, K) as in matmul_mx and the float32 bias (N,) added; the result is
+    (..., N) in `dtype`, or in x's dtype when `dtype` is None."""
+    if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim < 1:
+        raise ValueError("x must be a NumPy array or torch tensor of at least one dimension")
+    if x.dtype not in _ACT:
+        raise ValueError(f"x must be {_ACT[0]}, torch.bfloat16 or torch.float16 (got {x.dtype})")
+    if dtype is None:
+        dtype = _torch_dtype(x)
+    _out_dtype(dtype, x)
+    N, K = _weights(codes, scales)
+    if x.shape[-1] != K:
+        raise ValueError(f"x has {x.shape[-1]} columns but the layer has {K}")
+    _check_bias(bias, N)
+    lead = tuple(x.shape[:-1])
+    M = int(np.prod(lead, dtype=np.int64))
+    if M < 1 or M >= 1 << 31:
+        raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
+    Xd = dev.to_device(x, _torch_dtype(x)).reshape(M, K)
+    ac, asc, flag = _quantize_act(Xd, M, K)
+    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype)
+    _raise_finite(flag)
+    return dev.like_input(out.reshape(lead + (N,)), x)
+
+
+class MXLinear(torch.nn.Module):
+    """A linear layer kept in its packed MXFP4 form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
+    or None; forward(x) = linear_mxfp4(x, codes, scales, bias)."""
+
+    def __init__(self, in_features, out_features, bias=True, device=None):
+        super().__init__()
+        _blocks(int(in_features))
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        self.register_buffer("codes", torch.zeros((self.out_features, self.in_features // 2), dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.full((self.out_features, self.in_features // BLOCK), 127, dtype=torch.uint8, device=device))
+        self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=device) if bias else None)
+
+    @classmethod
+    def from_result(cls, layer, result):
+        """The module of a torch.nn.Linear and the MXResult that Sleekit(layer).quantize_mxfp4() returned (taken after the
+        call, so that a corrected bias comes along)."""
+        if not isinstance(layer, torch.nn.Linear):
+            raise ValueError(f"MXLinear.from_result takes a torch.nn.Linear (got {type(layer).__name__})")
+        N, K = _weights(result.codes, result.scales)
+        if (N, K) != (layer.out_features, layer.in_features):
+            raise ValueError(f"the result is of a ({N}, {K}) layer, not of this ({layer.out_features}, {layer.in_features}) one")
+        self = cls(K, N, layer.bias is not None, layer.weight.device)
+        self.codes.copy_(torch.as_tensor(result.codes))
+        self.scales.copy_(torch.as_tensor(result.scales))
+        if layer.bias is not None:
+            self.bias.copy_(layer.bias.detach().float())
+        return self
+
+    def forward(self, x):
+        return linear_mxfp4(x, self.codes, self.scales, self.bias)
+
+    def extra_repr(self):
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
