@@ -210,24 +210,20 @@ class HipBackend:
 
     def factorize(self, layer):
         eng = self.engine
-        W, H, n = layer["W"], layer["H"], layer["H"].shape[0]
-        mode = eng.order_mode_code(self.act_order)
-        miss = None
-        if mode == 4:  # inv_diag / combined_diag / pivot: sort keys from a kernel of their own
-            miss = eng.order_keys(H, n, self.damp, self.act_order)
-        elif mode >= 2:  # err / sqerr need the statistics of ALL rows, before sharding
-            cb = eng.require_uniform(self.quantizer)
-            if layer.get("gscale") is not None:  # (with the group quantizer, in original units)
-                from . import groups
-
-                miss = groups.column_miss_grouped(W, layer["gscale"], layer["group_size"], cb, mode == 3)
-            else:
-                Ws = eng.rows_divide(W, layer["scale"]) if layer.get("scale") is not None else W
-                miss = eng.column_miss(Ws, cb, mode == 3)
-        factor = eng.factorize(H, n, self.damp, mode, miss)
+        H, n = layer["H"], layer["H"].shape[0]
+        # (err / sqerr keys need the statistics of ALL rows, before sharding)
+        miss = eng.sort_keys(layer["W"], H, eng.require_uniform(self.quantizer), self.act_order, self.damp, scale=layer.get("scale"),
+                             gscale=layer.get("gscale"), group_size=layer.get("group_size"))
+        factor = eng.factorize(H, n, self.damp, eng.order_mode_code(self.act_order), miss)
         if self.with_error:  # the layer error wants to know whether H is symmetric: decided here, once per layer
             factor = factor + (self._symmetry(layer),)
         return factor
+
+    def _plain_order(self):
+        """none / diag: the orders whose keys come from H alone, inside the factorisation -- what a batched one can make."""
+        from . import _lib
+
+        return self.engine.order_mode_code(self.act_order) in (_lib.ORDER_NONE, _lib.ORDER_DIAG)
 
     def _symmetry(self, layer):
         """int32[1] on the device: 1 iff H is bit-wise symmetric.  A layer dict may VOUCH for it (`symmetric=True`: the caller
@@ -246,7 +242,7 @@ class HipBackend:
         eng = self.engine
         n = layers[0]["H"].shape[0]
         mode = eng.order_mode_code(self.act_order)
-        if mode not in (0, 1) or any(lay["H"].shape[0] != n for lay in layers) or len(layers) > 64:
+        if not self._plain_order() or any(lay["H"].shape[0] != n for lay in layers) or len(layers) > 64:
             return [self.factorize(lay) for lay in layers]
         order, U, info = eng.factorize_batch([lay["H"] for lay in layers], n, self.damp, mode)
         out = []
@@ -280,7 +276,7 @@ class HipBackend:
             return 0
         if not self.wants_local_batch(layer):
             # wide layers whose SHARDS are a few rows: a rank's factorisations of consecutive rounds in one chain (below)
-            if not (self.group_wide_rows and rows <= self.group_wide_rows and self.engine.order_mode_code(self.act_order) in (0, 1)):
+            if not (self.group_wide_rows and rows <= self.group_wide_rows and self._plain_order()):
                 return 0
         n = layer["H"].shape[0]
         padded = (rows + 127) // 128 * 128
@@ -315,22 +311,16 @@ class HipBackend:
             n, device = layer["W"].shape[1], layer["W"].device
             return dict(Q=torch.empty((0, n), dtype=torch.float32, device=device), idx=torch.empty((0, n), dtype=torch.uint8, device=device),
                         row_err=torch.empty(0, dtype=torch.float32, device=device) if self.with_error else None, rows=(lo, hi))
-        W = layer["W"][lo:hi].contiguous()
-        sc = layer["scale"][lo:hi].contiguous() if layer.get("scale") is not None else None
-        if layer.get("gscale") is not None:  # the grouped loop on the shard, from the factor it was handed (no search)
-            from . import groups
 
-            res = groups.quantize_layer_grouped(W, layer["gscale"][lo:hi].contiguous(), self.quantizer, layer["H"], layer["group_size"],
-                                                self.act_order, self.damp, want_idx=eng.require_uniform(self.quantizer)[0] <= 256,
-                                                factor=factor[:3])
-        else:
-            # a Hessian the caller vouches to be symmetric: the error comes with the search, or with the loop itself (the
-            # factor is this H's at self.damp on every rank) -- no product of its own
-            vouched = self.with_error and layer.get("symmetric") is True
-            # (lookahead = "alone on the GPU": with overlapping streams the loop takes the window kernel's least-chip-time form)
-            res = eng.quantize_layer(W, layer["H"], self.quantizer, sc, self.act_order, self.damp, self.moves, factor=factor[:3],
-                                     lookahead=not self.overlap, want_ls_error=vouched and self.moves > 0,
-                                     want_loop_error=vouched and self.moves == 0 and eng.loop_error_route())
+        def shard(key):
+            return layer[key][lo:hi].contiguous() if layer.get(key) is not None else None
+
+        W, sc, S = shard("W"), shard("scale"), shard("gscale")
+        carried = self._carried_error([layer])
+        # (lookahead = "alone on the GPU": with overlapping streams the loop takes the window kernel's least-chip-time form)
+        res = eng.quantize_layer(W, layer["H"], self.quantizer, sc, self.act_order, self.damp, self.moves, *self.blocks,
+                                 factor=factor[:3], lookahead=not self.overlap, want_ls_error=carried == "search",
+                                 want_loop_error=carried == "loop", gscale=S, group_size=layer.get("group_size"))
         err = None
         if res.ls_error is not None:  # carried through the search (scaled domain: times scale^2)
             err = res.ls_error if sc is None else (res.ls_error * sc) * sc
@@ -342,6 +332,18 @@ class HipBackend:
             err = eng.row_errors(W, res.Q, layer["H"])
         return dict(Q=res.Q, idx=res.idx, row_err=err, rows=(lo, hi))
 
+    blocks = (32, 8)  # min_block_size, num_blocks of every loop of the stream
+
+    def _carried_error(self, layers):
+        """Where the error of these layers (of one kind) comes from without a product of its own: "search" or "loop" for
+        Hessians the caller vouches to be symmetric (layer["symmetric"] is True) -- the search carries every row's error with it,
+        and so does the loop (the factor is this H's at self.damp on every rank; not with group scales, and unless
+        engine.loop_error_route() says no) -- else None: the product (engine.row_errors*)."""
+        if not self.with_error or layers[0].get("gscale") is not None or not all(lay.get("symmetric") is True for lay in layers):
+            return None
+        if self.moves > 0:
+            return "search"
+        return "loop" if self.engine.loop_error_route() else None
 
     # -- a whole round at once: the row shards of the G layers of a round go through every kernel together
     min_batch = 2  # (tests set 1 to send single-layer rounds through run_round as well)
@@ -356,7 +358,7 @@ class HipBackend:
 
     def run_round(self, round_layers, lo, hi, payloads):
         """Shards of the round's layers from their packed factors: unpack into one stacked factor, ONE loop and
-        ONE error evaluation over all the layers (engine.run_loop_batch) -- R / G rows of a single layer leave
+        ONE error evaluation over all the layers (engine.gptq_loop) -- R / G rows of a single layer leave
         most of the chip idle, the round's G shards together are a full layer's worth of rows."""
         from . import _device as dev
         from . import _lib
@@ -397,15 +399,14 @@ class HipBackend:
         streams (factor chains beside loops)."""
         R, n = layer["W"].shape
         small = n <= self.local_batch_cols or (n <= 2 * self.local_batch_cols and R <= 1024)
-        return self.local_batch > 1 and small and self.engine.order_mode_code(self.act_order) in (0, 1)
+        return self.local_batch > 1 and small and self._plain_order()
 
     def wants_stacked_loop(self, layer):
         """Wide layers with few rows (OPT-350M / BLOOM-560M's 1024 x 4096): the n^3 factorisation fills the chip, the loop
         does not -- its window kernel runs one workgroup per 16 rows, 64 of them for 1024 rows.  Such layers are
         factored one by one on the factor streams and LOOPED in stacks of 4096 rows (run_round_stacked)."""
         R, n = layer["W"].shape
-        return (self.local_batch > 1 and not self.wants_local_batch(layer) and R <= 2048
-                and self.engine.order_mode_code(self.act_order) in (0, 1))
+        return self.local_batch > 1 and not self.wants_local_batch(layer) and R <= 2048 and self._plain_order()
 
     def run_round_stacked(self, round_layers, factors):
         """All rows of a round's layers from their own factors (order, U, info[, symmetry flag]) made elsewhere on this
@@ -432,52 +433,45 @@ class HipBackend:
         device = round_layers[0]["W"].device
         rows = hi - lo
         Rp = (rows + 127) // 128 * 128  # the batch entry points want whole 128-row tiles per layer (96 rows at 768 / 8)
-        scaled = round_layers[0].get("scale") is not None
-        grouped = round_layers[0].get("gscale") is not None
-        # ragged shard: every layer's rows padded to whole tiles (zero weights, unit scale); rows never interact, so the
-        # padding rows are wasted work and nothing else -- they are cut off below.  One launch for the stack either way
+        Hs = [lay["H"] for lay in round_layers]
+        # ragged shard: every layer's rows padded to whole tiles (zero weights, unit scales); rows never interact, so the
+        # padding rows are wasted work and nothing else -- they are cut off below.  One launch per stack either way
         # (engine.stack_rows: a copy per layer was 120 small launches per step for one rank of 8 on OPT-125M).
-        W = eng.stack_rows([lay["W"][lo:hi] for lay in round_layers], Rp, 0.0)
-        sc = eng.stack_rows([lay["scale"][lo:hi] for lay in round_layers], Rp, 1.0) if scaled else None
+
+        def stacked(key, fill):
+            if round_layers[0].get(key) is None:
+                return None
+            return eng.stack_rows([lay[key][lo:hi] for lay in round_layers], Rp, fill)
+
+        W, sc, S = stacked("W", 0.0), stacked("scale", 1.0), stacked("gscale", 1.0)
         cb = eng.require_uniform(self.quantizer)
         want_idx = cb[0] <= 256  # (the kernels emit uint8 indices)
-        if grouped:
-            # group scales: padding rows get unit scales; the loop runs on the unscaled weights and Q comes back de-scaled, so
-            # the layer error is the unscaled layers' (quantize_stream refuses a local search here)
-            from . import groups
-
-            S = eng.stack_rows([lay["gscale"][lo:hi] for lay in round_layers], Rp, 1.0)
-            Q, idx = groups.run_loop_batch_grouped(W, S, order, U, cb, round_layers[0]["group_size"], 32, 8, want_idx=want_idx)
-            err = eng.row_errors_batch(W, Q, [lay["H"] for lay in round_layers], known) if self.with_error else None
-        elif self.moves > 0:
+        carried = self._carried_error(round_layers)
+        if self.moves > 0 and S is None:
             # local search works in the scaled domain (engine.quantize_layer): scaled copy in, ONE search over the stack
             # (engine.local_search_batch: a search per layer is ten small launches, and the shards of a round on several
             # ranks are a few hundred rows each), de-scale on the way out.  (Padding rows of a ragged shard search too:
             # rows never interact, they are cut off below.)
             Ws = eng.rows_divide(W.view(B * Rp, n), sc.reshape(-1)).view(B, Rp, n) if sc is not None else W
-            Q, idx = eng.run_loop_batch(Ws, None, order, U, cb, 32, 8, want_idx=want_idx)
-            # Hessians the caller vouches to be symmetric (layer["symmetric"] is True): the search carries every row's error with
-            # it (obq.py:254, 290 -- the gain of a move IS the change of the error when H is symmetric), so the layer error
-            # needs no product of its own; it comes out in the scaled domain, (W - Qw) = scale (Ws - Q): times scale^2.
+            Q, idx, _, _ = eng.gptq_loop(Ws, cb, order, U, *self.blocks, want_idx=want_idx)
+            # vouched Hessians: the search carries every row's error with it (obq.py:254, 290 -- the gain of a move IS the
+            # change of the error when H is symmetric), so the layer error needs no product of its own; it comes out in the
+            # scaled domain, (W - Qw) = scale (Ws - Q): times scale^2.
             # Per row it is as exact as the reference's own `ls.err` (float32 gains: a few 1e-5 relative on a rare row), the
             # layer's mean agrees with the recomputed product to ~1e-8 (BLOOM-560M, all 96 layers).
-            carried = self.with_error and all(lay.get("symmetric") is True for lay in round_layers)
-            err = torch.empty((B, Rp), dtype=torch.float32, device=device) if carried else None
-            eng.local_search_batch(Ws, Q, [lay["H"] for lay in round_layers], cb, self.moves, idx if want_idx else None, known, err)
+            err = torch.empty((B, Rp), dtype=torch.float32, device=device) if carried == "search" else None
+            eng.local_search_batch(Ws, Q, Hs, cb, self.moves, idx if want_idx else None, known, err)
             if sc is not None:
                 Q = eng.rows_divide(Q.view(B * Rp, n), sc.reshape(-1), invert=True).view(B, Rp, n)
                 if err is not None:
                     err = (err * sc) * sc
-            if self.with_error and err is None:
-                err = eng.row_errors_batch(W, Q, [lay["H"] for lay in round_layers], known)
-        elif self.with_error and all(lay.get("symmetric") is True for lay in round_layers) and eng.loop_error_route():
-            # vouched Hessians, no search: the loop carries every row's error (engine.run_loop_batch with Hs; the loop de-scales
-            # itself here whatever the order, so the error is that of the Q returned); `known` is not needed
-            Q, idx, err = eng.run_loop_batch(W, sc, order, U, cb, 32, 8, want_idx=want_idx, unscale=sc is not None,
-                                             Hs=[lay["H"] for lay in round_layers], damp=self.damp)
         else:
-            Q, idx = eng.run_loop_batch(W, sc, order, U, cb, 32, 8, want_idx=want_idx, unscale=sc is not None)
-            err = eng.row_errors_batch(W, Q, [lay["H"] for lay in round_layers], known) if self.with_error else None
+            # the loop de-scales itself here whatever the order (group scales: it runs on the unscaled weights and Q comes back
+            # de-scaled), so a carried error is that of the Q returned, and so is the product's
+            Q, idx, _, err = eng.gptq_loop(W, cb, order, U, *self.blocks, scale=sc, gscale=S, group_size=round_layers[0].get("group_size"),
+                                           want_idx=want_idx, unscale=sc is not None, Hs=Hs if carried == "loop" else None, damp=self.damp)
+        if self.with_error and err is None:
+            err = eng.row_errors_batch(W, Q, Hs, known)
         return [dict(Q=Q[b, :rows], idx=idx[b, :rows] if want_idx else None, row_err=None if err is None else err[b, :rows], rows=(lo, hi),
                      info=info[b:b + 1]) for b in range(B)]
 

@@ -147,75 +147,72 @@ def loop_error_route():
     return _lib.lib.slk_get_option(b"no_loop_error") == 0
 
 
+def gptq_loop(W, cb_abi, order, U, min_block, num_blocks, scale=None, gscale=None, group_size=None, goffset=None, want_idx=True,
+              want_E=False, unscale=False, latency=False, Hs=None, damp=None):
+    """The column-sequential loop on device tensors: the package's one binding of slk_gptq_quantize*.
+
+    W (R, n) float32 is one layer: order (n,) int64 (None: the columns as they lie), U (n, n) float64.  W (B, R, n) is a batch
+    of layers stacked by rows (R a multiple of 64): order (B, n), U (B, n, n), launches that cover all B layers.  At most one kind
+    of scales, shaped like W without its columns: `scale` (one per row; `unscale`: Q comes back de-scaled), or `gscale` over
+    groups of `group_size` columns (n / group_size per row; Q de-scaled), optionally with the offsets `goffset` beside it.
+    latency: the layer is alone on the GPU (SLK_LOOP_LATENCY: 16-row window workgroups; same results).
+    Hs (a list of the layers' (n, n) float32 Hessians) and damp: the rows' errors (W - Q) H (W - Q)^T carried by the loop
+    (slk_gptq_quantize_batch_error: H symmetric, U its factor at this damp; `scale` then needs `unscale`; not with group scales).
+    Returns (Q, idx, E, row_err): Q, idx (uint8) and E shaped like W, row_err like W without its columns; None when not asked for.
+    """
+    lead, n = tuple(W.shape[:-1]), W.shape[-1]
+    B, R = lead if len(lead) == 2 else (1,) + lead
+    assert W.is_contiguous() and U.shape == lead[:-1] + (n, n) and U.is_contiguous()
+    assert order is None or (order.shape == lead[:-1] + (n,) and order.is_contiguous())
+    assert scale is None or (gscale is None and scale.shape == lead and scale.is_contiguous())
+    assert (gscale is None) == (group_size is None) and (goffset is None or gscale is not None)
+    g = 0
+    if gscale is not None:
+        g = int(group_size)
+        assert g >= 1 and n % g == 0 and Hs is None
+        assert all(t is None or (t.shape == lead + (n // g,) and t.dtype == torch.float32 and t.is_contiguous()) for t in (gscale, goffset))
+    if Hs is not None:
+        assert len(Hs) == B and damp is not None and (scale is None or unscale)
+        assert all(H.shape == (n, n) and H.dtype == torch.float32 and H.is_contiguous() for H in Hs)
+    # (one layer: slk_workspace_bytes, whatever its scales; a batch: slk_workspace_bytes_batch, for the grouped loop at every size)
+    ws, ws_bytes = dev.workspace(R, n, batch=B, grouped=gscale is not None and len(lead) == 2)
+    Q = torch.empty_like(W, dtype=torch.float32)
+    idx = torch.empty(W.shape, dtype=torch.uint8, device=W.device) if want_idx else None
+    E = torch.empty_like(Q) if want_E else None
+    row_err = torch.empty(lead, dtype=torch.float32, device=W.device) if Hs is not None else None
+    levels, lo, hi, table = cb_abi
+    factor = (dev.ptr(order), dev.ptr(U))
+    rest = (B, R, n, levels, lo, hi, dev.ptr(table), int(min_block), int(num_blocks), (1 if unscale else 0) | (2 if latency else 0),
+            dev.ptr(Q), dev.ptr(idx), dev.ptr(E))
+    end = (dev.ptr(ws), ws_bytes, dev.stream_handle())
+    if goffset is not None:
+        rc = _lib.lib.slk_gptq_quantize_grouped_asym_batch(dev.ptr(W), dev.ptr(gscale), dev.ptr(goffset), g, *factor, *rest, *end)
+    elif gscale is not None:
+        rc = _lib.lib.slk_gptq_quantize_grouped_batch(dev.ptr(W), dev.ptr(gscale), g, *factor, *rest, *end)
+    elif Hs is not None:
+        ptrs = (ctypes.c_void_p * B)(*[dev.ptr(H) for H in Hs])
+        rc = _lib.lib.slk_gptq_quantize_batch_error(dev.ptr(W), dev.ptr(scale), *factor, ptrs, float(damp), *rest, dev.ptr(row_err), *end)
+    else:
+        rc = _lib.lib.slk_gptq_quantize_batch(dev.ptr(W), dev.ptr(scale), *factor, *rest, *end)
+    _lib.check(rc)
+    return Q, idx, E, row_err
+
+
 def run_loop(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=True, want_E=False, unscale=False, latency=False,
              H=None, damp=None):
-    """The column-sequential loop on device tensors. Returns (Q, idx, E); `unscale`: Q comes back de-scaled; `latency`:
-    this layer is alone on the GPU (SLK_LOOP_LATENCY: 16-row window workgroups; same results).
-    H (n, n) float32 and damp given: returns (Q, idx, E, row_err), row_err (R,) the rows' errors (W - Q) H (W - Q)^T carried
-    by the loop (slk_gptq_quantize_batch_error: H symmetric, U its factor at this damp; with `scale`, `unscale` is required)."""
-    R, n = W.shape
-    levels, lo, hi, table = cb_abi
-    ws, ws_bytes = dev.workspace(R, n)
-    Q = torch.empty((R, n), dtype=torch.float32, device=W.device)
-    idx = torch.empty((R, n), dtype=torch.uint8, device=W.device) if want_idx else None
-    E = torch.empty((R, n), dtype=torch.float32, device=W.device) if want_E else None
-    if H is not None:
-        assert H.shape == (n, n) and H.dtype == torch.float32 and H.is_contiguous() and damp is not None
-        row_err = torch.empty(R, dtype=torch.float32, device=W.device)
-        ptrs = (ctypes.c_void_p * 1)(dev.ptr(H))
-        _lib.check(
-            _lib.lib.slk_gptq_quantize_batch_error(
-                dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), ptrs, float(damp), 1, R, n, levels, lo, hi, dev.ptr(table),
-                int(min_block), int(num_blocks), (1 if unscale else 0) | (2 if latency else 0), dev.ptr(Q), dev.ptr(idx), dev.ptr(E),
-                dev.ptr(row_err), dev.ptr(ws), ws_bytes, dev.stream_handle(),
-            )
-        )
-        return Q, idx, E, row_err
-    _lib.check(
-        _lib.lib.slk_gptq_quantize(
-            dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), R, n, levels, lo, hi, dev.ptr(table), int(min_block),
-            int(num_blocks), (1 if unscale else 0) | (2 if latency else 0), dev.ptr(Q), dev.ptr(idx), dev.ptr(E), dev.ptr(ws), ws_bytes,
-            dev.stream_handle(),
-        )
-    )
-    return Q, idx, E
+    """gptq_loop for one layer W (R, n) with row scales or none.  Returns (Q, idx, E); with H (n, n) float32 and damp,
+    (Q, idx, E, row_err), row_err (R,) the rows' errors carried by the loop."""
+    out = gptq_loop(W, cb_abi, order, U, min_block, num_blocks, scale=scale, want_idx=want_idx, want_E=want_E, unscale=unscale,
+                    latency=latency, Hs=None if H is None else [H], damp=damp)
+    return out[:3] if H is None else out
 
 
 def run_loop_batch(W, scale, order, U, cb_abi, min_block, num_blocks, want_idx=True, unscale=False, Hs=None, damp=None):
-    """The loop over a batch of layers stacked by rows (slk_gptq_quantize_batch).
-
-    W (B, R, n) float32, scale (B, R) or None, order (B, n) int64, U (B, n, n) float64, all contiguous.
-    Returns (Q, idx) shaped (B, R, n): what B calls of run_loop return, in launches that cover all B layers.
-    Hs (a list of B (n, n) float32 Hessians) and damp given: returns (Q, idx, row_err), row_err (B, R) the rows' errors carried
-    by the loop (slk_gptq_quantize_batch_error; see run_loop).
-    """
-    B, R, n = W.shape
-    assert order.shape == (B, n) and U.shape == (B, n, n) and (scale is None or scale.shape == (B, R))
-    assert W.is_contiguous() and order.is_contiguous() and U.is_contiguous() and (scale is None or scale.is_contiguous())
-    levels, lo, hi, table = cb_abi
-    ws, ws_bytes = dev.workspace(R, n, batch=B)
-    Q = torch.empty((B, R, n), dtype=torch.float32, device=W.device)
-    idx = torch.empty((B, R, n), dtype=torch.uint8, device=W.device) if want_idx else None
-    if Hs is not None:
-        assert len(Hs) == B and damp is not None
-        assert all(H.shape == (n, n) and H.dtype == torch.float32 and H.is_contiguous() for H in Hs)
-        row_err = torch.empty((B, R), dtype=torch.float32, device=W.device)
-        ptrs = (ctypes.c_void_p * B)(*[dev.ptr(H) for H in Hs])
-        _lib.check(
-            _lib.lib.slk_gptq_quantize_batch_error(
-                dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), ptrs, float(damp), B, R, n, levels, lo, hi, dev.ptr(table),
-                int(min_block), int(num_blocks), 1 if unscale else 0, dev.ptr(Q), dev.ptr(idx), None, dev.ptr(row_err), dev.ptr(ws),
-                ws_bytes, dev.stream_handle(),
-            )
-        )
-        return Q, idx, row_err
-    _lib.check(
-        _lib.lib.slk_gptq_quantize_batch(
-            dev.ptr(W), dev.ptr(scale), dev.ptr(order), dev.ptr(U), B, R, n, levels, lo, hi, dev.ptr(table), int(min_block),
-            int(num_blocks), 1 if unscale else 0, dev.ptr(Q), dev.ptr(idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
-        )
-    )
-    return Q, idx
+    """gptq_loop over a batch W (B, R, n), scale (B, R) or None: what B calls of run_loop return.  Returns (Q, idx); with Hs
+    (a list of B Hessians) and damp, (Q, idx, row_err), row_err (B, R)."""
+    Q, idx, _, row_err = gptq_loop(W, cb_abi, order, U, min_block, num_blocks, scale=scale, want_idx=want_idx, unscale=unscale,
+                                   Hs=Hs, damp=damp)
+    return (Q, idx) if Hs is None else (Q, idx, row_err)
 
 
 def row_errors_batch(W, Q, Hs, symmetric=None):
@@ -241,15 +238,27 @@ def symmetry_flag(H):
     return flag
 
 
-def local_search(W, Q, H, cb_abi, moves, idx=None, want_trace=False, gains=None, gains_mode=0, row_err=None):
+def local_search(W, Q, H, cb_abi, moves, idx=None, want_trace=False, gains=None, gains_mode=0, row_err=None, gscale=None,
+                 group_size=None):
     """In place on Q (and idx).  want_trace: returns the (R, moves) int32 record of the moves taken
     (2 * column + up, -1 = none); gains / gains_mode: the carried state of a stateful search (slk_local_search);
-    row_err (R,) float32: receives the rows' errors (W - Q) H (W - Q)^T after the moves."""
+    row_err (R,) float32: receives the rows' errors (W - Q) H (W - Q)^T after the moves.
+    gscale (R, n / group_size) with group_size: the group quantizer's candidates (slk_local_search_grouped: W unscaled, Q
+    de-scaled; no carried state)."""
     R, n = W.shape
     levels, lo, hi, table = cb_abi
     ws, ws_bytes = dev.workspace(R, n)
     trace = torch.empty((R, int(moves)), dtype=torch.int32, device=W.device) if want_trace else None
     assert gains is None or (gains.shape == (R, 2, n) and gains.dtype == torch.float32 and gains.is_contiguous())
+    if gscale is not None:
+        assert gains is None and group_size is not None
+        _lib.check(
+            _lib.lib.slk_local_search_grouped(
+                dev.ptr(W), dev.ptr(Q), dev.ptr(H), dev.ptr(gscale), int(group_size), R, n, levels, lo, hi, dev.ptr(table), int(moves),
+                dev.ptr(idx), dev.ptr(trace), dev.ptr(row_err), dev.ptr(ws), ws_bytes, dev.stream_handle(),
+            )
+        )
+        return trace
     _lib.check(
         _lib.lib.slk_local_search(
             dev.ptr(W), dev.ptr(Q), dev.ptr(H), R, n, levels, lo, hi, dev.ptr(table), int(moves), dev.ptr(idx), dev.ptr(trace),
@@ -298,16 +307,35 @@ def rows_divide(x, scale, invert=False):
     return out
 
 
-def column_miss(W, cb_abi, squared):
+def column_miss(W, cb_abi, squared, gscale=None, group_size=None, goffset=None):
+    """Column sums of |Z(W) - W| (or squared) in NumPy's row-after-row order: Z the codebook, or with gscale (R, n / group_size)
+    the group quantizer (goffset beside it: the asymmetric one), in original units."""
     R, n = W.shape
     levels, lo, hi, table = cb_abi
     out = torch.empty(n, dtype=torch.float32, device=W.device)
-    _lib.check(
-        _lib.lib.slk_column_miss(
-            dev.ptr(W), R, n, levels, lo, hi, dev.ptr(table), 1 if squared else 0, dev.ptr(out), dev.stream_handle()
-        )
-    )
+    rest = (R, n, levels, lo, hi, dev.ptr(table), 1 if squared else 0, dev.ptr(out), dev.stream_handle())
+    if goffset is not None:
+        rc = _lib.lib.slk_column_miss_grouped_asym(dev.ptr(W), dev.ptr(gscale), dev.ptr(goffset), int(group_size), *rest)
+    elif gscale is not None:
+        rc = _lib.lib.slk_column_miss_grouped(dev.ptr(W), dev.ptr(gscale), int(group_size), *rest)
+    else:
+        rc = _lib.lib.slk_column_miss(dev.ptr(W), *rest)
+    _lib.check(rc)
     return out
+
+
+def sort_keys(W, H, cb_abi, act_order, damp, scale=None, gscale=None, group_size=None, goffset=None):
+    """The `miss` argument of slk_hessian_prepare for an order, a layer and its scales: None for none / diag, the kernel-made
+    keys of inv_diag / combined_diag / pivot, and for err / sqerr the statistics of ALL rows of the layer's quantizer -- the
+    codebook on W / scale (`scale` (R,), or W pre-divided already), or the group quantizer of gscale (and goffset) on W."""
+    mode = order_mode_code(act_order)
+    if mode == _lib.ORDER_KEYS:
+        return order_keys(H, H.shape[0], damp, act_order)
+    if mode < _lib.ORDER_ERR:
+        return None
+    if scale is not None:
+        W = rows_divide(W, scale)
+    return column_miss(W, cb_abi, mode == _lib.ORDER_SQERR, gscale, group_size, goffset)
 
 
 def row_errors(W, Q, H, want_G=False):
@@ -326,59 +354,66 @@ def row_errors(W, Q, H, want_G=False):
 def quantize_layer(
     W, H, quantizer, scale=None, act_order="diag", damp=0.01, nb_ls_moves=0, min_block_size=32, num_blocks=8,
     factor=None, unscale=True, want_idx=True, want_ls_trace=False, lookahead=True, want_ls_error=False, want_loop_error=False,
+    *, gscale=None, group_size=None, goffset=None,
 ):
     """One layer through the whole path, on device tensors.
 
     W (R, n) float32, H (n, n) float32, scale (R,) float32 or None.  `factor` = (order, U, info)
-    re-uses a factor computed elsewhere (another GPU: see sleekit_amd.dist).  Returns a
-    LayerResult whose Q is de-scaled when `scale` is given and `unscale` is true
+    re-uses a factor computed elsewhere (another GPU: see sleekit_amd.dist); its status is then the caller's to check.
+    Returns a LayerResult whose Q is de-scaled when `scale` is given and `unscale` is true
     (sleekit/scaling.py:58-81), else the codebook values in the scaled domain
     (sleekit/obq.py:169-217).  want_ls_trace: res.ls_trace = the local search's moves (slk_local_search).
     lookahead: this layer is alone on the GPU (the default of this single-layer API; sleekit_amd.dist passes False): the
     factorisation looks ahead (see factorize) and the loop's window kernel takes 16-row workgroups (SLK_LOOP_LATENCY).
+    want_ls_error: res.ls_error = the rows' errors after the moves, carried through the search, in the domain it ran in.
     want_loop_error: the caller vouches that H is bit-wise symmetric (and that `factor`, if given, is H's at this damp):
-    res.loop_error = the rows' errors (W - Q) H (W - Q)^T carried by the loop (run_loop with H) -- when there is no local
-    search and the loop itself de-scales (or there are no scales); None otherwise (err / sqerr orders with scales run the loop on a
-    pre-divided copy, in the scaled domain): the caller then computes the product.
+    res.loop_error = the rows' errors (W - Q) H (W - Q)^T carried by the loop (gptq_loop with Hs) -- when there is no local
+    search and the loop itself de-scales (or there are no scales); None otherwise: the caller then computes the product.
+    gscale (R, n / group_size) float32 with group_size, instead of `scale`: the group quantizer of sleekit_amd.groups (Q
+    de-scaled, idx the codebook indices of Q / s); goffset beside it: the asymmetric one (no local search).
+
+    What the kinds of scales change:
+    row scales   with err / sqerr keys or a local search, everything runs on the pre-divided copy W / scale, in the scaled
+                 domain, and Q is de-scaled at the end; otherwise the loop's last kernel de-scales on the way out (one pass
+                 over Q less) and can carry the error.
+    group scales the loop runs on the unscaled W (only its leaves scale) with the group quantizer's keys, the search on the
+                 de-scaled Q with that quantizer's candidates; res.ls_error is in original units, filled whenever there are
+                 moves.  The loop carries no error.
     """
     assert W.ndim == 2
     assert H.ndim == 2
     assert H.shape[0] == H.shape[1]
     assert H.shape[0] == W.shape[1]
     assert min_block_size >= 1
+    assert scale is None or gscale is None
+    if goffset is not None and nb_ls_moves > 0:
+        raise NotImplementedError("local search with group offsets is not supported (nb_ls_moves must be 0)")
     cb_abi = require_uniform(quantizer)
     if cb_abi[0] > 256:
         want_idx = False  # (the kernels emit uint8 indices; wider ones come from quantizer.quantize_index on the values)
     mode = order_mode_code(act_order)
     R, n = W.shape
     res = LayerResult()
+    group = dict(gscale=gscale, group_size=group_size)
 
     need_scaled_copy = scale is not None and (mode in (_lib.ORDER_ERR, _lib.ORDER_SQERR) or nb_ls_moves > 0)
     Ws, loop_scale = (rows_divide(W, scale), None) if need_scaled_copy else (W, scale)
 
+    check_factor = factor is None
     if factor is None:
-        if mode == _lib.ORDER_KEYS:
-            miss = order_keys(H, n, damp, act_order)
-        else:
-            miss = column_miss(Ws, cb_abi, mode == _lib.ORDER_SQERR) if mode >= _lib.ORDER_ERR else None
+        miss = sort_keys(Ws, H, cb_abi, act_order, damp, goffset=goffset, **group)
         factor = factorize(H, n, damp, mode, miss, lookahead=lookahead)
-        check_factor = True
-    else:
-        check_factor = False
-    res.order, res.U, res.info = factor
+    res.order, res.U, res.info = factor[:3]
 
-    # without local search the loop's last kernel de-scales on the way out (one pass over Q less)
-    fused = scale is not None and unscale and nb_ls_moves == 0 and loop_scale is not None
-    if want_loop_error and nb_ls_moves == 0 and (scale is None or fused):
-        res.Q, res.idx, _, res.loop_error = run_loop(Ws, loop_scale, res.order, res.U, cb_abi, min_block_size, num_blocks, want_idx,
-                                                     unscale=fused, latency=lookahead, H=H, damp=damp)
-    else:
-        res.Q, res.idx, _ = run_loop(Ws, loop_scale, res.order, res.U, cb_abi, min_block_size, num_blocks, want_idx, unscale=fused,
-                                     latency=lookahead)
+    fused = loop_scale is not None and unscale and nb_ls_moves == 0
+    carried = want_loop_error and nb_ls_moves == 0 and gscale is None and (scale is None or fused)
+    res.Q, res.idx, _, res.loop_error = gptq_loop(Ws, cb_abi, res.order, res.U, min_block_size, num_blocks, scale=loop_scale,
+                                                  goffset=goffset, want_idx=want_idx, unscale=fused, latency=lookahead,
+                                                  Hs=[H] if carried else None, damp=damp, **group)
     if nb_ls_moves > 0:
-        if want_ls_error:  # the rows' errors after the moves, in the scaled domain (res.ls_error)
+        if want_ls_error or gscale is not None:
             res.ls_error = torch.empty(R, dtype=torch.float32, device=W.device)
-        res.ls_trace = local_search(Ws, res.Q, H, cb_abi, nb_ls_moves, res.idx, want_trace=want_ls_trace, row_err=res.ls_error)
+        res.ls_trace = local_search(Ws, res.Q, H, cb_abi, nb_ls_moves, res.idx, want_trace=want_ls_trace, row_err=res.ls_error, **group)
     if scale is not None and unscale and not fused:
         res.Q = rows_divide(res.Q, scale, invert=True)
     # The factorisation's status word is read back only now, with the loop (and the search) already enqueued behind it: read

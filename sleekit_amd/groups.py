@@ -159,87 +159,31 @@ def compute_group_scaling(W, codebook, group_size, H=None, mode="mse", min_facto
 
 
 def column_miss_grouped(W, S, group_size, cb_abi, squared, O=None):
-    """Column sums of |Z(W) - W| (or squared) with the group quantizer Z, in NumPy's row-after-row order (device tensors);
-    O given: the asymmetric group quantizer."""
-    R, n = W.shape
-    levels, lo, hi, table = cb_abi
-    out = torch.empty(n, dtype=torch.float32, device=W.device)
-    if O is not None:
-        _lib.check(
-            _lib.lib.slk_column_miss_grouped_asym(
-                dev.ptr(W), dev.ptr(S), dev.ptr(O), int(group_size), R, n, levels, lo, hi, dev.ptr(table), 1 if squared else 0,
-                dev.ptr(out), dev.stream_handle(),
-            )
-        )
-        return out
-    _lib.check(
-        _lib.lib.slk_column_miss_grouped(
-            dev.ptr(W), dev.ptr(S), int(group_size), R, n, levels, lo, hi, dev.ptr(table), 1 if squared else 0, dev.ptr(out),
-            dev.stream_handle(),
-        )
-    )
-    return out
+    """engine.column_miss with the group quantizer (O given: the asymmetric one), device tensors."""
+    return engine.column_miss(W, cb_abi, squared, S, group_size, O)
 
 
 def grouped_keys(W, S, group_size, cb_abi, act_order, H, damp, O=None):
-    """The sort keys (`miss`) of act_order for a grouped layer: the err / sqerr statistics of the group quantizer (with
-    offsets O, the asymmetric one) over all rows, the kernel-made keys of inv_diag / combined_diag / pivot, None for the rest."""
-    mode = engine.order_mode_code(act_order)
-    if mode == _lib.ORDER_KEYS:
-        return engine.order_keys(H, H.shape[0], damp, act_order)
-    if mode >= _lib.ORDER_ERR:
-        return column_miss_grouped(W, S, group_size, cb_abi, mode == _lib.ORDER_SQERR, O)
-    return None
+    """engine.sort_keys of a grouped layer."""
+    return engine.sort_keys(W, H, cb_abi, act_order, damp, gscale=S, group_size=group_size, goffset=O)
 
 
 def run_loop_batch_grouped(W, S, order, U, cb_abi, group_size, min_block, num_blocks, want_idx=True, offsets=None):
-    """The grouped loop over a batch of layers stacked by rows (slk_gptq_quantize_grouped_batch).
+    """The grouped loop over a batch of layers stacked by rows (engine.gptq_loop).
 
     W (B, R, n) float32, S (B, R, n / group_size) float32, order (B, n) int64, U (B, n, n) float64, all contiguous.
     Returns (Q, idx) shaped (B, R, n), Q de-scaled: what B single-layer grouped loops return, in launches that cover all B.
-    offsets (B, R, n / group_size) float32, contiguous: the asymmetric loop (slk_gptq_quantize_grouped_asym_batch).
+    offsets (B, R, n / group_size) float32, contiguous: the asymmetric loop.
     """
-    B, R, n = W.shape
-    g, G = _groups(n, group_size)
-    assert S.shape == (B, R, G) and order.shape == (B, n) and U.shape == (B, n, n)
-    assert W.is_contiguous() and S.is_contiguous() and order.is_contiguous() and U.is_contiguous()
-    levels, lo, hi, table = cb_abi
-    ws, ws_bytes = dev.workspace(R, n, batch=B, grouped=True)
-    Q = torch.empty((B, R, n), dtype=torch.float32, device=W.device)
-    idx = torch.empty((B, R, n), dtype=torch.uint8, device=W.device) if want_idx else None
-    if offsets is not None:
-        assert offsets.shape == (B, R, G) and offsets.is_contiguous() and offsets.dtype == torch.float32
-        _lib.check(
-            _lib.lib.slk_gptq_quantize_grouped_asym_batch(
-                dev.ptr(W), dev.ptr(S), dev.ptr(offsets), g, dev.ptr(order), dev.ptr(U), B, R, n, levels, lo, hi, dev.ptr(table),
-                int(min_block), int(num_blocks), 0, dev.ptr(Q), dev.ptr(idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
-            )
-        )
-        return Q, idx
-    _lib.check(
-        _lib.lib.slk_gptq_quantize_grouped_batch(
-            dev.ptr(W), dev.ptr(S), g, dev.ptr(order), dev.ptr(U), B, R, n, levels, lo, hi, dev.ptr(table), int(min_block),
-            int(num_blocks), 0, dev.ptr(Q), dev.ptr(idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
-        )
-    )
-    return Q, idx
+    assert W.dim() == 3
+    g, _ = _groups(W.shape[2], group_size)
+    return engine.gptq_loop(W, cb_abi, order, U, min_block, num_blocks, gscale=S, group_size=g, goffset=offsets, want_idx=want_idx)[:2]
 
 
 def run_search_grouped(W, Q, S, H, cb_abi, group_size, moves, idx=None, want_trace=False, row_err=None):
-    """slk_local_search_grouped in place on Q (and idx) (device tensors): W, Q (R, n), S (R, n / group_size), H (n, n).
-    want_trace: returns the (R, moves) int32 record of the moves (engine.local_search); row_err (R,) float32: receives the
-    rows' errors after the moves."""
-    R, n = W.shape
-    levels, lo, hi, table = cb_abi
-    ws, ws_bytes = dev.workspace(R, n)
-    trace = torch.empty((R, int(moves)), dtype=torch.int32, device=W.device) if want_trace else None
-    _lib.check(
-        _lib.lib.slk_local_search_grouped(
-            dev.ptr(W), dev.ptr(Q), dev.ptr(H), dev.ptr(S), int(group_size), R, n, levels, lo, hi, dev.ptr(table), int(moves),
-            dev.ptr(idx), dev.ptr(trace), dev.ptr(row_err), dev.ptr(ws), ws_bytes, dev.stream_handle(),
-        )
-    )
-    return trace
+    """engine.local_search with the group quantizer's candidates, in place on Q (and idx) (device tensors): W, Q (R, n),
+    S (R, n / group_size), H (n, n)."""
+    return engine.local_search(W, Q, H, cb_abi, moves, idx, want_trace=want_trace, row_err=row_err, gscale=S, group_size=group_size)
 
 
 def _check_scales(S, R, n, g):
@@ -272,8 +216,8 @@ def local_search_grouped(W, Q, S, quantizer, H, group_size, nb_moves, return_ind
 
 def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,
                            want_idx=True, factor=None, lookahead=True, nb_ls_moves=0, want_ls_trace=False, offsets=None):
-    """The grouped layer on device tensors: W (R, n), S (R, n / group_size), H (n, n), all float32.  Returns an
-    engine.LayerResult (Q de-scaled, idx uint8 or None, order, U, info); raises LinAlgError if H + damping is not
+    """The grouped layer on device tensors (engine.quantize_layer with gscale): W (R, n), S (R, n / group_size), H (n, n), all
+    float32.  Returns an engine.LayerResult (Q de-scaled, idx uint8 or None, order, U, info); raises LinAlgError if H + damping is not
     positive definite.  `factor` = (order, U, info) re-uses a factor made elsewhere (sleekit_amd.dist: a row shard), as
     engine.quantize_layer does; its status is then the caller's to check.  lookahead: this layer is alone on the GPU
     (engine.factorize).  nb_ls_moves > 0: the local search (local_search_grouped) runs after the loop, on Q and idx in
@@ -291,41 +235,8 @@ def quantize_layer_grouped(W, S, quantizer, H, group_size, act_order="diag", dam
         if nb_ls_moves > 0:
             raise NotImplementedError("local search with group offsets is not supported (nb_ls_moves must be 0)")
         O = _check_offsets(offsets, R, n, g)
-    res = engine.LayerResult()
-    check_factor = factor is None
-    if factor is None:
-        miss = grouped_keys(W, S, g, cb_abi, act_order, H, damp, O)
-        factor = engine.factorize(H, n, damp, engine.order_mode_code(act_order), miss, lookahead=lookahead)
-    res.order, res.U, res.info = factor[:3]
-    levels, lo, hi, table = cb_abi
-    ws, ws_bytes = dev.workspace(R, n)
-    res.Q = torch.empty((R, n), dtype=torch.float32, device=W.device)
-    res.idx = torch.empty((R, n), dtype=torch.uint8, device=W.device) if want_idx else None
-    if O is not None:
-        _lib.check(
-            _lib.lib.slk_gptq_quantize_grouped_asym(
-                dev.ptr(W), dev.ptr(S), dev.ptr(O), g, dev.ptr(res.order), dev.ptr(res.U), R, n, levels, lo, hi, dev.ptr(table),
-                int(min_block_size), int(num_blocks), 2, dev.ptr(res.Q), dev.ptr(res.idx), None, dev.ptr(ws), ws_bytes,
-                dev.stream_handle(),
-            )
-        )
-        if check_factor:
-            dev.note_info(res.info, "compute_hessian_chol")
-        return res
-    _lib.check(
-        _lib.lib.slk_gptq_quantize_grouped(
-            dev.ptr(W), dev.ptr(S), g, dev.ptr(res.order), dev.ptr(res.U), R, n, levels, lo, hi, dev.ptr(table), int(min_block_size),
-            int(num_blocks), 2, dev.ptr(res.Q), dev.ptr(res.idx), None, dev.ptr(ws), ws_bytes, dev.stream_handle(),
-        )
-    )
-    if nb_ls_moves > 0:
-        res.ls_error = torch.empty(R, dtype=torch.float32, device=W.device)
-        res.ls_trace = run_search_grouped(W, res.Q, S, H, cb_abi, g, nb_ls_moves, res.idx, want_trace=want_ls_trace,
-                                          row_err=res.ls_error)
-    # read back behind the loop (and the search), as engine.quantize_layer does
-    if check_factor:
-        dev.note_info(res.info, "compute_hessian_chol")
-    return res
+    return engine.quantize_layer(W, H, quantizer, None, act_order, damp, nb_ls_moves, min_block_size, num_blocks, factor,
+                                 want_idx=want_idx, want_ls_trace=want_ls_trace, lookahead=lookahead, gscale=S, group_size=g, goffset=O)
 
 
 def quantize_grouped(W, S, quantizer, H, group_size, act_order="diag", damp=0.01, min_block_size=32, num_blocks=8,

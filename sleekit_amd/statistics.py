@@ -118,6 +118,26 @@ class Sleekit:
     quantize_sleekit_light = _preset_method("sleekit_light")
     quantize_sleekit_heavy = _preset_method("sleekit_heavy")
 
+    def _weight_and_hessian(self, bias_correction):
+        """The weight as an (out, features) float32 matrix and the Hessian to quantize against: H - mean mean^T under
+        bias_correction (a copy), else H itself."""
+        weight = self.layer.weight.data.flatten(1).float().contiguous()
+        H = self.hessian
+        if bias_correction:
+            centred = torch.empty_like(H)
+            _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
+            H = centred
+        return weight, H
+
+    def _store(self, result, weight, bias_correction):
+        """result.Q becomes the layer's weight; under bias_correction the expected output shift moves into the bias."""
+        target = self.layer.weight
+        target.data = result.Q.reshape(target.shape).to(target.dtype)
+        if bias_correction:
+            shift = ((weight - result.Q) * self.mean).sum(dim=1)
+            self.layer.bias.data += shift.to(self.layer.bias.dtype)
+        return result
+
     def quantize(self, nbits, scaling_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0,
                  grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, offsets=None, group_size=None):
         """The layer's weight replaced by its `nbits` quantization, in place (statistics.py:146-190).
@@ -137,22 +157,12 @@ class Sleekit:
             return self._quantize_grouped(nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
                                           max_factor, scale, group_size, offsets)
         codebook = UniformCodebook(2**nbits, -1, 1)
-        weight = self.layer.weight.data.flatten(1).float().contiguous()
-        H = self.hessian
-        if bias_correction:
-            centred = torch.empty_like(H)
-            _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
-            H = centred
+        weight, H = self._weight_and_hessian(bias_correction)
         if scale is None:
             scale = compute_scaling(weight, codebook, H=H, mode=scaling_mode, grid_size=grid_size, min_factor=min_factor,
                                     max_factor=max_factor)
         result = engine.quantize_layer(weight, H, codebook, dev.to_device(scale), order_mode, damp, nb_ls_moves)
-        target = self.layer.weight
-        target.data = result.Q.reshape(target.shape).to(target.dtype)
-        if bias_correction:
-            shift = ((weight - result.Q) * self.mean).sum(dim=1)
-            self.layer.bias.data += shift.to(self.layer.bias.dtype)
-        return result
+        return self._store(result, weight, bias_correction)
 
     def _quantize_grouped(self, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
                           max_factor, scale, group_size, offsets=None):
@@ -163,12 +173,7 @@ class Sleekit:
         if scaling_mode == "obq":
             raise NotImplementedError('the "obq" scaling mode is not supported with group scales')
         codebook = UniformCodebook(2**nbits, -1, 1)
-        weight = self.layer.weight.data.flatten(1).float().contiguous()
-        H = self.hessian
-        if bias_correction:
-            centred = torch.empty_like(H)
-            _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
-            H = centred
+        weight, H = self._weight_and_hessian(bias_correction)
         search = dict(H=H, mode=scaling_mode, grid_size=grid_size, min_factor=min_factor, max_factor=max_factor)
         if isinstance(offsets, str):
             if offsets != "mid":
@@ -186,12 +191,7 @@ class Sleekit:
         result = groups.quantize_layer_grouped(weight, scale, codebook, H, group_size, order_mode, damp, offsets=offsets)
         if offsets is not None:
             result.S, result.O = scale, offsets
-        target = self.layer.weight
-        target.data = result.Q.reshape(target.shape).to(target.dtype)
-        if bias_correction:
-            shift = ((weight - result.Q) * self.mean).sum(dim=1)
-            self.layer.bias.data += shift.to(self.layer.bias.dtype)
-        return result
+        return self._store(result, weight, bias_correction)
 
     def quantize_mxfp4(self, scale_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0):
         """The layer's weight replaced by its MXFP4 quantization, in place (sleekit_amd.mx): power-of-two scales per block of
@@ -200,20 +200,10 @@ class Sleekit:
         result.codes (uint8 (out, features / 2)) and result.scales (E8M0 bytes (out, features / 32))."""
         from . import mx
 
-        weight = self.layer.weight.data.flatten(1).float().contiguous()
-        H = self.hessian
-        if bias_correction:
-            centred = torch.empty_like(H)
-            _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
-            H = centred
+        weight, H = self._weight_and_hessian(bias_correction)
         packed, result = mx.quantize_layer_mxfp4(weight, H, order_mode, damp, scale_mode, nb_ls_moves)
         result.S, result.codes, result.scales = packed.S, packed.codes, packed.scales
-        target = self.layer.weight
-        target.data = result.Q.reshape(target.shape).to(target.dtype)
-        if bias_correction:
-            shift = ((weight - result.Q) * self.mean).sum(dim=1)
-            self.layer.bias.data += shift.to(self.layer.bias.dtype)
-        return result
+        return self._store(result, weight, bias_correction)
 
     def free(self):
         self.layer = self.mean = self.hessian = None

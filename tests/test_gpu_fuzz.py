@@ -127,3 +127,38 @@ def test_batched_rounds_against_single_layers(amd, seed):
         res = amd.engine.quantize_layer(lay["W"], lay["H"], cb, lay["scale"], order, damp, moves)
         assert torch.equal(sh["Q"], res.Q) and torch.equal(sh["idx"], res.idx), (B, R, n, levels, damp, moves, order)
         assert int(sh["info"].item()) == 0
+
+
+@pytest.mark.parametrize("act_order,moves", [("err", 0), ("sqerr", 0), ("inv_diag", 0), ("pivot", 0), ("sqerr", 4)])
+def test_stream_keys_of_row_scaled_layers(amd, act_order, moves):
+    """Row-scaled layers through the stream at the orders whose sort keys HipBackend.factorize has to make itself (err / sqerr:
+    the statistics of W / scale over all rows; inv_diag / pivot: the kernel-made keys) against engine.quantize_layer layer by
+    layer: bit-equal values and indices, and the shard's row errors within 1e-5 relative of the product, the bound the layer
+    error is held to.  70 rows are ragged against the 64- and 128-row tiles, 172 columns are no multiple of 64."""
+    import torch
+
+    from sleekit_amd import dist as sdist
+
+    rng = np.random.default_rng(1300)
+    R, n, damp = 70, 172, 0.01
+    cb = amd.codebook.UniformCodebook(8, -1, 1)
+    layers = []
+    for b in range(3):
+        T = 2 * n + 8
+        X = rng.standard_normal((T, n)) * (0.5 + 2.0 * rng.random(n))
+        H = (X.T @ X / T).astype(np.float32)
+        H = ((H + H.T) * np.float32(0.5)).astype(np.float32)
+        W = (rng.standard_normal((R, n)) * 0.05).astype(np.float32)
+        scale = (np.abs(W).max(axis=1) * np.float32(0.55) + np.float32(1e-6)).astype(np.float32)
+        layers.append({k: torch.from_numpy(v).cuda() for k, v in (("W", W), ("H", H), ("scale", scale))})
+    be = sdist.HipBackend(cb, act_order, damp, moves, with_error=True)
+    shards = sdist.quantize_stream(layers, be)
+    torch.cuda.synchronize()
+    for lay, sh in zip(layers, shards):
+        res = amd.engine.quantize_layer(lay["W"], lay["H"], cb, lay["scale"], act_order, damp, moves)
+        assert torch.equal(sh["Q"], res.Q) and torch.equal(sh["idx"], res.idx), (act_order, moves)
+        assert int(sh["info"].item()) == 0
+        want = amd.engine.row_errors(lay["W"], res.Q, lay["H"])
+        off = float(((sh["row_err"] - want).abs() / want.abs()).max())
+        print(f"{act_order} moves={moves}: largest relative row error difference {off:.3g}")
+        assert off <= 1e-5
