@@ -14,19 +14,14 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <type_traits>
 #include <vector>
 
-#include "mfma64.h"
+#include "window2.h"
 
 namespace slk {
 
 constexpr int OP_LEAF = 0, OP_UPDATE = 1;
-constexpr int WMAX = 512;     // widest window held in LDS
-constexpr int WPITCH = WMAX + 4;
-constexpr int RB = 16;        // rows per window workgroup
 constexpr int MAX_OPS = 60;   // ops per window kernel (kernel-argument table)
-constexpr int ULEAF = 32;     // leaves up to this width stage their U block in LDS
 
 struct Op {
     int kind, a, b, c;
@@ -236,11 +231,6 @@ __global__ __launch_bounds__(256) void k_permute_out_grouped(const float *__rest
 }
 
 // ------------------------------------------------------------------ window kernel
-struct LeafTables {
-    double u[ULEAF][ULEAF + 1];  // leaf block of U, STRICTLY upper part (zero on/below the diagonal and beyond the width)
-    double udr[ULEAF][2];        // its diagonal (1 beyond the width) and 1 / diagonal by true division
-    __device__ __forceinline__ static int col(int j) { return j; }  // where column j of a row of u sits
-};
 struct WindowSmem {
     // leaf tables first: their offsets fit the 16-bit immediate of ds_read, so the unrolled leaf
     // needs one address register instead of one per step.  Two copies: the helper waves fill the
@@ -251,118 +241,14 @@ struct WindowSmem {
     float e[RB][WPITCH];
     float cbt[512];  // a general codebook's values and limits (<= 256 entries), copied here for the leaves
 };
-
-// codebook.py:56-65 with the divide replaced by Markstein's sequence: with y = RN(1/step),
-//   q0 = RN(t0 y);  r = t0 - step q0 (exact in one fma);  t = RN(q0 + r y) == RN(t0 / step)
-// for every t0 whose quotient neither overflows nor underflows (rint of an underflowing
-// quotient is 0 either way).  Saves ~40 dependent cycles per column on the leaf's critical
-// path.  tests/test_gpu_parity.py::test_fast_quantizer_matches_true_divide sweeps it against
-// the true-divide kernel.  The clamp is one v_med3 (the leaf chain counts instructions).
-__device__ __forceinline__ float grid_value_fast(float x, const Grid g, float inv_step) {
-    const float t0 = x - g.zero;
-    const float q0 = t0 * inv_step;
-    const float r = __builtin_fmaf(-g.step, q0, t0);
-    float t = __builtin_fmaf(r, inv_step, q0);
-    t = rintf(t);
-    t = __builtin_amdgcn_fmed3f(t, 0.0f, g.top);
-    return t * g.step + g.zero;
-}
-
-// A column's error float64(x - q) / uii (obq.py:112).  FAST: the exact-division fma sequence with rii = RN(1 / uii) taken
-// once per leaf by a true division (exact unless uii's significand is all ones, which the caller has excluded).
-template <bool FAST>
-__device__ __forceinline__ double chain_err(float x, float q, double uii, double rii) {
-    const double d = (double)(x - q);
-    if constexpr (FAST) {
-        const double qq = d * rii;
-        const double rem = __builtin_fma(-uii, qq, d);
-        return __builtin_fma(rem, rii, qq);
-    } else {
-        return d / uii;
-    }
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// lane L of every 16-lane row, to all lanes of that row (DPP row_newbcast, gfx90a and later)
-template <int L>
-__device__ __forceinline__ float row_bcast(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + L, 0xf, 0xf, true));
-}
-
-// the per-row quantizer: nothing to read per step
-struct LeafRows {
-    struct Step {};
-    __device__ __forceinline__ Step at(int, int, int) const { return {}; }
-    template <bool FAST>
-    __device__ __forceinline__ static float q(float x, Step, const Grid g, float inv_step) {
-        return FAST ? grid_value_fast(x, g, inv_step) : cb_value(x, g);
-    }
+// the update's view of it (TileUpdate): one tile, E beside Q, column for column
+struct WindowTile {
+    WindowSmem &sm;
+    int w0;
+    __device__ __forceinline__ float *q(int, int row, int col) const { return &sm.q[row][col - w0]; }
+    __device__ __forceinline__ const float *e(int, int row, int k) const { return &sm.e[row][k - w0]; }
+    __device__ __forceinline__ static bool straight(int) { return true; }
 };
-
-// LEAF, register path (width <= 32, tables in LDS): a chain wave owns FOUR rows, 16 lanes per row; lane c16 keeps
-// columns c16 and 16 + c16 of its row's leaf in x0 and x1.  Step i: column i's value is broadcast inside its
-// 16-lane DPP row, every lane recomputes q_i and err_i for its own row (no second broadcast), then
-// updates its two columns:  x_c <- float32(float64(x_c) - err_i * U[i][c])   (obq.py:114-118)
-// FAST: Markstein divisions (chain_err, grid_value_fast); otherwise true divides / table look-ups.
-// The loop is issue-bound (~35 instructions a step with the per-step selection this chain no longer has), which is why
-// four rows share a wave and, in k_gptq_window, the other four waves of the workgroup stay parked at the barrier: two
-// waves per SIMD would just take turns (measured 430 -> ~230 cycles/step).
-// Steps beyond the width run on the padding (x = 0, U row = 0, diagonal = 1; the group tables
-// read 1.0 / slot GSLOTS there: a finite error that meets a zero U row) and change nothing: no per-step branch,
-// so the whole leaf is one basic block and the LDS reads of step i + 1 (U row, diagonal,
-// reciprocal, the policy's step) are issued before the arithmetic of step i.
-// The policy P is the quantizer: P::Step is what a step reads from LDS besides U (read one step
-// ahead, like the U row), pol.at(row, a, k) reads it for column a + k of tile row `row`, and P::q<FAST>(x, step, g, inv_step)
-// forms q.  (The tile's reads take a and k apart: one base address for s and rs, k in the offsets.)
-// On return q0, e0 (q1, e1) are the quantized value and scaled error of columns c16 (16 + c16); loading x and storing
-// q and e is the caller's.
-template <int NSTEP, bool FAST, class P>
-__device__ __forceinline__ void leaf_chain16(const LeafTables &lt, const P &pol, int row, int a, int c16, float x0, float x1, float &q0,
-                                             float &q1, float &e0, float &e1, const Grid g, float inv_step) {
-    static_assert(FAST || std::is_same<P, LeafRows>::value, "the group quantizers' slow path is the generic leaf");
-    double u0n = lt.u[0][c16], u1n = lt.u[0][c16 + 16], uiin = lt.udr[0][0], riin = lt.udr[0][1];
-    typename P::Step sn = pol.at(row, a, 0);
-    static_for<0, NSTEP>([&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-        const double u0 = u0n, u1 = u1n, uii = uiin, rii = riin;
-        const typename P::Step sc = sn;
-        if constexpr (i + 1 < NSTEP) {
-            u0n = lt.u[i + 1][c16];
-            u1n = lt.u[i + 1][c16 + 16];
-            uiin = lt.udr[i + 1][0];
-            riin = lt.udr[i + 1][1];
-            sn = pol.at(row, a, i + 1);
-        }
-        // the chain values pass through this point: the reads above are issued before step i starts
-        asm volatile("" : "+v"(x0), "+v"(x1)::"memory");
-        // column i of each of the wave's rows, broadcast inside its 16-lane DPP row; every lane recomputes the
-        // column's error for its own row.  The chain is bound by the ISSUE of these instructions: nothing is kept
-        // per step (the column's own q and e come after the loop, below)
-        const float xi = row_bcast<(i & 15)>(i < 16 ? x0 : x1);
-        const double err = chain_err<FAST>(xi, P::template q<FAST>(xi, sc, g, inv_step), uii, rii);
-        // the staged block is zero on and below the diagonal: only later columns move
-        if (i < 15) x0 = (float)((double)x0 - err * u0);
-        if (NSTEP > 16) x1 = (float)((double)x1 - err * u1);
-    });
-    // A lane's own columns are final once their step has passed: the block of U is zero on and below the diagonal, so
-    // the later steps subtract err * 0 (at most the sign of a zero changes, which no result can see).  Their q and e
-    // are the same expressions on the same value as in the step that broadcast it: computed once here instead of being
-    // selected into place in every step (two v_cndmask and a conversion per step less on the chain).  The policy's step
-    // of a lane's own column is a run-time k into the same tables.
-    q0 = P::template q<FAST>(x0, pol.at(row, a, c16), g, inv_step);
-    e0 = (float)chain_err<FAST>(x0, q0, lt.udr[c16][0], lt.udr[c16][1]);
-    if constexpr (NSTEP > 16) {
-        q1 = P::template q<FAST>(x1, pol.at(row, a, c16 + 16), g, inv_step);
-        e1 = (float)chain_err<FAST>(x1, q1, lt.udr[c16 + 16][0], lt.udr[c16 + 16][1]);
-    }
-}
 
 // the group quantizers: q = codebook(x / s) / rs (two true divides; the codebook step keeps the exact-division sequence),
 // OFFSET codebook((x - o) / s) / rs + o
@@ -432,45 +318,12 @@ __device__ __forceinline__ void leaf_tile16(WindowSmem &sm, const P &pol, const 
     }
 }
 
-// ---- staging of a leaf's tables by the 256 helper threads (ht = 0 ... 255): thread ht carries the slots e = ht + 256 h,
-// h < 4, of the 32 x 32 block, slot e = (row e >> 5, column e & 31).
-// registers <- U[a : a + w, a : a + w], w >= 1 (clamped, selected when written)
-__device__ __forceinline__ void fetch_leaf_block(const double *__restrict__ U, int n, int a, int w, int ht, double (&pu)[4]) {
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        const int e = ht + 256 * h, i = min(e >> 5, w - 1), j = min(e & 31, w - 1);
-        pu[h] = U[(size_t)(a + i) * n + a + j];
-    }
+// The generic leaves' quantizer (true divides): the codebook alone, or through the group's scale (and offset)
+template <bool GROUPED, bool OFFSET>
+__device__ __forceinline__ float generic_q(float x, const GroupQ<OFFSET> gq, const Grid g) {
+    if constexpr (GROUPED) return gq.value(x, g);
+    else return cb_value(x, g);
 }
-// table <- registers, all 32 x 32 slots (w = 0: an empty leaf).  Returns whether a diagonal entry met by this WAVE defeats
-// the exact-division shortcut: a significand that is all ones.
-template <class Tables>
-__device__ __forceinline__ bool write_leaf_tables(Tables &lt, const double (&pu)[4], int w, int ht) {
-    // a thread meets at most one diagonal slot (e = 33 i): one division, not four
-    double dgv = 1.0;
-    int di = -1;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        const int e = ht + 256 * h, i = e >> 5, j = e & 31;
-        const bool in = i < w && j < w;
-        lt.u[i][Tables::col(j)] = (in && j > i) ? pu[h] : 0.0;
-        if (i == j) {
-            dgv = in ? pu[h] : 1.0;
-            di = i;
-        }
-    }
-    bool odd = false;
-    if (di >= 0) {
-        lt.udr[di][0] = dgv;
-        lt.udr[di][1] = 1.0 / dgv;
-        odd = (__double_as_longlong(dgv) & 0xFFFFFFFFFFFFFLL) == 0xFFFFFFFFFFFFFLL;
-    }
-    return __builtin_amdgcn_ballot_w64(odd) != 0;
-}
-
-// cycle counters of workgroup 0 (SLK_WIN_DBG bit 3), read back by slk_probe_window_cycles
-__device__ long long g_win_cycles[16];
-__device__ long long g_win_trace[64];  // window2: busy cycles per period, chain wave 0 / helper wave 2 (+32)
 
 // One workgroup = 512 threads = 8 waves = RB rows, Q and E of the window resident in LDS.
 //
@@ -489,7 +342,8 @@ __device__ long long g_win_trace[64];  // window2: busy cycles per period, chain
 // updates, deferral, staging -- is the same code.
 // OFFSET (with GROUPED): the asymmetric group quantizer, offsets O (R x G) beside S; in LDS a GroupSlots behind WindowSmem
 // when G <= GSLOTS, otherwise every leaf is the generic one and reads S and O from memory.
-template <bool IN_LDS, bool GROUPED, bool OFFSET = false>
+// (A window wider than WMAX is a single leaf: k_gptq_wide_leaf.)
+template <bool GROUPED, bool OFFSET = false>
 __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, float *__restrict__ Eg,
                                                      const double *__restrict__ U, int R, int n, int w0, int w1,
                                                      Grid g, float inv_step, int fast_ok, int dbg, OpTable tab, int rpl,
@@ -498,52 +352,25 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
     static_assert(GROUPED || !OFFSET, "offsets come with group scales");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     WindowSmem &sm = *reinterpret_cast<WindowSmem *>(smem_raw);
-    GroupTile &gt = *reinterpret_cast<GroupTile *>(smem_raw + sizeof(WindowSmem));  // (GROUPED && IN_LDS only)
-    GroupSlots &gs = *reinterpret_cast<GroupSlots *>(smem_raw + sizeof(WindowSmem));  // (OFFSET && IN_LDS only)
-    const bool slots = OFFSET && IN_LDS && G <= GSLOTS;  // the leaves' s, rs, o in LDS
+    GroupTile &gt = *reinterpret_cast<GroupTile *>(smem_raw + sizeof(WindowSmem));  // (GROUPED only)
+    GroupSlots &gs = *reinterpret_cast<GroupSlots *>(smem_raw + sizeof(WindowSmem));  // (OFFSET only)
+    const bool slots = OFFSET && G <= GSLOTS;  // the leaves' s, rs, o in LDS
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const bool helper = wave >= 4;
     const int ht = t - 256;  // helper thread index
     const int r0 = blockIdx.x * RB;
     U += (size_t)(r0 / rpl) * n * n;  // a batch of layers stacked by rows: rows [b rpl, (b + 1) rpl) use factor b
     if constexpr (GROUPED) pg += (size_t)(r0 / rpl) * n;  // ... and group table b (a tile never straddles two layers)
-    if (IN_LDS && g.table) {  // the leaves search the codebook once per column: keep it next to them
+    if (g.table) {  // the leaves search the codebook once per column: keep it next to them
         for (int i = t; i < 2 * g.n - 1; i += 512) sm.cbt[i] = g.table[i];
         g.table = sm.cbt;  // visible after the first barrier below
     }
     const int width = w1 - w0;
-    // cycle accounting (debug): wave-uniform accumulators, written out once at the end
-    const bool timing = (dbg & 8) && blockIdx.x == 0;
-    long long tmark = timing ? (long long)__builtin_readcyclecounter() : 0;
-    const long long tstart = tmark;
-    long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    // adds the cycles since the last mark to counter `slot` (wave `w` only)
-    auto lap = [&](int slot, int w) {
-        if (timing) {
-            const long long now = (long long)__builtin_readcyclecounter();
-            if (wave == w) tacc[slot] += now - tmark;
-            tmark = now;
-        }
-    };
-
-    // tile accessors: LDS copy of the window, or the global arrays themselves (very wide leaves).
-    // Plain accesses: every producer/consumer pair below is separated by a __syncthreads().
-    auto qld = [&](int r, int c) -> float { return IN_LDS ? sm.q[r][c - w0] : Qp[(size_t)(r0 + r) * n + c]; };
-    auto eld = [&](int r, int c) -> float { return IN_LDS ? sm.e[r][c - w0] : Eg[(size_t)(r0 + r) * n + c]; };
-    auto qst = [&](int r, int c, float v) {
-        if (IN_LDS) sm.q[r][c - w0] = v; else Qp[(size_t)(r0 + r) * n + c] = v;
-    };
-    auto est = [&](int r, int c, float v) {
-        if (IN_LDS) sm.e[r][c - w0] = v; else Eg[(size_t)(r0 + r) * n + c] = v;
-    };
-    // columns [c_lo, c_hi) of the Q tile, global -> LDS, by `nth` threads of which this is number `tid`
-    auto load_cols = [&](int c_lo, int c_hi, int tid, int nth) {
-        const int cw = c_hi - c_lo;
-        for (int e = tid; e < RB * cw; e += nth) {
-            const int r = e / cw, c = c_lo + e % cw;
-            sm.q[r][c - w0] = (r0 + r < R) ? Qp[(size_t)(r0 + r) * n + c] : 0.0f;
-        }
-    };
+    Laps laps(dbg);  // cycle accounting (debug)
+    auto lap = [&](int slot, int w) { laps.lap(slot, wave == w); };
+    // Plain accesses to the tile: every producer/consumer pair below is separated by a __syncthreads().
+    const bool vec4 = tile_vec4(Qp, n, w0);
+    auto load_cols = [&](int c_lo, int c_hi, int tid, int nth) { load_tile_cols<RB>(sm.q, Qp, r0, R, n, w0, vec4, c_lo, c_hi, tid, nth); };
 
     // ---- staging pipeline of the leaf tables (helpers only): registers <- U two staged leaves
     // ahead, LDS buffer <- registers one leaf ahead.
@@ -567,7 +394,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
         if (lane == 0) sm.odd[buf][wave - 4] = any ? 1 : 0;
     };
 
-    if constexpr (OFFSET && IN_LDS) {  // every group of the tile's rows (s = 1, o = 0 beyond G and R), read after the barrier below
+    if constexpr (OFFSET) {  // every group of the tile's rows (s = 1, o = 0 beyond G and R), read after the barrier below
         if (slots) {
             for (int e = t; e < RB * (GSLOTS + 1); e += 512) {
                 const int r = e / (GSLOTS + 1), k = e % (GSLOTS + 1);
@@ -580,7 +407,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             for (int c = t; c < GPITCH; c += 512) gs.slot[c] = c < width ? pg[w0 + c] : GSLOTS;
         }
     }
-    if constexpr (GROUPED && !OFFSET && IN_LDS) {  // the window's scales (1.0 on the padding and on rows beyond R), read after the barrier below
+    if constexpr (GROUPED && !OFFSET) {  // the window's scales (1.0 on the padding and on rows beyond R), read after the barrier below
         for (int e = t; e < RB * GPITCH; e += 512) {
             const int r = e / GPITCH, c = e % GPITCH;
             const float sv = (c < width && r0 + r < R) ? Sg[(size_t)(r0 + r) * G + pg[w0 + c]] : 1.0f;
@@ -592,7 +419,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
     // Warm this XCD's L2 with the window's block of U (workgroup i runs on XCD i % 8; the
     // workgroups of an XCD share the lines, one 4-byte touch per 128-byte line).
     float warm = 0.0f;
-    if (IN_LDS && !(dbg & 16)) {
+    if (!(dbg & 16)) {
         const int per_xcd = max(1, min(32, (int)gridDim.x >> 3));
         const int slice = (blockIdx.x >> 3) % per_xcd;
         const int lpr = (width + 15) >> 4, total = width * lpr;
@@ -605,154 +432,52 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
 
     // Prologue: only the first leaf's columns are needed before the first barrier; the rest of the
     // tile is loaded by the helpers during that leaf.
-    int rest_from = w1;  // columns [rest_from, w1) of the tile still to be loaded
-    if (IN_LDS) {
-        if (helper) fetch_block();
-        const int first_end = (tab.op[0].kind == OP_LEAF && !(dbg & 32)) ? tab.op[0].b : w1;
-        load_cols(w0, first_end, t, 512);
-        rest_from = first_end;
-        if (helper) {
-            if (fetch_w) write_block(0);
-            fetch_block();
-        }
+    if (helper) fetch_block();
+    const int first_end = (tab.op[0].kind == OP_LEAF && !(dbg & 32)) ? tab.op[0].b : w1;
+    load_cols(w0, first_end, t, 512);
+    int rest_from = first_end;  // columns [rest_from, w1) of the tile still to be loaded
+    if (helper) {
+        if (fetch_w) write_block(0);
+        fetch_block();
     }
     __syncthreads();
     lap(7, 0);
 
-    // ---- UPDATE machinery: Q[:, lo:hi] -= E[:, a:b] @ U[a:b, lo:hi] on the 16 rows of this tile.
-    // A ROUND is (16-column block, 64-deep K chunk).  Operands of U come straight from global memory
-    // (every workgroup streams the same panel out of L2), so the loads of round r+1 are issued before
-    // the MFMAs of round r, and the chain waves issue round 0 of the urgent part BEFORE their leaf.
-    const int lr = lane & 15, lk = lane >> 4;
-    const bool row_ok = IN_LDS || r0 + lr < R;
-    double cur[16];
+    // ---- UPDATE: Q[:, lo:hi] -= E[:, a:b] @ U[a:b, lo:hi] on the 16 rows of this tile (TileUpdate); the chain waves issue
+    // round 0 of the urgent part BEFORE their leaf.  Layers wider than 16384 columns come here too: 64-bit offsets then.
+    TileUpdate<1, WindowTile, false> upd{{sm, w0}, U, n, n <= 16384, lane & 15, lane >> 4};
     bool primed = false;
-    auto load_round = [&](int a, int b, int lo, int hi, int blk, int kc, double(&bv)[16]) {
-        // Clamped addresses, no masking: rows beyond b meet a zero E operand, columns beyond hi are
-        // never stored -- and any arithmetic on the loaded value here would make the wave wait for
-        // the load at once instead of after the MFMAs of the round before.
-        const int cc = min(lo + blk * 16 + lr, hi - 1);
-#pragma unroll
-        for (int s4 = 0; s4 < 16; ++s4) {
-            const int k = a + 64 * kc + 4 * s4 + lk;
-            bv[s4] = U[(size_t)min(k, b - 1) * n + cc];
-        }
-    };
-    // one round of MFMAs: acc += E[:, chunk kc of a:b] @ bv.  Full and half chunks (K = 64, 32: all
-    // the reference's default schedules) take straight-line code: 16 (8) LDS reads, then the MFMAs.
-    auto mac_round = [&](int a, int b, int kc, const double(&bv)[16], double4_t &acc) {
-        const int kbase = a + 64 * kc, kcount = min(64, b - kbase);
-        if (IN_LDS && (kcount == 64 || kcount == 32)) {
-            const float *ep = &sm.e[lr][kbase - w0 + lk];
-            float av[16];
-#pragma unroll
-            for (int s4 = 0; s4 < 8; ++s4) av[s4] = ep[4 * s4];
-            if (kcount == 64) {
-#pragma unroll
-                for (int s4 = 8; s4 < 16; ++s4) av[s4] = ep[4 * s4];
-            }
-#pragma unroll
-            for (int s4 = 0; s4 < 8; ++s4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[s4], bv[s4], acc, 0, 0, 0);
-            if (kcount == 64) {
-#pragma unroll
-                for (int s4 = 8; s4 < 16; ++s4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[s4], bv[s4], acc, 0, 0, 0);
-            }
-        } else {
-            const int er = IN_LDS ? lr : min(lr, R - 1 - r0);  // clamped: the load is unconditional, the value is selected
-#pragma unroll
-            for (int s4 = 0; s4 < 16; ++s4) {
-                const int k = kbase + 4 * s4 + lk;
-                const float ev = eld(er, min(k, b - 1));
-                const double av = (k < b && row_ok) ? (double)ev : 0.0;
-                if (4 * s4 < kcount) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[s4], acc, 0, 0, 0);
-            }
-        }
-    };
-    auto store_block = [&](int lo, int hi, int blk, const double4_t &acc) {
-        const int col = lo + blk * 16 + lr;
-        if (col < hi) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = lk + 4 * r;
-                if (IN_LDS || r0 + row < R) qst(row, col, (float)((double)qld(row, col) - acc[r]));
-            }
-        }
-    };
-    // blocks wid, wid + nw, ... of [lo, hi); `ready`: cur already holds (block wid, chunk 0).
-    // Two register buffers in ping-pong, so that the loads of a round are in flight during the
-    // MFMAs of the round before and no copy ties the two together.
-    auto run_update = [&](int a, int b, int lo, int hi, int wid, int nw, bool ready) {
-        const int nblk = (hi - lo + 15) / 16, nchunk = (b - a + 63) / 64;
-        if (wid >= nblk) return;
-        const int nr = (nblk - wid + nw - 1) / nw * nchunk;
-        double other[16];
-        if (!ready) load_round(a, b, lo, hi, wid, 0, cur);
-        double4_t acc = {0.0, 0.0, 0.0, 0.0};
-        const double4_t zero4 = {0.0, 0.0, 0.0, 0.0};
-        int blk = wid, kc = 0;
-        for (int r = 0; r < nr; r += 2) {
-            int blk1 = blk, kc1 = kc + 1;
-            if (kc1 == nchunk) kc1 = 0, blk1 += nw;
-            const bool has1 = r + 1 < nr;
-            if (has1) load_round(a, b, lo, hi, blk1, kc1, other);
-            mac_round(a, b, kc, cur, acc);
-            if (kc + 1 == nchunk) {
-                store_block(lo, hi, blk, acc);
-                acc = zero4;
-            }
-            if (!has1) break;
-            int blk2 = blk1, kc2 = kc1 + 1;
-            if (kc2 == nchunk) kc2 = 0, blk2 += nw;
-            if (r + 2 < nr) load_round(a, b, lo, hi, blk2, kc2, cur);
-            mac_round(a, b, kc1, other, acc);
-            if (kc1 + 1 == nchunk) {
-                store_block(lo, hi, blk1, acc);
-                acc = zero4;
-            }
-            blk = blk2, kc = kc2;
-        }
-    };
     // generic leaf (any width, true divides): the whole workgroup in lockstep, 32 lanes per row,
     // one barrier per column.  Rare (width > 32, or a diagonal hitting the exact-division
     // exception), so simplicity wins.
     auto generic_leaf = [&](int a, int b, bool staged, int buf) {
         const LeafTables &lt = sm.lt[buf];
         const int myrow = 2 * wave + (lane >> 5), l = lane & 31;
-        const bool live = IN_LDS || (r0 + myrow < R);
+        float *qrow = sm.q[myrow], *erow = sm.e[myrow];  // of window columns
         for (int i = a; i < b; ++i) {
-            float x = 0.0f, q = 0.0f;
-            double err = 0.0;
-            if (live) {
-                x = qld(myrow, i);
-                if constexpr (OFFSET) {
-                    GroupQ<true> gq = {1.0f, 1.0f, 0.0f};  // the in-LDS tile's padding rows (x = 0) past R: nothing of S or O to read
-                    if (slots) {
-                        const int k = gs.slot[i - w0];
-                        gq = {gs.s[myrow][k], gs.rs[myrow][k], gs.o[myrow][k]};
-                    } else if (r0 + myrow < R) {
-                        gq = GroupQ<true>::at(Sg, Og, (size_t)(r0 + myrow) * G + pg[i]);
-                    }
-                    q = gq.value(x, g);
-                } else if constexpr (GROUPED) {
-                    const float sv = IN_LDS ? gt.s[myrow][i - w0] : Sg[(size_t)(r0 + myrow) * G + pg[i]];
-                    q = GroupQ<false>{sv, IN_LDS ? gt.rs[myrow][i - w0] : 1.0f / sv}.value(x, g);
-                } else {
-                    q = cb_value(x, g);
+            GroupQ<OFFSET> gq = {1.0f, 1.0f, 0.0f};  // (the tile's padding rows (x = 0) past R: nothing of S or O to read)
+            if constexpr (OFFSET) {
+                if (slots) {
+                    const int k = gs.slot[i - w0];
+                    gq = {gs.s[myrow][k], gs.rs[myrow][k], gs.o[myrow][k]};
+                } else if (r0 + myrow < R) {
+                    gq = GroupQ<true>::at(Sg, Og, (size_t)(r0 + myrow) * G + pg[i]);
                 }
-                const double uii = staged ? lt.udr[i - a][0] : U[(size_t)i * n + i];
-                err = (double)(x - q) / uii;
+            } else if constexpr (GROUPED) {
+                gq = {gt.s[myrow][i - w0], gt.rs[myrow][i - w0], 0.0f};
             }
+            const float x = qrow[i - w0], q = generic_q<GROUPED>(x, gq, g);
+            const double uii = staged ? lt.udr[i - a][0] : U[(size_t)i * n + i];
+            const double err = (double)(x - q) / uii;
             __syncthreads();  // everyone has read column i before lane 0 overwrites it
-            if (live) {
-                for (int j = i + 1 + l; j < b; j += 32) {
-                    const double uij = staged ? lt.u[i - a][j - a] : U[(size_t)i * n + j];
-                    const double p = err * uij;
-                    qst(myrow, j, (float)((double)qld(myrow, j) - p));
-                }
-                if (l == 0) {
-                    est(myrow, i, (float)err);
-                    qst(myrow, i, q);
-                }
+            for (int j = i + 1 + l; j < b; j += 32) {
+                const double uij = staged ? lt.u[i - a][j - a] : U[(size_t)i * n + j];
+                const double p = err * uij;
+                qrow[j - w0] = (float)((double)qrow[j - w0] - p);
+            }
+            if (l == 0) {
+                erow[i - w0] = (float)err;
+                qrow[i - w0] = q;
             }
             __syncthreads();
         }
@@ -769,7 +494,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
     int sbuf = 0;  // LDS buffer holding the tables of the next staged leaf
 
     // One pass per op plus a final pass that folds in whatever is still pending.  Each pass: at most
-    // one update job per wave (ONE call site of run_update: it is big), then the leaf, then a barrier.
+    // one update job per wave (ONE call site of upd.run: it is big), then the leaf, then a barrier.
     for (int oi = 0; oi <= tab.count; ++oi) {
         const bool fin = oi == tab.count;
         const Op op = tab.op[fin ? 0 : oi];
@@ -782,28 +507,33 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
         bool uready = false, redo = false, use_fast = false, staged = false;
         if (is_leaf) {
             const int w = op.b - op.a;
-            staged = IN_LDS && w <= ULEAF;
+            staged = w <= ULEAF;
             use_fast = staged && fast_ok;
             if (use_fast) use_fast = (sm.odd[sbuf][0] | sm.odd[sbuf][1] | sm.odd[sbuf][2] | sm.odd[sbuf][3]) == 0;
             if constexpr (OFFSET) use_fast = use_fast && slots;
             lap(1, 0);
+        }
+        // the rest of the tile goes in during the first leaf, behind a fast one by the helpers, otherwise by everyone (or here
+        // at the end where no leaf ran: debug modes).  ONE call site: the loader is big too.
+        const bool rest = (is_leaf || fin) && rest_from < w1;
+        if (rest && (helper || !use_fast)) load_cols(rest_from, w1, use_fast ? ht : t, use_fast ? 256 : 512);
+        if (rest) rest_from = w1;
+        if (is_leaf) {
             if (use_fast) {
                 // this leaf's share of the pending blocks, in whole turns of the four helpers
                 const int take = prem > 0 ? min(prem, ((prem + pleaves - 1) / pleaves + 3) & ~3) : 0;
                 if (helper) {
-                    if (rest_from < w1) load_cols(rest_from, w1, ht, 256);
                     if (fetch_w) write_block(sbuf ^ 1);
                     fetch_block();
                     ua = pa, ub = pb, ulo = plo, uhi = min(pc, plo + 16 * take), uwid = wave - 4, unw = 4;
                 } else if (oi + 1 < tab.count && tab.op[oi + 1].kind == OP_UPDATE && !no_updates) {
                     const Op nx = tab.op[oi + 1];
-                    load_round(nx.a, nx.b, nx.b, nx.m, wave, 0, cur);
+                    upd.load_round(nx.a, nx.b, nx.b, nx.m, wave, 0, upd.cur);
                     primed = true;
                 }
                 pdone += take;
                 pleaves = max(1, pleaves - 1);
             } else {
-                if (rest_from < w1) load_cols(rest_from, w1, t, 512);
                 if (helper && staged) {
                     if (fetch_w) write_block(sbuf ^ 1);
                     fetch_block();
@@ -811,11 +541,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
                 ua = pa, ub = pb, ulo = plo, uhi = pc;  // everything pending, all eight waves
                 pdone += prem;
             }
-            rest_from = w1;
         } else if (fin) {
-            const bool rest = rest_from < w1;  // no leaf ran (debug modes)
-            if (rest) load_cols(rest_from, w1, t, 512);
-            rest_from = w1;
             if (prem <= 0 && !rest) break;
             ua = pa, ub = pb, ulo = plo, uhi = pc;
             pdone += prem;
@@ -834,7 +560,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
             if (op.m < op.c) pa = op.a, pb = op.b, pm = op.m, pc = op.c, pdone = 0, pleaves = max(1, op.nl);
         }
         if (!is_leaf) lap(10, 0);
-        if (ulo < uhi) run_update(ua, ub, ulo, uhi, uwid, unw, uready);
+        if (ulo < uhi) upd.run(ua, ub, ulo, uhi, uwid, unw, uready);
         if (is_leaf) {
             if (use_fast) {
                 if (!helper && !no_leaf_regs) {
@@ -863,30 +589,50 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
         if (redo) --oi;
     }
 
-    if (IN_LDS) {
-        for (int e = t; e < RB * width; e += 512) {
-            const int r = e / width, c = e % width;
-            if (r0 + r < R) {
-                Qp[(size_t)(r0 + r) * n + w0 + c] = sm.q[r][c];
-                Eg[(size_t)(r0 + r) * n + w0 + c] = sm.e[r][c];
-            }
-        }
-    }
+    store_tile<RB>(sm.q, Qp, r0, R, n, w0, width, vec4, t);
+    store_tile<RB>(sm.e, Eg, r0, R, n, w0, width, tile_vec4(Eg, n, w0), t);
     if (warm == 1.2345e-30f) g_win_cycles[15] = 1;  // keeps the touches alive
     lap(8, 0);
-    if (timing && lane == 0) {
-        if (wave == 0) tacc[9] += (long long)__builtin_readcyclecounter() - tstart;
-        if (wave == 0 || wave == 4) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k)
-                if (tacc[k]) g_win_cycles[k] += tacc[k];
-        }
-    }
+    laps.flush(lane, wave);
 }
 
-}  // namespace slk
-#include "window2.h"
-namespace slk {
+// A window wider than WMAX is one LEAF (plan() cuts anything else down to WMAX): the generic leaf on global memory, the
+// whole workgroup in lockstep, 16 rows per workgroup and 32 lanes per row, S, O and the codebook read where they are.
+template <bool GROUPED, bool OFFSET = false>
+__global__ __launch_bounds__(512) void k_gptq_wide_leaf(float *__restrict__ Qp, float *__restrict__ Eg, const double *__restrict__ U,
+                                                        int R, int n, int a, int b, Grid g, int rpl, const float *__restrict__ Sg,
+                                                        const int *__restrict__ pg, int G, const float *__restrict__ Og) {
+    static_assert(GROUPED || !OFFSET, "offsets come with group scales");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 31;
+    const int r0 = blockIdx.x * RB, row = r0 + 2 * wave + (lane >> 5);
+    const bool live = row < R;
+    U += (size_t)(r0 / rpl) * n * n;  // a batch of layers stacked by rows, as in k_gptq_window
+    if constexpr (GROUPED) pg += (size_t)(r0 / rpl) * n;
+    float *qrow = Qp + (size_t)min(row, R - 1) * n, *erow = Eg + (size_t)min(row, R - 1) * n;  // (touched where live)
+    for (int i = a; i < b; ++i) {
+        float q = 0.0f;
+        double err = 0.0;
+        if (live) {
+            GroupQ<OFFSET> gq = {1.0f, 1.0f, 0.0f};
+            if constexpr (GROUPED) gq = GroupQ<OFFSET>::at(Sg, Og, (size_t)row * G + pg[i]);
+            const float x = qrow[i];
+            q = generic_q<GROUPED>(x, gq, g);
+            err = (double)(x - q) / U[(size_t)i * n + i];
+        }
+        __syncthreads();  // everyone has read column i before lane 0 overwrites it
+        if (live) {
+            for (int j = i + 1 + l; j < b; j += 32) {
+                const double p = err * U[(size_t)i * n + j];
+                qrow[j] = (float)((double)qrow[j] - p);
+            }
+            if (l == 0) {
+                erow[i] = (float)err;
+                qrow[i] = q;
+            }
+        }
+        __syncthreads();
+    }
+}
 
 // ------------------------------------------------------------------ trailing update
 // Qp[:, ja:jb] = float32(float64(Qp[:, ja:jb]) - E[:, ka:kb] @ U[ka:kb, ja:jb]), 64 x 64 tiles.
@@ -1123,21 +869,25 @@ extern "C" int slk_gptq_quantize(const float *W, const float *scale, const long 
 }
 
 // The general window kernel's LDS: the tile, then the group quantizer's tables behind it.
-template <bool IN_LDS, bool GROUPED, bool OFFSET>
+template <bool GROUPED, bool OFFSET>
 constexpr size_t window_lds() {
-    return !IN_LDS ? 0 : sizeof(WindowSmem) + (OFFSET ? sizeof(GroupSlots) : GROUPED ? sizeof(GroupTile) : 0);
+    return sizeof(WindowSmem) + (OFFSET ? sizeof(GroupSlots) : GROUPED ? sizeof(GroupTile) : 0);
 }
-// One launch of it: the LDS size and the profile name follow from the template arguments (gptq_loop has opted in to the LDS).
-template <bool IN_LDS, bool GROUPED, bool OFFSET>
+// One launch of it, or of the wide leaf for a window beyond WMAX (one LEAF op): the kernel, the LDS size and the profile name
+// follow from the template arguments and the width (gptq_loop has opted in to the LDS).
+template <bool GROUPED, bool OFFSET>
 static int launch_window(double flops, double bytes, int row_tiles, hipStream_t s, float *Qp, float *Eg, const double *U, int R, int n,
                          int w0, int w1, Grid g, float inv_step, int fast_ok, int dbg, const OpTable &tab, int rpl, const float *Sg,
                          const int *pg, int G, const float *Og) {
-    constexpr size_t lds = window_lds<IN_LDS, GROUPED, OFFSET>();
-    const char *name = IN_LDS ? (OFFSET ? "gptq_window_grouped_asym" : GROUPED ? "gptq_window_grouped" : "gptq_window")
-                              : (OFFSET ? "gptq_window_wide_grouped_asym" : GROUPED ? "gptq_window_wide_grouped" : "gptq_window_wide");
-    SLK_RUN(name, flops, bytes, s,
-            k_gptq_window<IN_LDS, GROUPED, OFFSET><<<row_tiles, 512, lds, s>>>(Qp, Eg, U, R, n, w0, w1, g, inv_step, fast_ok, dbg, tab, rpl, Sg, pg, G,
-                                                                             Og));
+    if (w1 - w0 > WMAX) {
+        SLK_REQUIRE(tab.count == 1 && tab.op[0].kind == OP_LEAF, "a window of %d columns that is not one leaf", w1 - w0);
+        SLK_RUN(OFFSET ? "gptq_window_wide_grouped_asym" : GROUPED ? "gptq_window_wide_grouped" : "gptq_window_wide", flops, bytes, s,
+                k_gptq_wide_leaf<GROUPED, OFFSET><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, w0, w1, g, rpl, Sg, pg, G, Og));
+        return SLK_OK;
+    }
+    SLK_RUN(OFFSET ? "gptq_window_grouped_asym" : GROUPED ? "gptq_window_grouped" : "gptq_window", flops, bytes, s,
+            k_gptq_window<GROUPED, OFFSET><<<row_tiles, 512, window_lds<GROUPED, OFFSET>(), s>>>(Qp, Eg, U, R, n, w0, w1, g, inv_step, fast_ok, dbg,
+                                                                                               tab, rpl, Sg, pg, G, Og));
     return SLK_OK;
 }
 
@@ -1190,9 +940,9 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     const int dbg = opt(OPT_WIN_DBG) & (8 | 16 | 32 | 64 | 128);  // cycle counters, no L2 warm-up, whole tile loaded up front: same results
 #endif
     const bool no_defer = opt(OPT_NO_DEFER) != 0;
-    if (asym) SLK_LDS_OPT_IN((k_gptq_window<true, true, true>), (window_lds<true, true, true>()));
-    else if (grouped) SLK_LDS_OPT_IN((k_gptq_window<true, true, false>), (window_lds<true, true, false>()));
-    else SLK_LDS_OPT_IN((k_gptq_window<true, false, false>), (window_lds<true, false, false>()));
+    if (asym) SLK_LDS_OPT_IN((k_gptq_window<true, true>), (window_lds<true, true>()));
+    else if (grouped) SLK_LDS_OPT_IN((k_gptq_window<true, false>), (window_lds<true, false>()));
+    else SLK_LDS_OPT_IN((k_gptq_window<false, false>), (window_lds<false, false>()));
     SLK_LDS_OPT_IN(k_gptq_window2<1>, sizeof(Window2SmemT<1>));
     SLK_LDS_OPT_IN(k_gptq_window2<2>, sizeof(Window2SmemT<2>));
     // 32 rows per workgroup (eight rows per chain wave, ONE quantizer instruction stream for them: leaf_chain8) halve the CUs
@@ -1227,62 +977,58 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     const int row_tiles = (R + RB - 1) / RB;
     for (const Plan::Step &st : p.steps) {
         if (st.kind == 0) {
-            const bool in_lds = (st.b - st.a) <= WMAX;
-            // a window's op list may exceed the table only when it is a single wide leaf
-            for (size_t o = 0; o < st.ops.size(); o += MAX_OPS) {
-                OpTable tab;
-                tab.count = (int)(st.ops.size() - o < (size_t)MAX_OPS ? st.ops.size() - o : MAX_OPS);
-                double fl = 0, ub = 0;  // float64 flops per row; bytes of U the window touches
-                for (int i = 0; i < tab.count; ++i) {
-                    const Op &q = tab.op[i] = st.ops[o + i];
-                    if (q.kind == OP_LEAF) {
-                        const double w = q.b - q.a;
-                        fl += w * (w - 1);
-                        ub += 4.0 * w * (w + 1);
-                    } else {
-                        fl += 2.0 * (q.b - q.a) * (q.c - q.b);
-                        ub += 8.0 * (q.b - q.a) * (q.c - q.b);
+            // plan() cuts a window until its ops fit the table (a single leaf, however wide, is one op)
+            SLK_REQUIRE(st.ops.size() <= (size_t)MAX_OPS, "a window of %d ops (the table holds %d)", (int)st.ops.size(), MAX_OPS);
+            OpTable tab;
+            tab.count = (int)st.ops.size();
+            double fl = 0, ub = 0;  // float64 flops per row; bytes of U the window touches
+            for (int i = 0; i < tab.count; ++i) {
+                const Op &q = tab.op[i] = st.ops[i];
+                if (q.kind == OP_LEAF) {
+                    const double w = q.b - q.a;
+                    fl += w * (w - 1);
+                    ub += 4.0 * w * (w + 1);
+                } else {
+                    fl += 2.0 * (q.b - q.a) * (q.c - q.b);
+                    ub += 8.0 * (q.b - q.a) * (q.c - q.b);
+                }
+            }
+            // split every update at the end of the sibling sub-tree that follows it: the columns
+            // beyond are not touched again before that sibling's own update (same c, a == this b)
+            for (int i = 0; i < tab.count; ++i) {
+                Op &q = tab.op[i];
+                if (q.kind != OP_UPDATE) continue;
+                q.m = q.c;
+                q.nl = 1;
+                if (no_defer) continue;
+                int leaves = 0;
+                for (int j = i + 1; j < tab.count; ++j) {
+                    const Op &x = tab.op[j];
+                    if (x.kind == OP_LEAF) ++leaves;
+                    if (x.kind == OP_UPDATE && x.c == q.c && x.a == q.b) {
+                        q.m = x.b;
+                        q.nl = leaves > 0 ? leaves : 1;
+                        break;
                     }
                 }
-                // split every update at the end of the sibling sub-tree that follows it: the columns
-                // beyond are not touched again before that sibling's own update (same c, a == this b)
-                for (int i = 0; i < tab.count; ++i) {
-                    Op &q = tab.op[i];
-                    if (q.kind != OP_UPDATE) continue;
-                    q.m = q.c;
-                    q.nl = 1;
-                    if (no_defer) continue;
-                    int leaves = 0;
-                    for (int j = i + 1; j < tab.count; ++j) {
-                        const Op &x = tab.op[j];
-                        if (x.kind == OP_LEAF) ++leaves;
-                        if (x.kind == OP_UPDATE && x.c == q.c && x.a == q.b) {
-                            q.m = x.b;
-                            q.nl = leaves > 0 ? leaves : 1;
-                            break;
-                        }
-                    }
-                }
-                const double wbytes = 12.0 * R * (st.b - st.a) + ub;  // Q in/out + E out, U once
-                PeriodTable pt;
-                if (in_lds && periods_ok && st.ops.size() <= (size_t)MAX_OPS && as_periods(st.ops, st.a, st.b, pt)) {
-                    if (window_rows == 32)
-                        SLK_RUN_W("gptq_window", fl * R, wbytes, (R + 2 * RB - 1) / (2 * RB), s,
-                                  k_gptq_window2<2><<<(R + 2 * RB - 1) / (2 * RB), 512, sizeof(Window2SmemT<2>), s>>>(
-                                      Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg & (24 | 64 | 128), pt, rpl));
-                    else
-                        SLK_RUN_W("gptq_window", fl * R, wbytes, row_tiles, s,
-                                  k_gptq_window2<1><<<row_tiles, 512, sizeof(Window2SmemT<1>), s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step,
-                                                                                                 fast_ok, dbg & 24, pt, rpl));
-                }
-                else {
-                    const auto launch = asym      ? (in_lds ? launch_window<true, true, true> : launch_window<false, true, true>)
-                                        : grouped ? (in_lds ? launch_window<true, true, false> : launch_window<false, true, false>)
-                                                  : (in_lds ? launch_window<true, false, false> : launch_window<false, false, false>);
-                    const int rc = launch(fl * R, wbytes, row_tiles, s, Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G,
-                                          goffset);
-                    if (rc != SLK_OK) return rc;
-                }
+            }
+            const double wbytes = 12.0 * R * (st.b - st.a) + ub;  // Q in/out + E out, U once
+            PeriodTable pt;
+            if (st.b - st.a <= WMAX && periods_ok && as_periods(st.ops, st.a, st.b, pt)) {
+                if (window_rows == 32)
+                    SLK_RUN_W("gptq_window", fl * R, wbytes, (R + 2 * RB - 1) / (2 * RB), s,
+                              k_gptq_window2<2><<<(R + 2 * RB - 1) / (2 * RB), 512, sizeof(Window2SmemT<2>), s>>>(
+                                  Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg & (24 | 64 | 128), pt, rpl));
+                else
+                    SLK_RUN_W("gptq_window", fl * R, wbytes, row_tiles, s,
+                              k_gptq_window2<1><<<row_tiles, 512, sizeof(Window2SmemT<1>), s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step,
+                                                                                             fast_ok, dbg & 24, pt, rpl));
+            }
+            else {
+                const auto launch = asym ? launch_window<true, true> : grouped ? launch_window<true, false> : launch_window<false, false>;
+                const int rc = launch(fl * R, wbytes, row_tiles, s, Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G,
+                                      goffset);
+                if (rc != SLK_OK) return rc;
             }
         } else {
             const double K = st.b - st.a, N = st.c - st.b;
@@ -1347,17 +1093,23 @@ extern "C" int slk_gptq_quantize_batch_error(const float *W, const float *scale,
                      workspace, ws_bytes, stream, nullptr, 0, nullptr, H, damp, row_err);
 }
 
+// what both grouped entries ask of their arguments (`tables`: gscale, and goffset where there is one)
+static int check_grouped(bool tables, const float *W, const double *U, const float *Q, int flags, int rows_per_layer, int n, int group_size) {
+    SLK_REQUIRE(W && tables && U && Q, "null pointer");
+    SLK_REQUIRE((flags & ~SLK_LOOP_LATENCY) == 0, "the grouped loop takes SLK_LOOP_LATENCY only");
+    SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
+    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
+                group_size);
+    return SLK_OK;
+}
+
 // `batch` layers with one scale per row and per group of `group_size` original columns (gscale: (batch rows_per_layer) x
 // n / group_size, positive), stacked by rows like slk_gptq_quantize_batch.
 extern "C" int slk_gptq_quantize_grouped_batch(const float *W, const float *gscale, int group_size, const long long *order,
                                                const double *U, int batch, int rows_per_layer, int n, int levels, double lo,
                                                double hi, const float *table, int min_block, int num_blocks, int flags, float *Q,
                                                uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream) {
-    SLK_REQUIRE(W && gscale && U && Q, "null pointer");
-    SLK_REQUIRE((flags & ~SLK_LOOP_LATENCY) == 0, "the grouped loop takes SLK_LOOP_LATENCY only");
-    SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
-    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
-                group_size);
+    if (const int rc = check_grouped(gscale != nullptr, W, U, Q, flags, rows_per_layer, n, group_size)) return rc;
     return gptq_loop(W, nullptr, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
                      workspace, ws_bytes, stream, gscale, group_size, nullptr);
 }
@@ -1378,11 +1130,7 @@ extern "C" int slk_gptq_quantize_grouped_asym_batch(const float *W, const float 
                                                     int levels, double lo, double hi, const float *table, int min_block,
                                                     int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace,
                                                     size_t ws_bytes, slk_stream_t stream) {
-    SLK_REQUIRE(W && gscale && goffset && U && Q, "null pointer");
-    SLK_REQUIRE((flags & ~SLK_LOOP_LATENCY) == 0, "the grouped loop takes SLK_LOOP_LATENCY only");
-    SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
-    SLK_REQUIRE(group_size >= 1 && n % group_size == 0, "group_size must be >= 1 and divide n (%d columns, group_size %d)", n,
-                group_size);
+    if (const int rc = check_grouped(gscale && goffset, W, U, Q, flags, rows_per_layer, n, group_size)) return rc;
     return gptq_loop(W, nullptr, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
                      workspace, ws_bytes, stream, gscale, group_size, goffset);
 }

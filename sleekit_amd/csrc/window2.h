@@ -17,6 +17,8 @@
 //   helpers:  ... B_p [rest of period p's update; tables, blocks for period p+2 / update p+1] B_p+1 ...
 #pragma once
 
+#include "window_tile.h"
+
 namespace slk {
 
 constexpr int ERING = 128;  // columns of E kept in LDS (two periods)
@@ -56,6 +58,15 @@ struct Window2SmemT {
     float cbt[512];          // a general codebook's values and limits (<= 256 entries)
 };
 using Window2Smem = Window2SmemT<1>;
+// the helper waves' view of it (TileUpdate): E is a ring of ERING columns
+template <int SETS>
+struct Window2Tile {
+    Window2SmemT<SETS> &sm;
+    int w0;
+    __device__ __forceinline__ float *q(int st, int row, int col) const { return &sm.q[RB * st + row][col - w0]; }
+    __device__ __forceinline__ const float *e(int st, int row, int k) const { return &sm.e[RB * st + row][(k - w0) & (ERING - 1)]; }
+    __device__ __forceinline__ bool straight(int k) const { return ((k - w0) & 31) == 0; }  // 32-aligned: the chunk does not wrap
+};
 
 // spin on an LDS counter another wave of the workgroup bumps (acquire: what that wave wrote before is visible after)
 __device__ __forceinline__ void lds_wait_ge(int *counter, int target) {
@@ -131,18 +142,10 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
     // readfirstlane: tells the compiler the wave index is wave-uniform (scalar branches, SGPR addressing)
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     // cycle accounting (debug, SLK_WIN_DBG bit 3): wave-uniform, workgroup 0, waves 0 and 4
-    const bool timing = (prof & 8) && blockIdx.x == 0;
-    long long tmark = timing ? (long long)__builtin_readcyclecounter() : 0;
-    const long long tstart = tmark;
-    long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long tper = tmark;  // start of the current period / interval
-    auto lap = [&](int slot) {
-        if (timing) {
-            const long long now = (long long)__builtin_readcyclecounter();
-            tacc[slot] += now - tmark;
-            tmark = now;
-        }
-    };
+    Laps laps(prof);
+    const bool timing = laps.on;
+    long long tper = laps.mark;  // start of the current period / interval
+    auto lap = [&](int slot) { laps.lap(slot); };
     // Waves go round the four SIMDs (wave i on SIMD i % 4).  A leaf chain is bound by the ISSUE of its own instructions,
     // not by their latency: two chains on one SIMD take turns, oldest first -- tools/micro_leaf.py: 127 cycles a column
     // for one chain wave per SIMD, 189 for the slower of two, 348 of four (round 1 timed wave 0 only, the oldest, and
@@ -170,48 +173,8 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
     }
     auto ring = [&](int c) { return (c - w0) & (ERING - 1); };
 
-    // columns [c_lo, c_hi) of the Q tile, global -> LDS, by `nth` threads of which this is number `tid`:
-    // 16-byte loads when the layout allows, eight (four) loads in flight per thread either way
-    // (a load-wait-store loop pays the full latency per element)
-    const bool vec4 = n % 4 == 0 && (w0 & 3) == 0 && ((uintptr_t)Qp & 15) == 0;
-    auto load_cols = [&](int c_lo, int c_hi, int tid, int nth) {
-        const int cw = c_hi - c_lo;
-        if (vec4 && (c_lo & 3) == 0 && (cw & 3) == 0) {
-            const int cw4 = cw >> 2, total = RBX * cw4;
-            for (int e0 = tid; e0 < total; e0 += 4 * nth) {
-                float4v_t v[4];
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const int e = min(e0 + h * nth, total - 1);
-                    const int r = e / cw4, c = c_lo + 4 * (e % cw4);
-                    v[h] = *reinterpret_cast<const float4v_t *>(Qp + (size_t)min(r0 + r, R - 1) * n + c);
-                }
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const int e = e0 + h * nth;
-                    const int r = e / cw4, c = c_lo + 4 * (e % cw4);
-                    if (e < total) *reinterpret_cast<float4v_t *>(&sm.q[r][c - w0]) = (r0 + r < R) ? v[h] : (float4v_t){0.0f, 0.0f, 0.0f, 0.0f};
-                }
-            }
-            return;
-        }
-        const int total = RBX * cw;
-        for (int e0 = tid; e0 < total; e0 += 8 * nth) {
-            float v[8];
-#pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                const int e = min(e0 + h * nth, total - 1);
-                const int r = e / cw, c = c_lo + e % cw;
-                v[h] = Qp[(size_t)min(r0 + r, R - 1) * n + c];
-            }
-#pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                const int e = e0 + h * nth;
-                const int r = e / cw, c = c_lo + e % cw;
-                if (e < total) sm.q[r][c - w0] = (r0 + r < R) ? v[h] : 0.0f;
-            }
-        }
-    };
+    const bool vec4 = tile_vec4(Qp, n, w0);
+    auto load_cols = [&](int c_lo, int c_hi, int tid, int nth) { load_tile_cols<RBX>(sm.q, Qp, r0, R, n, w0, vec4, c_lo, c_hi, tid, nth); };
     const Period P0 = tab.p[0];
     const int end0 = P0.s + P0.w1 + P0.w2;
     if (SETS == 2 && t == 0) sm.n_done = 0, sm.s_count = 0;  // visible after B_start
@@ -416,115 +379,8 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
         const integral_constant<int, 2> steps_s{};  // 32 x 32 block: 16 chunks
         double2_t nreg[8], sreg[2];
 
-        // ---- the 16-row MFMA update of v1 on four waves: Q[:, lo:hi] -= E[:, a:b] @ U[a:b, lo:hi]
-        const int lr = lane & 15, lk = lane >> 4;
-        double cur[16];
-        // (Scalar per-row-group bases with one vector offset were tried to take the address arithmetic
-        // off the vector ALU, which the float64 MFMA shares: the SALU chain it needs is slower, 36 vs 31 us.)
-        // The helpers share their SIMDs' issue slots with the chain waves, so the address arithmetic counts: a full chunk
-        // of 64 rows (the common case) is read at a uniform base + a 32-bit byte offset that advances by a constant
-        // (one v_add_u32 per load; the clamped form below costs an add, a min, a 64-bit multiply-add and a 64-bit
-        // shift-add each).  n <= 16384 (checked on the host) keeps the offset below 2^32.
-        const char *Ubytes = reinterpret_cast<const char *>(U);
-        const unsigned row4 = 32u * (unsigned)n;  // bytes from row k to row k + 4
-        auto load_round = [&](int a, int b, int lo, int hi, int blk, int kc, double(&bv)[16]) {
-            const int cc = min(lo + blk * 16 + lr, hi - 1);
-            const int kbase = a + 64 * kc;
-            if (kbase + 64 <= b) {
-                unsigned off = ((unsigned)(kbase + lk) * (unsigned)n + (unsigned)cc) * 8u;
-#pragma unroll
-                for (int s4 = 0; s4 < 16; ++s4) {
-                    bv[s4] = *reinterpret_cast<const double *>(Ubytes + off);
-                    off += row4;
-                }
-                return;
-            }
-#pragma unroll
-            for (int s4 = 0; s4 < 16; ++s4) {
-                const int k = kbase + 4 * s4 + lk;
-                bv[s4] = U[(size_t)min(k, b - 1) * n + cc];
-            }
-        };
-        auto mac_round = [&](int a, int b, int kc, const double(&bv)[16], double4_t(&acc)[SETS]) {
-            const int kbase = a + 64 * kc, kcount = min(64, b - kbase);
-            if ((kcount == 64 || kcount == 32) && ((kbase - w0) & 31) == 0) {
-#pragma unroll
-                for (int st = 0; st < SETS; ++st) {  // the round of U in registers serves every 16-row tile
-                    const float *ep = &sm.e[RB * st + lr][ring(kbase) + lk];  // 32-aligned: the chunk does not wrap
-                    float av[16];
-#pragma unroll
-                    for (int s4 = 0; s4 < 8; ++s4) av[s4] = ep[4 * s4];
-                    if (kcount == 64) {
-#pragma unroll
-                        for (int s4 = 8; s4 < 16; ++s4) av[s4] = ep[4 * s4];
-                    }
-#pragma unroll
-                    for (int s4 = 0; s4 < 8; ++s4) acc[st] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[s4], bv[s4], acc[st], 0, 0, 0);
-                    if (kcount == 64) {
-#pragma unroll
-                        for (int s4 = 8; s4 < 16; ++s4) acc[st] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[s4], bv[s4], acc[st], 0, 0, 0);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int s4 = 0; s4 < 16; ++s4) {
-                    const int k = kbase + 4 * s4 + lk;
-#pragma unroll
-                    for (int st = 0; st < SETS; ++st) {
-                        const float ev = sm.e[RB * st + lr][ring(min(k, b - 1))];
-                        const double av = k < b ? (double)ev : 0.0;
-                        if (4 * s4 < kcount) acc[st] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[s4], acc[st], 0, 0, 0);
-                    }
-                }
-            }
-        };
-        auto store_block = [&](int lo, int hi, int blk, double4_t(&acc)[SETS]) {  // and clear the accumulators
-            const int col = lo + blk * 16 + lr;
-#pragma unroll
-            for (int st = 0; st < SETS; ++st) {
-                if (col < hi) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int rr = RB * st + lk + 4 * r;
-                        sm.q[rr][col - w0] = (float)((double)sm.q[rr][col - w0] - acc[st][r]);
-                    }
-                }
-                acc[st] = (double4_t){0.0, 0.0, 0.0, 0.0};
-            }
-        };
-        // Rounds in pairs on two register buffers.  The loads of the round after next are issued
-        // UNCONDITIONALLY (clamped to the last round when there is none): with a fixed number of loads
-        // between a buffer's fill and its use the compiler can wait with vmcnt(16); a conditional
-        // load in the loop makes it fall back to vmcnt(0), which serialises load and MFMA.
-        auto run_update = [&](int a, int b, int lo, int hi, int wid, int nw) {
-            const int nblk = (hi - lo + 15) / 16, nchunk = (b - a + 63) / 64;
-            if (wid >= nblk) return;
-            const int nr = (nblk - wid + nw - 1) / nw * nchunk;
-            const int last_blk = wid + ((nblk - wid - 1) / nw) * nw;
-            double other[16];
-            load_round(a, b, lo, hi, wid, 0, cur);
-            double4_t acc[SETS];
-#pragma unroll
-            for (int st = 0; st < SETS; ++st) acc[st] = (double4_t){0.0, 0.0, 0.0, 0.0};
-            int blk = wid, kc = 0;
-            for (int r = 0; r < nr; r += 2) {
-                int blk1 = blk, kc1 = kc + 1;
-                if (kc1 == nchunk) kc1 = 0, blk1 += nw;
-                const bool has1 = r + 1 < nr;
-                load_round(a, b, lo, hi, has1 ? blk1 : last_blk, has1 ? kc1 : nchunk - 1, other);
-                mac_round(a, b, kc, cur, acc);
-                if (kc + 1 == nchunk) store_block(lo, hi, blk, acc);
-                int blk2 = blk1, kc2 = kc1 + 1;
-                if (kc2 == nchunk) kc2 = 0, blk2 += nw;
-                const bool has2 = r + 2 < nr;
-                load_round(a, b, lo, hi, has2 ? blk2 : last_blk, has2 ? kc2 : nchunk - 1, cur);
-                if (has1) {
-                    mac_round(a, b, kc1, other, acc);
-                    if (kc1 + 1 == nchunk) store_block(lo, hi, blk1, acc);
-                }
-                blk = blk2, kc = kc2;
-            }
-        };
+        // ---- the 16-row MFMA update on four waves; n <= 16384 (checked on the host) keeps its byte offsets below 2^32
+        TileUpdate<SETS, Window2Tile<SETS>, true> upd{{sm, w0}, U, n, true, lane & 15, lane >> 4};
 
         // ---- prologue: tables and the inner block of period 0
         fetch_tables(0);
@@ -564,7 +420,7 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
                 // the rest of period p-1's update: beyond period p, whose columns the chain waves have done
                 const Period M = tab.p[p - 1];
                 const int lo = P.s + K;
-                if (lo < w1) run_update(M.s, M.s + M.w1 + M.w2, lo, w1, role_wave, 4);
+                if (lo < w1) upd.run(M.s, M.s + M.w1 + M.w2, lo, w1, role_wave, 4, false);
             }
             lap(5);
             if (SETS == 2) lds_wait_ge(&sm.n_done, 4 * p);  // single nblk: the chain waves are through with period p - 1's block
@@ -578,24 +434,8 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
     }
 
     // every column is final: the tile goes back (E went out leaf by leaf)
-    if (vec4 && (width & 3) == 0) {
-        const int cw4 = width >> 2;
-        for (int e = t; e < RBX * cw4; e += 512) {
-            const int r = e / cw4, c = 4 * (e % cw4);
-            if (r0 + r < R) *reinterpret_cast<float4v_t *>(Qp + (size_t)(r0 + r) * n + w0 + c) = *reinterpret_cast<const float4v_t *>(&sm.q[r][c]);
-        }
-    } else {
-        for (int e = t; e < RBX * width; e += 512) {
-            const int r = e / width, c = e % width;
-            if (r0 + r < R) Qp[(size_t)(r0 + r) * n + w0 + c] = sm.q[r][c];
-        }
-    }
-    if (timing && lane == 0 && (wave == 0 || wave == first_helper)) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k)
-            if (tacc[k] && k != 9) g_win_cycles[k] += tacc[k];
-        if (wave == 0) g_win_cycles[9] += (long long)__builtin_readcyclecounter() - tstart;
-    }
+    store_tile<RBX>(sm.q, Qp, r0, R, n, w0, width, vec4, t);
+    laps.flush(lane, wave);
 }
 
 }  // namespace slk

@@ -85,8 +85,8 @@ def _factor(W, S, g, H, cb, act_order, damp=0.01):
     return order, U
 
 
-# (batch, rows per layer, n, g, codebook, act_order, min_block, num_blocks).  Leaves wider than 512 columns run the window
-# kernel from global memory (IN_LDS = false): 768 columns in one leaf, and 550-column leaves of 1100.
+# (batch, rows per layer, n, g, codebook, act_order, min_block, num_blocks).  Leaves wider than 512 columns run on global
+# memory in a kernel of their own (k_gptq_wide_leaf): 768 columns in one leaf, and 550-column leaves of 1100.
 BATCH_CASES = [
     (2, 64, 128, 32, "8", "none", 32, 8),
     (5, 320, 128, 128, "nf4", "diag", 32, 8),

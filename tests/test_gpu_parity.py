@@ -457,6 +457,28 @@ def test_window_kernels_agree(amd, n, odd_diagonal, slkopt):
         np.testing.assert_allclose(out[0][1], E0, rtol=1e-6, atol=1e-7)
 
 
+@pytest.mark.parametrize("n", [513, 600])
+@pytest.mark.parametrize("codebook", ["uniform", "nf4"])
+def test_wide_leaf_kernel_matches_oracle(amd, n, codebook):
+    """A leaf wider than the window's 512 columns of LDS runs in a kernel of its own, on global memory (min_block = n: the
+    whole layer is one leaf): ungrouped, against the oracle's schedule.  513 is the first such width and odd (no 16-byte
+    path, plain permutes); 17 rows are one full row tile and a one-row tile; a uniform and a table codebook."""
+    rng = np.random.default_rng(n)
+    R = 17
+    W = (rng.standard_normal((R, n)) * 0.6).astype(np.float32)
+    U = np.triu(rng.standard_normal((n, n)) * (0.3 / np.sqrt(n))) + np.diag(1.0 + rng.random(n))
+    if codebook == "nf4":
+        cb, g = amd.codebook.Codebook.nf4(), grid.TableGrid.nf4()
+    else:
+        cb, g = amd.codebook.UniformCodebook(8, -1, 1), grid.UniformGrid(8, -1, 1)
+    Q0, E0 = W.copy(), np.zeros_like(W)
+    obq_ref.run_schedule(Q0, E0, U, g, obq_ref.block_schedule(n, n, 8))
+    Q1, E1 = W.copy(), np.zeros_like(W)
+    amd.obq._quantize_opt_block(Q1, E1, U, cb, n, 8)
+    assert np.array_equal(Q1, Q0)
+    np.testing.assert_allclose(E1, E0, rtol=1e-6, atol=1e-7)
+
+
 @pytest.mark.parametrize("levels,lo,hi", [(2, -1, 1), (3, -1, 1), (4, -1, 1), (8, -1, 1), (16, -1, 1), (256, -1, 1), (5, -0.75, 1.25), (7, 0.0, 3.0)])
 def test_fast_quantizer_matches_true_divide(amd, levels, lo, hi):
     """The leaf kernel replaces the float32 divide by an exact-division fma sequence; with an
