@@ -84,7 +84,8 @@ typedef void *slk_stream_t;
  * beside the scale): slk_gptq_quantize_grouped_asym, slk_gptq_quantize_grouped_asym_batch, slk_column_miss_grouped_asym,
  * slk_dequantize_grouped_asym, slk_group_midpoints and slk_group_center, then bit-packed indices: slk_pack_indices,
  * slk_unpack_indices and slk_dequantize_packed, then slk_gptq_quantize_batch_error (the loop that carries the layer error)
- * and the option "no_loop_error".   */
+ * and the option "no_loop_error", then slk_gptq_quantize_layers (the same loop over layers that are not one stack: per-layer
+ * pointers).   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -303,6 +304,24 @@ int slk_gptq_quantize_batch_error(const float *W, const float *scale, const long
                                   double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
                                   float *Q, uint8_t *idx, float *E_out, float *row_err, void *workspace, size_t ws_bytes,
                                   slk_stream_t stream);
+
+/* (e'') The loop of (e) and (e') over `batch` layers that are NOT one stack: W, scale, order, U (and H) are HOST arrays of
+ *     `batch` device pointers, one per layer -- W[b] rows_per_layer x n, scale[b] rows_per_layer entries, order[b] n, U[b]
+ *     n x n -- each contiguous, anywhere in memory and in any order: no copy into a stack before the loop (two 4096-column
+ *     factors are 268 MB read and written).  The kernels read every layer through a table of these pointers (one scalar
+ *     load per workgroup); the stacked entries fill the same table from their base pointers.  What the call WRITES stays one
+ *     stack: Q, idx, E_out (batch * rows_per_layer) x n and row_err (batch * rows_per_layer), layer b at rows
+ *     [b * rows_per_layer, (b + 1) * rows_per_layer).  Results: those of `batch` separate calls, bit for bit.
+ *     scale may be NULL (no scales; otherwise every entry is given).  H and row_err both given: the error-carrying loop of
+ *     (e') with `damp`; both NULL: the plain one (damp ignored).  batch in 1..16 (the table's size); batch > 1 needs
+ *     rows_per_layer % 64 == 0.  A U that is not 16-byte aligned sends every layer of the call to the general window kernel.
+ *     gscale / group_size: must be NULL / 0 -- group scales are taken stacked only (slk_gptq_quantize_grouped_batch); SLK_E_ARG
+ *     otherwise.  Everything else, and the workspace, as slk_gptq_quantize_batch.                                 */
+int slk_gptq_quantize_layers(const float *const *W, const float *const *scale, const long long *const *order,
+                             const double *const *U, const float *const *H, float damp, const float *const *gscale,
+                             int group_size, int batch, int rows_per_layer, int n, int levels, double lo, double hi,
+                             const float *table, int min_block, int num_blocks, int flags, float *Q, uint8_t *idx,
+                             float *E_out, float *row_err, void *workspace, size_t ws_bytes, slk_stream_t stream);
 
 /* Group scales.  gscale: R x G float32, positive, G = n / group_size (group_size >= 1 must divide n); element (r, c)
  * belongs to group c / group_size.  The group quantizer maps x in column c of row r to

@@ -77,6 +77,10 @@ PROTOTYPES = {
         c_int,
         [P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P],
     ),
+    "slk_gptq_quantize_layers": (
+        c_int,
+        [P, P, P, P, P, c_float, P, c_int, c_int, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, P, c_size_t, P],
+    ),
     "slk_gptq_quantize_grouped": (
         c_int,
         [P, P, c_int, P, P, c_int, c_int, c_int, c_double, c_double, P, c_int, c_int, c_int, P, P, P, P, c_size_t, P],

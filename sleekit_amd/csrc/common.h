@@ -115,6 +115,25 @@ struct PtrTable {
     const float *p[64];
 };
 
+// What the column loop READS of every layer of a batch -- W, the row scales (all nullptr: none), the column order (all
+// nullptr: the identity, one layer) and the factor U -- as per-layer base pointers, passed by value to the loop's kernels: a
+// workgroup picks its layer's with the uniform r0 / rpl it computes anyway (one scalar load).  The layers of
+// slk_gptq_quantize_layers are caller-owned tensors anywhere in memory, at most LOOP_LAYERS of them.  A batch stacked by rows
+// in ONE allocation (the batch entries, up to 64 layers) is the same table: entry i is layer i's base, and layer b >=
+// LOOP_LAYERS lies (b - b % LOOP_LAYERS) layer strides behind entry b % LOOP_LAYERS (layer_base; the strides follow from
+// rpl and n).  The loop's workspace and its outputs are one stack either way, indexed by the stacked row.
+constexpr int LOOP_LAYERS = 16;
+struct LayerTable {
+    const float *W[LOOP_LAYERS], *scale[LOOP_LAYERS];
+    const long long *order[LOOP_LAYERS];
+    const double *U[LOOP_LAYERS];
+};
+// layer b's base from one column of the table, `stride` elements a layer in a stack
+template <class T>
+__device__ __forceinline__ const T *layer_base(const T *const (&column)[LOOP_LAYERS], int b, size_t stride) {
+    return column[b % LOOP_LAYERS] + (size_t)(b - b % LOOP_LAYERS) * stride;
+}
+
 // the layer error of a stack of `batch` layers (rows [b rpl, (b + 1) rpl) against Hs[b]) WITH the products G = (Q - W) H
 // the local search starts from (sgemm.hip; the public entries are slk_row_errors / slk_row_errors_batch)
 int row_errors_products(const float *W, const float *Q, const float *const *Hs, int batch, int rpl, int n, const int *sym_known,

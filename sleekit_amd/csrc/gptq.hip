@@ -65,21 +65,22 @@ __device__ __forceinline__ void store_elems(float *p, const float (&v)[V]) {
     else *p = v[0];
 }
 
-// Qp[r][c] = W[r][order[c]] (/ scale[r]);  E is cleared by the window kernels as they go.  order == nullptr (never with LDS):
-// the identity.
+// Qp[r][c] = W[r][order[c]] (/ scale[r]);  E is cleared by the window kernels as they go.  No orders in the table (never with
+// LDS): the identity.
 template <bool LDS>
-__global__ __launch_bounds__(256) void k_permute_in(const float *__restrict__ W, const float *__restrict__ scale,
-                                                    const long long *__restrict__ order, int R, int n,
-                                                    float *__restrict__ Qp, int *__restrict__ inv_order, int rpl) {
+__global__ __launch_bounds__(256) void k_permute_in(LayerTable lt, int R, int n, float *__restrict__ Qp,
+                                                    int *__restrict__ inv_order, int rpl) {
     extern __shared__ __attribute__((aligned(16))) float rowbuf[];  // (LDS only)
     constexpr int V = LDS ? 4 : 1;
     const int t = threadIdx.x;
-    // (a batch of layers stacked by rows: rows [b rpl, (b + 1) rpl) follow order[b], inv_order[b])
+    const bool scale = lt.scale[0] != nullptr, order = lt.order[0] != nullptr;
+    // (a batch of layers: stacked rows [b rpl, (b + 1) rpl) are layer b's, and follow order[b], inv_order[b])
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
-        const float *src = W + (size_t)r * n;
-        const long long *ord = (LDS || order) ? order + (size_t)(r / rpl) * n : nullptr;
+        const int b = r / rpl, rl = r - b * rpl;
+        const float *__restrict__ src = layer_base(lt.W, b, (size_t)rpl * n) + (size_t)rl * n;
+        const long long *__restrict__ ord = (LDS || order) ? layer_base(lt.order, b, n) : nullptr;
         stage_row<LDS>(rowbuf, src, n);
-        const float s = scale ? scale[r] : 1.0f;
+        const float s = scale ? layer_base(lt.scale, b, rpl)[rl] : 1.0f;
         for (int c = V * t; c < n; c += V * 256) {
             long long from[V];  // all of an iteration's order entries first: wide loads, in flight together
             float v[V];
@@ -93,8 +94,10 @@ __global__ __launch_bounds__(256) void k_permute_in(const float *__restrict__ W,
             store_elems<V>(Qp + (size_t)r * n + c, v);
         }
     }
-    for (int b = blockIdx.x; b < (R + rpl - 1) / rpl; b += gridDim.x)
-        for (int c = t; c < n; c += 256) inv_order[(size_t)b * n + (order ? order[(size_t)b * n + c] : c)] = c;
+    for (int b = blockIdx.x; b < (R + rpl - 1) / rpl; b += gridDim.x) {
+        const long long *__restrict__ ord = order ? layer_base(lt.order, b, n) : nullptr;
+        for (int c = t; c < n; c += 256) inv_order[(size_t)b * n + (ord ? ord[c] : c)] = c;
+    }
 }
 
 // Q[r][j] = Qp[r][inv[j]];  idx[r][j] = grid index of that value (codebook.py:43-54).
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(256) void k_permute_in(const float *__restrict__ W,
 // damping term the factor was made with (hmean[64 b]: loop_error_means).  E is in processing order, W and Q in the
 // original one: the sums do not care.  One fixed-order workgroup reduction and one store per row: the same bits every run.
 struct RowErrArgs {
-    const float *W, *E, *scale, *hmean;  // scale: nullptr = 1
+    const float *E, *hmean;  // (W and the scales: the layers' own, from the table)
     float damp;
     float *row_err;
 };
@@ -114,8 +117,8 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;  // lane 0 holds the sum
 }
-// the row's two sums over the workgroup's 256 threads, then the store (red: 8 doubles of LDS)
-__device__ __forceinline__ void row_error_store(double se, double sd, double *red, const RowErrArgs &a, int r, int rpl) {
+// the row's two sums over the workgroup's 256 threads, then the store (red: 8 doubles of LDS; scale: the row's, 1 without)
+__device__ __forceinline__ void row_error_store(double se, double sd, double *red, const RowErrArgs &a, int r, int rpl, float scale) {
     se = wave_sum_f64(se);
     sd = wave_sum_f64(sd);
     const int t = threadIdx.x;
@@ -126,7 +129,7 @@ __device__ __forceinline__ void row_error_store(double se, double sd, double *re
     __syncthreads();
     if (t == 0) {
         const double SE = ((red[0] + red[1]) + red[2]) + red[3], SD = ((red[4] + red[5]) + red[6]) + red[7];
-        const double s = a.scale ? (double)a.scale[r] : 1.0;
+        const double s = (double)scale;
         const float lambda = a.damp * a.hmean[64 * (r / rpl)];  // float32 product, as k_diag_prepare forms it
         a.row_err[r] = (float)((s * s) * SE - (double)lambda * SD);
     }
@@ -135,16 +138,19 @@ __device__ __forceinline__ void row_error_store(double se, double sd, double *re
 
 template <bool LDS, bool ERR>
 __global__ __launch_bounds__(256) void k_permute_out(const float *__restrict__ Qp, const int *__restrict__ inv_order,
-                                                     int R, int n, Grid g, const float *__restrict__ unscale,
-                                                     float *__restrict__ Q, uint8_t *__restrict__ idx, int rpl, RowErrArgs ea) {
+                                                     int R, int n, Grid g, int unscale, float *__restrict__ Q,
+                                                     uint8_t *__restrict__ idx, int rpl, RowErrArgs ea, LayerTable lt) {
     extern __shared__ __attribute__((aligned(16))) float rowbuf[];  // (LDS only)
     __shared__ double red[ERR ? 8 : 1];
     constexpr int V = LDS ? 4 : 1;
     for (int r = blockIdx.x; r < R; r += gridDim.x) {
         const float *src = Qp + (size_t)r * n;
-        const int *inv_o = inv_order + (size_t)(r / rpl) * n;
+        const int b = r / rpl, rl = r - b * rpl;
+        const int *inv_o = inv_order + (size_t)b * n;
         stage_row<LDS>(rowbuf, src, n);
-        const float inv = unscale ? 1.0f / unscale[r] : 1.0f;  // scaling.py:80: a division by the reciprocal
+        const float scale = unscale ? layer_base(lt.scale, b, rpl)[rl] : 1.0f;
+        const float inv = unscale ? 1.0f / scale : 1.0f;  // scaling.py:80: a division by the reciprocal
+        const float *__restrict__ wrow = ERR ? layer_base(lt.W, b, (size_t)rpl * n) + (size_t)rl * n : nullptr;
         double se = 0.0, sd = 0.0;
         for (int j = V * threadIdx.x; j < n; j += V * 256) {
             float qw[V];
@@ -162,7 +168,7 @@ __global__ __launch_bounds__(256) void k_permute_out(const float *__restrict__ Q
             }
             if constexpr (ERR) {
                 float w[V], ev[V];
-                load_elems<V>(ea.W + (size_t)r * n + j, w);
+                load_elems<V>(wrow + j, w);
                 load_elems<V>(ea.E + (size_t)r * n + j, ev);
 #pragma unroll
                 for (int e = 0; e < V; ++e) {
@@ -172,7 +178,7 @@ __global__ __launch_bounds__(256) void k_permute_out(const float *__restrict__ Q
                 }
             }
         }
-        if constexpr (ERR) row_error_store(se, sd, red, ea, r, rpl);
+        if constexpr (ERR) row_error_store(se, sd, red, ea, r, rpl, scale);
     }
 }
 // one launch of either permute kernel: the LDS form stages a row of n floats
@@ -345,7 +351,7 @@ __device__ __forceinline__ float generic_q(float x, const GroupQ<OFFSET> gq, con
 // (A window wider than WMAX is a single leaf: k_gptq_wide_leaf.)
 template <bool GROUPED, bool OFFSET = false>
 __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, float *__restrict__ Eg,
-                                                     const double *__restrict__ U, int R, int n, int w0, int w1,
+                                                     LayerTable lt, int R, int n, int w0, int w1,
                                                      Grid g, float inv_step, int fast_ok, int dbg, OpTable tab, int rpl,
                                                      const float *__restrict__ Sg, const int *__restrict__ pg, int G,
                                                      const float *__restrict__ Og) {
@@ -359,7 +365,7 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
     const bool helper = wave >= 4;
     const int ht = t - 256;  // helper thread index
     const int r0 = blockIdx.x * RB;
-    U += (size_t)(r0 / rpl) * n * n;  // a batch of layers stacked by rows: rows [b rpl, (b + 1) rpl) use factor b
+    const double *__restrict__ U = layer_base(lt.U, r0 / rpl, (size_t)n * n);  // a batch of layers: rows [b rpl, (b + 1) rpl) use factor b
     if constexpr (GROUPED) pg += (size_t)(r0 / rpl) * n;  // ... and group table b (a tile never straddles two layers)
     if (g.table) {  // the leaves search the codebook once per column: keep it next to them
         for (int i = t; i < 2 * g.n - 1; i += 512) sm.cbt[i] = g.table[i];
@@ -599,14 +605,14 @@ __global__ __launch_bounds__(512) void k_gptq_window(float *__restrict__ Qp, flo
 // A window wider than WMAX is one LEAF (plan() cuts anything else down to WMAX): the generic leaf on global memory, the
 // whole workgroup in lockstep, 16 rows per workgroup and 32 lanes per row, S, O and the codebook read where they are.
 template <bool GROUPED, bool OFFSET = false>
-__global__ __launch_bounds__(512) void k_gptq_wide_leaf(float *__restrict__ Qp, float *__restrict__ Eg, const double *__restrict__ U,
+__global__ __launch_bounds__(512) void k_gptq_wide_leaf(float *__restrict__ Qp, float *__restrict__ Eg, LayerTable lt,
                                                         int R, int n, int a, int b, Grid g, int rpl, const float *__restrict__ Sg,
                                                         const int *__restrict__ pg, int G, const float *__restrict__ Og) {
     static_assert(GROUPED || !OFFSET, "offsets come with group scales");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l = lane & 31;
     const int r0 = blockIdx.x * RB, row = r0 + 2 * wave + (lane >> 5);
     const bool live = row < R;
-    U += (size_t)(r0 / rpl) * n * n;  // a batch of layers stacked by rows, as in k_gptq_window
+    const double *__restrict__ U = layer_base(lt.U, r0 / rpl, (size_t)n * n);  // a batch of layers, as in k_gptq_window
     if constexpr (GROUPED) pg += (size_t)(r0 / rpl) * n;
     float *qrow = Qp + (size_t)min(row, R - 1) * n, *erow = Eg + (size_t)min(row, R - 1) * n;  // (touched where live)
     for (int i = a; i < b; ++i) {
@@ -637,7 +643,7 @@ __global__ __launch_bounds__(512) void k_gptq_wide_leaf(float *__restrict__ Qp, 
 // ------------------------------------------------------------------ trailing update
 // Qp[:, ja:jb] = float32(float64(Qp[:, ja:jb]) - E[:, ka:kb] @ U[ka:kb, ja:jb]), 64 x 64 tiles.
 __global__ __launch_bounds__(256) void k_gptq_trailing(float *__restrict__ Qp, const float *__restrict__ Eg,
-                                                       const double *__restrict__ U, int R, int n, int ka, int kb,
+                                                       LayerTable lt, int R, int n, int ka, int kb,
                                                        int ja, int jb, int vec_ok, int rpl) {
 #ifdef SLK_TRAILING_F64_IMAGE
     __shared__ __attribute__((aligned(16))) Tile64Smem sm;
@@ -645,7 +651,7 @@ __global__ __launch_bounds__(256) void k_gptq_trailing(float *__restrict__ Qp, c
     __shared__ __attribute__((aligned(16))) Tile64SmemAf sm;  // E stays float32 in LDS (mfma64.h)
 #endif
     const int r0 = blockIdx.y * TILE, j0 = ja + blockIdx.x * TILE;
-    U += (size_t)(r0 / rpl) * n * n;  // batch of layers stacked by rows (rpl a multiple of the tile)
+    const double *__restrict__ U = layer_base(lt.U, r0 / rpl, (size_t)n * n);  // a batch of layers (rpl a multiple of the tile)
     const int t = threadIdx.x;
     Acc64 acc;
     acc.zero();
@@ -876,40 +882,59 @@ constexpr size_t window_lds() {
 // One launch of it, or of the wide leaf for a window beyond WMAX (one LEAF op): the kernel, the LDS size and the profile name
 // follow from the template arguments and the width (gptq_loop has opted in to the LDS).
 template <bool GROUPED, bool OFFSET>
-static int launch_window(double flops, double bytes, int row_tiles, hipStream_t s, float *Qp, float *Eg, const double *U, int R, int n,
-                         int w0, int w1, Grid g, float inv_step, int fast_ok, int dbg, const OpTable &tab, int rpl, const float *Sg,
+static int launch_window(double flops, double bytes, int row_tiles, hipStream_t s, float *Qp, float *Eg, const LayerTable &lt, int R,
+                         int n, int w0, int w1, Grid g, float inv_step, int fast_ok, int dbg, const OpTable &tab, int rpl, const float *Sg,
                          const int *pg, int G, const float *Og) {
     if (w1 - w0 > WMAX) {
         SLK_REQUIRE(tab.count == 1 && tab.op[0].kind == OP_LEAF, "a window of %d columns that is not one leaf", w1 - w0);
         SLK_RUN(OFFSET ? "gptq_window_wide_grouped_asym" : GROUPED ? "gptq_window_wide_grouped" : "gptq_window_wide", flops, bytes, s,
-                k_gptq_wide_leaf<GROUPED, OFFSET><<<row_tiles, 512, 0, s>>>(Qp, Eg, U, R, n, w0, w1, g, rpl, Sg, pg, G, Og));
+                k_gptq_wide_leaf<GROUPED, OFFSET><<<row_tiles, 512, 0, s>>>(Qp, Eg, lt, R, n, w0, w1, g, rpl, Sg, pg, G, Og));
         return SLK_OK;
     }
     SLK_RUN(OFFSET ? "gptq_window_grouped_asym" : GROUPED ? "gptq_window_grouped" : "gptq_window", flops, bytes, s,
-            k_gptq_window<GROUPED, OFFSET><<<row_tiles, 512, window_lds<GROUPED, OFFSET>(), s>>>(Qp, Eg, U, R, n, w0, w1, g, inv_step, fast_ok, dbg,
+            k_gptq_window<GROUPED, OFFSET><<<row_tiles, 512, window_lds<GROUPED, OFFSET>(), s>>>(Qp, Eg, lt, R, n, w0, w1, g, inv_step, fast_ok, dbg,
                                                                                                tab, rpl, Sg, pg, G, Og));
     return SLK_OK;
 }
 
-// `batch` layers of one shape stacked by rows: every launch of the loop covers all of them, each row tile
-// reading its own layer's factor.  What a row shard of a multi-GPU run needs: R / G rows alone leave most of
-// the chip idle (the window kernel runs one workgroup per 16 rows), G layers' shards together fill it.
+// The table of a batch stacked by rows in one allocation: W, scale (batch rows_per_layer) (x n), order batch x n, U batch x n x n.
+static LayerTable stacked_layers(const float *W, const float *scale, const long long *order, const double *U, int batch,
+                                 int rows_per_layer, int n) {
+    LayerTable lt{};
+    for (int b = 0; b < batch && b < LOOP_LAYERS; ++b) {
+        lt.W[b] = W + (size_t)b * rows_per_layer * n;
+        lt.scale[b] = scale ? scale + (size_t)b * rows_per_layer : nullptr;
+        lt.order[b] = order ? order + (size_t)b * n : nullptr;
+        lt.U[b] = U + (size_t)b * n * n;
+    }
+    return lt;
+}
+
+// `batch` layers of one shape, their rows stacked in the workspace and in the outputs: every launch of the loop covers all
+// of them, each row tile reading its own layer's factor.  What a row shard of a multi-GPU run needs: R / G rows alone leave
+// most of the chip idle (the window kernel runs one workgroup per 16 rows), G layers' shards together fill it; and what two
+// full-height layers need to fill the chip with 32-row window workgroups without another stream's help.
+// lt: where every layer's W, scale, order and U lie (stacked_layers, or the caller's own pointers: slk_gptq_quantize_layers).
 // gscale != nullptr: the grouped loop (slk_gptq_quantize_grouped_batch), no row scale.  Arena: Qp and Eg (R n floats
 // each), the inverse orders (batch n ints) and, grouped, the group tables (batch n ints): four 256-byte-aligned takes.
 // row_err != nullptr (slk_gptq_quantize_batch_error; Hs: host array of the layers' Hessians): the last kernel also leaves the
 // rows' errors (k_permute_out<true>), from the diagonal means of a fifth take (64 floats per layer).
-static int gptq_loop(const float *W, const float *scale, const long long *order, const double *U, int batch, int rows_per_layer,
-                     int n, int levels, double lo, double hi, const float *table, int min_block, int num_blocks, int flags,
-                     float *Q, uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream,
+static int gptq_loop(const LayerTable &lt, int batch, int rows_per_layer, int n, int levels, double lo, double hi, const float *table,
+                     int min_block, int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream,
                      const float *gscale, int group_size, const float *goffset, const float *const *Hs = nullptr, float damp = 0.0f,
                      float *row_err = nullptr) {
     const bool grouped = gscale != nullptr, asym = goffset != nullptr;
     const int unscale = flags & SLK_LOOP_UNSCALE;
+    const bool scale = lt.scale[0] != nullptr, order = lt.order[0] != nullptr;
     SLK_REQUIRE(!unscale || scale, "unscale needs the row scales");
     SLK_REQUIRE(rows_per_layer > 0 && n > 0, "empty layer");
     SLK_REQUIRE(batch >= 1 && batch <= 64, "batch must be 1..64");
     SLK_REQUIRE(batch == 1 || rows_per_layer % TILE == 0, "a batch needs rows_per_layer to be a multiple of 64");
     SLK_REQUIRE(batch == 1 || order, "a batch needs the column orders");
+    // what the 16-byte forms ask of the inputs holds for every layer or for none (the layers of a stack beyond the table
+    // follow its entries by whole strides, which the forms' conditions on n keep aligned)
+    uintptr_t W_bits = 0, U_bits = 0;
+    for (int b = 0; b < batch && b < LOOP_LAYERS; ++b) W_bits |= (uintptr_t)lt.W[b], U_bits |= (uintptr_t)lt.U[b];
     SLK_REQUIRE((long long)batch * rows_per_layer <= 0x7fffffffLL, "too many rows");
     const int R = batch * rows_per_layer, rpl = rows_per_layer;
     SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
@@ -956,21 +981,21 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
     const int window_rows = opt(OPT_WINDOW_ROWS) == 16 || opt(OPT_WINDOW_ROWS) == 32 ? opt(OPT_WINDOW_ROWS)
                                                                                      : (((flags & SLK_LOOP_LATENCY) || R < 2048) ? 16 : 32);
     // the grouped loop runs on k_gptq_window alone (16 rows per workgroup whatever window_rows / SLK_LOOP_LATENCY ask)
-    const bool periods_ok = !grouped && n % 2 == 0 && n <= 16384 && (uintptr_t)U % 16 == 0 && !opt(OPT_NO_WINDOW2) && (dbg & ~(24 | 64 | 128)) == 0;
+    const bool periods_ok = !grouped && n % 2 == 0 && n <= 16384 && U_bits % 16 == 0 && !opt(OPT_NO_WINDOW2) && (dbg & ~(24 | 64 | 128)) == 0;
 
     // rows staged through LDS when they fit and 16-byte accesses line up
-    const bool perm_lds = order && n % 4 == 0 && n <= PERM_MAX && ((uintptr_t)W | (uintptr_t)Q | (uintptr_t)workspace) % 16 == 0 &&
+    const bool perm_lds = order && n % 4 == 0 && n <= PERM_MAX && (W_bits | (uintptr_t)Q | (uintptr_t)workspace) % 16 == 0 &&
                           (idx == nullptr || (uintptr_t)idx % 4 == 0);
     {
-        const int rc = launch_permute("permute_in", 0, 8.0 * R * n, perm_lds ? k_permute_in<true> : k_permute_in<false>, perm_lds, R, n, s, W, scale,
-                                      order, R, n, Qp, inv_order, rpl);
+        const int rc = launch_permute("permute_in", 0, 8.0 * R * n, perm_lds ? k_permute_in<true> : k_permute_in<false>, perm_lds, R, n, s, lt, R,
+                                      n, Qp, inv_order, rpl);
         if (rc != SLK_OK) return rc;
     }
 
     const int G = grouped ? n / group_size : 0;
     if (grouped)
         SLK_RUN("group_of_column", 0, 12.0 * batch * n, s,
-                k_group_of_column<<<(batch * n + 255) / 256, 256, 0, s>>>(order, batch, n, group_size, pg));
+                k_group_of_column<<<(batch * n + 255) / 256, 256, 0, s>>>(lt.order[0], batch, n, group_size, pg));
 
     Plan p;
     plan(0, n, min_block, num_blocks, p);
@@ -1018,25 +1043,25 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
                 if (window_rows == 32)
                     SLK_RUN_W("gptq_window", fl * R, wbytes, (R + 2 * RB - 1) / (2 * RB), s,
                               k_gptq_window2<2><<<(R + 2 * RB - 1) / (2 * RB), 512, sizeof(Window2SmemT<2>), s>>>(
-                                  Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg & (24 | 64 | 128), pt, rpl));
+                                  Qp, Eg, lt, R, n, st.a, st.b, g, inv_step, fast_ok, dbg & (24 | 64 | 128), pt, rpl));
                 else
                     SLK_RUN_W("gptq_window", fl * R, wbytes, row_tiles, s,
-                              k_gptq_window2<1><<<row_tiles, 512, sizeof(Window2SmemT<1>), s>>>(Qp, Eg, U, R, n, st.a, st.b, g, inv_step,
+                              k_gptq_window2<1><<<row_tiles, 512, sizeof(Window2SmemT<1>), s>>>(Qp, Eg, lt, R, n, st.a, st.b, g, inv_step,
                                                                                              fast_ok, dbg & 24, pt, rpl));
             }
             else {
                 const auto launch = asym ? launch_window<true, true> : grouped ? launch_window<true, false> : launch_window<false, false>;
-                const int rc = launch(fl * R, wbytes, row_tiles, s, Qp, Eg, U, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G,
+                const int rc = launch(fl * R, wbytes, row_tiles, s, Qp, Eg, lt, R, n, st.a, st.b, g, inv_step, fast_ok, dbg, tab, rpl, gscale, pg, G,
                                       goffset);
                 if (rc != SLK_OK) return rc;
             }
         } else {
             const double K = st.b - st.a, N = st.c - st.b;
-            const int vec_ok = n % 4 == 0 && st.a % 4 == 0 && st.b % 2 == 0 && (uintptr_t)U % 16 == 0;
+            const int vec_ok = n % 4 == 0 && st.a % 4 == 0 && st.b % 2 == 0 && U_bits % 16 == 0;
             {
                 dim3 grid((st.c - st.b + TILE - 1) / TILE, (R + TILE - 1) / TILE);
                 SLK_RUN("gptq_trailing", 2.0 * R * K * N, 4.0 * R * K + 8.0 * K * N + 8.0 * R * N, s,
-                        k_gptq_trailing<<<grid, 256, 0, s>>>(Qp, Eg, U, R, n, st.a, st.b, st.b, st.c, vec_ok, rpl));
+                        k_gptq_trailing<<<grid, 256, 0, s>>>(Qp, Eg, lt, R, n, st.a, st.b, st.b, st.c, vec_ok, rpl));
             }
         }
     }
@@ -1054,13 +1079,13 @@ static int gptq_loop(const float *W, const float *scale, const long long *order,
         if (row_err) {
             const int rc = loop_error_means(Hs, batch, n, hmean, s);
             if (rc != SLK_OK) return rc;
-            ea = RowErrArgs{W, Eg, unscale ? scale : nullptr, hmean, damp, row_err};
+            ea = RowErrArgs{Eg, hmean, damp, row_err};
         }
         const auto kernel = row_err ? (perm_lds ? k_permute_out<true, true> : k_permute_out<false, true>)
                                     : (perm_lds ? k_permute_out<true, false> : k_permute_out<false, false>);
         const int rc = launch_permute(row_err ? "permute_out_error" : "permute_out", row_err ? 4.0 * R * n : 0,
                                       (row_err ? (idx ? 17.0 : 16.0) : (idx ? 9.0 : 8.0)) * R * n, kernel, perm_lds, R, n, s, Qp, inv_order, R, n, g,
-                                      unscale ? scale : nullptr, Q, idx, rpl, ea);
+                                      unscale, Q, idx, rpl, ea, lt);
         if (rc != SLK_OK) return rc;
     }
     if (E_out) copy_async(E_out, Eg, sizeof(float) * (size_t)R * n, s);
@@ -1073,8 +1098,8 @@ extern "C" int slk_gptq_quantize_batch(const float *W, const float *scale, const
                                        float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream) {
     SLK_REQUIRE(W && U && Q, "null pointer");
     SLK_REQUIRE((flags & ~(SLK_LOOP_UNSCALE | SLK_LOOP_LATENCY)) == 0, "unknown flags");
-    return gptq_loop(W, scale, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
-                     workspace, ws_bytes, stream, nullptr, 0, nullptr);
+    return gptq_loop(stacked_layers(W, scale, order, U, batch, rows_per_layer, n), batch, rows_per_layer, n, levels, lo, hi, table,
+                     min_block, num_blocks, flags, Q, idx, E_out, workspace, ws_bytes, stream, nullptr, 0, nullptr);
 }
 
 // slk_gptq_quantize_batch that also leaves the rows' errors (W - Qw) H (W - Qw)^T, carried by the loop (k_permute_out<true>).
@@ -1089,8 +1114,33 @@ extern "C" int slk_gptq_quantize_batch_error(const float *W, const float *scale,
     for (int b = 0; b < batch; ++b) SLK_REQUIRE(H[b] != nullptr, "null Hessian (layer %d)", b);
     SLK_REQUIRE(scale == nullptr || (flags & SLK_LOOP_UNSCALE),
                 "the carried error is that of the de-scaled Q: row scales need SLK_LOOP_UNSCALE");
-    return gptq_loop(W, scale, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
-                     workspace, ws_bytes, stream, nullptr, 0, nullptr, H, damp, row_err);
+    return gptq_loop(stacked_layers(W, scale, order, U, batch, rows_per_layer, n), batch, rows_per_layer, n, levels, lo, hi, table,
+                     min_block, num_blocks, flags, Q, idx, E_out, workspace, ws_bytes, stream, nullptr, 0, nullptr, H, damp, row_err);
+}
+
+// The same loop over `batch` layers that lie anywhere in memory: HOST arrays of the layers' device pointers instead of stacks
+// (scale may be nullptr: no scales; H and row_err both given: the error-carrying form).  Q, idx, E_out and row_err are
+// written here and stay one stack.  Group scales stay with the stacked entries.
+extern "C" int slk_gptq_quantize_layers(const float *const *W, const float *const *scale, const long long *const *order,
+                                        const double *const *U, const float *const *H, float damp, const float *const *gscale,
+                                        int group_size, int batch, int rows_per_layer, int n, int levels, double lo, double hi,
+                                        const float *table, int min_block, int num_blocks, int flags, float *Q, uint8_t *idx,
+                                        float *E_out, float *row_err, void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    SLK_REQUIRE(W && order && U && Q, "null pointer");
+    SLK_REQUIRE(gscale == nullptr && group_size == 0,
+                "group scales are not taken per layer: stack the layers (slk_gptq_quantize_grouped_batch)");
+    SLK_REQUIRE((flags & ~(SLK_LOOP_UNSCALE | SLK_LOOP_LATENCY)) == 0, "unknown flags");
+    SLK_REQUIRE(batch >= 1 && batch <= LOOP_LAYERS, "the layer table holds 1..%d layers (batch %d)", LOOP_LAYERS, batch);
+    SLK_REQUIRE((H == nullptr) == (row_err == nullptr), "the carried error needs both the Hessians and row_err");
+    SLK_REQUIRE(!H || scale == nullptr || (flags & SLK_LOOP_UNSCALE),
+                "the carried error is that of the de-scaled Q: row scales need SLK_LOOP_UNSCALE");
+    LayerTable lt{};
+    for (int b = 0; b < batch; ++b) {
+        SLK_REQUIRE(W[b] && order[b] && U[b] && (!scale || scale[b]) && (!H || H[b]), "null pointer (layer %d)", b);
+        lt.W[b] = W[b], lt.scale[b] = scale ? scale[b] : nullptr, lt.order[b] = order[b], lt.U[b] = U[b];
+    }
+    return gptq_loop(lt, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out, workspace,
+                     ws_bytes, stream, nullptr, 0, nullptr, H, damp, row_err);
 }
 
 // what both grouped entries ask of their arguments (`tables`: gscale, and goffset where there is one)
@@ -1110,8 +1160,8 @@ extern "C" int slk_gptq_quantize_grouped_batch(const float *W, const float *gsca
                                                double hi, const float *table, int min_block, int num_blocks, int flags, float *Q,
                                                uint8_t *idx, float *E_out, void *workspace, size_t ws_bytes, slk_stream_t stream) {
     if (const int rc = check_grouped(gscale != nullptr, W, U, Q, flags, rows_per_layer, n, group_size)) return rc;
-    return gptq_loop(W, nullptr, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
-                     workspace, ws_bytes, stream, gscale, group_size, nullptr);
+    return gptq_loop(stacked_layers(W, nullptr, order, U, batch, rows_per_layer, n), batch, rows_per_layer, n, levels, lo, hi, table,
+                     min_block, num_blocks, flags, Q, idx, E_out, workspace, ws_bytes, stream, gscale, group_size, nullptr);
 }
 
 // One layer with group scales: the batch of one.
@@ -1131,8 +1181,8 @@ extern "C" int slk_gptq_quantize_grouped_asym_batch(const float *W, const float 
                                                     int num_blocks, int flags, float *Q, uint8_t *idx, float *E_out, void *workspace,
                                                     size_t ws_bytes, slk_stream_t stream) {
     if (const int rc = check_grouped(gscale && goffset, W, U, Q, flags, rows_per_layer, n, group_size)) return rc;
-    return gptq_loop(W, nullptr, order, U, batch, rows_per_layer, n, levels, lo, hi, table, min_block, num_blocks, flags, Q, idx, E_out,
-                     workspace, ws_bytes, stream, gscale, group_size, goffset);
+    return gptq_loop(stacked_layers(W, nullptr, order, U, batch, rows_per_layer, n), batch, rows_per_layer, n, levels, lo, hi, table,
+                     min_block, num_blocks, flags, Q, idx, E_out, workspace, ws_bytes, stream, gscale, group_size, goffset);
 }
 
 // One layer with group scales and offsets: the batch of one.

@@ -134,7 +134,7 @@ __device__ __forceinline__ void leaf_chain8(const LeafTables8 &lt, int sub, floa
 
 template <int SETS>
 __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, float *__restrict__ Eg,
-                                                      const double *__restrict__ U, int R, int n, int w0, int w1,
+                                                      LayerTable lt, int R, int n, int w0, int w1,
                                                       Grid g, float inv_step, int fast_ok, int prof, PeriodTable tab, int rpl) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     Window2SmemT<SETS> &sm = *reinterpret_cast<Window2SmemT<SETS> *>(smem_raw);
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(512) void k_gptq_window2(float *__restrict__ Qp, fl
     if (!helper && (prof & 128)) __builtin_amdgcn_s_setprio(3);
     const int ht = role_wave * 64 + lane;                   // thread index within the role, 0-255
     const int r0 = blockIdx.x * RBX;
-    U += (size_t)(r0 / rpl) * n * n;  // a batch of layers stacked by rows: rows [b rpl, (b + 1) rpl) use factor b
+    const double *__restrict__ U = layer_base(lt.U, r0 / rpl, (size_t)n * n);  // a batch of layers: rows [b rpl, (b + 1) rpl) use factor b
     const int np = tab.count;
     const int width = w1 - w0;
     if (g.table) {  // the leaves search the codebook once per column: keep it next to them

@@ -151,6 +151,7 @@ class HipBackend:
         self.group_rows = int(os.environ.get("SLK_GROUP_ROWS", self.group_rows))
         self.short_factor_batch = int(os.environ.get("SLK_SHORT_FACTOR_BATCH", self.short_factor_batch))
         self.short_rows = int(os.environ.get("SLK_SHORT_ROWS", self.short_rows))
+        self.tall_stack = int(os.environ.get("SLK_TALL_STACK", self.tall_stack))
         self.group_wide_rows = int(os.environ.get("SLK_GROUP_WIDE_ROWS", self.group_wide_rows))
         self.group_bytes = int(os.environ.get("SLK_GROUP_BYTES", self.group_bytes))
 
@@ -411,8 +412,7 @@ class HipBackend:
     def run_round_stacked(self, round_layers, factors):
         """All rows of a round's layers from their own factors (order, U, info[, symmetry flag]) made elsewhere on this
         GPU: stacked, then ONE loop / error over all of them."""
-        order = _stack_views([f[0] for f in factors])
-        U = _stack_views([f[1] for f in factors])  # (factors that came out of ONE batched factorisation are a stack already)
+        order, U = [f[0] for f in factors], [f[1] for f in factors]  # (stacked by _run_stacked only where a stack is needed)
         info = torch.cat([f[2] for f in factors])
         known = torch.cat([f[3] for f in factors]) if all(len(f) > 3 for f in factors) else None
         return self._run_stacked(round_layers, 0, round_layers[0]["W"].shape[0], order, U, info, known)
@@ -426,14 +426,24 @@ class HipBackend:
         return self._run_stacked(round_layers, 0, round_layers[0]["W"].shape[0], order, U, info, None)
 
     def _run_stacked(self, round_layers, lo, hi, order, U, info, known):
-        """Rows [lo, hi) of every layer of the round through ONE loop and ONE error evaluation, from stacked factors
-        order (B, n), U (B, n, n), info (B,); known: the symmetry verdicts of the Hessians, or None (checked here)."""
+        """Rows [lo, hi) of every layer of the round through ONE loop and ONE error evaluation, from the layers' factors --
+        stacked, order (B, n), U (B, n, n), or a list of each, one per layer -- and info (B,); known: the symmetry verdicts of
+        the Hessians, or None (checked here)."""
         eng = self.engine
         B, n = len(round_layers), round_layers[0]["H"].shape[0]
         device = round_layers[0]["W"].device
         rows = hi - lo
         Rp = (rows + 127) // 128 * 128  # the batch entry points want whole 128-row tiles per layer (96 rows at 768 / 8)
         Hs = [lay["H"] for lay in round_layers]
+        carried = self._carried_error(round_layers)
+        # Whole tiles, row scales or none, no search and no product of the error: the loop is all there is, and it reads every
+        # layer's W, scale, order and U where they lie (engine.gptq_loop with lists) -- no copy into stacks (six 4096-column
+        # factors that were not made by one batched factorisation: 0.8 GB read and written).
+        if (rows == Rp and B <= LOOP_LAYERS and round_layers[0].get("gscale") is None and self.moves == 0
+                and (carried == "loop" or not self.with_error)):
+            return self._shards(round_layers, lo, hi, self._loop_layers(round_layers, lo, hi, list(order), list(U), carried == "loop"), info.split(1))
+        if isinstance(order, list):
+            order, U = _stack_views(order), _stack_views(U)  # (factors that came out of ONE batched factorisation are a stack already)
         # ragged shard: every layer's rows padded to whole tiles (zero weights, unit scales); rows never interact, so the
         # padding rows are wasted work and nothing else -- they are cut off below.  One launch per stack either way
         # (engine.stack_rows: a copy per layer was 120 small launches per step for one rank of 8 on OPT-125M).
@@ -446,7 +456,6 @@ class HipBackend:
         W, sc, S = stacked("W", 0.0), stacked("scale", 1.0), stacked("gscale", 1.0)
         cb = eng.require_uniform(self.quantizer)
         want_idx = cb[0] <= 256  # (the kernels emit uint8 indices)
-        carried = self._carried_error(round_layers)
         if self.moves > 0 and S is None:
             # local search works in the scaled domain (engine.quantize_layer): scaled copy in, ONE search over the stack
             # (engine.local_search_batch: a search per layer is ten small launches, and the shards of a round on several
@@ -472,8 +481,53 @@ class HipBackend:
                                            want_idx=want_idx, unscale=sc is not None, Hs=Hs if carried == "loop" else None, damp=self.damp)
         if self.with_error and err is None:
             err = eng.row_errors_batch(W, Q, Hs, known)
-        return [dict(Q=Q[b, :rows], idx=idx[b, :rows] if want_idx else None, row_err=None if err is None else err[b, :rows], rows=(lo, hi),
-                     info=info[b:b + 1]) for b in range(B)]
+        return self._shards(round_layers, lo, hi, (Q, idx if want_idx else None, err), info.split(1))
+
+    @staticmethod
+    def _shards(round_layers, lo, hi, stacks, infos):
+        """A loop's stacked results (Q, idx, row_err: (B, padded rows, ...), idx / row_err may be None) as one shard per layer,
+        each with its layer's factorisation status word."""
+        Q, idx, err = stacks
+        rows = hi - lo
+        return [dict(Q=Q[b, :rows], idx=None if idx is None else idx[b, :rows], row_err=None if err is None else err[b, :rows],
+                     rows=(lo, hi), info=infos[b]) for b in range(len(round_layers))]
+
+    def _loop_layers(self, stack_layers, lo, hi, orders, Us, carry, latency=False):
+        """Rows [lo, hi) of same-shaped layers (row scales or none) through ONE loop that reads every layer's tensors where they
+        lie; carry: the loop carries the rows' errors (_carried_error "loop").  Returns the stacked (Q, idx, row_err)."""
+        eng = self.engine
+        cb = eng.require_uniform(self.quantizer)
+        scaled = stack_layers[0].get("scale") is not None
+        Q, idx, _, err = eng.gptq_loop([lay["W"][lo:hi].contiguous() for lay in stack_layers], cb, orders, Us, *self.blocks,
+                                       scale=[lay["scale"][lo:hi].contiguous() for lay in stack_layers] if scaled else None,
+                                       want_idx=cb[0] <= 256, unscale=scaled, latency=latency,
+                                       Hs=[lay["H"] for lay in stack_layers] if carry else None, damp=self.damp)
+        return Q, idx, err
+
+    # -- one rank, full-height layers: `tall_stack` consecutive ones of a shape and kind share ONE set of loop launches
+    # A window launch of one 4096-row layer is 128 workgroups of 32 rows, each alone on its CU (158 KB of LDS): half the chip,
+    # left to the factor streams' kernels to fill -- which the streams that share the loop stream's hardware queue cannot (at 4
+    # queues a third of the factorisations).  Two layers are 256 workgroups, the whole chip for the same duration; four are two
+    # full rounds and a quarter of the launches.  The loop reads every layer where it lies (_loop_layers): nothing is copied.
+    # Headline, ms per step, alternating with the parent: 24.15 layer by layer, 21.49 in stacks of 2, 21.20 of 4 (DESIGN.md 8.9;
+    # with `--streams 2,1`, where nothing shares the loop stream's queue, the stacks lose 0.9 ms instead).  1: layer by layer
+    # (run_rows).
+    tall_stack = 4
+
+    def wants_tall_stack(self, layer):
+        """Layers whose loop may share its launches with the next ones of the same shape and kind (quantize_stream's
+        layer-by-layer route on one rank): plain orders, row scales or none, no search, the error carried by the loop."""
+        return (self.tall_stack > 1 and self._plain_order() and self.moves == 0 and layer.get("gscale") is None
+                and layer["W"].shape[0] % 64 == 0 and self._carried_error([layer]) == "loop")
+
+    def run_tall(self, stack_layers, factors):
+        """All rows of up to tall_stack same-shaped layers from their own factors through one loop: the shards of run_rows."""
+        R = stack_layers[0]["W"].shape[0]
+        stacks = self._loop_layers(stack_layers, 0, R, [f[0] for f in factors], [f[1] for f in factors], True, latency=not self.overlap)
+        return self._shards(stack_layers, 0, R, stacks, [f[2] for f in factors])
+
+
+LOOP_LAYERS = 16  # layers one loop takes as a list of tensors (slk_gptq_quantize_layers)
 
 
 def _guard_inputs(layers, stream):
@@ -846,6 +900,21 @@ def _quantize_stream(layers, backend, comm_device=None, join=True, _local=True):
             st.wait_stream(here)
     # (batched rounds rotate over the loop streams across calls, like the factorisations above)
     batched_rounds = getattr(backend, "_loop_rotation", 0) if side else 0
+    # one rank: consecutive full-height layers of one shape and kind share one loop (HipBackend.tall_stack at a time; a
+    # remainder goes through the same call with fewer): tall[first member] = the stack, tall[later member] = ()
+    tall = {}
+    if not exchange and hasattr(backend, "run_tall"):
+        per = min(int(backend.tall_stack), LOOP_LAYERS)
+        run, run_key = [], None
+        for l in [l for g in rounds for l in g] + [None]:
+            key = None if l is None or not backend.wants_tall_stack(layers[l]) else (tuple(layers[l]["W"].shape), _layer_kind(layers[l]))
+            if key != run_key or len(run) == per:
+                for m in run:
+                    tall[m] = run if m == run[0] else ()
+                run = []
+            run_key = key
+            if key is not None:
+                run.append(l)
     for gi, members_g in enumerate(groups):
         members = [l for g in members_g for l in rounds[g]]
         lo, hi = row_range(layers[members[0]]["W"].shape[0], rank, size)
@@ -875,6 +944,24 @@ def _quantize_stream(layers, backend, comm_device=None, join=True, _local=True):
                 out[l] = shard
             continue
         for l in members:
+            if l in tall:
+                stack = tall[l]
+                if not stack:  # a later member: it went with the first
+                    continue
+                ls = lstreams[l % len(lstreams)] if side else None
+                if not join:
+                    _guard_inputs([layers[m] for m in stack], ls)
+                with on(ls):
+                    for m in stack:
+                        if ready[m] is not None:
+                            ls.wait_event(ready[m])  # behind EVERY member's factorisation
+                    for m, shard in zip(stack, backend.run_tall([layers[m] for m in stack], [factors[m] for m in stack])):
+                        out[m] = shard
+                    if side:  # made on the factor streams, read on this one
+                        for m in stack:
+                            for t in factors[m]:
+                                t.record_stream(ls)
+                continue
             layer = layers[l]
             ls = lstreams[l % len(lstreams)] if side else None
             if not join:

@@ -152,7 +152,10 @@ def gptq_loop(W, cb_abi, order, U, min_block, num_blocks, scale=None, gscale=Non
     """The column-sequential loop on device tensors: the package's one binding of slk_gptq_quantize*.
 
     W (R, n) float32 is one layer: order (n,) int64 (None: the columns as they lie), U (n, n) float64.  W (B, R, n) is a batch
-    of layers stacked by rows (R a multiple of 64): order (B, n), U (B, n, n), launches that cover all B layers.  At most one kind
+    of layers stacked by rows (R a multiple of 64): order (B, n), U (B, n, n), launches that cover all B layers.  A LIST of B
+    layers' W (R, n) -- with lists of their orders, factors and (if any) row scales, every tensor contiguous, anywhere in memory
+    -- is the same batch without the copies into stacks (slk_gptq_quantize_layers: at most 16 layers, no group scales); what
+    comes back is stacked, as for a stacked batch.  At most one kind
     of scales, shaped like W without its columns: `scale` (one per row; `unscale`: Q comes back de-scaled), or `gscale` over
     groups of `group_size` columns (n / group_size per row; Q de-scaled), optionally with the offsets `goffset` beside it.
     latency: the layer is alone on the GPU (SLK_LOOP_LATENCY: 16-row window workgroups; same results).
@@ -160,11 +163,22 @@ def gptq_loop(W, cb_abi, order, U, min_block, num_blocks, scale=None, gscale=Non
     (slk_gptq_quantize_batch_error: H symmetric, U its factor at this damp; `scale` then needs `unscale`; not with group scales).
     Returns (Q, idx, E, row_err): Q, idx (uint8) and E shaped like W, row_err like W without its columns; None when not asked for.
     """
-    lead, n = tuple(W.shape[:-1]), W.shape[-1]
-    B, R = lead if len(lead) == 2 else (1,) + lead
-    assert W.is_contiguous() and U.shape == lead[:-1] + (n, n) and U.is_contiguous()
-    assert order is None or (order.shape == lead[:-1] + (n,) and order.is_contiguous())
-    assert scale is None or (gscale is None and scale.shape == lead and scale.is_contiguous())
+    layers = isinstance(W, (list, tuple))
+    if layers:
+        (R, n), device = W[0].shape, W[0].device
+        B, lead = len(W), (len(W), R)
+        assert gscale is None and len(order) == B and len(U) == B and (scale is None or len(scale) == B)
+        for b in range(B):
+            assert W[b].shape == (R, n) and W[b].dtype == torch.float32 and W[b].is_contiguous()
+            assert order[b].shape == (n,) and order[b].dtype == torch.int64 and order[b].is_contiguous()
+            assert U[b].shape == (n, n) and U[b].dtype == torch.float64 and U[b].is_contiguous()
+            assert scale is None or (scale[b].shape == (R,) and scale[b].dtype == torch.float32 and scale[b].is_contiguous())
+    else:
+        lead, n, device = tuple(W.shape[:-1]), W.shape[-1], W.device
+        B, R = lead if len(lead) == 2 else (1,) + lead
+        assert W.is_contiguous() and U.shape == lead[:-1] + (n, n) and U.is_contiguous()
+        assert order is None or (order.shape == lead[:-1] + (n,) and order.is_contiguous())
+        assert scale is None or (gscale is None and scale.shape == lead and scale.is_contiguous())
     assert (gscale is None) == (group_size is None) and (goffset is None or gscale is not None)
     g = 0
     if gscale is not None:
@@ -176,22 +190,28 @@ def gptq_loop(W, cb_abi, order, U, min_block, num_blocks, scale=None, gscale=Non
         assert all(H.shape == (n, n) and H.dtype == torch.float32 and H.is_contiguous() for H in Hs)
     # (one layer: slk_workspace_bytes, whatever its scales; a batch: slk_workspace_bytes_batch, for the grouped loop at every size)
     ws, ws_bytes = dev.workspace(R, n, batch=B, grouped=gscale is not None and len(lead) == 2)
-    Q = torch.empty_like(W, dtype=torch.float32)
-    idx = torch.empty(W.shape, dtype=torch.uint8, device=W.device) if want_idx else None
+    Q = torch.empty(lead + (n,), dtype=torch.float32, device=device)
+    idx = torch.empty(lead + (n,), dtype=torch.uint8, device=device) if want_idx else None
     E = torch.empty_like(Q) if want_E else None
-    row_err = torch.empty(lead, dtype=torch.float32, device=W.device) if Hs is not None else None
+    row_err = torch.empty(lead, dtype=torch.float32, device=device) if Hs is not None else None
     levels, lo, hi, table = cb_abi
-    factor = (dev.ptr(order), dev.ptr(U))
+
+    def pointers(tensors):
+        return None if tensors is None else (ctypes.c_void_p * B)(*[dev.ptr(t) for t in tensors])
+
+    factor = (pointers(order), pointers(U)) if layers else (dev.ptr(order), dev.ptr(U))
     rest = (B, R, n, levels, lo, hi, dev.ptr(table), int(min_block), int(num_blocks), (1 if unscale else 0) | (2 if latency else 0),
             dev.ptr(Q), dev.ptr(idx), dev.ptr(E))
     end = (dev.ptr(ws), ws_bytes, dev.stream_handle())
-    if goffset is not None:
+    if layers:
+        rc = _lib.lib.slk_gptq_quantize_layers(pointers(W), pointers(scale), *factor, pointers(Hs), float(damp or 0.0), None, 0, *rest,
+                                               dev.ptr(row_err), *end)
+    elif goffset is not None:
         rc = _lib.lib.slk_gptq_quantize_grouped_asym_batch(dev.ptr(W), dev.ptr(gscale), dev.ptr(goffset), g, *factor, *rest, *end)
     elif gscale is not None:
         rc = _lib.lib.slk_gptq_quantize_grouped_batch(dev.ptr(W), dev.ptr(gscale), g, *factor, *rest, *end)
     elif Hs is not None:
-        ptrs = (ctypes.c_void_p * B)(*[dev.ptr(H) for H in Hs])
-        rc = _lib.lib.slk_gptq_quantize_batch_error(dev.ptr(W), dev.ptr(scale), *factor, ptrs, float(damp), *rest, dev.ptr(row_err), *end)
+        rc = _lib.lib.slk_gptq_quantize_batch_error(dev.ptr(W), dev.ptr(scale), *factor, pointers(Hs), float(damp), *rest, dev.ptr(row_err), *end)
     else:
         rc = _lib.lib.slk_gptq_quantize_batch(dev.ptr(W), dev.ptr(scale), *factor, *rest, *end)
     _lib.check(rc)
