@@ -196,8 +196,11 @@ int slk_factor_load(const double *M, int n, double *A, slk_stream_t stream);
 /* a6  compute_hessian_chol  (sleekit/obq.py:38-55)
  *     A: output of slk_hessian_prepare (destroyed).  U: n x n float64 row-major,
  *     upper triangular with U^T U = Hd[order][:, order]^-1, zeros below the diagonal.
- *     info[0] = 0 on success, else 1 + the (permuted) column where a non-positive
- *     pivot appeared -- the reference raises numpy.linalg.LinAlgError there.    */
+ *     info[0] = 0 on success, else 1 + k, k the first index IN THE ORDER OF THE FACTORISATION whose pivot is not > 0
+ *     (negative, zero or NaN): row k of the index-reversed matrix A, that is column n - 1 - k of Hd[order][:, order],
+ *     column order[n - 1 - k] of H -- the reference raises numpy.linalg.LinAlgError there.  With several such pivots
+ *     the smallest k; the padding rows of A never count; in a batch every matrix has its own word.  (Or
+ *     SLK_INFO_HANDOFF_TIMEOUT, see above.)  U is void when info[0] != 0.                                        */
 int slk_chol_inverse_upper(double *A, int n, double *U, int *info, void *workspace,
                            size_t ws_bytes, slk_stream_t stream);
 /*     The same with LOOK-AHEAD: after a block's panels only the next block's tile columns are updated on `stream`, the

@@ -123,7 +123,11 @@ def raise_not_pd(code, what):
     """numpy.linalg.LinAlgError, what np.linalg.cholesky raises in the reference (sleekit/obq.py:49-50)."""
     if code == HANDOFF_TIMEOUT:
         raise RuntimeError(f"{what}: the factorisation's workgroups lost one another (hand-off timed out after 2 s); results are void")
-    raise np.linalg.LinAlgError(f"{what}: Matrix is not positive definite (pivot {code - 1})")
+    # code - 1 counts in the order of the factorisation (include/sleekit_amd.h, slk_chol_inverse_upper): NOT a column of H
+    raise np.linalg.LinAlgError(
+        f"{what}: Matrix is not positive definite (pivot {code - 1} in the order of the factorisation, which runs from the "
+        "last column of the ordered Hessian to its first, is not > 0)"
+    )
 
 
 def _raise_if_failed(info, what):
