@@ -85,7 +85,8 @@ typedef void *slk_stream_t;
  * slk_dequantize_grouped_asym, slk_group_midpoints and slk_group_center, then bit-packed indices: slk_pack_indices,
  * slk_unpack_indices and slk_dequantize_packed, then slk_gptq_quantize_batch_error (the loop that carries the layer error)
  * and the option "no_loop_error", then slk_gptq_quantize_layers (the same loop over layers that are not one stack: per-layer
- * pointers).   */
+ * pointers), then slk_packed_gemm (a linear layer computed from the packed indices; an addition within 8, nothing existing
+ * changed).   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -479,6 +480,28 @@ int slk_mx_dequantize_act(const uint8_t *a_codes, const uint8_t *a_scales, int M
                           slk_stream_t stream);
 int slk_mx_gemm(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
                 const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream);
+
+/* A linear layer from packed indices (the format of slk_pack_indices above), de-quantized inside a bfloat16 / float16 MFMA
+ * GEMM (v_mfma_f32_16x16x32_bf16 / _f16): no de-quantized weight is written to memory and there is no workspace.
+ * slk_packed_gemm: out[m][n] = sum_k Xc[m][k] Wc[n][k] (+ bias[n]) for a layer of N rows (output features) and K columns:
+ *   - Wc is bit for bit slk_dequantize_packed(words, N, K, ..., out_dtype = compute_dtype): value(min(index, levels - 1))
+ *     / (1 / s) [+ o] in float32, true divides in this order, rounded once to nearest even to the compute type;
+ *     (scale | gscale [, goffset], group_size) as there;
+ *   - Xc is X (M x K row-major, `x_dtype`) rounded to nearest even to the compute type (the identity when it has it);
+ *   - compute_dtype is SLK_DTYPE_BF16 or SLK_DTYPE_F16; the products are exact in float32, the sums float32 over K in a
+ *     fixed order (no atomics: a repeated call gives the same bits); the float32 bias (N, may be NULL) is added in float32
+ *     and the result rounded once to `out_dtype` (M x N row-major).
+ *   X is not looked at for NaN or infinity (they propagate); 16-bit subnormals behave as the hardware defines them.
+ *   Any M, N >= 1; K >= 8 and K % 8 == 0; with gscale, group_size % 8 == 0 and group_size divides K (so that the 8 consecutive
+ *   k a lane feeds the MFMA lie inside one row under one scale; K % 32 != 0 is fine).  Up to M = 16 a workgroup is one
+ *   16-column tile of out whose 8 waves share K; above, a workgroup is a 64 x 64 tile that de-quantizes its weights into LDS.
+ *   SLK_E_ARG, before any launch, with slk_last_error() naming the offender: K % 8 != 0 or K < 8, M or N < 1, bits outside
+ *   1..8, levels < 2 or > 2^bits, scale together with gscale, goffset without gscale, group_size % 8 != 0 or not dividing K,
+ *   a NULL X, words or out, an unknown x_dtype or out_dtype, compute_dtype not BF16 or F16, X or out off 16-byte alignment,
+ *   words off 4, and, for M > 16, ceil(M / 64) * ceil(N / 64) above 2^31 - 1 (the 64 x 64 tiles of one launch).  Layers outside these shapes: slk_dequantize_packed and any GEMM. */
+int slk_packed_gemm(const void *X, int x_dtype, const uint32_t *words, int bits, int levels, double lo, double hi, const float *table,
+                    const float *scale, const float *gscale, const float *goffset, int group_size, const float *bias, int M, int N,
+                    int K, int compute_dtype, int out_dtype, void *out, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -1,6 +1,6 @@
 """sleekit_amd: MI355X-native GPTQ/OBQ layer quantization behind the sleekit function surface.
 
-    from sleekit_amd import obq, scaling, codebook, groups, packing, mx, Sleekit, MXLinear
+    from sleekit_amd import obq, scaling, codebook, groups, packing, mx, Sleekit, MXLinear, PackedLinear
 
 mirrors `sleekit.obq`, `sleekit.scaling`, `sleekit.codebook` and `sleekit.Sleekit` of
 Coloquinte/sleekit for the hot path.  Submodules are imported lazily
@@ -24,4 +24,6 @@ def __getattr__(name):
         return importlib.import_module(f"{__name__}.statistics").Sleekit
     if name == "MXLinear":
         return importlib.import_module(f"{__name__}.mx").MXLinear
+    if name == "PackedLinear":
+        return importlib.import_module(f"{__name__}.packing").PackedLinear
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -21,7 +21,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 OK, E_ARG, E_NOT_PD, E_HIP, E_WS = 0, -1, -2, -3, -4
 CB_VALUE, CB_INDEX, CB_UP, CB_DOWN, CB_INDEX16, CB_INDEX32 = 0, 1, 2, 3, 4, 5
-DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2  # slk_dequantize_packed `out_dtype`
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2  # slk_dequantize_packed `out_dtype`, slk_packed_gemm's dtypes
 MX_MAX, MX_MSE, MX_DIAG = 0, 1, 2  # slk_mx_scale_search `mode`
 ORDER_NONE, ORDER_DIAG, ORDER_ERR, ORDER_SQERR, ORDER_KEYS = 0, 1, 2, 3, 4
 ORDER_MODES = {"none": ORDER_NONE, "diag": ORDER_DIAG, "err": ORDER_ERR, "sqerr": ORDER_SQERR}
@@ -114,6 +114,10 @@ PROTOTYPES = {
     "slk_mx_quantize_act": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
     "slk_mx_dequantize_act": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "slk_mx_gemm": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "slk_packed_gemm": (
+        c_int,
+        [P, c_int, P, c_int, c_int, c_double, c_double, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P],
+    ),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

@@ -153,19 +153,28 @@ class Sleekit:
         """
         if offsets is not None and group_size is None:
             raise ValueError("offsets need group_size: an offset per row and group of input features")
+        return self._quantize(False, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
+                              max_factor, scale, group_size, offsets)
+
+    def _quantize(self, keep_scales, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
+                  max_factor, scale, group_size, offsets):
+        """`quantize`; keep_scales (quantize_packed): the result carries the scales it was made with on every path."""
         if group_size is not None:
             return self._quantize_grouped(nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                                          max_factor, scale, group_size, offsets)
+                                          max_factor, scale, group_size, offsets, keep_scales)
         codebook = UniformCodebook(2**nbits, -1, 1)
         weight, H = self._weight_and_hessian(bias_correction)
         if scale is None:
             scale = compute_scaling(weight, codebook, H=H, mode=scaling_mode, grid_size=grid_size, min_factor=min_factor,
                                     max_factor=max_factor)
-        result = engine.quantize_layer(weight, H, codebook, dev.to_device(scale), order_mode, damp, nb_ls_moves)
+        scale = dev.to_device(scale)
+        result = engine.quantize_layer(weight, H, codebook, scale, order_mode, damp, nb_ls_moves)
+        if keep_scales:
+            result.S = scale
         return self._store(result, weight, bias_correction)
 
     def _quantize_grouped(self, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                          max_factor, scale, group_size, offsets=None):
+                          max_factor, scale, group_size, offsets=None, keep_scales=False):
         from . import groups
 
         if nb_ls_moves > 0:
@@ -191,7 +200,19 @@ class Sleekit:
         result = groups.quantize_layer_grouped(weight, scale, codebook, H, group_size, order_mode, damp, offsets=offsets)
         if offsets is not None:
             result.S, result.O = scale, offsets
+        elif keep_scales:
+            result.S = scale
         return self._store(result, weight, bias_correction)
+
+    def quantize_packed(self, nbits, scaling_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0,
+                        grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, offsets=None, group_size=None):
+        """`quantize` with the same arguments and the same result, which also carries its scales on EVERY path: result.S is
+        (out,) per row or (out, features / group_size) grouped, result.O the group offsets when there are any -- what
+        packing.PackedLinear.from_result packs beside result.idx.  (`quantize` keeps the scales of the offset path only.)"""
+        if offsets is not None and group_size is None:
+            raise ValueError("offsets need group_size: an offset per row and group of input features")
+        return self._quantize(True, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
+                              max_factor, scale, group_size, offsets)
 
     def quantize_mxfp4(self, scale_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0):
         """The layer's weight replaced by its MXFP4 quantization, in place (sleekit_amd.mx): power-of-two scales per block of
