@@ -158,9 +158,15 @@ int slk_hessian_patch_dead(float *H, float *W, int R, int n, void *workspace, si
 /* a1  Sleekit.add_batch, Linear branch  (sleekit/statistics.py:41-43, 76-87)
  *     X: T tokens x n features, row-major.  With c = count_before, c' = c + T:
  *     mean = mean * (c/c') + colsum(X) / c';   H = H * (c/c') + X^T X / c'.
- *     Matches the reference to float32 GEMM tolerance: float32 MFMA, or -- n a multiple of 128 and a
- *     workspace given (6 n bytes per token, chunked to what fits) -- float32-grade products of three
- *     bfloat16 pieces per operand on the bfloat16 MFMA.  workspace may be NULL.                    */
+ *     In float32, one rounding per operation: f = (float)((double)c / c'), cnt = (float)c' (c' past 2^24
+ *     rounds), mean = fl(fl(mean f) + fl(s / cnt)), H = fl(fl(H f) + fl(V / cnt)); H comes out bit-wise
+ *     symmetric (the lower triangle is computed and mirrored).  V = X^T X matches the reference to float32
+ *     GEMM tolerance: a float32 MFMA chain over the tokens, or -- n a multiple of 128 and a workspace of at
+ *     least 4096 + 6 n 32 bytes -- six of the nine products of three bfloat16 pieces per operand (mfma_bf16x3.h)
+ *     on the bfloat16 MFMA.  That path takes the tokens in chunks of (ws_bytes - 4096) / (6 n) rounded down to
+ *     a multiple of 32; the first chunk applies f, each later one adds fl(V_chunk / cnt) to what is there, so
+ *     a chunked call rounds once more per chunk than a whole one.  X needs no alignment.  workspace may be
+ *     NULL (float32 MFMA at every width).                                                                   */
 int slk_hessian_accumulate(float *H, float *mean, const float *X, int n, int T,
                            long long count_before, void *workspace, size_t ws_bytes, slk_stream_t stream);
 
