@@ -86,7 +86,7 @@ typedef void *slk_stream_t;
  * slk_unpack_indices and slk_dequantize_packed, then slk_gptq_quantize_batch_error (the loop that carries the layer error)
  * and the option "no_loop_error", then slk_gptq_quantize_layers (the same loop over layers that are not one stack: per-layer
  * pointers), then slk_packed_gemm (a linear layer computed from the packed indices; an addition within 8, nothing existing
- * changed).   */
+ * changed), then slk_hadamard_rows (the block Hadamard rotation of sleekit_amd/rotation.py; likewise).   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -508,6 +508,29 @@ int slk_mx_gemm(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *
 int slk_packed_gemm(const void *X, int x_dtype, const uint32_t *words, int bits, int levels, double lo, double hi, const float *table,
                     const float *scale, const float *gscale, const float *goffset, int group_size, const float *bias, int M, int N,
                     int K, int compute_dtype, int out_dtype, void *out, slk_stream_t stream);
+
+/* The randomized block Hadamard rotation of the input features (sleekit_amd/rotation.py): no reference counterpart.
+ * slk_hadamard_rows: Y = X R (transposed == 0) or Y = X R^T (transposed != 0), R = diag(s) blockdiag(H_block) / sqrt(block),
+ *   H_block the Sylvester-Hadamard matrix.  X and Y are rows x n, contiguous; s = `signs`, n float32 of +-1, or NULL for all +1.
+ *   Per row and per block of `block` consecutive columns, with v in the compute type -- float64 when X is float64 (Y then
+ *   must be too), float32 otherwise (Y float32, bfloat16 or float16) -- one rounding per operation, no fused multiply-add:
+ *     1. v_i = x_i, converted (exact); transposed == 0: v_i = s_i v_i (a sign flip, exact).
+ *     2. for h = 1, 2, 4, ..., block / 2 in this order, every pair (i, i + h) with (i & h) == 0:
+ *            (v_i, v_{i+h}) <- (v_i + v_{i+h}, v_i - v_{i+h})        (the upper element takes lower - upper).
+ *     3. y_i = v_i c, c the compute-type rounding of 1.0 / sqrt((double)block); transposed != 0: y_i = s_i y_i.
+ *     4. y_i converted to y_dtype, round to nearest even (a NaN becomes the quiet NaN 0x7fc0 in bfloat16).
+ *   The network fixes the two operands of every addition, so the bits do not depend on how a kernel spreads the stages
+ *   over registers, lanes and waves, and a repeated call gives the same bits.  A non-finite element reaches its own block
+ *   of its own row and nothing else.  For block a power of 4, c is a power of two and X R R^T == X wherever nothing
+ *   overflows or goes subnormal on the way.
+ *   In place (Y == X, same dtype) is allowed; any other overlap is not.  No alignment beyond the element's own is asked
+ *   for; where X, Y and signs start on 16 bytes and n % 16 == 0 the kernel moves 16 bytes at a time.  No workspace.
+ *   SLK_E_ARG, before any launch: block not a power of two in 2 .. 4096, n % block != 0, rows or n < 1, a NULL X or Y, an
+ *   unknown dtype, float64 on one side only, rows * ceil(n / 16) above (2^31 - 1) * 256 (one grid covers the matrix: about
+ *   8.8e12 elements).  rows may pass 65535 (and 2^31).                                                                  */
+#define SLK_DTYPE_F64 3 /* slk_hadamard_rows only */
+int slk_hadamard_rows(const void *X, int x_dtype, void *Y, int y_dtype, long long rows, int n, int block,
+                      const float *signs, int transposed, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -1,6 +1,7 @@
 """sleekit_amd: MI355X-native GPTQ/OBQ layer quantization behind the sleekit function surface.
 
-    from sleekit_amd import obq, scaling, codebook, groups, packing, mx, Sleekit, MXLinear, PackedLinear
+    from sleekit_amd import obq, scaling, codebook, groups, packing, mx, rotation, Sleekit, MXLinear, PackedLinear
+    from sleekit_amd import Rotation, RotatedLinear
 
 mirrors `sleekit.obq`, `sleekit.scaling`, `sleekit.codebook` and `sleekit.Sleekit` of
 Coloquinte/sleekit for the hot path.  Submodules are imported lazily
@@ -14,7 +15,7 @@ import importlib
 # queue count to the process environment: the GPU is shared, and more queues per process than the machine allows are not
 # ours to take.)
 
-_SUBMODULES = ("codebook", "obq", "scaling", "statistics", "engine", "dist", "synth", "groups", "packing", "mx", "_lib", "_device")
+_SUBMODULES = ("codebook", "obq", "scaling", "statistics", "engine", "dist", "synth", "groups", "packing", "mx", "rotation", "_lib", "_device")
 
 
 def __getattr__(name):
@@ -26,4 +27,6 @@ def __getattr__(name):
         return importlib.import_module(f"{__name__}.mx").MXLinear
     if name == "PackedLinear":
         return importlib.import_module(f"{__name__}.packing").PackedLinear
+    if name in ("Rotation", "RotatedLinear"):
+        return getattr(importlib.import_module(f"{__name__}.rotation"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -22,6 +22,7 @@ lib = ctypes.CDLL(LIB_PATH)
 OK, E_ARG, E_NOT_PD, E_HIP, E_WS = 0, -1, -2, -3, -4
 CB_VALUE, CB_INDEX, CB_UP, CB_DOWN, CB_INDEX16, CB_INDEX32 = 0, 1, 2, 3, 4, 5
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2  # slk_dequantize_packed `out_dtype`, slk_packed_gemm's dtypes
+DTYPE_F64 = 3  # slk_hadamard_rows only
 MX_MAX, MX_MSE, MX_DIAG = 0, 1, 2  # slk_mx_scale_search `mode`
 ORDER_NONE, ORDER_DIAG, ORDER_ERR, ORDER_SQERR, ORDER_KEYS = 0, 1, 2, 3, 4
 ORDER_MODES = {"none": ORDER_NONE, "diag": ORDER_DIAG, "err": ORDER_ERR, "sqerr": ORDER_SQERR}
@@ -118,6 +119,7 @@ PROTOTYPES = {
         c_int,
         [P, c_int, P, c_int, c_int, c_double, c_double, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P],
     ),
+    "slk_hadamard_rows": (c_int, [P, c_int, P, c_int, c_longlong, c_int, c_int, P, c_int, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

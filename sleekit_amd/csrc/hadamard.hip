@@ -1,0 +1,269 @@
+// slk_hadamard_rows: Y = X R or X R^T, R = diag(s) blockdiag(H_block) / sqrt(block) (the contract: include/sleekit_amd.h).
+//
+// The map.  A row is cut into CHUNKS of 16 consecutive columns and a lane owns one chunk, so inside a block of `block`
+// columns element i sits in lane i / 16 (counted from the block's first lane) at register i % 16:
+//   strides 1, 2, 4, 8           registers of one lane (blocks below 16: a lane holds 16 / block whole blocks)
+//   strides 16, 32, 64, 128      lane distances 1, 2, 4, 8: DPP on the vector ALU (quad_perm; half-mirror then reversed quads;
+//                                row_ror:8)
+//   strides 256, 512             lane distances 16 and 32: v_permlane16_swap / v_permlane32_swap (gfx950), VALU as well
+//   strides 1024, 2048           the 2 or 4 waves of a block, through LDS: one exchange in which a lane reads the chunks of its
+//                                one or three partner lanes and repeats their first stage itself (the same two operands in the
+//                                same operation: the same bits)
+// Chunks are numbered through the whole matrix (row * chunks-per-row + chunk), a workgroup of 256 lanes takes 256
+// consecutive ones, in a grid that covers them all: a block's lanes are consecutive and aligned to their count because
+// chunks-per-row is a multiple of block / 16, whatever the row.  The butterfly fixes which two values meet in each addition,
+// so none of this shows in the result.
+#include "common.h"
+
+#include <math.h>
+
+namespace slk {
+
+constexpr int HD_CHUNK = 16;     // elements a lane
+constexpr int HD_THREADS = 256;  // four waves: a block of 4096
+
+// element types in memory: T is what the kernel holds them as
+template <int D> struct HdType;
+template <> struct HdType<SLK_DTYPE_F32> { typedef float T; };
+template <> struct HdType<SLK_DTYPE_BF16> { typedef unsigned short T; };
+template <> struct HdType<SLK_DTYPE_F16> { typedef _Float16 T; };
+template <> struct HdType<SLK_DTYPE_F64> { typedef double T; };
+
+__device__ __forceinline__ void hd_get(float &v, float x) { v = x; }
+__device__ __forceinline__ void hd_get(float &v, unsigned short x) { v = __uint_as_float((unsigned)x << 16); }
+__device__ __forceinline__ void hd_get(float &v, _Float16 x) { v = (float)x; }
+__device__ __forceinline__ void hd_get(double &v, double x) { v = x; }
+__device__ __forceinline__ void hd_put(float &y, float v) { y = v; }
+__device__ __forceinline__ void hd_put(unsigned short &y, float v) { y = pk_bf16(v); }
+__device__ __forceinline__ void hd_put(_Float16 &y, float v) { y = (_Float16)v; }
+__device__ __forceinline__ void hd_put(double &y, double v) { y = v; }
+
+// 16 elements as 16-byte pieces
+template <class T>
+struct alignas(16) HdPiece {
+    T e[16 / sizeof(T)];
+};
+
+// the value lane (l ^ D) holds, for a 32-bit word
+template <int D>
+__device__ __forceinline__ int hd_xor_word(int x, int lane) {
+    if constexpr (D == 1) return dpp_i<DPP_XOR1>(x);
+    else if constexpr (D == 2) return dpp_i<DPP_XOR2>(x);
+    else if constexpr (D == 4) return dpp_i<0x1B>(dpp_i<DPP_HALF_MIRROR>(x));  // (i ^ 7) ^ 3
+    else if constexpr (D == 8) return dpp_i<0x128>(x);                          // row_ror:8 of a row of 16
+    else if constexpr (D == 16) {
+        // rows 1 and 3 of the first operand change places with rows 0 and 2 of the second: [0] = rows 0 0 2 2, [1] = 1 1 3 3
+        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
+        return (int)((lane & 16) ? r[0] : r[1]);
+    } else {
+        // the upper half of the first operand changes places with the lower half of the second: [0] = lower lower, [1] = upper upper
+        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
+        return (int)((lane & 32) ? r[0] : r[1]);
+    }
+}
+template <int D>
+__device__ __forceinline__ float hd_xor(float x, int lane) { return __int_as_float(hd_xor_word<D>(__float_as_int(x), lane)); }
+template <int D>
+__device__ __forceinline__ double hd_xor(double x, int lane) {
+    const long long b = __double_as_longlong(x);
+    const unsigned lo = (unsigned)hd_xor_word<D>((int)(b & 0xffffffffLL), lane);
+    const unsigned hi = (unsigned)hd_xor_word<D>((int)(b >> 32), lane);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// one stage between lanes: the lower element takes lower + upper, the upper one lower - upper.  (Written as p + (-v) under a
+// per-lane sign mask instead of the select, an earlier form of this kernel took 162 to 210 registers instead of 64 to 113
+// and ran 8 to 14 % slower at 4096 rows: DESIGN.md section 16.)
+template <int D, class C>
+__device__ __forceinline__ void hd_lane_stage(C (&v)[HD_CHUNK], int lane) {
+    const bool upper = lane & D;
+#pragma unroll
+    for (int e = 0; e < HD_CHUNK; ++e) {
+        const C p = hd_xor<D>(v[e], lane);
+        v[e] = upper ? p - v[e] : v[e] + p;
+    }
+}
+
+// VEC: X, Y and the signs start on 16 bytes and n is a multiple of 16, so every chunk is whole and moves in 16-byte pieces;
+// otherwise element by element, the last chunk of a row cut at n (blocks below 16 only: a larger block makes n a multiple of 16).
+template <class C, class XT, class YT, bool VEC>
+__global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X, YT *Y, size_t rows, int n,
+                                                                      int lb, const float *__restrict__ signs, int transposed, C c) {
+    // (register, lane): a register's 256 values lie in consecutive banks.  Dynamic: blocks up to 1024 get none.
+    extern __shared__ __align__(16) unsigned char hd_lds[];
+    C(*xch)[HD_THREADS] = reinterpret_cast<C(*)[HD_THREADS]>(hd_lds);
+    const int cpr = (n + HD_CHUNK - 1) / HD_CHUNK;
+    const size_t total = rows * (size_t)cpr;
+    const int t = threadIdx.x, lane = t & 63;
+    const size_t g = (size_t)blockIdx.x * HD_THREADS + t;  // one trip: the grid covers every chunk
+    const bool live = g < total;
+    const size_t row = live ? g / cpr : 0;
+    const int col = live ? (int)(g - row * cpr) * HD_CHUNK : 0;
+    const int count = live ? min(HD_CHUNK, n - col) : 0;
+    C v[HD_CHUNK], s[HD_CHUNK];
+#pragma unroll
+    for (int e = 0; e < HD_CHUNK; ++e) v[e] = (C)0, s[e] = (C)1;
+    if constexpr (VEC) {
+        if (live) {
+            constexpr int PER = 16 / sizeof(XT);
+            const HdPiece<XT> *src = reinterpret_cast<const HdPiece<XT> *>(X + row * n + col);
+#pragma unroll
+            for (int p = 0; p < HD_CHUNK / PER; ++p) {
+                const HdPiece<XT> piece = src[p];
+#pragma unroll
+                for (int e = 0; e < PER; ++e) hd_get(v[p * PER + e], piece.e[e]);
+            }
+            if (signs) {
+                const HdPiece<float> *sp = reinterpret_cast<const HdPiece<float> *>(signs + col);
+#pragma unroll
+                for (int p = 0; p < HD_CHUNK / 4; ++p) {
+                    const HdPiece<float> piece = sp[p];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s[p * 4 + e] = (C)piece.e[e];
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < HD_CHUNK; ++e)
+            if (e < count) {
+                hd_get(v[e], X[row * n + col + e]);
+                if (signs) s[e] = (C)signs[col + e];
+            }
+    }
+    if (!transposed) {
+#pragma unroll
+        for (int e = 0; e < HD_CHUNK; ++e) v[e] = s[e] * v[e];
+    }
+    // strides 1 .. 8
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (lb > k) {
+            const int h = 1 << k;
+#pragma unroll
+            for (int i = 0; i < HD_CHUNK; ++i)
+                if ((i & h) == 0) {
+                    const C a = v[i], b = v[i + h];
+                    v[i] = a + b;
+                    v[i + h] = a - b;
+                }
+        }
+    }
+    // strides 16 .. 512: lanes of one wave (lb is uniform, and so is every branch here)
+    if (lb > 4) hd_lane_stage<1>(v, lane);
+    if (lb > 5) hd_lane_stage<2>(v, lane);
+    if (lb > 6) hd_lane_stage<4>(v, lane);
+    if (lb > 7) hd_lane_stage<8>(v, lane);
+    if (lb > 8) hd_lane_stage<16>(v, lane);
+    if (lb > 9) hd_lane_stage<32>(v, lane);
+    // strides 1024 and 2048: waves of one workgroup
+    if (lb > 10) {
+#pragma unroll
+        for (int e = 0; e < HD_CHUNK; ++e) xch[e][t] = v[e];
+        __syncthreads();
+        const bool up1 = t & 64, up2 = t & 128;
+#pragma unroll
+        for (int e = 0; e < HD_CHUNK; ++e) {
+            const C p = xch[e][t ^ 64];
+            const C mine = up1 ? p - v[e] : v[e] + p;
+            if (lb > 11) {
+                // the partner two waves away went through the same first stage with ITS neighbour
+                const C q = xch[e][t ^ 128], r = xch[e][t ^ 192];
+                const C theirs = up1 ? r - q : q + r;
+                v[e] = up2 ? theirs - mine : mine + theirs;
+            } else {
+                v[e] = mine;
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < HD_CHUNK; ++e) {
+        v[e] = v[e] * c;
+        if (transposed) v[e] = s[e] * v[e];
+    }
+    if constexpr (VEC) {
+        if (live) {
+            constexpr int PER = 16 / sizeof(YT);
+            HdPiece<YT> *dst = reinterpret_cast<HdPiece<YT> *>(Y + row * n + col);
+#pragma unroll
+            for (int p = 0; p < HD_CHUNK / PER; ++p) {
+                HdPiece<YT> piece;
+#pragma unroll
+                for (int e = 0; e < PER; ++e) hd_put(piece.e[e], v[p * PER + e]);
+                dst[p] = piece;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < HD_CHUNK; ++e)
+            if (e < count) hd_put(Y[row * n + col + e], v[e]);
+    }
+}
+
+template <class C, int XD, int YD>
+static void launch_hadamard(const void *X, void *Y, long long rows, int n, int lb, const float *signs, int transposed, hipStream_t s) {
+    typedef typename HdType<XD>::T XT;
+    typedef typename HdType<YD>::T YT;
+    const C c = (C)(1.0 / sqrt((double)(1 << lb)));
+    const size_t total = (size_t)rows * (size_t)((n + HD_CHUNK - 1) / HD_CHUNK);
+    const size_t need = (total + HD_THREADS - 1) / HD_THREADS;
+    const unsigned grid = (unsigned)need;  // (the entry point refuses what does not fit one grid)
+    const size_t lds = lb > 10 ? sizeof(C) * HD_CHUNK * HD_THREADS : 0;
+    const bool vec = n % HD_CHUNK == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)Y % 16 == 0 && (uintptr_t)signs % 16 == 0;
+    if (vec)
+        k_hadamard_rows<C, XT, YT, true><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), static_cast<YT *>(Y), (size_t)rows, n, lb,
+                                                                     signs, transposed, c);
+    else
+        k_hadamard_rows<C, XT, YT, false><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), static_cast<YT *>(Y), (size_t)rows, n, lb,
+                                                                      signs, transposed, c);
+}
+
+template <int XD>
+static void launch_hadamard_out(int y_dtype, const void *X, void *Y, long long rows, int n, int lb, const float *signs, int transposed,
+                                hipStream_t s) {
+    if (y_dtype == SLK_DTYPE_BF16)
+        launch_hadamard<float, XD, SLK_DTYPE_BF16>(X, Y, rows, n, lb, signs, transposed, s);
+    else if (y_dtype == SLK_DTYPE_F16)
+        launch_hadamard<float, XD, SLK_DTYPE_F16>(X, Y, rows, n, lb, signs, transposed, s);
+    else
+        launch_hadamard<float, XD, SLK_DTYPE_F32>(X, Y, rows, n, lb, signs, transposed, s);
+}
+
+static inline double hd_bytes(int dtype) { return dtype == SLK_DTYPE_F64 ? 8.0 : dtype == SLK_DTYPE_F32 ? 4.0 : 2.0; }
+
+}  // namespace slk
+
+using namespace slk;
+
+extern "C" {
+
+int slk_hadamard_rows(const void *X, int x_dtype, void *Y, int y_dtype, long long rows, int n, int block, const float *signs,
+                      int transposed, slk_stream_t stream) {
+    SLK_REQUIRE(block >= 2 && block <= 4096 && (block & (block - 1)) == 0, "block must be a power of two in 2..4096 (got %d)", block);
+    SLK_REQUIRE(rows > 0 && n > 0, "bad shape (rows = %lld, n = %d)", rows, n);
+    SLK_REQUIRE(n % block == 0, "block %d does not divide n = %d", block, n);
+    SLK_REQUIRE(X && Y, "null pointer");
+    SLK_REQUIRE(x_dtype >= SLK_DTYPE_F32 && x_dtype <= SLK_DTYPE_F64, "unknown x_dtype %d", x_dtype);
+    SLK_REQUIRE(y_dtype >= SLK_DTYPE_F32 && y_dtype <= SLK_DTYPE_F64, "unknown y_dtype %d", y_dtype);
+    SLK_REQUIRE((x_dtype == SLK_DTYPE_F64) == (y_dtype == SLK_DTYPE_F64), "float64 goes to float64 and nothing else does (x_dtype %d, y_dtype %d)",
+                x_dtype, y_dtype);
+    SLK_REQUIRE(rows <= (long long)((~(size_t)0 >> 1) / (size_t)n / 8), "rows * n * 8 must fit the address space (rows = %lld, n = %d)", rows, n);
+    SLK_REQUIRE((unsigned long long)rows * (unsigned long long)((n + HD_CHUNK - 1) / HD_CHUNK) <= 0x7fffffffULL * HD_THREADS,
+                "rows * ceil(n / 16) must not pass 2^31 - 1 workgroups of 256 chunks (rows = %lld, n = %d)", rows, n);
+    hipStream_t s = as_stream(stream);
+    int lb = 0;
+    while ((1 << lb) < block) ++lb;
+    const double elems = (double)rows * n;
+    const double flops = elems * (lb + 1), bytes = elems * (hd_bytes(x_dtype) + hd_bytes(y_dtype));
+    if (x_dtype == SLK_DTYPE_F64)
+        SLK_RUN("hadamard_rows", flops, bytes, s, (launch_hadamard<double, SLK_DTYPE_F64, SLK_DTYPE_F64>(X, Y, rows, n, lb, signs, transposed, s)));
+    else if (x_dtype == SLK_DTYPE_BF16)
+        SLK_RUN("hadamard_rows", flops, bytes, s, launch_hadamard_out<SLK_DTYPE_BF16>(y_dtype, X, Y, rows, n, lb, signs, transposed, s));
+    else if (x_dtype == SLK_DTYPE_F16)
+        SLK_RUN("hadamard_rows", flops, bytes, s, launch_hadamard_out<SLK_DTYPE_F16>(y_dtype, X, Y, rows, n, lb, signs, transposed, s));
+    else
+        SLK_RUN("hadamard_rows", flops, bytes, s, launch_hadamard_out<SLK_DTYPE_F32>(y_dtype, X, Y, rows, n, lb, signs, transposed, s));
+    return SLK_OK;
+}
+
+}  // extern "C"

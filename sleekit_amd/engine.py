@@ -75,12 +75,13 @@ def require_uniform(quantizer):
 class LayerResult:
     """Device tensors produced for one layer."""
 
-    __slots__ = ("Q", "idx", "order", "U", "info", "E", "ls_trace", "ls_error", "loop_error", "S", "O", "codes", "scales")
+    __slots__ = ("Q", "idx", "order", "U", "info", "E", "ls_trace", "ls_error", "loop_error", "S", "O", "codes", "scales", "rotation")
 
     def __init__(self):
         self.Q = self.idx = self.order = self.U = self.info = self.E = self.ls_trace = self.ls_error = self.loop_error = None
         self.S = self.O = None  # group scales and offsets (Sleekit.quantize with offsets)
         self.codes = self.scales = None  # the MXFP4 packed form (Sleekit.quantize_mxfp4)
+        self.rotation = None  # the Rotation whose basis Q, idx and the scales are in (Sleekit.quantize*(..., rotation=))
 
 
 def factorize(H, n, damp, mode, miss=None, keep=None, lookahead=False):

@@ -68,7 +68,7 @@ def _preset_method(name):
 class Sleekit:
     """Running statistics of one layer's inputs and its quantization; interface of the reference's class."""
 
-    def __init__(self, layer):
+    def __init__(self, layer, rotation=None):
         if not isinstance(layer, _SUPPORTED):
             raise ValueError(f"Unsupported layer type {type(layer)}")
         if not layer.weight.is_cuda:
@@ -78,6 +78,8 @@ class Sleekit:
         self.count = 0
         self.mean = torch.zeros(features, dtype=torch.float32, device=self.device)
         self.hessian = torch.zeros((features, features), dtype=torch.float32, device=self.device)
+        # the Rotation quantize_mxfp4 uses (None: none); quantize and quantize_packed take theirs as a keyword and ignore this
+        self.rotation = self._check_rotation(rotation)
 
     @property
     def device(self):
@@ -118,19 +120,38 @@ class Sleekit:
     quantize_sleekit_light = _preset_method("sleekit_light")
     quantize_sleekit_heavy = _preset_method("sleekit_heavy")
 
-    def _weight_and_hessian(self, bias_correction):
+    def _check_rotation(self, rotation):
+        """`rotation` (None: none); a ValueError unless it is a Rotation over the layer's features."""
+        if rotation is None:
+            return None
+        from .rotation import Rotation
+
+        if not isinstance(rotation, Rotation):
+            raise ValueError(f"rotation must be a sleekit_amd.Rotation (got {type(rotation).__name__})")
+        if rotation.n != self.mean.numel():
+            raise ValueError(f"the rotation has {rotation.n} features but the layer has {self.mean.numel()}")
+        return rotation
+
+    def _weight_and_hessian(self, bias_correction, rotation=None):
         """The weight as an (out, features) float32 matrix and the Hessian to quantize against: H - mean mean^T under
-        bias_correction (a copy), else H itself."""
+        bias_correction (a copy), else H itself.  With a rotation R, the pair in the rotated basis: (W R, R^T H R), the mean
+        stripped first."""
         weight = self.layer.weight.data.flatten(1).float().contiguous()
         H = self.hessian
         if bias_correction:
             centred = torch.empty_like(H)
             _lib.check(_lib.lib.slk_hessian_strip_mean(dev.ptr(H), dev.ptr(self.mean), H.shape[0], dev.ptr(centred), dev.stream_handle()))
             H = centred
+        if rotation is not None:
+            return rotation.apply(weight), rotation.hessian(H)
         return weight, H
 
-    def _store(self, result, weight, bias_correction):
-        """result.Q becomes the layer's weight; under bias_correction the expected output shift moves into the bias."""
+    def _store(self, result, weight, bias_correction, rotation=None):
+        """result.Q becomes the layer's weight; under bias_correction the expected output shift moves into the bias.
+        With a rotation R the layer's weight is Q R^T -- on unrotated inputs the function the rotated layer computes on
+        rotated ones -- and the shift is taken in the original basis; Q, idx and the scales stay in the rotated one."""
+        if rotation is not None:
+            return self._store_rotated(result, bias_correction, rotation)
         target = self.layer.weight
         target.data = result.Q.reshape(target.shape).to(target.dtype)
         if bias_correction:
@@ -138,8 +159,19 @@ class Sleekit:
             self.layer.bias.data += shift.to(self.layer.bias.dtype)
         return result
 
+    def _store_rotated(self, result, bias_correction, rotation):
+        target = self.layer.weight
+        weight = target.data.flatten(1).float().contiguous()
+        back = rotation.apply_t(result.Q)
+        target.data = back.reshape(target.shape).to(target.dtype)
+        if bias_correction:
+            shift = ((weight - back) * self.mean).sum(dim=1)
+            self.layer.bias.data += shift.to(self.layer.bias.dtype)
+        result.rotation = rotation
+        return result
+
     def quantize(self, nbits, scaling_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0,
-                 grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, offsets=None, group_size=None):
+                 grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, rotation=None, offsets=None, group_size=None):
         """The layer's weight replaced by its `nbits` quantization, in place (statistics.py:146-190).
 
         bias_correction: quantize against H - mean mean^T and move the expected output shift into the bias.
@@ -150,20 +182,25 @@ class Sleekit:
         offsets (optional, with group_size): an offset per row and group beside the scale (the asymmetric group quantizer
         of sleekit_amd.groups): "mid" for each group's midpoint, or an (out, features / group_size) array used as given;
         the scale search then runs on the centred weight.  The result carries S and O (result.S, result.O) beside idx.
+        rotation (optional, a sleekit_amd.Rotation R over the layer's features): everything above runs on (W R, R^T H R); the
+        layer's weight becomes Q R^T, while result.Q, idx and the scales stay in the rotated basis and result.rotation is R
+        (what RotatedLinear.from_result wraps the stored layer in).  A `scale` given is a scale of W R.  None: no
+        rotation (the object's `rotation` attribute is quantize_mxfp4's alone).
         """
         if offsets is not None and group_size is None:
             raise ValueError("offsets need group_size: an offset per row and group of input features")
         return self._quantize(False, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                              max_factor, scale, group_size, offsets)
+                              max_factor, scale, group_size, offsets, rotation)
 
     def _quantize(self, keep_scales, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                  max_factor, scale, group_size, offsets):
+                  max_factor, scale, group_size, offsets, rotation=None):
         """`quantize`; keep_scales (quantize_packed): the result carries the scales it was made with on every path."""
+        rotation = self._check_rotation(rotation)
         if group_size is not None:
             return self._quantize_grouped(nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                                          max_factor, scale, group_size, offsets, keep_scales)
+                                          max_factor, scale, group_size, offsets, keep_scales, rotation)
         codebook = UniformCodebook(2**nbits, -1, 1)
-        weight, H = self._weight_and_hessian(bias_correction)
+        weight, H = self._weight_and_hessian(bias_correction, rotation)
         if scale is None:
             scale = compute_scaling(weight, codebook, H=H, mode=scaling_mode, grid_size=grid_size, min_factor=min_factor,
                                     max_factor=max_factor)
@@ -171,10 +208,10 @@ class Sleekit:
         result = engine.quantize_layer(weight, H, codebook, scale, order_mode, damp, nb_ls_moves)
         if keep_scales:
             result.S = scale
-        return self._store(result, weight, bias_correction)
+        return self._store(result, weight, bias_correction, rotation)
 
     def _quantize_grouped(self, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                          max_factor, scale, group_size, offsets=None, keep_scales=False):
+                          max_factor, scale, group_size, offsets=None, keep_scales=False, rotation=None):
         from . import groups
 
         if nb_ls_moves > 0:
@@ -182,7 +219,7 @@ class Sleekit:
         if scaling_mode == "obq":
             raise NotImplementedError('the "obq" scaling mode is not supported with group scales')
         codebook = UniformCodebook(2**nbits, -1, 1)
-        weight, H = self._weight_and_hessian(bias_correction)
+        weight, H = self._weight_and_hessian(bias_correction, rotation)
         search = dict(H=H, mode=scaling_mode, grid_size=grid_size, min_factor=min_factor, max_factor=max_factor)
         if isinstance(offsets, str):
             if offsets != "mid":
@@ -202,29 +239,32 @@ class Sleekit:
             result.S, result.O = scale, offsets
         elif keep_scales:
             result.S = scale
-        return self._store(result, weight, bias_correction)
+        return self._store(result, weight, bias_correction, rotation)
 
     def quantize_packed(self, nbits, scaling_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0,
-                        grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, offsets=None, group_size=None):
+                        grid_size=100, min_factor=0.05, max_factor=1.0, scale=None, rotation=None, offsets=None, group_size=None):
         """`quantize` with the same arguments and the same result, which also carries its scales on EVERY path: result.S is
         (out,) per row or (out, features / group_size) grouped, result.O the group offsets when there are any -- what
         packing.PackedLinear.from_result packs beside result.idx.  (`quantize` keeps the scales of the offset path only.)"""
         if offsets is not None and group_size is None:
             raise ValueError("offsets need group_size: an offset per row and group of input features")
         return self._quantize(True, nbits, scaling_mode, order_mode, bias_correction, damp, nb_ls_moves, grid_size, min_factor,
-                              max_factor, scale, group_size, offsets)
+                              max_factor, scale, group_size, offsets, rotation)
 
     def quantize_mxfp4(self, scale_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0):
         """The layer's weight replaced by its MXFP4 quantization, in place (sleekit_amd.mx): power-of-two scales per block of
         32 input features (scale_mode "max", "mse" or "diag"), FP4 E2M1 elements, nb_ls_moves of the local search after the
         loop.  bias_correction as in `quantize`.  The result (the grouped loop's) carries S, and the packed form as
-        result.codes (uint8 (out, features / 2)) and result.scales (E8M0 bytes (out, features / 32))."""
+        result.codes (uint8 (out, features / 2)) and result.scales (E8M0 bytes (out, features / 32)).  The object's rotation
+        (`Sleekit(layer, rotation=R)`, or `st.rotation = R`; `st.rotation = None` turns it off) applies as in `quantize`:
+        the blocks of 32 are then blocks of rotated features.  (This method's parameter list is kept as it was: the rotation is not a keyword here.)"""
         from . import mx
 
-        weight, H = self._weight_and_hessian(bias_correction)
+        rotation = self._check_rotation(self.rotation)
+        weight, H = self._weight_and_hessian(bias_correction, rotation)
         packed, result = mx.quantize_layer_mxfp4(weight, H, order_mode, damp, scale_mode, nb_ls_moves)
         result.S, result.codes, result.scales = packed.S, packed.codes, packed.scales
-        return self._store(result, weight, bias_correction)
+        return self._store(result, weight, bias_correction, rotation)
 
     def free(self):
         self.layer = self.mean = self.hessian = None
