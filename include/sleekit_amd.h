@@ -96,7 +96,9 @@ const char *slk_last_error(void);
  * switch; one call at a time asks for it through slk_chol_inverse_upper_lookahead instead), "window_rows" (16 or 32 rows per
  * window workgroup, forced; 0 = 32, or 16 under SLK_LOOP_LATENCY), "panel_split" (the factorisation's panel step: 1 = two launches, diagonal tile then
  * the rest, 2 = one launch in which every workgroup below the diagonal tile repeats its pivot chain; 0 = two for batches and from 8192
- * columns up, one otherwise and always in the look-ahead form) (case-insensitive,
+ * columns up, one otherwise and always in the look-ahead form), "chain_carries_below" (the chain's launch also makes the rows below the diagonal block,
+ * wherever the cap on waiting workgroups allows and the call does not look ahead: 1 = yes, 2 = never, 0 = the rule; "rows_below_wide" 1 | 2 and
+ * "panel_split" 1 | 2 force the launches they name) (case-insensitive,
  * an "SLK_" prefix is accepted).  Initial values are read ONCE from the environment (SLK_NO_WINDOW2=1 ...);
  * afterwards only these calls change them.  Process-wide, thread-safe; no reference counterpart.              */
 int slk_set_option(const char *name, int value);

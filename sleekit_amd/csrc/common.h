@@ -87,6 +87,7 @@ enum Opt {
     OPT_PANEL_SPLIT,           // factorisation: 0 / 3: an outer block's panels as a chain of workgroups in one launch; 1 / 2: the panel kernel, two launches / one per panel
     OPT_ROWS_BELOW_WIDE,       // factorisation: the rows below a diagonal block 64 rows per workgroup (1) or 16 (2) whatever the batch (0: 64 from 1024 strips per launch up)
     OPT_NO_LOOP_ERROR,         // layer error: sleekit_amd's callers never take the error the loop carries (slk_gptq_quantize_batch_error); the product instead
+    OPT_CHAIN_CARRIES_BELOW,   // factorisation: the rows below a diagonal block in the chain's own launch wherever the cap on waiting workgroups allows (1), never (2), by the rule (0)
     OPT_COUNT
 };
 int opt(Opt o);

@@ -525,6 +525,8 @@ __global__ __launch_bounds__(256) void k_panel_below(double *__restrict__ A, int
 //   is on the critical path: no launch gap, no staging of anything but X, no update of older panels.
 //   The rows BELOW the diagonal block wait for nobody: one wide launch afterwards (k_chol_rows_below) makes them all,
 //   16 rows per workgroup, the row strip's own L tiles resident in LDS.  Then the outer update, as before.
+//   (Since DESIGN 8.10, wherever few enough workgroups would wait at once, they ride in the chain's own launch instead,
+//   64 rows per workgroup behind the same flags: k_chol_chain_below, and the block is chain -> outer update.)
 //   Per 4096-column factor: 8 x (chain + rows below + outer update) = 22 launches instead of 72; the chain occupies
 //   nb CUs instead of up to 64 (171 at 11008 columns).
 //
@@ -545,6 +547,10 @@ constexpr bool slk_chain_addressable(int ld) { return (size_t)ld * (size_t)ld * 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 constexpr int AUX_SC1 = 16;
+// k_chol_chain_below: most workgroups (chain rows + rows below, all matrices) of one launch -- see the launch for the argument
+constexpr int CHAIN_CARRY_CAP = 80;
+// "chain_carries_below" = 0: on (true) or off (false) wherever the cap allows -- set by the measurement in DESIGN 8.10
+constexpr bool CHAIN_CARRY_BY_RULE = true;
 
 struct GBuf {  // a matrix as a buffer resource: 16-byte accesses at 32-bit byte offsets, write-through / L1-bypassing on demand
     __amdgpu_buffer_rsrc_t rs;
@@ -727,15 +733,23 @@ __device__ __forceinline__ int diag_tile_factor(PanelSmem &sm, int lane, int wav
 // makes L(r, q) for all nb panels.  The wide form of k_chol_rows_below -- 64 rows per workgroup instead of 16: a quarter of
 // the workgroups, each step 64 MFMAs a wave for two staged operands instead of 16 for one -- for factorisations that share
 // the chip with other layers' kernels (what it costs the chip counts there, not how long a launch lasts).
-template <bool BELOW>
-__global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, int ld, int K0, int nb, double *__restrict__ Xall,
-                                                    int *__restrict__ info, int *__restrict__ flags_all, int dbg) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    PanelSmem &sm = *reinterpret_cast<PanelSmem *>(smem_raw);
+// CHAIN_AND_BELOW: both in ONE grid of nb + below_tiles workgroups per matrix -- the rows-below launch rides in
+// the chain's.  Workgroups x < nb are the chain's rows, unchanged; a workgroup x >= nb owns tile row x below the diagonal
+// block and walks all nb panels as BELOW_ROWS does, but beside the chain instead of behind it: it WAITS as a chain row does,
+// on rowdone[q + 1] before each L(q + 1, s) and on xready[q] before the two parts of X_q, reads every handed-off tile (and
+// its own earlier stores) with sc1 loads, and publishes nothing.  Its work per panel (103 us / 8) runs under the chain's
+// latency per panel (136 us / 8).  The role is uniform in the workgroup; the arithmetic of a row is BELOW_ROWS': same U bit
+// for bit.  A waiting workgroup holds a CU: the host launches this form only under CHAIN_CARRY_CAP (there: why it ends).
+enum ChainForm { CHAIN_ROWS, BELOW_ROWS, CHAIN_AND_BELOW };
+template <int FORM>
+__device__ __forceinline__ void chol_chain_walk(PanelSmem &sm, double *__restrict__ Aall, int ld, int K0, int nb, double *__restrict__ Xall,
+                                                int *__restrict__ info, int *__restrict__ flags_all, int dbg) {
+    const bool BELOW = FORM == BELOW_ROWS || (FORM == CHAIN_AND_BELOW && (int)blockIdx.x >= nb);  // (a constant but in the carrying form)
+    constexpr bool WAITS = FORM != BELOW_ROWS;
     // roles of the four images while this workgroup walks its row:  t: L(q', s) operand   x: X_q
     //                                                                a21: C_q (complete, waits for X_q)   lb: L(r, s) operand, L(r, q)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int r = BELOW ? nb + (int)blockIdx.x : (int)blockIdx.x, nt = ld / PANEL, p0 = K0 / PANEL;
+    const int r = FORM == BELOW_ROWS ? nb + (int)blockIdx.x : (int)blockIdx.x, nt = ld / PANEL, p0 = K0 / PANEL;
     const int rq = BELOW ? nb : r;  // panels this row walks
     const size_t mat = (size_t)ld * ld;
     double *A = Aall + (size_t)blockIdx.z * mat;
@@ -760,7 +774,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
 
     // T_r, blocks on and below the diagonal, in registers (D layout): the i-th such block belongs to wave i & 3 (block_syrk's split)
     double4_t tp[3];
-    if constexpr (!BELOW) {
+    if (!BELOW) {
         int i = 0;
 #pragma unroll
         for (int rb = 0; rb < 4; ++rb)
@@ -789,7 +803,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
 
     // L(r, 0 .. count-1) are in memory: this workgroup's own later loads may see them; the other rows of the chain are told
     auto row_done = [&](int count) {
-        if constexpr (BELOW) {
+        if (BELOW) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         } else {
@@ -812,7 +826,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
                     for (int j = 0; j < 4; ++j)
                         cn[cb][j] = A[(size_t)(row0 + 16 * wave + (lane >> 4) + 4 * j) * ld + K0 + PANEL * (q + 1) + 16 * cb + (lane & 15)];
                 if (q > 0) {
-                    if (!BELOW) alive = alive && flag_wait(&rowdone[p0 + q + 1], 1);
+                    if (WAITS) alive = alive && flag_wait(&rowdone[p0 + q + 1], 1);
                     tile_fetch<AUX_SC1>(ra, ga, elem(r, 0), ld);
                     tile_fetch<AUX_SC1>(rb_, ga, elem(q + 1, 0), ld);
                 }
@@ -822,7 +836,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
                     tile_stash(sm.t, rb_);
                     __syncthreads();
                     if (s + 1 < q) {  // the next pair is in flight during the products
-                        if (!BELOW && alive) alive = flag_wait(&rowdone[p0 + q + 1], s + 2);
+                        if (WAITS && alive) alive = flag_wait(&rowdone[p0 + q + 1], s + 2);
                         tile_fetch<AUX_SC1>(ra, ga, elem(r, s + 1), ld);
                         tile_fetch<AUX_SC1>(rb_, ga, elem(q + 1, s + 1), ld);
                     }
@@ -856,7 +870,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
                             tacc[i >> 2] = acc;
                         }
             };
-            if (!BELOW && alive) alive = flag_wait(&xready[p0 + q], 1);
+            if (WAITS && alive) alive = flag_wait(&xready[p0 + q], 1);
             tile_fetch<AUX_SC1, 0, 4>(ra, gx, elem(q, q), ld);
             __syncthreads();
             tile_stash<0, 4>(sm.x, ra);
@@ -865,7 +879,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
             l_block(1);
             __syncthreads();
             if (!BELOW) t_terms(0, 2);
-            if (!BELOW && alive) alive = flag_wait(&xready[p0 + q], 2);
+            if (WAITS && alive) alive = flag_wait(&xready[p0 + q], 2);
             if (last) lap(-1);  // the clock of the critical path starts when the LAST part of X_{r-1} is seen
             tile_fetch<AUX_SC1, 4, 8>(ra, gx, elem(q, q), ld);
             tile_stash<4, 8>(sm.x, ra);  // (rows 32 .. 63 of the image: nobody has read them since the barriers above)
@@ -877,7 +891,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
             if (last) lap(1);  // the last two column blocks of L(r, r-1)
             // L(r, q) to memory (write-through); the last terms of T_r's update meanwhile
             tile_store_from_lds<AUX_SC1>(ga, elem(r, q), ld, sm.lb);
-            if constexpr (!BELOW) {
+            if (!BELOW) {
                 t_terms(2, 4);
                 int i = 0;
 #pragma unroll
@@ -894,7 +908,7 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
             }
             if (more) {
                 // (3) the last update of C_{q+1}: panel q's, with the L(r, q) just made (in lb) and L(q+1, q) from its owner
-                if (!BELOW && alive) alive = flag_wait(&rowdone[p0 + q + 1], q + 1);
+                if (WAITS && alive) alive = flag_wait(&rowdone[p0 + q + 1], q + 1);
                 tile_fetch<AUX_SC1>(rb_, ga, elem(q + 1, q), ld);
                 tile_stash(sm.t, rb_);  // (t's readers finished before the barriers of (2))
                 row_done(q + 1);  // (its barrier also closes the stash)
@@ -921,7 +935,11 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
         for (int e = t; e < PANEL * PANEL; e += 256) sm.x[e >> 6][e & 63] = 0.0;
         __syncthreads();
     }
-    if constexpr (BELOW) return;
+    if (BELOW) {
+        // (a row below has no turn; one that gave up waiting says so as a chain row does)
+        if (WAITS && !alive && t == 0) __hip_atomic_store(info, INFO_HANDOFF_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
     // ---- the turn: factor, invert, publish
     lap(4);  // T_r into its image
     // (the early publication: waves 1 and 2 store a row block of X each during the last strip; each drains its own stores, and the
@@ -956,6 +974,19 @@ __global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, i
     flag_publish(&xready[p0 + r], 2);
     lap(6);  // X_r's last row block stored, drained, published
     if (timing && lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&g_panel_cycles[15]), 1ull);
+}
+
+template <bool BELOW>
+__global__ __launch_bounds__(256) void k_chol_chain(double *__restrict__ Aall, int ld, int K0, int nb, double *__restrict__ Xall,
+                                                    int *__restrict__ info, int *__restrict__ flags_all, int dbg) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    chol_chain_walk<BELOW ? BELOW_ROWS : CHAIN_ROWS>(*reinterpret_cast<PanelSmem *>(smem_raw), Aall, ld, K0, nb, Xall, info, flags_all, dbg);
+}
+// grid: (nb + below_tiles, 1, batch)
+__global__ __launch_bounds__(256) void k_chol_chain_below(double *__restrict__ Aall, int ld, int K0, int nb, double *__restrict__ Xall,
+                                                          int *__restrict__ info, int *__restrict__ flags_all, int dbg) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    chol_chain_walk<CHAIN_AND_BELOW>(*reinterpret_cast<PanelSmem *>(smem_raw), Aall, ld, K0, nb, Xall, info, flags_all, dbg);
 }
 
 // The rows below an outer block's diagonal block, after k_chol_chain: for every 16-row strip, panel by panel (left-looking,
@@ -1198,6 +1229,7 @@ static int chol_inverse_impl(double *A, int batch, int n, double *U, int *info, 
     if (chain) {
         SLK_LDS_OPT_IN(k_chol_chain<false>, sizeof(PanelSmem));
         SLK_LDS_OPT_IN(k_chol_chain<true>, sizeof(PanelSmem));
+        SLK_LDS_OPT_IN(k_chol_chain_below, sizeof(PanelSmem));
         SLK_LDS_OPT_IN(k_chol_rows_below, sizeof(RowsBelowSmem));
     }
     // The inverse, level by level: level `lvl` merges the inverted halves of nodes of 2 lvl tiles (k_trtri_level).  A node can
@@ -1249,10 +1281,31 @@ static int chol_inverse_impl(double *A, int batch, int n, double *U, int *info, 
     for (int K0 = 0; K0 < ld; K0 += OUTER) {
         const int K1 = K0 + OUTER < ld ? K0 + OUTER : ld;
         if (chain) {
-            const int nb = (K1 - K0) / PANEL, below_tiles = (ld - K1) / PANEL;
+            const int nb = (K1 - K0) / PANEL;
+            int below_tiles = (ld - K1) / PANEL;
             const double e = 64.0 * nb;
-            SLK_RUN_W("chol_chain", Bd * e * e * e / 3.0, Bd * 12.0 * e * e, nb * batch, s,
-                      k_chol_chain<false><<<dim3(nb, 1, B), 256, sizeof(PanelSmem), s>>>(A, ld, K0, nb, X, info, flags, opt(OPT_WIN_DBG) & 8));
+            // The rows below ride in the chain's launch ("chain_carries_below"): as a launch of their own behind the
+            // chain they cost every factor stream 45 us alone and 121 us in the timed run, seven times per 4096-column factor,
+            // and the loop stream whatever shares its queue; their 103 us of work per workgroup fit under the chain's 136.
+            // A waiting workgroup holds a CU, so: the workgroups of a launch go round the 8 XCDs and each XCD starts its own in
+            // order; the first workgroup of a launch that has not ended waits for nobody that has not ended, and on its XCD
+            // every later workgroup of its launch stands behind it.  It can be kept from a CU only by an XCD whose 32 CUs all
+            // hold waiting workgroups of OTHER launches.  Under the cap a launch puts at most 10 on an XCD, and no more than
+            // four launches run at once on the four hardware queues this project runs with: 3 x 10 < 32.  (With more queues
+            // and five such launches at once the argument fails; the waits are bounded and the status word would say so.)
+            // Not in the look-ahead route: there the rows below wait for the helper stream's event and the chain must not.
+            // rows_below_wide = 1 | 2 force the two launches (they name the second one's kernel), panel_split = 3 does not.
+            const int cc = opt(OPT_CHAIN_CARRIES_BELOW);
+            const bool carry = below_tiles > 0 && !lookahead && opt(OPT_ROWS_BELOW_WIDE) == 0 && (nb + below_tiles) * batch <= CHAIN_CARRY_CAP &&
+                               (cc == 1 || (cc == 0 && CHAIN_CARRY_BY_RULE));
+            if (carry) {
+                SLK_RUN_W("chol_chain", Bd * (e * e * e / 3.0 + 64.0 * below_tiles * e * e), Bd * (12.0 * e * e + 16.0 * 64 * below_tiles * e + 4.0 * e * e),
+                          (nb + below_tiles) * batch, s,
+                          k_chol_chain_below<<<dim3(nb + below_tiles, 1, B), 256, sizeof(PanelSmem), s>>>(A, ld, K0, nb, X, info, flags, opt(OPT_WIN_DBG) & 8));
+                below_tiles = 0;  // (nothing left for a second launch)
+            } else
+                SLK_RUN_W("chol_chain", Bd * e * e * e / 3.0, Bd * 12.0 * e * e, nb * batch, s,
+                          k_chol_chain<false><<<dim3(nb, 1, B), 256, sizeof(PanelSmem), s>>>(A, ld, K0, nb, X, info, flags, opt(OPT_WIN_DBG) & 8));
             if (below_tiles > 0 && forked >= 0) {
                 // look-ahead: the rows below read tiles that the REST of the previous block's outer update (helper stream)
                 // writes; the chain above did not -- it ran beside it
@@ -1263,7 +1316,8 @@ static int chol_inverse_impl(double *A, int batch, int n, double *U, int *info, 
             // "rows_below_wide" = 1, 64 rows per workgroup (k_chol_chain<true>: 103 us, a quarter of the workgroups: 0.6 of the
             // chip time).  Measured on whole streams, wide against narrow: headline 5257 / 5272 Mweights/s, one rank of 8
             // 3.66 / 3.61 ms per step, BLOOM-560M 5139 / 5084 -- nothing in it, and a single factorisation is 0.4 ms longer:
-            // narrow stays.
+            // narrow stays.  (The wide form lost as a LAUNCH, 58 us longer behind the chain; beside the chain, in its grid, it
+            // is the form the carrying launch above uses.)
             // ... EXCEPT for chains of several wide factorisations (OPT-350M / BLOOM-560M's 1024 x 4096 layers go six to eight
             // to a chain): 4 x 56 x 8 strips are seven rounds of the chip at 45 us, the 64-row form under two at 103.
             const int rw = opt(OPT_ROWS_BELOW_WIDE);
