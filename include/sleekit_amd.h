@@ -86,7 +86,8 @@ typedef void *slk_stream_t;
  * slk_unpack_indices and slk_dequantize_packed, then slk_gptq_quantize_batch_error (the loop that carries the layer error)
  * and the option "no_loop_error", then slk_gptq_quantize_layers (the same loop over layers that are not one stack: per-layer
  * pointers), then slk_packed_gemm (a linear layer computed from the packed indices; an addition within 8, nothing existing
- * changed), then slk_hadamard_rows (the block Hadamard rotation of sleekit_amd/rotation.py; likewise).   */
+ * changed), then slk_hadamard_rows (the block Hadamard rotation of sleekit_amd/rotation.py; likewise), then MXFP4
+ * activations: slk_mx_quantize_act4, slk_mx_gemm_a4 and slk_mx_rotate_quantize_act (likewise).   */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -533,6 +534,39 @@ int slk_packed_gemm(const void *X, int x_dtype, const uint32_t *words, int bits,
 #define SLK_DTYPE_F64 3 /* slk_hadamard_rows only */
 int slk_hadamard_rows(const void *X, int x_dtype, void *Y, int y_dtype, long long rows, int n, int block,
                       const float *signs, int transposed, slk_stream_t stream);
+
+/* MXFP4 activations: W4A4 on the block-scaled MFMA (both operands E2M1: twice the E4M3 rate, half the activation bytes).
+ * X is M x K row-major, K % 32 == 0, float32, bfloat16 or float16.
+ *   - a_scales: uint8 M x K / 32, E8M0: the MXFP8 rule above with 6 in place of 448.  Per block, b0 = max(amax / 6, 1e-16)
+ *     in float32, the scale s the smallest power of two >= b0, the byte its exponent + 127.  A block of zeros gives byte 74.
+ *     The scale does not saturate.
+ *   - elements: x / s (exact) rounded to nearest on the E2M1 grid 0, .5, 1, 1.5, 2, 3, 4, 6, ties to the even code
+ *     (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), magnitudes clamped at 6; code = sign << 3 |
+ *     magnitude index.  A zero magnitude is written as 0x0, never 0x8.
+ *   - a_codes: uint8 M x K / 2, the even k in the low nibble: the weights' own layout, so slk_mx_dequantize reads it.
+ *   Known answers: a block whose amax is 6.0 has byte 127 and its elements 6, -0.3, 0.75, 2.5 the codes 7 9 2 4; amax 1.0
+ *   gives byte 125 (s = 0.25) and 1.0, -1.0, 0.3, 0.0625 the codes 6 e 2 0.
+ * slk_mx_quantize_act4: X -> a_codes, a_scales.  flag[0] = 1 (DEVICE int, zeroed by the call, required) if X holds a NaN or
+ *   an infinity; the outputs are then not meaningful.  Arguments and refusals as slk_mx_quantize_act.
+ * slk_mx_gemm_a4: slk_mx_gemm with such activations (a_codes M x K / 2): the same contract -- exact products, float32 sums
+ *   inside the MFMA over K in a fixed order, no atomics, a repeated call gives the same bits, any M, N >= 1 -- and the
+ *   same refusals.
+ * slk_mx_rotate_quantize_act: the rotation of slk_hadamard_rows fused into the quantizer.  a_codes, a_scales and flag are,
+ *   bit for bit, those of slk_hadamard_rows(X -> float32 Y, transposed = 0) followed by slk_mx_quantize_act (fmt
+ *   SLK_MX_ACT_FP8; a_codes rows x n) or slk_mx_quantize_act4 (SLK_MX_ACT_FP4; rows x n / 2) on Y: steps 1 to 3 of the
+ *   transform's contract unchanged, no step-4 rounding, then the quantizer on the float32 value.  Y is never written: the
+ *   call reads X and writes the codes.  block: a power of two in 2 .. 4096 dividing n; n % 32 == 0; signs n float32 or NULL.
+ *   SLK_E_ARG, before any launch, slk_last_error() naming the offender: such a block or n, rows < 1, a NULL X, a_codes,
+ *   a_scales or flag, an unknown x_dtype (float64 included) or fmt, X, signs or a_codes off 16-byte alignment, the grid
+ *   limit of slk_hadamard_rows. */
+#define SLK_MX_ACT_FP8 0
+#define SLK_MX_ACT_FP4 1
+int slk_mx_quantize_act4(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag,
+                         slk_stream_t stream);
+int slk_mx_gemm_a4(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                   const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream);
+int slk_mx_rotate_quantize_act(const void *X, int x_dtype, long long rows, int n, int block, const float *signs, int fmt,
+                               uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -1,4 +1,4 @@
-// slk_hadamard_rows: Y = X R or X R^T, R = diag(s) blockdiag(H_block) / sqrt(block) (the contract: include/sleekit_amd.h).
+// slk_hadamard_rows (and slk_mx_rotate_quantize_act, the same butterflies ending in the MX quantizer): Y = X R or X R^T, R = diag(s) blockdiag(H_block) / sqrt(block) (the contract: include/sleekit_amd.h).
 //
 // The map.  A row is cut into CHUNKS of 16 consecutive columns and a lane owns one chunk, so inside a block of `block`
 // columns element i sits in lane i / 16 (counted from the block's first lane) at register i % 16:
@@ -14,6 +14,7 @@
 // chunks-per-row is a multiple of block / 16, whatever the row.  The butterfly fixes which two values meet in each addition,
 // so none of this shows in the result.
 #include "common.h"
+#include "mxquant.h"
 
 #include <math.h>
 
@@ -84,29 +85,36 @@ __device__ __forceinline__ void hd_lane_stage(C (&v)[HD_CHUNK], int lane) {
     }
 }
 
-// VEC: X, Y and the signs start on 16 bytes and n is a multiple of 16, so every chunk is whole and moves in 16-byte pieces;
-// otherwise element by element, the last chunk of a row cut at n (blocks below 16 only: a larger block makes n a multiple of 16).
-template <class C, class XT, class YT, bool VEC>
-__global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X, YT *Y, size_t rows, int n,
-                                                                      int lb, const float *__restrict__ signs, int transposed, C c) {
-    // (register, lane): a register's 256 values lie in consecutive banks.  Dynamic: blocks up to 1024 get none.
-    extern __shared__ __align__(16) unsigned char hd_lds[];
-    C(*xch)[HD_THREADS] = reinterpret_cast<C(*)[HD_THREADS]>(hd_lds);
+// Where a lane's chunk lies: chunks are numbered through the whole matrix, one trip, the grid covers every chunk.
+struct HdChunk {
+    size_t row;
+    int col, count;  // first column, and how many of the 16 lie inside the row (0: a lane past the last chunk)
+    bool live;
+};
+__device__ __forceinline__ HdChunk hd_chunk(size_t rows, int n, int t) {
     const int cpr = (n + HD_CHUNK - 1) / HD_CHUNK;
     const size_t total = rows * (size_t)cpr;
-    const int t = threadIdx.x, lane = t & 63;
-    const size_t g = (size_t)blockIdx.x * HD_THREADS + t;  // one trip: the grid covers every chunk
-    const bool live = g < total;
-    const size_t row = live ? g / cpr : 0;
-    const int col = live ? (int)(g - row * cpr) * HD_CHUNK : 0;
-    const int count = live ? min(HD_CHUNK, n - col) : 0;
-    C v[HD_CHUNK], s[HD_CHUNK];
+    const size_t g = (size_t)blockIdx.x * HD_THREADS + t;
+    HdChunk k;
+    k.live = g < total;
+    k.row = k.live ? g / cpr : 0;
+    k.col = k.live ? (int)(g - k.row * cpr) * HD_CHUNK : 0;
+    k.count = k.live ? min(HD_CHUNK, n - k.col) : 0;
+    return k;
+}
+
+// A lane's 16 elements and their signs (zeros and ones past the matrix).
+// VEC: X and the signs start on 16 bytes and n is a multiple of 16, so every chunk is whole and moves in 16-byte pieces;
+// otherwise element by element, the last chunk of a row cut at n (blocks below 16 only: a larger block makes n a multiple of 16).
+template <class C, class XT, bool VEC>
+__device__ __forceinline__ void hd_load(const XT *X, const float *__restrict__ signs, int n, const HdChunk k, C (&v)[HD_CHUNK],
+                                        C (&s)[HD_CHUNK]) {
 #pragma unroll
     for (int e = 0; e < HD_CHUNK; ++e) v[e] = (C)0, s[e] = (C)1;
     if constexpr (VEC) {
-        if (live) {
+        if (k.live) {
             constexpr int PER = 16 / sizeof(XT);
-            const HdPiece<XT> *src = reinterpret_cast<const HdPiece<XT> *>(X + row * n + col);
+            const HdPiece<XT> *src = reinterpret_cast<const HdPiece<XT> *>(X + k.row * n + k.col);
 #pragma unroll
             for (int p = 0; p < HD_CHUNK / PER; ++p) {
                 const HdPiece<XT> piece = src[p];
@@ -114,7 +122,7 @@ __global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X
                 for (int e = 0; e < PER; ++e) hd_get(v[p * PER + e], piece.e[e]);
             }
             if (signs) {
-                const HdPiece<float> *sp = reinterpret_cast<const HdPiece<float> *>(signs + col);
+                const HdPiece<float> *sp = reinterpret_cast<const HdPiece<float> *>(signs + k.col);
 #pragma unroll
                 for (int p = 0; p < HD_CHUNK / 4; ++p) {
                     const HdPiece<float> piece = sp[p];
@@ -126,15 +134,18 @@ __global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X
     } else {
 #pragma unroll
         for (int e = 0; e < HD_CHUNK; ++e)
-            if (e < count) {
-                hd_get(v[e], X[row * n + col + e]);
-                if (signs) s[e] = (C)signs[col + e];
+            if (e < k.count) {
+                hd_get(v[e], X[k.row * n + k.col + e]);
+                if (signs) s[e] = (C)signs[k.col + e];
             }
     }
-    if (!transposed) {
-#pragma unroll
-        for (int e = 0; e < HD_CHUNK; ++e) v[e] = s[e] * v[e];
-    }
+}
+
+// The butterflies of a block of 2^lb over the lanes' chunks (step 2 of the contract), for every kernel that rotates.
+// xch: (register, lane), so that a register's 256 values lie in consecutive banks; read for blocks above 1024 only.
+template <class C>
+__device__ __forceinline__ void hd_butterfly(C (&v)[HD_CHUNK], int lb, int t, C (*xch)[HD_THREADS]) {
+    const int lane = t & 63;
     // strides 1 .. 8
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -176,15 +187,33 @@ __global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X
             }
         }
     }
+}
+
+// VEC: as in hd_load, and Y starts on 16 bytes too.
+template <class C, class XT, class YT, bool VEC>
+__global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X, YT *Y, size_t rows, int n,
+                                                                      int lb, const float *__restrict__ signs, int transposed, C c) {
+    // Dynamic: blocks up to 1024 get none.
+    extern __shared__ __align__(16) unsigned char hd_lds[];
+    C(*xch)[HD_THREADS] = reinterpret_cast<C(*)[HD_THREADS]>(hd_lds);
+    const int t = threadIdx.x;
+    const HdChunk k = hd_chunk(rows, n, t);
+    C v[HD_CHUNK], s[HD_CHUNK];
+    hd_load<C, XT, VEC>(X, signs, n, k, v, s);
+    if (!transposed) {
+#pragma unroll
+        for (int e = 0; e < HD_CHUNK; ++e) v[e] = s[e] * v[e];
+    }
+    hd_butterfly(v, lb, t, xch);
 #pragma unroll
     for (int e = 0; e < HD_CHUNK; ++e) {
         v[e] = v[e] * c;
         if (transposed) v[e] = s[e] * v[e];
     }
     if constexpr (VEC) {
-        if (live) {
+        if (k.live) {
             constexpr int PER = 16 / sizeof(YT);
-            HdPiece<YT> *dst = reinterpret_cast<HdPiece<YT> *>(Y + row * n + col);
+            HdPiece<YT> *dst = reinterpret_cast<HdPiece<YT> *>(Y + k.row * n + k.col);
 #pragma unroll
             for (int p = 0; p < HD_CHUNK / PER; ++p) {
                 HdPiece<YT> piece;
@@ -196,8 +225,69 @@ __global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X
     } else {
 #pragma unroll
         for (int e = 0; e < HD_CHUNK; ++e)
-            if (e < count) hd_put(Y[row * n + col + e], v[e]);
+            if (e < k.count) hd_put(Y[k.row * n + k.col + e], v[e]);
     }
+}
+
+// slk_mx_rotate_quantize_act: steps 1 to 3 of the transform (transposed == 0) with the MX activation quantizer as the
+// epilogue, applied to the float32 value -- the bits of slk_hadamard_rows to float32 followed by slk_mx_quantize_act /
+// _act4, without the float32 matrix in between.  n % 32 == 0, so a block of 32 is the chunks of an even lane and its right
+// neighbour in one row: one DPP step joins their maxima, the even lane stores the scale byte, and each lane its 16 codes
+// (16 bytes of E4M3, 8 of E2M1).  Lanes past the matrix come in pairs too (rows * n / 16 is even) and carry zeros.
+template <class XT, int FMT>
+__global__ __launch_bounds__(HD_THREADS) static void k_hadamard_quantize(const XT *X, size_t rows, int n, int lb,
+                                                                          const float *__restrict__ signs, float c,
+                                                                          uint8_t *__restrict__ codes, uint8_t *__restrict__ E,
+                                                                          int *__restrict__ flag) {
+    extern __shared__ __align__(16) unsigned char hd_lds[];
+    float(*xch)[HD_THREADS] = reinterpret_cast<float(*)[HD_THREADS]>(hd_lds);
+    const int t = threadIdx.x;
+    const HdChunk k = hd_chunk(rows, n, t);
+    float v[HD_CHUNK], s[HD_CHUNK];
+    hd_load<float, XT, true>(X, signs, n, k, v, s);
+#pragma unroll
+    for (int e = 0; e < HD_CHUNK; ++e) v[e] = s[e] * v[e];
+    hd_butterfly(v, lb, t, xch);
+    int top = 0;
+#pragma unroll
+    for (int e = 0; e < HD_CHUNK; ++e) {
+        v[e] = v[e] * c;
+        top = max(top, (int)(__float_as_uint(v[e]) & 0x7fffffffu));
+    }
+    top = max(top, dpp_i<DPP_XOR1>(top));
+    const unsigned eb = mxa_scale_byte<FMT>(top);
+    const float inv = mxa_inverse(eb);
+    constexpr int BITS = FMT == MXA_E2M1 ? 4 : 8, PER = 32 / BITS, WORDS = HD_CHUNK / PER;
+    unsigned w[WORDS];
+#pragma unroll
+    for (int i = 0; i < WORDS; ++i) w[i] = 0u;
+#pragma unroll
+    for (int e = 0; e < HD_CHUNK; ++e) w[e / PER] |= mxa_code<FMT>(v[e], inv) << (BITS * (e % PER));
+    if (k.live) {
+        const size_t at = k.row * n + k.col;  // a multiple of 16
+        if constexpr (FMT == MXA_E2M1) {
+            typedef unsigned u2 __attribute__((ext_vector_type(2)));
+            *reinterpret_cast<u2 *>(codes + at / 2) = (u2){w[0], w[1]};
+        } else {
+            typedef unsigned u4 __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<u4 *>(codes + at) = (u4){w[0], w[1], w[2], w[3]};
+        }
+        if ((k.col & 16) == 0) E[at / 32] = (uint8_t)eb;
+        if (top >= 0x7f800000) *flag = 1;
+    }
+}
+
+template <class XT>
+static void launch_hadamard_quantize(const void *X, long long rows, int n, int lb, const float *signs, int fmt, uint8_t *codes,
+                                     uint8_t *E, int *flag, hipStream_t s) {
+    const float c = (float)(1.0 / sqrt((double)(1 << lb)));
+    const size_t total = (size_t)rows * (size_t)(n / HD_CHUNK);
+    const unsigned grid = (unsigned)((total + HD_THREADS - 1) / HD_THREADS);  // (the entry point refuses what does not fit one grid)
+    const size_t lds = lb > 10 ? sizeof(float) * HD_CHUNK * HD_THREADS : 0;
+    if (fmt == SLK_MX_ACT_FP4)
+        k_hadamard_quantize<XT, MXA_E2M1><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), (size_t)rows, n, lb, signs, c, codes, E, flag);
+    else
+        k_hadamard_quantize<XT, MXA_E4M3><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), (size_t)rows, n, lb, signs, c, codes, E, flag);
 }
 
 template <class C, int XD, int YD>
@@ -263,6 +353,35 @@ int slk_hadamard_rows(const void *X, int x_dtype, void *Y, int y_dtype, long lon
         SLK_RUN("hadamard_rows", flops, bytes, s, launch_hadamard_out<SLK_DTYPE_F16>(y_dtype, X, Y, rows, n, lb, signs, transposed, s));
     else
         SLK_RUN("hadamard_rows", flops, bytes, s, launch_hadamard_out<SLK_DTYPE_F32>(y_dtype, X, Y, rows, n, lb, signs, transposed, s));
+    return SLK_OK;
+}
+
+int slk_mx_rotate_quantize_act(const void *X, int x_dtype, long long rows, int n, int block, const float *signs, int fmt,
+                               uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    SLK_REQUIRE(block >= 2 && block <= 4096 && (block & (block - 1)) == 0, "block must be a power of two in 2..4096 (got %d)", block);
+    SLK_REQUIRE(rows > 0 && n >= 32 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (rows = %lld, n = %d)", rows, n);
+    SLK_REQUIRE(n % block == 0, "block %d does not divide n = %d", block, n);
+    SLK_REQUIRE(x_dtype == SLK_DTYPE_F32 || x_dtype == SLK_DTYPE_BF16 || x_dtype == SLK_DTYPE_F16, "unknown x_dtype %d", x_dtype);
+    SLK_REQUIRE(fmt == SLK_MX_ACT_FP8 || fmt == SLK_MX_ACT_FP4, "unknown fmt %d", fmt);
+    SLK_REQUIRE(X && a_codes && a_scales && flag, "null pointer");
+    SLK_REQUIRE((uintptr_t)X % 16 == 0 && (uintptr_t)a_codes % 16 == 0 && (uintptr_t)signs % 16 == 0,
+                "X, signs and a_codes must be aligned to 16 bytes");
+    SLK_REQUIRE(rows <= (long long)((~(size_t)0 >> 1) / (size_t)n / 8), "rows * n * 8 must fit the address space (rows = %lld, n = %d)", rows, n);
+    SLK_REQUIRE((unsigned long long)rows * (unsigned long long)(n / HD_CHUNK) <= 0x7fffffffULL * HD_THREADS,
+                "rows * n / 16 must not pass 2^31 - 1 workgroups of 256 chunks (rows = %lld, n = %d)", rows, n);
+    hipStream_t s = as_stream(stream);
+    int lb = 0;
+    while ((1 << lb) < block) ++lb;
+    zero_async(flag, sizeof(int), s);
+    const double elems = (double)rows * n;
+    const double flops = elems * (lb + 1);
+    const double bytes = elems * (hd_bytes(x_dtype) + (fmt == SLK_MX_ACT_FP4 ? 17.0 : 33.0) / 32.0);
+    if (x_dtype == SLK_DTYPE_BF16)
+        SLK_RUN("mx_rotate_quantize_act", flops, bytes, s, launch_hadamard_quantize<unsigned short>(X, rows, n, lb, signs, fmt, a_codes, a_scales, flag, s));
+    else if (x_dtype == SLK_DTYPE_F16)
+        SLK_RUN("mx_rotate_quantize_act", flops, bytes, s, launch_hadamard_quantize<_Float16>(X, rows, n, lb, signs, fmt, a_codes, a_scales, flag, s));
+    else
+        SLK_RUN("mx_rotate_quantize_act", flops, bytes, s, launch_hadamard_quantize<float>(X, rows, n, lb, signs, fmt, a_codes, a_scales, flag, s));
     return SLK_OK;
 }
 

@@ -1,8 +1,9 @@
-// A linear layer computed from the packed MXFP4 form on the block-scaled MFMA (slk_mx_quantize_act,
-// slk_mx_dequantize_act, slk_mx_gemm; the formats are pinned in include/sleekit_amd.h and INTEGRATION.md).
+// A linear layer computed from the packed MXFP4 form on the block-scaled MFMA (slk_mx_quantize_act, slk_mx_quantize_act4,
+// slk_mx_dequantize_act, slk_mx_gemm, slk_mx_gemm_a4; the formats are pinned in include/sleekit_amd.h and INTEGRATION.md).
 //
 // Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns.
-// Activations are quantized on the fly to MXFP8: E4M3 codes, one a byte, under the same kind of block scale.
+// Activations are quantized on the fly to MXFP8: E4M3 codes, one a byte, under the same kind of block scale -- or to
+// MXFP4, in the weights' own form.
 //
 // v_mfma_scale_f32_16x16x128_f8f6f4, as found on the hardware and held by the one-hot test of
 // tests/test_gpu_mx_gemm.py.  Lane l = i + 16 q carries row (A) or column (B) i.
@@ -11,11 +12,13 @@
 //      instruction runs as two halves of 64 -- so a lane's bytes are two 16-byte pieces of its row, from two blocks.
 //   scales: the byte of lane i + 16 b's scale VGPR that op_sel names is the E8M0 scale of (row or column i, block b) for
 //      both operands, whichever lanes carry that block's elements.
+//   A, E2M1 (4 VGPRs; slk_mx_gemm_a4, MXFP4 activations): as B -- the 32 consecutive k of block q, the even k low.
 // The stored forms feed the instruction with plain 16-byte loads: no shuffle, no pre-swizzle, no LDS.
 // D: lane l holds column l & 15, rows 4 (l >> 4) + 0 .. 3.
 #include <type_traits>
 
 #include "common.h"
+#include "mxquant.h"
 
 namespace slk {
 
@@ -29,16 +32,6 @@ __device__ __forceinline__ float mxg_e8m0(unsigned b) {
     return __uint_as_float(b == 0u ? 0x00400000u : (b == 255u ? 0x7fc00000u : b << 23));
 }
 
-// ---------------------------------------------------------------- E4M3
-// |y| as float32 bits -> the OCP E4M3 code of its nearest value, ties to even, clamped at 448 (0x7e).  From 2^-6 up
-// the grid is the floats of three mantissa bits: add half of the last kept bit (less one, plus that bit: to even), cut
-// 20 bits, and the exponent and mantissa fields are the code's after the bias moves from 127 to 7.  Below 2^-6 the
-// grid is k 2^-9, k = 0 .. 8, and k = 8 is code 0x08, the first normal.
-__device__ __forceinline__ unsigned e4m3_code(unsigned a) {
-    const unsigned normal = min(((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3), 0x7eu);
-    const unsigned sub = (unsigned)rintf(__uint_as_float(a) * 512.0f);
-    return a >= 0x3c800000u ? normal : sub;
-}
 // the float32 value of a code; 0x7f / 0xff are NaN
 __device__ __forceinline__ float e4m3_value(unsigned c) {
     const unsigned e = (c >> 3) & 15u, m = c & 7u;
@@ -57,16 +50,19 @@ template <>
 __device__ __forceinline__ float act_f32<_Float16>(_Float16 x) { return (float)x; }
 
 // Four lanes a block, eight elements a lane: the block's largest |x| over a quad on DPP, the scale byte from lane 0 of
-// the quad, eight codes (8 bytes) from every lane.  A NaN or an infinity has the largest magnitude bits of its block, so
-// the integer maximum finds it and raises the flag.
-template <class T>
+// the quad, eight codes from every lane -- 8 bytes of E4M3 (MXFP8), or one 32-bit word of E2M1 nibbles, the even k in the
+// low ones, which is the weights' own layout (MXFP4).  A NaN or an infinity has the largest magnitude bits of its block,
+// so the integer maximum finds it and raises the flag.
+template <class T, int FMT>
 __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X, size_t blocks, uint8_t *__restrict__ codes,
                                                          uint8_t *__restrict__ E, int *__restrict__ flag) {
     typedef T V __attribute__((ext_vector_type(8)));
+    constexpr int BITS = FMT == MXA_E2M1 ? 4 : 8, PER = 32 / BITS, WORDS = 8 / PER;  // codes a word, words a lane
+    typedef typename std::conditional<WORDS == 1, unsigned, u2v>::type C;
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
     const size_t units = 4 * blocks, rounds = (units + threads - 1) / threads;
     const V *src = reinterpret_cast<const V *>(X);
-    u2v *dst = reinterpret_cast<u2v *>(codes);
+    C *dst = reinterpret_cast<C *>(codes);
     bool bad = false;
     for (size_t r = 0; r < rounds; ++r) {  // (every lane of a quad takes every round: units is a multiple of 4, and so is threads)
         const size_t i = r * threads + gid;
@@ -86,22 +82,16 @@ __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X
         top = max(top, dpp_i<DPP_XOR1>(top));
         top = max(top, dpp_i<DPP_XOR2>(top));
         bad |= top >= 0x7f800000;
-        // the smallest power of two >= max(amax / 448, 1e-16), as its exponent field: 74 (the floor) .. 247
-        const float b0 = fmaxf(__uint_as_float((unsigned)min(top, 0x7f7fffff)) / 448.0f, 1.0e-16f);
-        const unsigned eb = ((__float_as_uint(b0) + 0x7fffffu) >> 23) & 0xffu;
-        const float inv = __uint_as_float((254u - eb) << 23);  // 1 / scale: x * inv is the exact quotient
-        unsigned w[2] = {0u, 0u};
+        const unsigned eb = mxa_scale_byte<FMT>(top);
+        const float inv = mxa_inverse(eb);
+        unsigned w[WORDS];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const unsigned u = __float_as_uint(x[e] * inv);
-            const unsigned c = e4m3_code(u & 0x7fffffffu);
-            w[e >> 2] |= (c ? c | ((u >> 24) & 0x80u) : 0u) << (8 * (e & 3));  // (a zero magnitude is written as 0x00, never -0)
-        }
+        for (int k = 0; k < WORDS; ++k) w[k] = 0u;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) w[e / PER] |= mxa_code<FMT>(x[e], inv) << (BITS * (e % PER));
         if (live) {
-            u2v o;
-            o.x = w[0];
-            o.y = w[1];
-            dst[i] = o;
+            if constexpr (WORDS == 1) dst[i] = w[0];
+            else dst[i] = (u2v){w[0], w[1]};
             if ((i & 3) == 0) E[i >> 2] = (uint8_t)eb;
         }
     }
@@ -177,10 +167,34 @@ __device__ __forceinline__ FragB load_b(const uint8_t *__restrict__ codes, const
     }
     return f;
 }
+// The A fragment of either activation format.  E2M1 activations are stored like the weights and map like them (held by
+// the one-hot test of tests/test_gpu_mx_act4.py): lane i + 16 q carries the 32 consecutive k of block q of row i, one
+// 16-byte load, under that block's scale.
+template <bool A4>
+struct FragOfA {
+    typedef FragA T;
+};
+template <>
+struct FragOfA<true> {
+    typedef FragB T;
+};
+template <bool A4>
+__device__ __forceinline__ typename FragOfA<A4>::T load_a_fmt(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, int row,
+                                                              int rows, int step, int q, int bpr) {
+    if constexpr (A4) return load_b(codes, E, row, rows, 4 * step + q, bpr);
+    else return load_a(codes, E, row, rows, step, q, bpr);
+}
 // acc += A (E4M3, 16 x 128) B^T (E2M1, 16 x 128), each lane's block under its own scale
 __device__ __forceinline__ v4f mx_mfma(const FragA a, const FragB b, v4f acc) {
     const v8i bv = {b.v.x, b.v.y, b.v.z, b.v.w, 0, 0, 0, 0};
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a.v, bv, acc, 0 /* A: E4M3 */, 4 /* B: E2M1 */, 0, a.sc, 0, b.sc);
+}
+
+// ... and with A in E2M1 as well (cbsz = 4): four VGPRs a side, the instruction at twice the E4M3 rate
+__device__ __forceinline__ v4f mx_mfma(const FragB a, const FragB b, v4f acc) {
+    const v8i av = {a.v.x, a.v.y, a.v.z, a.v.w, 0, 0, 0, 0};
+    const v8i bv = {b.v.x, b.v.y, b.v.z, b.v.w, 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, 4 /* A: E2M1 */, 4 /* B: E2M1 */, 0, a.sc, 0, b.sc);
 }
 
 template <int OUT>
@@ -200,7 +214,7 @@ __device__ __forceinline__ void store_tile(v4f acc, const float *__restrict__ bi
 // the SK partial tiles in wave order.  Both orders are fixed, so a result does not depend on timing.
 constexpr int MXG_SK = 8;
 constexpr int MXG_SPLIT_MAX_M = 64;
-template <int OUT>
+template <int OUT, bool A4 = false>
 __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                                 const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                                 const float *__restrict__ bias, int M, int N, int K,
@@ -211,7 +225,7 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *_
     const int m = blockIdx.y * 16 + (lane & 15), n = blockIdx.x * 16 + (lane & 15), q = lane >> 4;
     v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int s = wave; s < steps; s += 2 * MXG_SK) {  // two steps' loads in flight; a step past the end loads zeros
-        const FragA a0 = load_a(Ac, As, m, M, s, q, bpr), a1 = load_a(Ac, As, m, M, s + MXG_SK, q, bpr);
+        const typename FragOfA<A4>::T a0 = load_a_fmt<A4>(Ac, As, m, M, s, q, bpr), a1 = load_a_fmt<A4>(Ac, As, m, M, s + MXG_SK, q, bpr);
         const FragB b0 = load_b(Wc, Ws, n, N, 4 * s + q, bpr), b1 = load_b(Wc, Ws, n, N, 4 * (s + MXG_SK) + q, bpr);
         acc = mx_mfma(a0, b0, acc);
         acc = mx_mfma(a1, b1, acc);
@@ -226,7 +240,7 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *_
 
 // Many rows: a wave holds a 32 x 32 tile of Y as 2 x 2 MFMA tiles, so each fragment it loads feeds two MFMAs, and the four
 // waves of a workgroup cover 64 x 64; the fragments two waves share come to the second of them from the cache.
-template <int OUT>
+template <int OUT, bool A4 = false>
 __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                        const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                        const float *__restrict__ bias, int M, int N, int K,
@@ -240,11 +254,11 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
     for (int s = 0; s < steps; ++s) {
-        FragA a[2];
+        typename FragOfA<A4>::T a[2];
         FragB b[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            a[i] = load_a(Ac, As, m0 + 16 * i + (lane & 15), M, s, q, bpr);
+            a[i] = load_a_fmt<A4>(Ac, As, m0 + 16 * i + (lane & 15), M, s, q, bpr);
             b[i] = load_b(Wc, Ws, n0 + 16 * i + (lane & 15), N, 4 * s + q, bpr);
         }
 #pragma unroll
@@ -264,19 +278,20 @@ static inline int mxg_grid(size_t units) {
     return b < 1 ? 1 : (int)b;
 }
 
-template <int OUT>
+template <int OUT, bool A4 = false>
 static int mx_gemm_launch(const uint8_t *Ac, const uint8_t *As, const uint8_t *Wc, const uint8_t *Ws, const float *bias, int M, int N,
                           int K, void *out, hipStream_t s) {
     typedef typename PkOut<OUT>::T T;
     const double flops = 2.0 * M * N * K;
-    const double bytes = (double)M * K * 33.0 / 32.0 + (double)N * K * 17.0 / 32.0 + (double)M * N * sizeof(T);
+    const double bytes = (double)M * K * (A4 ? 17.0 : 33.0) / 32.0 + (double)N * K * 17.0 / 32.0 + (double)M * N * sizeof(T);
+    const char *name = A4 ? "mx_gemm_a4" : "mx_gemm";
     if (M <= MXG_SPLIT_MAX_M) {
         const dim3 grid((N + 15) / 16, (M + 15) / 16);
-        SLK_RUN("mx_gemm", flops, bytes, s,
-                k_mx_gemm_splitk<OUT><<<grid, 64 * MXG_SK, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out)));
+        SLK_RUN(name, flops, bytes, s,
+                (k_mx_gemm_splitk<OUT, A4><<<grid, 64 * MXG_SK, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out))));
     } else {
         const dim3 grid((N + 63) / 64, (M + 63) / 64);
-        SLK_RUN("mx_gemm", flops, bytes, s, k_mx_gemm_tiled<OUT><<<grid, 256, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out)));
+        SLK_RUN(name, flops, bytes, s, (k_mx_gemm_tiled<OUT, A4><<<grid, 256, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out))));
     }
     return SLK_OK;
 }
@@ -288,9 +303,10 @@ using namespace slk;
 static inline bool aligned16(const void *p) { return (uintptr_t)p % 16 == 0; }
 static inline bool known_dtype(int d) { return d == SLK_DTYPE_F32 || d == SLK_DTYPE_BF16 || d == SLK_DTYPE_F16; }
 
-extern "C" {
-
-int slk_mx_quantize_act(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+// slk_mx_quantize_act (FMT MXA_E4M3) and slk_mx_quantize_act4 (MXA_E2M1)
+template <int FMT>
+static int mx_quantize_act(const char *name, const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag,
+                           slk_stream_t stream) {
     SLK_REQUIRE(M > 0 && K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (M = %d, K = %d)", M, K);
     SLK_REQUIRE(known_dtype(x_dtype), "unknown x_dtype %d", x_dtype);
     SLK_REQUIRE(X && a_codes && a_scales && flag, "null pointer");
@@ -298,18 +314,28 @@ int slk_mx_quantize_act(const void *X, int x_dtype, int M, int K, uint8_t *a_cod
     hipStream_t s = as_stream(stream);
     const size_t blocks = (size_t)M * (K / 32);
     zero_async(flag, sizeof(int), s);
-    const double bytes = (33.0 + 32.0 * (x_dtype == SLK_DTYPE_F32 ? 4.0 : 2.0)) * blocks;
+    const double bytes = ((FMT == MXA_E2M1 ? 17.0 : 33.0) + 32.0 * (x_dtype == SLK_DTYPE_F32 ? 4.0 : 2.0)) * blocks;
     const int grid = mxg_grid(4 * blocks);
     if (x_dtype == SLK_DTYPE_BF16)
-        SLK_RUN("mx_quantize_act", 0, bytes, s,
-                k_mx_quantize_act<unsigned short><<<grid, 256, 0, s>>>(static_cast<const unsigned short *>(X), blocks, a_codes, a_scales, flag));
+        SLK_RUN(name, 0, bytes, s,
+                (k_mx_quantize_act<unsigned short, FMT><<<grid, 256, 0, s>>>(static_cast<const unsigned short *>(X), blocks, a_codes, a_scales, flag)));
     else if (x_dtype == SLK_DTYPE_F16)
-        SLK_RUN("mx_quantize_act", 0, bytes, s,
-                k_mx_quantize_act<_Float16><<<grid, 256, 0, s>>>(static_cast<const _Float16 *>(X), blocks, a_codes, a_scales, flag));
+        SLK_RUN(name, 0, bytes, s,
+                (k_mx_quantize_act<_Float16, FMT><<<grid, 256, 0, s>>>(static_cast<const _Float16 *>(X), blocks, a_codes, a_scales, flag)));
     else
-        SLK_RUN("mx_quantize_act", 0, bytes, s,
-                k_mx_quantize_act<float><<<grid, 256, 0, s>>>(static_cast<const float *>(X), blocks, a_codes, a_scales, flag));
+        SLK_RUN(name, 0, bytes, s,
+                (k_mx_quantize_act<float, FMT><<<grid, 256, 0, s>>>(static_cast<const float *>(X), blocks, a_codes, a_scales, flag)));
     return SLK_OK;
+}
+
+extern "C" {
+
+int slk_mx_quantize_act(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    return mx_quantize_act<MXA_E4M3>("mx_quantize_act", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
+}
+
+int slk_mx_quantize_act4(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    return mx_quantize_act<MXA_E2M1>("mx_quantize_act4", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
 }
 
 int slk_mx_dequantize_act(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
@@ -346,6 +372,20 @@ int slk_mx_gemm(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *
     if (out_dtype == SLK_DTYPE_BF16) return mx_gemm_launch<PK_BF16>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
     if (out_dtype == SLK_DTYPE_F16) return mx_gemm_launch<PK_F16>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
     return mx_gemm_launch<PK_F32>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+}
+
+int slk_mx_gemm_a4(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
+                   int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
+    SLK_REQUIRE(M > 0 && N > 0, "M and N must be at least 1 (M = %d, N = %d)", M, N);
+    SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);
+    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
+    SLK_REQUIRE(a_codes && a_scales && w_codes && w_scales && out, "null pointer");
+    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(out), "a_codes, w_codes and out must be aligned to 16 bytes");
+    SLK_REQUIRE((M + 63) / 64 <= 65535, "M is above the 65535 row tiles of one launch (M = %d)", M);
+    hipStream_t s = as_stream(stream);
+    if (out_dtype == SLK_DTYPE_BF16) return mx_gemm_launch<PK_BF16, true>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+    if (out_dtype == SLK_DTYPE_F16) return mx_gemm_launch<PK_F16, true>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+    return mx_gemm_launch<PK_F32, true>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
 }
 
 }  // extern "C"

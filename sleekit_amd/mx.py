@@ -38,6 +38,20 @@ LINEAR.  The packed layer runs on the block-scaled MFMA without being de-quantiz
 Known answers: amax 1.0 gives byte 119 and 1.0, -0.3, 0.001, 0 the codes 78 ea 28 00; amax 1.75 gives byte 119 and 1.75,
 -1.75, 0.01, 1e-5 the codes 7e fe 42 01.  The product does not look for scale byte 255: it yields NaN, as the hardware does.
 
+W4A4.  `activations="mxfp4"` (matmul_mx, linear_mxfp4, MXLinear) quantizes x to MXFP4 instead: the same instruction with
+E2M1 on both sides runs at twice the E4M3 rate and the activation operand is half the bytes.
+    a_codes, a_scales = quantize_mxfp4_act(X)              # (M, K / 2) and (M, K / 32); dequantize_mxfp4 inverts it
+  activations  the MXFP8 rule with 6 in place of 448: scale byte = exponent + 127 of the smallest power of two >=
+            max(amax / 6, 1e-16), elements x / s rounded to nearest onto 0, .5, 1, 1.5, 2, 3, 4, 6, ties to the even code,
+            clamped at 6, code = sign << 3 | index, a zero magnitude 0x0 (never 0x8); two codes a byte, the even k in the
+            low nibble -- the layer's own layout.
+Known answers: amax 6.0 gives byte 127 and 6, -0.3, 0.75, 2.5 the codes 7 9 2 4; amax 1.0 gives byte 125 and 1.0, -1.0,
+0.3, 0.0625 the codes 6 e 2 0.
+FP4 keeps 2 significant bits, so one outlier channel costs its whole block its small values: this format is meant to
+follow a rotation (sleekit_amd.rotation), which spreads an outlier over its block.  `rotation=R` in linear_mxfp4 runs the
+rotation inside the quantizer (slk_mx_rotate_quantize_act: x is read once and only the codes are written); the result is
+linear_mxfp4(R.apply(x, dtype=torch.float32), ...) bit for bit.
+
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
 everything runs on the GPU on the current stream, and there is no CPU fallback.
 """
@@ -250,13 +264,48 @@ def _quantize_act(Xd, M, K):
     return codes, scales, flag
 
 
+def _quantize_act4(Xd, M, K):
+    """_quantize_act for MXFP4 activations: a_codes (M, K / 2)."""
+    Xd = _aligned(Xd)
+    codes = torch.empty((M, K // 2), dtype=torch.uint8, device=Xd.device)
+    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
+    _lib.check(_lib.lib.slk_mx_quantize_act4(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
+    return codes, scales, flag
+
+
+def _rotate_quantize_act(Xd, M, K, rotation, fp4):
+    """(a_codes, a_scales, flag) of (X R) without X R in memory: the transform's float32 value goes into the quantizer."""
+    Xd = _aligned(Xd)
+    signs = rotation.signs if rotation.signs.device == Xd.device else rotation.signs.to(Xd.device)
+    signs = _aligned(signs)
+    codes = torch.empty((M, K // 2 if fp4 else K), dtype=torch.uint8, device=Xd.device)
+    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
+    _lib.check(_lib.lib.slk_mx_rotate_quantize_act(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs),
+                                                   _lib.MX_ACT_FP4 if fp4 else _lib.MX_ACT_FP8, dev.ptr(codes), dev.ptr(scales),
+                                                   dev.ptr(flag), dev.stream_handle()))
+    return codes, scales, flag
+
+
+_ACTIVATIONS = ("mxfp8", "mxfp4")
+
+
+def _activations(activations):
+    """True for MXFP4 activations, False for MXFP8."""
+    if activations not in _ACTIVATIONS:
+        raise ValueError(f'activations must be "mxfp8" or "mxfp4" (got {activations!r})')
+    return activations == "mxfp4"
+
+
 def _raise_finite(flag):
     _raise_flag(flag, "activations must be finite: X holds a NaN or an infinity")
 
 
-def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype):
+def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fp4=False):
     out = torch.empty((M, N), dtype=dtype, device=ac.device)
-    _lib.check(_lib.lib.slk_mx_gemm(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _OUT[dtype], dev.ptr(out),
+    entry = _lib.lib.slk_mx_gemm_a4 if fp4 else _lib.lib.slk_mx_gemm
+    _lib.check(entry(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _OUT[dtype], dev.ptr(out),
                                     dev.stream_handle()))
     return out
 
@@ -290,6 +339,16 @@ def quantize_mxfp8(X):
     return dev.like_input(codes, X), dev.like_input(scales, X)
 
 
+def quantize_mxfp4_act(X):
+    """X (M, K) float32, bfloat16 or float16 -> (a_codes uint8 (M, K / 2), a_scales uint8 (M, K / 32)): MXFP4 activations
+    (module docstring, W4A4); dequantize_mxfp4(a_codes, a_scales) is the inverse.  A NaN or an infinity in X: ValueError."""
+    M, K = _matrix(X, "X", _ACT)
+    _blocks(K)
+    codes, scales, flag = _quantize_act4(dev.to_device(X, _torch_dtype(X)), M, K)
+    _raise_finite(flag)
+    return dev.like_input(codes, X), dev.like_input(scales, X)
+
+
 def dequantize_mxfp8(a_codes, a_scales, dtype=torch.float32):
     """value(code) * 2^(b - 127), (M, K) of `dtype` (bfloat16 or float16: the float32 value rounded to nearest even)."""
     _out_dtype(dtype, a_codes)
@@ -305,11 +364,15 @@ def dequantize_mxfp8(a_codes, a_scales, dtype=torch.float32):
     return dev.like_input(out, a_codes)
 
 
-def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32):
+def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, activations="mxfp8"):
     """Y (M, N) = deq(a_codes, a_scales) @ deq(codes, scales).T + bias on the block-scaled MFMA: MXFP8 activations (M, K)
-    against an MXFP4 layer (N, K), float32 sums in a fixed order, the result rounded once to `dtype`."""
+    -- or, with activations="mxfp4", MXFP4 activations (M, K / 2) -- against an MXFP4 layer (N, K), float32 sums in a fixed
+    order, the result rounded once to `dtype`."""
+    fp4 = _activations(activations)
     _out_dtype(dtype, a_codes)
     M, K = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    if fp4:
+        K *= 2
     _blocks(K)
     _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(a_scales, M, K, "activation scale bytes")
@@ -318,14 +381,22 @@ def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32):
         raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
     _check_bias(bias, N)
     out = _gemm(_aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), _aligned(dev.to_device(codes, torch.uint8)),
-                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype)
+                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fp4)
     return dev.like_input(out, a_codes)
 
 
-def linear_mxfp4(x, codes, scales, bias=None, dtype=None):
+def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", rotation=None):
     """torch.nn.functional.linear with a packed MXFP4 weight: x (..., K) float32, bfloat16 or float16 is quantized to MXFP8
-    (quantize_mxfp8), multiplied with the layer (N, K) as in matmul_mx and the float32 bias (N,) added; the result is
-    (..., N) in `dtype`, or in x's dtype when `dtype` is None."""
+    (quantize_mxfp8; activations="mxfp4": to MXFP4, quantize_mxfp4_act, the W4A4 path), multiplied with the layer (N, K) as
+    in matmul_mx and the float32 bias (N,) added; the result is (..., N) in `dtype`, or in x's dtype when `dtype` is None.
+    rotation (a rotation.Rotation over K features): x R is quantized instead of x, the rotation running inside the
+    quantizer -- bit for bit linear_mxfp4(rotation.apply(x, dtype=torch.float32), ...) with the same `dtype` result."""
+    fp4 = _activations(activations)
+    if rotation is not None:
+        from .rotation import Rotation
+
+        if not isinstance(rotation, Rotation):
+            raise ValueError(f"rotation must be a Rotation (got {type(rotation).__name__})")
     if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim < 1:
         raise ValueError("x must be a NumPy array or torch tensor of at least one dimension")
     if x.dtype not in _ACT:
@@ -336,32 +407,62 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None):
     N, K = _weights(codes, scales)
     if x.shape[-1] != K:
         raise ValueError(f"x has {x.shape[-1]} columns but the layer has {K}")
+    if rotation is not None and rotation.n != K:
+        raise ValueError(f"the rotation has {rotation.n} features but the layer has {K}")
     _check_bias(bias, N)
     lead = tuple(x.shape[:-1])
     M = int(np.prod(lead, dtype=np.int64))
     if M < 1 or M >= 1 << 31:
         raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
     Xd = dev.to_device(x, _torch_dtype(x)).reshape(M, K)
-    ac, asc, flag = _quantize_act(Xd, M, K)
-    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype)
+    if rotation is not None:
+        ac, asc, flag = _rotate_quantize_act(Xd, M, K, rotation, fp4)
+    else:
+        ac, asc, flag = (_quantize_act4 if fp4 else _quantize_act)(Xd, M, K)
+    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fp4)
     _raise_finite(flag)
     return dev.like_input(out.reshape(lead + (N,)), x)
 
 
 class MXLinear(torch.nn.Module):
     """A linear layer kept in its packed MXFP4 form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
-    or None; forward(x) = linear_mxfp4(x, codes, scales, bias)."""
+    or None; forward(x) = linear_mxfp4(x, codes, scales, bias, activations=activations).  `activations` ("mxfp8", the
+    default, or "mxfp4") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8"."""
 
-    def __init__(self, in_features, out_features, bias=True, device=None):
+    def __init__(self, in_features, out_features, bias=True, device=None, activations="mxfp8"):
         super().__init__()
         _blocks(int(in_features))
+        _activations(activations)
+        self.activations = activations
         self.in_features, self.out_features = int(in_features), int(out_features)
         self.register_buffer("codes", torch.zeros((self.out_features, self.in_features // 2), dtype=torch.uint8, device=device))
         self.register_buffer("scales", torch.full((self.out_features, self.in_features // BLOCK), 127, dtype=torch.uint8, device=device))
         self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=device) if bias else None)
 
+    # `activations` travels as the module's extra state, written only when it is not the default: the state dict of a
+    # default module has the keys it always had, and a state dict without the key -- every one saved before -- means "mxfp8"
+    _STATE_KEY = torch.nn.modules.module._EXTRA_STATE_KEY_SUFFIX
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        if self.activations != "mxfp8":
+            destination[prefix + self._STATE_KEY] = {"activations": self.activations}
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        key = prefix + self._STATE_KEY
+        activations = "mxfp8"
+        if key in state_dict:
+            state = state_dict[key]
+            activations = state.get("activations", "mxfp8") if isinstance(state, dict) else None
+            if activations not in _ACTIVATIONS:
+                error_msgs.append(f'{key}: activations must be "mxfp8" or "mxfp4" (got {activations!r})')
+                activations = self.activations
+            state_dict = {k: v for k, v in state_dict.items() if k != key}  # (the base class knows no such key)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        self.activations = activations
+
     @classmethod
-    def from_result(cls, layer, result):
+    def from_result(cls, layer, result, activations="mxfp8"):
         """The module of a torch.nn.Linear and the MXResult that Sleekit(layer).quantize_mxfp4() returned (taken after the
         call, so that a corrected bias comes along)."""
         if not isinstance(layer, torch.nn.Linear):
@@ -369,15 +470,16 @@ class MXLinear(torch.nn.Module):
         N, K = _weights(result.codes, result.scales)
         if (N, K) != (layer.out_features, layer.in_features):
             raise ValueError(f"the result is of a ({N}, {K}) layer, not of this ({layer.out_features}, {layer.in_features}) one")
-        self = cls(K, N, layer.bias is not None, layer.weight.device)
+        self = cls(K, N, layer.bias is not None, layer.weight.device, activations)
         self.codes.copy_(torch.as_tensor(result.codes))
         self.scales.copy_(torch.as_tensor(result.scales))
         if layer.bias is not None:
             self.bias.copy_(layer.bias.detach().float())
         return self
 
-    def forward(self, x):
-        return linear_mxfp4(x, self.codes, self.scales, self.bias)
+    def forward(self, x, rotation=None):
+        return linear_mxfp4(x, self.codes, self.scales, self.bias, activations=self.activations, rotation=rotation)
 
     def extra_repr(self):
-        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
+        return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
+                f"activations={self.activations}")

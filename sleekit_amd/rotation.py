@@ -155,12 +155,24 @@ class RotatedLinear(torch.nn.Module):
     """A stored layer behind its rotation: forward(x) = inner(x R), the transform's output in x's dtype.  `inner` is the module
     of a layer quantized in the rotated basis (PackedLinear, MXLinear).  The rotation is kept as the buffer `signs` (n,)
     float32 and `block` (extra state).  `.half()` / `.bfloat16()` cast the buffer like any other; the transform then takes
-    a float32 copy of it (+-1 is exact in every float type).  Forward only (inference)."""
+    a float32 copy of it (+-1 is exact in every float type).  Forward only (inference).
 
-    def __init__(self, inner, rotation):
+    fused=True (an MXLinear inside; anything else: ValueError) hands the rotation to mx.linear_mxfp4, which runs it inside the
+    activation quantizer: x is read once and only the codes are written.  That path quantizes the transform's float32 value,
+    so for a 16-bit x it differs from the default forward by the one rounding of x R to x's dtype that the default makes
+    between the transform and the layer -- which is why it is opt-in; for a float32 x the two give the same bits.  `fused`
+    is extra state beside `block`; a state dict without it means False."""
+
+    def __init__(self, inner, rotation, fused=False):
         super().__init__()
         if not isinstance(rotation, Rotation):
             raise ValueError(f"RotatedLinear takes a Rotation (got {type(rotation).__name__})")
+        self.fused = bool(fused)
+        if self.fused:
+            from .mx import MXLinear
+
+            if not isinstance(inner, MXLinear):
+                raise ValueError(f"fused=True needs an MXLinear inside (got {type(inner).__name__})")
         features = getattr(inner, "in_features", None)
         if features is not None and int(features) != rotation.n:
             raise ValueError(f"the rotation has {rotation.n} features but the layer takes {features}")
@@ -173,31 +185,42 @@ class RotatedLinear(torch.nn.Module):
         return Rotation._of(self.signs, self.block)
 
     def get_extra_state(self):
-        return {"block": self.block}
+        return {"block": self.block, "fused": True} if self.fused else {"block": self.block}
 
     def set_extra_state(self, state):
         self.block = _check_block(int(self.signs.numel()), state["block"])
+        fused = bool(state.get("fused", False))
+        if fused:
+            from .mx import MXLinear
+
+            if not isinstance(self.inner, MXLinear):
+                raise ValueError(f"fused=True needs an MXLinear inside (got {type(self.inner).__name__})")
+        self.fused = fused
 
     @classmethod
-    def from_result(cls, layer, result, codebook=None, **kw):
+    def from_result(cls, layer, result, codebook=None, fused=False, activations="mxfp8", **kw):
         """The module of a torch.nn.Linear and the result of Sleekit(layer).quantize_packed / quantize_mxfp4(..., rotation=):
         MXLinear.from_result(layer, result) inside when the result carries `codes`, else PackedLinear.from_result(layer,
-        result, codebook, **kw)."""
+        result, codebook, **kw).  fused and activations ("mxfp8" | "mxfp4") are the MXLinear's (class docstring, mx.MXLinear)."""
         rotation = getattr(result, "rotation", None)
         if rotation is None:
             raise ValueError("the result carries no rotation: it was not quantized with rotation=")
         if getattr(result, "codes", None) is not None:
             from .mx import MXLinear
 
-            inner = MXLinear.from_result(layer, result)
+            inner = MXLinear.from_result(layer, result, activations=activations)
         else:
             from .packing import PackedLinear
 
+            if activations != "mxfp8":
+                raise ValueError("activations is the MXLinear's: this result carries no MX codes")
             inner = PackedLinear.from_result(layer, result, codebook, **kw)
-        return cls(inner, rotation)
+        return cls(inner, rotation, fused)
 
     def forward(self, x):
+        if self.fused:
+            return self.inner(x, rotation=self.rotation)
         return self.inner(self.rotation.apply(x))
 
     def extra_repr(self):
-        return f"features={self.signs.numel()}, block={self.block}"
+        return f"features={self.signs.numel()}, block={self.block}" + (", fused=True" if self.fused else "")
