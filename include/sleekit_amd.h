@@ -174,7 +174,8 @@ int slk_hessian_accumulate(float *H, float *mean, const float *X, int n, int T,
                            long long count_before, void *workspace, size_t ws_bytes, slk_stream_t stream);
 
 /* a4  column statistics for the err / sqerr orders  (sleekit/obq.py:60-69)
- *     miss[j] = sum over rows, in row order, of |q(W) - W| (squared == 0) or its square. */
+ *     miss[j] = sum over rows, in row order, of |q(W) - W| (squared == 0) or its square; for n == 1 in NumPy's pairwise
+ *     order over the R rows, which is how NumPy reduces an (R, 1) array along axis 0 (the grouped forms likewise). */
 int slk_column_miss(const float *W, int R, int n, int levels, double lo, double hi, const float *table,
                     int squared, float *miss, slk_stream_t stream);
 
@@ -627,7 +628,8 @@ int slk_local_search_grouped(const float *W, float *Q, const float *H, const flo
 
 /* Scale selection: the callers' pre-step -------------------------- */
 /* compute_non_saturating_scaling (sleekit/scaling.py:44-55): scale[r] = max(max_r / hi_code,
- * min_r / lo_code, 1e-16) with the codebook's extreme values lo_code < 0 < hi_code.          */
+ * min_r / lo_code, 1e-16) with the codebook's extreme values lo_code < 0 < hi_code; NaN for a
+ * row that holds a NaN, like NumPy's min / max / maximum (slk_scale_norm likewise).          */
 int slk_scale_minmax(const float *W, int R, int n, double lo_code, double hi_code, float *scale,
                      slk_stream_t stream);
 /* compute_norm_scaling (sleekit/scaling.py:35-41): sqrt(max(mean(row^2), 1e-16)), float32,

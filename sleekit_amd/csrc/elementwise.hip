@@ -3,7 +3,7 @@
 // layout allows, grid-stride over at most 2048 blocks (guide: Guideline 11/13).
 #include <stdarg.h>
 
-#include "common.h"
+#include "npsum.h"
 
 namespace slk {
 
@@ -167,6 +167,32 @@ __global__ __launch_bounds__(256) void k_column_miss(const float *__restrict__ W
     }
     if (t < CM_COLS && j0 + t < n) miss[j0 + t] = acc;
 }
+// n == 1: the one column is a contiguous vector, and NumPy reduces an (R, 1) array along axis 0 as that vector -- its
+// pairwise sum of R elements (npsum.h), not the row-after-row order of wider matrices.  One workgroup.  (Nothing sorts by the
+// key of a lone column; the value is held to the reference all the same.)
+template <bool GROUPED, bool OFFSET = false>
+__global__ __launch_bounds__(256) void k_column_miss_single(const float *__restrict__ W, int R, Grid g, int squared,
+                                                            float *__restrict__ miss, const float *__restrict__ S,
+                                                            const float *__restrict__ O) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    SumTree *trees = reinterpret_cast<SumTree *>(smem_raw);
+    float *terms = reinterpret_cast<float *>(smem_raw + 2 * sizeof(SumTree));
+    prepare_trees(trees, R);
+    const float total = row_sum_numpy(trees, terms, R, [&](int r) {
+        const float w = W[r];
+        float qv;
+        if constexpr (GROUPED) {
+            qv = GroupQ<OFFSET>::at(S, O, (size_t)r).value(w, g);
+        } else {
+            qv = cb_value(w, g);
+        }
+        const float d = qv - w;
+        return squared ? d * d : fabsf(d);
+    });
+    if (threadIdx.x == 0) miss[0] = total;
+}
+static size_t single_smem(int R) { return 2 * sizeof(SumTree) + sizeof(float) * (size_t)(R < NP_CHUNK ? R : NP_CHUNK); }
+
 // Q[r][c] = value(idx[r][c]) / RN(1 / S[r][c / gsize]): the grouped loop's result rebuilt from its compact form.  The value
 // of index t is formed like the quantizer's (t * step + zero in float32, codebook.py:58-63) or read from the table.
 // OFFSET: Q[r][c] = value / RN(1 / s) + o, o = O[r][c / gsize] (slk_dequantize_grouped_asym).
@@ -235,6 +261,15 @@ static int column_miss_grouped(const float *W, const float *gscale, const float 
     hipStream_t s = as_stream(stream);
     const Grid g = make_grid(levels, lo, hi, table);
     const int blocks = (n + CM_COLS - 1) / CM_COLS, vec_ok = n % 4 == 0 && (uintptr_t)W % 16 == 0;
+    if (n == 1) {
+        if (goffset)
+            SLK_RUN("column_miss_grouped_asym", 0, 4.0 * R, s,
+                    k_column_miss_single<true, true><<<1, 256, single_smem(R), s>>>(W, R, g, squared, miss, gscale, goffset));
+        else
+            SLK_RUN("column_miss_grouped", 0, 4.0 * R, s,
+                    k_column_miss_single<true><<<1, 256, single_smem(R), s>>>(W, R, g, squared, miss, gscale, nullptr));
+        return SLK_OK;
+    }
     if (goffset)
         SLK_RUN("column_miss_grouped_asym", 0, 4.0 * R * n, s,
                 k_column_miss<true, true><<<blocks, 256, 0, s>>>(W, R, n, g, squared, miss, vec_ok, gscale, group_size, goffset));
@@ -357,6 +392,12 @@ int slk_column_miss(const float *W, int R, int n, int levels, double lo, double 
     SLK_REQUIRE(levels >= 2 && (table || lo < hi), "codebook needs levels >= 2 and lo < hi");
     SLK_REQUIRE(R >= 0 && n > 0 && W && miss, "bad arguments");
     hipStream_t s = as_stream(stream);
+    if (n == 1 && R > 0) {
+        SLK_RUN("column_miss", 0, 4.0 * R, s,
+                k_column_miss_single<false><<<1, 256, single_smem(R), s>>>(W, R, make_grid(levels, lo, hi, table), squared, miss,
+                                                                             nullptr, nullptr));
+        return SLK_OK;
+    }
     SLK_RUN("column_miss", 0, 4.0 * R * n, s,
             k_column_miss<false><<<(n + CM_COLS - 1) / CM_COLS, 256, 0, s>>>(W, R, n, make_grid(levels, lo, hi, table), squared, miss,
                                                                              n % 4 == 0 && (uintptr_t)W % 16 == 0, nullptr, 1, nullptr));

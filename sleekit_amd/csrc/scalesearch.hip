@@ -14,31 +14,40 @@
 namespace slk {
 
 // ------------------------------------------------------------------ closed-form scales
+// fminf / fmaxf drop a NaN where NumPy's min, max and maximum carry it: a NaN anywhere in the row is counted beside the
+// extremes and makes the scale NaN, as in the reference.  Rows without one go through the same operations as before.
 __global__ __launch_bounds__(256) void k_row_minmax_scale(const float *__restrict__ W, int R, int n, float lo_code,
                                                           float hi_code, float *__restrict__ scale) {
     __shared__ float smin[4], smax[4];
+    __shared__ int snan[4];
     const int r = blockIdx.x;
     const float *w = W + (size_t)r * n;
     float mn = w[0], mx = w[0];
+    int saw_nan = 0;
     for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        mn = fminf(mn, w[j]);
-        mx = fmaxf(mx, w[j]);
+        const float x = w[j];
+        saw_nan |= (int)(x != x);
+        mn = fminf(mn, x);
+        mx = fmaxf(mx, x);
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         mn = fminf(mn, __shfl_xor(mn, m, 64));
         mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+        saw_nan |= __shfl_xor(saw_nan, m, 64);
     }
     if ((threadIdx.x & 63) == 0) {
         smin[threadIdx.x >> 6] = mn;
         smax[threadIdx.x >> 6] = mx;
+        snan[threadIdx.x >> 6] = saw_nan;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         mn = fminf(fminf(smin[0], smin[1]), fminf(smin[2], smin[3]));
         mx = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
         const float s = fmaxf(mx / hi_code, mn / lo_code);  // scaling.py:53
-        scale[r] = fmaxf(s, 1.0e-16f);                      // scaling.py:54
+        const bool any_nan = (snan[0] | snan[1] | snan[2] | snan[3]) != 0;
+        scale[r] = any_nan ? __builtin_nanf("") : fmaxf(s, 1.0e-16f);  // scaling.py:54
     }
 }
 
@@ -50,7 +59,10 @@ __global__ __launch_bounds__(256) void k_row_norm_scale(const float *__restrict_
     const float *w = W + (size_t)blockIdx.x * n;
     prepare_trees(trees, n);
     const float total = row_sum_numpy(trees, terms, n, [&](int j) { return w[j] * w[j]; });
-    if (threadIdx.x == 0) scale[blockIdx.x] = sqrtf(fmaxf(total / (float)n, 1.0e-16f));  // scaling.py:40-41
+    if (threadIdx.x == 0) {
+        const float ms = total / (float)n;
+        scale[blockIdx.x] = sqrtf(ms != ms ? ms : fmaxf(ms, 1.0e-16f));  // scaling.py:40-41; np.maximum carries a NaN, fmaxf drops it
+    }
 }
 
 // a / b, correctly rounded, from y = RN(1 / b) by Markstein's sequence (q0 = RN(a y); r = a - b q0, exact in one fma;

@@ -329,8 +329,9 @@ def rows_divide(x, scale, invert=False):
 
 
 def column_miss(W, cb_abi, squared, gscale=None, group_size=None, goffset=None):
-    """Column sums of |Z(W) - W| (or squared) in NumPy's row-after-row order: Z the codebook, or with gscale (R, n / group_size)
-    the group quantizer (goffset beside it: the asymmetric one), in original units."""
+    """Column sums of |Z(W) - W| (or squared) in NumPy's row-after-row order (n == 1: its pairwise order over the rows, as NumPy
+    reduces a single column): Z the codebook, or with gscale (R, n / group_size) the group quantizer (goffset beside it: the
+    asymmetric one), in original units."""
     R, n = W.shape
     levels, lo, hi, table = cb_abi
     out = torch.empty(n, dtype=torch.float32, device=W.device)
