@@ -87,7 +87,8 @@ typedef void *slk_stream_t;
  * and the option "no_loop_error", then slk_gptq_quantize_layers (the same loop over layers that are not one stack: per-layer
  * pointers), then slk_packed_gemm (a linear layer computed from the packed indices; an addition within 8, nothing existing
  * changed), then slk_hadamard_rows (the block Hadamard rotation of sleekit_amd/rotation.py; likewise), then MXFP4
- * activations: slk_mx_quantize_act4, slk_mx_gemm_a4 and slk_mx_rotate_quantize_act (likewise).   */
+ * activations: slk_mx_quantize_act4, slk_mx_gemm_a4 and slk_mx_rotate_quantize_act (likewise), then MXFP6 (E2M3)
+ * activations: slk_mx_quantize_act6, slk_mx_dequantize_act6, slk_mx_gemm_a6 and slk_mx_rotate_quantize_act6 (likewise). */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -568,6 +569,45 @@ int slk_mx_gemm_a4(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_
                    const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream);
 int slk_mx_rotate_quantize_act(const void *X, int x_dtype, long long rows, int n, int block, const float *signs, int fmt,
                                uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream);
+
+/* MXFP6 activations: W4A6 on the block-scaled MFMA (A in E2M3, cbsz = 2: the E2M1 rate -- FP6 runs at the FP4 rate on this
+ * chip -- on three quarters of MXFP8's activation bytes, with E4M3's three mantissa bits inside a block).
+ * X is M x K row-major, K % 32 == 0, float32, bfloat16 or float16.  Blocks of 32 along K, one E8M0 byte per (row, block).
+ *   - a_scales: uint8 M x K / 32, E8M0: the MXFP8 rule above with 7.5 in place of 448.  Per block, b0 = max(amax /
+ *     float32(7.5), float32(1e-16)) in float32 (amax the block's largest |x| as float32), the scale s the smallest power of
+ *     two >= b0, the byte its exponent + 127.  A block of zeros gives byte 74.  The scale does not saturate.
+ *   - elements: x / s (exact) rounded to nearest onto OCP E2M3: bias 1, no infinities or NaNs, subnormals m / 8 (m = 0 ..
+ *     7), normals 2^(e - 1) (1 + m / 8) for e = 1 .. 3 -- the 32 magnitudes 0, 0.125 .. 1.875 in steps of 0.125, 2 .. 3.75
+ *     in steps of 0.25, 4 .. 7.5 in steps of 0.5.  Ties go to the even code (every midpoint, those at 1 / 2 / 4 where the
+ *     spacing changes included, lies between an odd and an even code), magnitudes are clamped at 7.5.
+ *     code = sign << 5 | e << 3 | m.  A zero magnitude is written as 0x00, never 0x20.
+ *   - a_codes: uint8 M x 3 K / 4.  A row is a little-endian bit stream, element k at bits 6 k .. 6 k + 5: a block is 24
+ *     bytes, and four elements c0 .. c3 make the three bytes of c0 | c1 << 6 | c2 << 12 | c3 << 18.  a_codes must start on
+ *     16 bytes; rows then start on 8.
+ *   Known answers: amax 7.5 gives byte 127, and 7.5, -0.3, 0.0625, 0.1875 the codes 1f 22 00 02 (0.0625 ties to 0, 0.1875
+ *   to 0.25), bytes 9f 08 08; amax 1.0 gives byte 125, and 1.0, -1.0, 0.3, 0.0625 the codes 18 38 0a 02, bytes 18 ae 08;
+ *   under amax 7.5, 1.0625, 3.9, -3.875, 5.25 give 08 18 38 1a, bytes 08 86 6b; amax 1.75 gives byte 125 and +-1.75 the
+ *   codes 1e / 3e; amax 1e-20 gives byte 74 and all codes 0.
+ * slk_mx_quantize_act6: X -> a_codes, a_scales.  flag[0] = 1 (DEVICE int, zeroed by the call, required) if X holds a NaN or
+ *   an infinity; the outputs are then not meaningful.
+ * slk_mx_dequantize_act6: out[m][k] = value(code) * 2^(b - 127), M x K: exact in float32, or that value rounded once to
+ *   nearest even as bfloat16 / float16.  flag (may be NULL): 1 if a scale byte is 255.
+ * slk_mx_gemm_a6: slk_mx_gemm with such activations (a_codes M x 3 K / 4): the same contract -- exact products (4 + 2
+ *   significant bits), float32 sums inside the MFMA over K in a fixed order, no atomics, a repeated call gives the same
+ *   bits, any M, N >= 1.  Nothing past the 3 M K / 4 bytes of a_codes is read.
+ * slk_mx_rotate_quantize_act6: slk_mx_rotate_quantize_act for this format: a_codes (rows x 3 n / 4), a_scales and flag are,
+ *   bit for bit, those of slk_hadamard_rows(X -> float32 Y, transposed = 0) followed by slk_mx_quantize_act6 on Y.
+ * SLK_E_ARG, before any launch, slk_last_error() naming the offender: K (n) % 32 != 0 or < 32, M, N or rows < 1, a NULL
+ *   required pointer (bias and the de-quantizer's flag may be NULL), an unknown dtype, X, a_codes, w_codes, signs or out off
+ *   16-byte alignment; for the rotation also what slk_mx_rotate_quantize_act refuses of block and grid.                  */
+int slk_mx_quantize_act6(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag,
+                         slk_stream_t stream);
+int slk_mx_dequantize_act6(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
+                           slk_stream_t stream);
+int slk_mx_gemm_a6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                   const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream);
+int slk_mx_rotate_quantize_act6(const void *X, int x_dtype, long long rows, int n, int block, const float *signs,
+                                uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

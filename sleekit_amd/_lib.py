@@ -124,6 +124,10 @@ PROTOTYPES = {
     "slk_mx_quantize_act4": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
     "slk_mx_gemm_a4": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "slk_mx_rotate_quantize_act": (c_int, [P, c_int, c_longlong, c_int, c_int, P, c_int, P, P, P, P]),
+    "slk_mx_quantize_act6": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
+    "slk_mx_dequantize_act6": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
+    "slk_mx_gemm_a6": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "slk_mx_rotate_quantize_act6": (c_int, [P, c_int, c_longlong, c_int, c_int, P, P, P, P, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

@@ -1,9 +1,9 @@
-// A linear layer computed from the packed MXFP4 form on the block-scaled MFMA (slk_mx_quantize_act, slk_mx_quantize_act4,
-// slk_mx_dequantize_act, slk_mx_gemm, slk_mx_gemm_a4; the formats are pinned in include/sleekit_amd.h and INTEGRATION.md).
+// A linear layer computed from the packed MXFP4 form on the block-scaled MFMA (slk_mx_quantize_act, _act4, _act6,
+// slk_mx_dequantize_act, _act6, slk_mx_gemm, _a4, _a6; the formats are pinned in include/sleekit_amd.h and INTEGRATION.md).
 //
 // Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns.
 // Activations are quantized on the fly to MXFP8: E4M3 codes, one a byte, under the same kind of block scale -- or to
-// MXFP4, in the weights' own form.
+// MXFP4, in the weights' own form, or to MXFP6 (E2M3, 24 bytes a block).
 //
 // v_mfma_scale_f32_16x16x128_f8f6f4, as found on the hardware and held by the one-hot test of
 // tests/test_gpu_mx_gemm.py.  Lane l = i + 16 q carries row (A) or column (B) i.
@@ -13,7 +13,10 @@
 //   scales: the byte of lane i + 16 b's scale VGPR that op_sel names is the E8M0 scale of (row or column i, block b) for
 //      both operands, whichever lanes carry that block's elements.
 //   A, E2M1 (4 VGPRs; slk_mx_gemm_a4, MXFP4 activations): as B -- the 32 consecutive k of block q, the even k low.
-// The stored forms feed the instruction with plain 16-byte loads: no shuffle, no pre-swizzle, no LDS.
+//   A, E2M3 (6 VGPRs; slk_mx_gemm_a6, MXFP6 activations): the 32 consecutive k of block q as one little-endian stream of
+//      192 bits, element j of the block at bits 6 j .. 6 j + 5 of VGPRs 0-5 -- not cut in halves, the stored form as it is
+//      (held by the one-hot test of tests/test_gpu_mx_act6.py).
+// The stored forms feed the instruction with plain loads (16 bytes a piece; 16 + 8 for E2M3): no shuffle, no pre-swizzle, no LDS.
 // D: lane l holds column l & 15, rows 4 (l >> 4) + 0 .. 3.
 #include <type_traits>
 
@@ -56,6 +59,7 @@ __device__ __forceinline__ float act_f32<_Float16>(_Float16 x) { return (float)x
 template <class T, int FMT>
 __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X, size_t blocks, uint8_t *__restrict__ codes,
                                                          uint8_t *__restrict__ E, int *__restrict__ flag) {
+    static_assert(FMT == MXA_E4M3 || FMT == MXA_E2M1, "E2M3 has its own shape: k_mx_quantize_act6");
     typedef T V __attribute__((ext_vector_type(8)));
     constexpr int BITS = FMT == MXA_E2M1 ? 4 : 8, PER = 32 / BITS, WORDS = 8 / PER;  // codes a word, words a lane
     typedef typename std::conditional<WORDS == 1, unsigned, u2v>::type C;
@@ -96,6 +100,100 @@ __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X
         }
     }
     if (bad) *flag = 1;
+}
+
+// MXFP6 (E2M3): eight 6-bit codes are 6 bytes, which no lane can store as whole dwords at a 6-byte stride.  So LPB = 2
+// lanes a block, sixteen elements a lane: the block's largest |x| over the pair on one DPP step, the scale byte from the
+// even lane, and each lane's 16 codes as 96 bits of the row's little-endian bit stream -- three whole dwords at a 12-byte
+// stride, every one of them aligned (a row is 24 bytes a block).  LPB = 1 (a lane a block: 32 elements, six dwords, no
+// DPP) is the other shape that was measured; DESIGN.md section 20 has both.
+constexpr int MXQ6_LPB = 2;
+template <int WORDS>
+struct alignas(4) CodeWords {
+    unsigned w[WORDS];
+};
+typedef CodeWords<3> Codes12;
+template <class T, int LPB>
+__global__ __launch_bounds__(256) void k_mx_quantize_act6(const T *__restrict__ X, size_t blocks, uint8_t *__restrict__ codes,
+                                                          uint8_t *__restrict__ E, int *__restrict__ flag) {
+    static_assert(LPB == 1 || LPB == 2, "one or two lanes a block");
+    constexpr int EPL = 32 / LPB, WORDS = 6 / LPB;                // elements and code words a lane
+    constexpr int PER = 16 / (int)sizeof(T), PIECES = EPL / PER;  // elements a 16-byte piece, pieces a lane
+    typedef T V __attribute__((ext_vector_type(PER)));
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    const size_t units = LPB * blocks, rounds = (units + threads - 1) / threads;
+    const V *src = reinterpret_cast<const V *>(X);
+    CodeWords<WORDS> *dst = reinterpret_cast<CodeWords<WORDS> *>(codes);
+    bool bad = false;
+    for (size_t r = 0; r < rounds; ++r) {  // (both lanes of a pair take every round: units is a multiple of LPB, and so is threads)
+        const size_t i = r * threads + gid;
+        const bool live = i < units;
+        float x[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) x[e] = 0.0f;
+        if (live) {
+#pragma unroll
+            for (int p = 0; p < PIECES; ++p) {
+                const V v = src[PIECES * i + p];
+#pragma unroll
+                for (int e = 0; e < PER; ++e) x[p * PER + e] = act_f32<T>(v[e]);
+            }
+        }
+        int top = 0;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) top = max(top, (int)(__float_as_uint(x[e]) & 0x7fffffffu));
+        if constexpr (LPB == 2) top = max(top, dpp_i<DPP_XOR1>(top));
+        bad |= top >= 0x7f800000;
+        const unsigned eb = mxa_scale_byte<MXA_E2M3>(top);
+        CodeWords<WORDS> c;
+        mxa_pack<MXA_E2M3>(x, mxa_inverse(eb), c.w);
+        if (live) {
+            dst[i] = c;
+            if (i % LPB == 0) E[i / LPB] = (uint8_t)eb;
+        }
+    }
+    if (bad) *flag = 1;
+}
+
+// the float32 value of an E2M3 code (bias 1, subnormals m / 8, no NaN)
+__device__ __forceinline__ float e2m3_value(unsigned c) {
+    const unsigned e = (c >> 3) & 3u, m = c & 7u;
+    const float mag = e ? __uint_as_float(((e + 126u) << 23) | (m << 20)) : (float)m * 0.125f;
+    return (c & 0x20u) ? -mag : mag;
+}
+
+// ... and back: a lane reads the 12 bytes of sixteen codes and stores sixteen values (64 or 32 bytes, 16 at a time).
+template <int OUT>
+__global__ __launch_bounds__(256) void k_mx_dequantize_act6(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E,
+                                                            size_t blocks, typename PkOut<OUT>::T *__restrict__ out,
+                                                            int *__restrict__ flag) {
+    typedef typename PkOut<OUT>::T T;
+    constexpr int PER = 16 / (int)sizeof(T), PIECES = 16 / PER;
+    typedef T V __attribute__((ext_vector_type(PER)));
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    const Codes12 *src = reinterpret_cast<const Codes12 *>(codes);
+    V *dst = reinterpret_cast<V *>(out);
+    const size_t units = 2 * blocks;
+    bool bad = false;
+    for (size_t i = gid; i < units; i += threads) {
+        const Codes12 c = src[i];
+        const unsigned b = E[i >> 1];
+        bad |= b == 255u;
+        const float sc = mxg_e8m0(b);
+#pragma unroll
+        for (int p = 0; p < PIECES; ++p) {
+            V v;
+#pragma unroll
+            for (int e = 0; e < PER; ++e) {
+                const int at = 6 * (p * PER + e), word = at >> 5, shift = at & 31;
+                unsigned code = c.w[word] >> shift;
+                if (shift > 26) code |= c.w[word + 1] << (32 - shift);
+                v[e] = PkOut<OUT>::cvt(e2m3_value(code & 0x3fu) * sc);
+            }
+            dst[PIECES * i + p] = v;
+        }
+    }
+    if (bad && flag) *flag = 1;
 }
 
 // A unit is the 16 bytes a lane stores: 4 float32 values from 4 codes, or 8 16-bit values from 8 codes.
@@ -167,21 +265,52 @@ __device__ __forceinline__ FragB load_b(const uint8_t *__restrict__ codes, const
     }
     return f;
 }
-// The A fragment of either activation format.  E2M1 activations are stored like the weights and map like them (held by
+// The A fragment of each activation format.  E2M1 activations are stored like the weights and map like them (held by
 // the one-hot test of tests/test_gpu_mx_act4.py): lane i + 16 q carries the 32 consecutive k of block q of row i, one
-// 16-byte load, under that block's scale.
-template <bool A4>
+// 16-byte load, under that block's scale.  E2M3 activations (tests/test_gpu_mx_act6.py) map the same way -- the 32
+// consecutive k of block q in VGPRs 0-5, in the stored bit order -- so a lane's fragment is the 24 bytes of its block.
+// A row starts on 8 bytes and a block every 24, so the fragment is three 8-byte loads: 24 bytes exactly, and the last
+// block of the last row reads nothing past the buffer's 3 M K / 4 bytes, which a 16-byte pair of loads would.
+struct FragA6 {
+    int v[6];
+    int sc;
+};
+__device__ __forceinline__ FragA6 load_a6(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, int row, int rows, int kb,
+                                          int bpr) {
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    FragA6 f;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) f.v[i] = 0;
+    f.sc = 127;
+    if (row < rows && kb < bpr) {
+        const size_t blk = (size_t)row * bpr + kb;
+        const v2i *p = reinterpret_cast<const v2i *>(codes + 24 * blk);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const v2i w = p[i];
+            f.v[2 * i] = w.x, f.v[2 * i + 1] = w.y;
+        }
+        f.sc = E[blk];
+    }
+    return f;
+}
+template <int AF>
 struct FragOfA {
     typedef FragA T;
 };
 template <>
-struct FragOfA<true> {
+struct FragOfA<MXA_E2M1> {
     typedef FragB T;
 };
-template <bool A4>
-__device__ __forceinline__ typename FragOfA<A4>::T load_a_fmt(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, int row,
+template <>
+struct FragOfA<MXA_E2M3> {
+    typedef FragA6 T;
+};
+template <int AF>
+__device__ __forceinline__ typename FragOfA<AF>::T load_a_fmt(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, int row,
                                                               int rows, int step, int q, int bpr) {
-    if constexpr (A4) return load_b(codes, E, row, rows, 4 * step + q, bpr);
+    if constexpr (AF == MXA_E2M1) return load_b(codes, E, row, rows, 4 * step + q, bpr);
+    else if constexpr (AF == MXA_E2M3) return load_a6(codes, E, row, rows, 4 * step + q, bpr);
     else return load_a(codes, E, row, rows, step, q, bpr);
 }
 // acc += A (E4M3, 16 x 128) B^T (E2M1, 16 x 128), each lane's block under its own scale
@@ -195,6 +324,13 @@ __device__ __forceinline__ v4f mx_mfma(const FragB a, const FragB b, v4f acc) {
     const v8i av = {a.v.x, a.v.y, a.v.z, a.v.w, 0, 0, 0, 0};
     const v8i bv = {b.v.x, b.v.y, b.v.z, b.v.w, 0, 0, 0, 0};
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, 4 /* A: E2M1 */, 4 /* B: E2M1 */, 0, a.sc, 0, b.sc);
+}
+
+// ... and with A in E2M3 (cbsz = 2): six VGPRs of A, the instruction at the E2M1 rate
+__device__ __forceinline__ v4f mx_mfma(const FragA6 a, const FragB b, v4f acc) {
+    const v8i av = {a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5], 0, 0};
+    const v8i bv = {b.v.x, b.v.y, b.v.z, b.v.w, 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, 2 /* A: E2M3 */, 4 /* B: E2M1 */, 0, a.sc, 0, b.sc);
 }
 
 template <int OUT>
@@ -214,7 +350,7 @@ __device__ __forceinline__ void store_tile(v4f acc, const float *__restrict__ bi
 // the SK partial tiles in wave order.  Both orders are fixed, so a result does not depend on timing.
 constexpr int MXG_SK = 8;
 constexpr int MXG_SPLIT_MAX_M = 64;
-template <int OUT, bool A4 = false>
+template <int OUT, int AF = MXA_E4M3>
 __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                                 const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                                 const float *__restrict__ bias, int M, int N, int K,
@@ -225,7 +361,7 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *_
     const int m = blockIdx.y * 16 + (lane & 15), n = blockIdx.x * 16 + (lane & 15), q = lane >> 4;
     v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int s = wave; s < steps; s += 2 * MXG_SK) {  // two steps' loads in flight; a step past the end loads zeros
-        const typename FragOfA<A4>::T a0 = load_a_fmt<A4>(Ac, As, m, M, s, q, bpr), a1 = load_a_fmt<A4>(Ac, As, m, M, s + MXG_SK, q, bpr);
+        const typename FragOfA<AF>::T a0 = load_a_fmt<AF>(Ac, As, m, M, s, q, bpr), a1 = load_a_fmt<AF>(Ac, As, m, M, s + MXG_SK, q, bpr);
         const FragB b0 = load_b(Wc, Ws, n, N, 4 * s + q, bpr), b1 = load_b(Wc, Ws, n, N, 4 * (s + MXG_SK) + q, bpr);
         acc = mx_mfma(a0, b0, acc);
         acc = mx_mfma(a1, b1, acc);
@@ -240,7 +376,7 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *_
 
 // Many rows: a wave holds a 32 x 32 tile of Y as 2 x 2 MFMA tiles, so each fragment it loads feeds two MFMAs, and the four
 // waves of a workgroup cover 64 x 64; the fragments two waves share come to the second of them from the cache.
-template <int OUT, bool A4 = false>
+template <int OUT, int AF = MXA_E4M3>
 __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                        const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                        const float *__restrict__ bias, int M, int N, int K,
@@ -254,11 +390,11 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
     for (int s = 0; s < steps; ++s) {
-        typename FragOfA<A4>::T a[2];
+        typename FragOfA<AF>::T a[2];
         FragB b[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            a[i] = load_a_fmt<A4>(Ac, As, m0 + 16 * i + (lane & 15), M, s, q, bpr);
+            a[i] = load_a_fmt<AF>(Ac, As, m0 + 16 * i + (lane & 15), M, s, q, bpr);
             b[i] = load_b(Wc, Ws, n0 + 16 * i + (lane & 15), N, 4 * s + q, bpr);
         }
 #pragma unroll
@@ -278,20 +414,20 @@ static inline int mxg_grid(size_t units) {
     return b < 1 ? 1 : (int)b;
 }
 
-template <int OUT, bool A4 = false>
+template <int OUT, int AF = MXA_E4M3>
 static int mx_gemm_launch(const uint8_t *Ac, const uint8_t *As, const uint8_t *Wc, const uint8_t *Ws, const float *bias, int M, int N,
                           int K, void *out, hipStream_t s) {
     typedef typename PkOut<OUT>::T T;
     const double flops = 2.0 * M * N * K;
-    const double bytes = (double)M * K * (A4 ? 17.0 : 33.0) / 32.0 + (double)N * K * 17.0 / 32.0 + (double)M * N * sizeof(T);
-    const char *name = A4 ? "mx_gemm_a4" : "mx_gemm";
+    const double bytes = (double)M * K * (1.0 + 4.0 * mxa_bits<AF>()) / 32.0 + (double)N * K * 17.0 / 32.0 + (double)M * N * sizeof(T);
+    const char *name = AF == MXA_E2M1 ? "mx_gemm_a4" : AF == MXA_E2M3 ? "mx_gemm_a6" : "mx_gemm";
     if (M <= MXG_SPLIT_MAX_M) {
         const dim3 grid((N + 15) / 16, (M + 15) / 16);
         SLK_RUN(name, flops, bytes, s,
-                (k_mx_gemm_splitk<OUT, A4><<<grid, 64 * MXG_SK, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out))));
+                (k_mx_gemm_splitk<OUT, AF><<<grid, 64 * MXG_SK, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out))));
     } else {
         const dim3 grid((N + 63) / 64, (M + 63) / 64);
-        SLK_RUN(name, flops, bytes, s, (k_mx_gemm_tiled<OUT, A4><<<grid, 256, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out))));
+        SLK_RUN(name, flops, bytes, s, (k_mx_gemm_tiled<OUT, AF><<<grid, 256, 0, s>>>(Ac, As, Wc, Ws, bias, M, N, K, static_cast<T *>(out))));
     }
     return SLK_OK;
 }
@@ -383,9 +519,68 @@ int slk_mx_gemm_a4(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_
     SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(out), "a_codes, w_codes and out must be aligned to 16 bytes");
     SLK_REQUIRE((M + 63) / 64 <= 65535, "M is above the 65535 row tiles of one launch (M = %d)", M);
     hipStream_t s = as_stream(stream);
-    if (out_dtype == SLK_DTYPE_BF16) return mx_gemm_launch<PK_BF16, true>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
-    if (out_dtype == SLK_DTYPE_F16) return mx_gemm_launch<PK_F16, true>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
-    return mx_gemm_launch<PK_F32, true>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+    if (out_dtype == SLK_DTYPE_BF16) return mx_gemm_launch<PK_BF16, MXA_E2M1>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+    if (out_dtype == SLK_DTYPE_F16) return mx_gemm_launch<PK_F16, MXA_E2M1>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+    return mx_gemm_launch<PK_F32, MXA_E2M1>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+}
+
+int slk_mx_quantize_act6(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    SLK_REQUIRE(M > 0 && K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (M = %d, K = %d)", M, K);
+    SLK_REQUIRE(known_dtype(x_dtype), "unknown x_dtype %d", x_dtype);
+    SLK_REQUIRE(X && a_codes && a_scales && flag, "null pointer");
+    SLK_REQUIRE(aligned16(X) && aligned16(a_codes), "X and a_codes must be aligned to 16 bytes");
+    hipStream_t s = as_stream(stream);
+    const size_t blocks = (size_t)M * (K / 32);
+    zero_async(flag, sizeof(int), s);
+    const double bytes = (25.0 + 32.0 * (x_dtype == SLK_DTYPE_F32 ? 4.0 : 2.0)) * blocks;
+    const int grid = mxg_grid(MXQ6_LPB * blocks);
+    if (x_dtype == SLK_DTYPE_BF16)
+        SLK_RUN("mx_quantize_act6", 0, bytes, s,
+                (k_mx_quantize_act6<unsigned short, MXQ6_LPB><<<grid, 256, 0, s>>>(static_cast<const unsigned short *>(X), blocks, a_codes, a_scales, flag)));
+    else if (x_dtype == SLK_DTYPE_F16)
+        SLK_RUN("mx_quantize_act6", 0, bytes, s,
+                (k_mx_quantize_act6<_Float16, MXQ6_LPB><<<grid, 256, 0, s>>>(static_cast<const _Float16 *>(X), blocks, a_codes, a_scales, flag)));
+    else
+        SLK_RUN("mx_quantize_act6", 0, bytes, s,
+                (k_mx_quantize_act6<float, MXQ6_LPB><<<grid, 256, 0, s>>>(static_cast<const float *>(X), blocks, a_codes, a_scales, flag)));
+    return SLK_OK;
+}
+
+int slk_mx_dequantize_act6(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
+                           slk_stream_t stream) {
+    SLK_REQUIRE(M > 0 && K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (M = %d, K = %d)", M, K);
+    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
+    SLK_REQUIRE(a_codes && a_scales && out, "null pointer");
+    SLK_REQUIRE(aligned16(a_codes) && aligned16(out), "a_codes and out must be aligned to 16 bytes");
+    hipStream_t s = as_stream(stream);
+    const size_t blocks = (size_t)M * (K / 32);
+    if (flag) zero_async(flag, sizeof(int), s);
+    const double bytes = (25.0 + 32.0 * (out_dtype == SLK_DTYPE_F32 ? 4.0 : 2.0)) * blocks;
+    const int grid = mxg_grid(2 * blocks);
+    if (out_dtype == SLK_DTYPE_BF16)
+        SLK_RUN("mx_dequantize_act6", 0, bytes, s,
+                k_mx_dequantize_act6<PK_BF16><<<grid, 256, 0, s>>>(a_codes, a_scales, blocks, static_cast<unsigned short *>(out), flag));
+    else if (out_dtype == SLK_DTYPE_F16)
+        SLK_RUN("mx_dequantize_act6", 0, bytes, s,
+                k_mx_dequantize_act6<PK_F16><<<grid, 256, 0, s>>>(a_codes, a_scales, blocks, static_cast<_Float16 *>(out), flag));
+    else
+        SLK_RUN("mx_dequantize_act6", 0, bytes, s,
+                k_mx_dequantize_act6<PK_F32><<<grid, 256, 0, s>>>(a_codes, a_scales, blocks, static_cast<float *>(out), flag));
+    return SLK_OK;
+}
+
+int slk_mx_gemm_a6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
+                   int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
+    SLK_REQUIRE(M > 0 && N > 0, "M and N must be at least 1 (M = %d, N = %d)", M, N);
+    SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);
+    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
+    SLK_REQUIRE(a_codes && a_scales && w_codes && w_scales && out, "null pointer");
+    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(out), "a_codes, w_codes and out must be aligned to 16 bytes");
+    SLK_REQUIRE((M + 63) / 64 <= 65535, "M is above the 65535 row tiles of one launch (M = %d)", M);
+    hipStream_t s = as_stream(stream);
+    if (out_dtype == SLK_DTYPE_BF16) return mx_gemm_launch<PK_BF16, MXA_E2M3>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+    if (out_dtype == SLK_DTYPE_F16) return mx_gemm_launch<PK_F16, MXA_E2M3>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
+    return mx_gemm_launch<PK_F32, MXA_E2M3>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out, s);
 }
 
 }  // extern "C"

@@ -52,6 +52,21 @@ follow a rotation (sleekit_amd.rotation), which spreads an outlier over its bloc
 rotation inside the quantizer (slk_mx_rotate_quantize_act: x is read once and only the codes are written); the result is
 linear_mxfp4(R.apply(x, dtype=torch.float32), ...) bit for bit.
 
+W4A6.  `activations="mxfp6_e2m3"` quantizes x to MXFP6 (E2M3) instead: FP6 operands run at the FP4 rate on this chip, so the
+product costs what W4A4's does, on three quarters of MXFP8's activation bytes, and inside a block of 32 under a power-of-two
+scale E2M3 carries the three mantissa bits E4M3 carries -- behind a rotation W4A6's output error is W4A8's to three digits
+(DESIGN.md section 20).  The bare "mxfp6" is refused: there are two FP6 element formats.
+    a_codes, a_scales = quantize_mxfp6_act(X)              # (M, 3 K / 4) and (M, K / 32); dequantize_mxfp6_act inverts it
+  activations  the MXFP8 rule with 7.5 in place of 448: scale byte = exponent + 127 of the smallest power of two >=
+            max(amax / 7.5, 1e-16), elements x / s rounded to nearest onto OCP E2M3 (bias 1, subnormals m / 8, normals
+            2^(e - 1) (1 + m / 8), e = 1 .. 3: 0 .. 1.875 in steps of 0.125, 2 .. 3.75 of 0.25, 4 .. 7.5 of 0.5), ties to the
+            even code, clamped at 7.5, code = sign << 5 | e << 3 | m, a zero magnitude 0x00 (never 0x20).  A row of a_codes
+            is a little-endian bit stream, element k at bits 6 k .. 6 k + 5: 24 bytes a block, four codes c0 .. c3 the three
+            bytes of c0 | c1 << 6 | c2 << 12 | c3 << 18.
+Known answers: amax 7.5 gives byte 127 and 7.5, -0.3, 0.0625, 0.1875 the codes 1f 22 00 02, bytes 9f 08 08; amax 1.0 gives
+byte 125 and 1.0, -1.0, 0.3, 0.0625 the codes 18 38 0a 02, bytes 18 ae 08.
+`rotation=R` works as for the other formats (slk_mx_rotate_quantize_act6).
+
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
 everything runs on the GPU on the current stream, and there is no CPU fallback.
 """
@@ -274,39 +289,63 @@ def _quantize_act4(Xd, M, K):
     return codes, scales, flag
 
 
-def _rotate_quantize_act(Xd, M, K, rotation, fp4):
-    """(a_codes, a_scales, flag) of (X R) without X R in memory: the transform's float32 value goes into the quantizer."""
+def _quantize_act6(Xd, M, K):
+    """_quantize_act for MXFP6 (E2M3) activations: a_codes (M, 3 K / 4)."""
     Xd = _aligned(Xd)
-    signs = rotation.signs if rotation.signs.device == Xd.device else rotation.signs.to(Xd.device)
-    signs = _aligned(signs)
-    codes = torch.empty((M, K // 2 if fp4 else K), dtype=torch.uint8, device=Xd.device)
+    codes = torch.empty((M, 3 * K // 4), dtype=torch.uint8, device=Xd.device)
     scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
     flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
-    _lib.check(_lib.lib.slk_mx_rotate_quantize_act(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs),
-                                                   _lib.MX_ACT_FP4 if fp4 else _lib.MX_ACT_FP8, dev.ptr(codes), dev.ptr(scales),
-                                                   dev.ptr(flag), dev.stream_handle()))
+    _lib.check(_lib.lib.slk_mx_quantize_act6(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
     return codes, scales, flag
 
 
-_ACTIVATIONS = ("mxfp8", "mxfp4")
+# An activation format: the bits of a code (a_codes is (M, K bits / 8)), its plain quantizer and its product.
+_Format = collections.namedtuple("_Format", "name bits quantize gemm")
+_FORMATS = {
+    "mxfp8": _Format("mxfp8", 8, _quantize_act, "slk_mx_gemm"),
+    "mxfp4": _Format("mxfp4", 4, _quantize_act4, "slk_mx_gemm_a4"),
+    "mxfp6_e2m3": _Format("mxfp6_e2m3", 6, _quantize_act6, "slk_mx_gemm_a6"),
+}
+_ACTIVATIONS = tuple(_FORMATS)
+_ACTIVATIONS_ARE = 'activations must be "mxfp8", "mxfp4" or "mxfp6_e2m3"'
 
 
 def _activations(activations):
-    """True for MXFP4 activations, False for MXFP8."""
-    if activations not in _ACTIVATIONS:
-        raise ValueError(f'activations must be "mxfp8" or "mxfp4" (got {activations!r})')
-    return activations == "mxfp4"
+    """The _Format of an `activations` value.  (The bare "mxfp6" names two element formats and is refused.)"""
+    if not isinstance(activations, str) or activations not in _FORMATS:
+        raise ValueError(f"{_ACTIVATIONS_ARE} (got {activations!r})")
+    return _FORMATS[activations]
+
+
+def _rotate_quantize_act(Xd, M, K, rotation, fmt):
+    """(a_codes, a_scales, flag) of (X R) without X R in memory: the transform's float32 value goes into the quantizer.
+    fmt: a _Format, or False / True for MXFP8 / MXFP4."""
+    if isinstance(fmt, bool):
+        fmt = _FORMATS["mxfp4" if fmt else "mxfp8"]
+    Xd = _aligned(Xd)
+    signs = rotation.signs if rotation.signs.device == Xd.device else rotation.signs.to(Xd.device)
+    signs = _aligned(signs)
+    codes = torch.empty((M, K * fmt.bits // 8), dtype=torch.uint8, device=Xd.device)
+    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
+    if fmt.bits == 6:
+        _lib.check(_lib.lib.slk_mx_rotate_quantize_act6(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs), dev.ptr(codes),
+                                                        dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
+    else:
+        _lib.check(_lib.lib.slk_mx_rotate_quantize_act(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs),
+                                                       _lib.MX_ACT_FP4 if fmt.bits == 4 else _lib.MX_ACT_FP8, dev.ptr(codes), dev.ptr(scales),
+                                                       dev.ptr(flag), dev.stream_handle()))
+    return codes, scales, flag
 
 
 def _raise_finite(flag):
     _raise_flag(flag, "activations must be finite: X holds a NaN or an infinity")
 
 
-def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fp4=False):
+def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"]):
     out = torch.empty((M, N), dtype=dtype, device=ac.device)
-    entry = _lib.lib.slk_mx_gemm_a4 if fp4 else _lib.lib.slk_mx_gemm
-    _lib.check(entry(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _OUT[dtype], dev.ptr(out),
-                                    dev.stream_handle()))
+    _lib.check(getattr(_lib.lib, fmt.gemm)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _OUT[dtype],
+                                           dev.ptr(out), dev.stream_handle()))
     return out
 
 
@@ -349,6 +388,39 @@ def quantize_mxfp4_act(X):
     return dev.like_input(codes, X), dev.like_input(scales, X)
 
 
+def quantize_mxfp6_act(X):
+    """X (M, K) float32, bfloat16 or float16 -> (a_codes uint8 (M, 3 K / 4), a_scales uint8 (M, K / 32)): MXFP6 E2M3
+    activations (module docstring, W4A6); dequantize_mxfp6_act is the inverse.  A NaN or an infinity in X: ValueError."""
+    M, K = _matrix(X, "X", _ACT)
+    _blocks(K)
+    codes, scales, flag = _quantize_act6(dev.to_device(X, _torch_dtype(X)), M, K)
+    _raise_finite(flag)
+    return dev.like_input(codes, X), dev.like_input(scales, X)
+
+
+def _columns6(width):
+    """K of an MXFP6 a_codes of `width` bytes a row (24 bytes a block of 32)."""
+    if width < 24 or width % 24 != 0:
+        raise ValueError(f"MXFP6 blocks of {BLOCK} columns are 24 bytes: a_codes must have a positive multiple of 24 columns (got {width})")
+    return width // 24 * BLOCK
+
+
+def dequantize_mxfp6_act(a_codes, a_scales, dtype=torch.float32):
+    """value(code) * 2^(b - 127) of MXFP6 E2M3 activations, (M, K) of `dtype`: exact in float32; bfloat16 or float16: that
+    value rounded to nearest even."""
+    _out_dtype(dtype, a_codes)
+    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    K = _columns6(width)
+    _matrix(a_scales, "scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(a_scales, M, K, "scale bytes")
+    cd, sd = _aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8)
+    out = torch.empty((M, K), dtype=dtype, device=cd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=cd.device)
+    _lib.check(_lib.lib.slk_mx_dequantize_act6(dev.ptr(cd), dev.ptr(sd), M, K, _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.stream_handle()))
+    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
+    return dev.like_input(out, a_codes)
+
+
 def dequantize_mxfp8(a_codes, a_scales, dtype=torch.float32):
     """value(code) * 2^(b - 127), (M, K) of `dtype` (bfloat16 or float16: the float32 value rounded to nearest even)."""
     _out_dtype(dtype, a_codes)
@@ -366,13 +438,14 @@ def dequantize_mxfp8(a_codes, a_scales, dtype=torch.float32):
 
 def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, activations="mxfp8"):
     """Y (M, N) = deq(a_codes, a_scales) @ deq(codes, scales).T + bias on the block-scaled MFMA: MXFP8 activations (M, K)
-    -- or, with activations="mxfp4", MXFP4 activations (M, K / 2) -- against an MXFP4 layer (N, K), float32 sums in a fixed
-    order, the result rounded once to `dtype`."""
-    fp4 = _activations(activations)
+    -- or, with activations="mxfp4", MXFP4 activations (M, K / 2), or, with "mxfp6_e2m3", MXFP6 ones (M, 3 K / 4) -- against
+    an MXFP4 layer (N, K), float32 sums in a fixed order, the result rounded once to `dtype`."""
+    fmt = _activations(activations)
     _out_dtype(dtype, a_codes)
-    M, K = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    if fp4:
-        K *= 2
+    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    if 8 * width % fmt.bits != 0:
+        raise ValueError(f"a_codes has {width} columns of bytes, which is no whole number of {fmt.bits}-bit codes")
+    K = 8 * width // fmt.bits
     _blocks(K)
     _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(a_scales, M, K, "activation scale bytes")
@@ -381,17 +454,18 @@ def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, 
         raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
     _check_bias(bias, N)
     out = _gemm(_aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), _aligned(dev.to_device(codes, torch.uint8)),
-                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fp4)
+                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt)
     return dev.like_input(out, a_codes)
 
 
 def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", rotation=None):
     """torch.nn.functional.linear with a packed MXFP4 weight: x (..., K) float32, bfloat16 or float16 is quantized to MXFP8
-    (quantize_mxfp8; activations="mxfp4": to MXFP4, quantize_mxfp4_act, the W4A4 path), multiplied with the layer (N, K) as
+    (quantize_mxfp8; activations="mxfp4": to MXFP4, quantize_mxfp4_act, the W4A4 path; "mxfp6_e2m3": to MXFP6,
+    quantize_mxfp6_act, the W4A6 path), multiplied with the layer (N, K) as
     in matmul_mx and the float32 bias (N,) added; the result is (..., N) in `dtype`, or in x's dtype when `dtype` is None.
     rotation (a rotation.Rotation over K features): x R is quantized instead of x, the rotation running inside the
     quantizer -- bit for bit linear_mxfp4(rotation.apply(x, dtype=torch.float32), ...) with the same `dtype` result."""
-    fp4 = _activations(activations)
+    fmt = _activations(activations)
     if rotation is not None:
         from .rotation import Rotation
 
@@ -416,10 +490,10 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
         raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
     Xd = dev.to_device(x, _torch_dtype(x)).reshape(M, K)
     if rotation is not None:
-        ac, asc, flag = _rotate_quantize_act(Xd, M, K, rotation, fp4)
+        ac, asc, flag = _rotate_quantize_act(Xd, M, K, rotation, fmt)
     else:
-        ac, asc, flag = (_quantize_act4 if fp4 else _quantize_act)(Xd, M, K)
-    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fp4)
+        ac, asc, flag = fmt.quantize(Xd, M, K)
+    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt)
     _raise_finite(flag)
     return dev.like_input(out.reshape(lead + (N,)), x)
 
@@ -427,7 +501,7 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
 class MXLinear(torch.nn.Module):
     """A linear layer kept in its packed MXFP4 form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
     or None; forward(x) = linear_mxfp4(x, codes, scales, bias, activations=activations).  `activations` ("mxfp8", the
-    default, or "mxfp4") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8"."""
+    default, "mxfp4" or "mxfp6_e2m3") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8"."""
 
     def __init__(self, in_features, out_features, bias=True, device=None, activations="mxfp8"):
         super().__init__()
@@ -454,8 +528,8 @@ class MXLinear(torch.nn.Module):
         if key in state_dict:
             state = state_dict[key]
             activations = state.get("activations", "mxfp8") if isinstance(state, dict) else None
-            if activations not in _ACTIVATIONS:
-                error_msgs.append(f'{key}: activations must be "mxfp8" or "mxfp4" (got {activations!r})')
+            if not isinstance(activations, str) or activations not in _ACTIVATIONS:
+                error_msgs.append(f"{key}: {_ACTIVATIONS_ARE} (got {activations!r})")
                 activations = self.activations
             state_dict = {k: v for k, v in state_dict.items() if k != key}  # (the base class knows no such key)
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
