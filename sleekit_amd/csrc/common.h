@@ -278,22 +278,38 @@ template <int OUT>
 struct PkOut;
 template <>
 struct PkOut<PK_F32> {
+    static constexpr int OUT = PK_F32;
     typedef float T;
     typedef float V __attribute__((ext_vector_type(4)));
     static __device__ __forceinline__ float cvt(float v) { return v; }
 };
 template <>
 struct PkOut<PK_BF16> {
+    static constexpr int OUT = PK_BF16;
     typedef unsigned short T;
     typedef unsigned short V __attribute__((ext_vector_type(4)));
     static __device__ __forceinline__ unsigned short cvt(float v) { return pk_bf16(v); }
 };
 template <>
 struct PkOut<PK_F16> {
+    static constexpr int OUT = PK_F16;
     typedef _Float16 T;
     typedef _Float16 V __attribute__((ext_vector_type(4)));
     static __device__ __forceinline__ _Float16 cvt(float v) { return (_Float16)v; }
 };
+
+// The entries' checks of a 16-bit or float32 `dtype` argument and of a pointer the kernels move 16 bytes at a time through
+static inline bool known_dtype(int d) { return d == SLK_DTYPE_F32 || d == SLK_DTYPE_BF16 || d == SLK_DTYPE_F16; }
+static inline bool aligned16(const void *p) { return (uintptr_t)p % 16 == 0; }
+
+// f(PkOut<..>()) for a known_dtype: the one place a SLK_DTYPE_* becomes a type.
+//   return with_dtype(x_dtype, [&](auto t) -> int { typedef typename decltype(t)::T T; SLK_RUN(..., kernel<T><<<...>>>(...)); return SLK_OK; });
+template <class F>
+static inline int with_dtype(int dtype, F &&f) {
+    if (dtype == SLK_DTYPE_BF16) return f(PkOut<PK_BF16>());
+    if (dtype == SLK_DTYPE_F16) return f(PkOut<PK_F16>());
+    return f(PkOut<PK_F32>());
+}
 
 // Broadcast lane `src` (wave-uniform index) of a double to the whole wave through SGPRs.
 __device__ __forceinline__ double readlane_f64(double v, int src) {

@@ -262,36 +262,10 @@ __global__ __launch_bounds__(HD_THREADS) static void k_hadamard_quantize(const X
     mxa_pack<FMT>(v, inv, w);
     if (k.live) {
         const size_t at = k.row * n + k.col;  // a multiple of 16
-        if constexpr (FMT == MXA_E2M1) {
-            typedef unsigned u2 __attribute__((ext_vector_type(2)));
-            *reinterpret_cast<u2 *>(codes + at / 2) = (u2){w[0], w[1]};
-        } else if constexpr (FMT == MXA_E2M3) {
-            struct alignas(4) Codes12 {
-                unsigned w[3];
-            };
-            *reinterpret_cast<Codes12 *>(codes + at / 4 * 3) = (Codes12){{w[0], w[1], w[2]}};  // 12 bytes: three aligned dwords
-        } else {
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<u4 *>(codes + at) = (u4){w[0], w[1], w[2], w[3]};
-        }
+        mxa_store<FMT, HD_CHUNK>(codes + mxa_byte_of<FMT>(at), w);
         if ((k.col & 16) == 0) E[at / 32] = (uint8_t)eb;
         if (top >= 0x7f800000) *flag = 1;
     }
-}
-
-template <class XT>
-static void launch_hadamard_quantize(const void *X, long long rows, int n, int lb, const float *signs, int fmt, uint8_t *codes,
-                                     uint8_t *E, int *flag, hipStream_t s) {
-    const float c = (float)(1.0 / sqrt((double)(1 << lb)));
-    const size_t total = (size_t)rows * (size_t)(n / HD_CHUNK);
-    const unsigned grid = (unsigned)((total + HD_THREADS - 1) / HD_THREADS);  // (the entry point refuses what does not fit one grid)
-    const size_t lds = lb > 10 ? sizeof(float) * HD_CHUNK * HD_THREADS : 0;
-    if (fmt == MXA_E2M3)
-        k_hadamard_quantize<XT, MXA_E2M3><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), (size_t)rows, n, lb, signs, c, codes, E, flag);
-    else if (fmt == MXA_E2M1)
-        k_hadamard_quantize<XT, MXA_E2M1><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), (size_t)rows, n, lb, signs, c, codes, E, flag);
-    else
-        k_hadamard_quantize<XT, MXA_E4M3><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), (size_t)rows, n, lb, signs, c, codes, E, flag);
 }
 
 template <class C, int XD, int YD>
@@ -329,16 +303,16 @@ static inline double hd_bytes(int dtype) { return dtype == SLK_DTYPE_F64 ? 8.0 :
 
 using namespace slk;
 
-// slk_mx_rotate_quantize_act (fmt MXA_E4M3, MXA_E2M1) and slk_mx_rotate_quantize_act6 (MXA_E2M3)
-static int mx_rotate_quantize(const char *name, const void *X, int x_dtype, long long rows, int n, int block, const float *signs, int fmt,
+// slk_mx_rotate_quantize_act (FMT MXA_E4M3, MXA_E2M1) and slk_mx_rotate_quantize_act6 (MXA_E2M3)
+template <int FMT>
+static int mx_rotate_quantize(const char *name, const void *X, int x_dtype, long long rows, int n, int block, const float *signs,
                               uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
     SLK_REQUIRE(block >= 2 && block <= 4096 && (block & (block - 1)) == 0, "block must be a power of two in 2..4096 (got %d)", block);
     SLK_REQUIRE(rows > 0 && n >= 32 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (rows = %lld, n = %d)", rows, n);
     SLK_REQUIRE(n % block == 0, "block %d does not divide n = %d", block, n);
-    SLK_REQUIRE(x_dtype == SLK_DTYPE_F32 || x_dtype == SLK_DTYPE_BF16 || x_dtype == SLK_DTYPE_F16, "unknown x_dtype %d", x_dtype);
+    SLK_REQUIRE(known_dtype(x_dtype), "unknown x_dtype %d", x_dtype);
     SLK_REQUIRE(X && a_codes && a_scales && flag, "null pointer");
-    SLK_REQUIRE((uintptr_t)X % 16 == 0 && (uintptr_t)a_codes % 16 == 0 && (uintptr_t)signs % 16 == 0,
-                "X, signs and a_codes must be aligned to 16 bytes");
+    SLK_REQUIRE(aligned16(X) && aligned16(a_codes) && aligned16(signs), "X, signs and a_codes must be aligned to 16 bytes");
     SLK_REQUIRE(rows <= (long long)((~(size_t)0 >> 1) / (size_t)n / 8), "rows * n * 8 must fit the address space (rows = %lld, n = %d)", rows, n);
     SLK_REQUIRE((unsigned long long)rows * (unsigned long long)(n / HD_CHUNK) <= 0x7fffffffULL * HD_THREADS,
                 "rows * n / 16 must not pass 2^31 - 1 workgroups of 256 chunks (rows = %lld, n = %d)", rows, n);
@@ -346,16 +320,18 @@ static int mx_rotate_quantize(const char *name, const void *X, int x_dtype, long
     int lb = 0;
     while ((1 << lb) < block) ++lb;
     zero_async(flag, sizeof(int), s);
+    const float c = (float)(1.0 / sqrt((double)(1 << lb)));
+    const size_t total = (size_t)rows * (size_t)(n / HD_CHUNK);
+    const unsigned grid = (unsigned)((total + HD_THREADS - 1) / HD_THREADS);  // (what does not fit one grid is refused above)
+    const size_t lds = lb > 10 ? sizeof(float) * HD_CHUNK * HD_THREADS : 0;
     const double elems = (double)rows * n;
-    const double flops = elems * (lb + 1);
-    const double bytes = elems * (hd_bytes(x_dtype) + (fmt == MXA_E2M1 ? 17.0 : fmt == MXA_E2M3 ? 25.0 : 33.0) / 32.0);
-    if (x_dtype == SLK_DTYPE_BF16)
-        SLK_RUN(name, flops, bytes, s, launch_hadamard_quantize<unsigned short>(X, rows, n, lb, signs, fmt, a_codes, a_scales, flag, s));
-    else if (x_dtype == SLK_DTYPE_F16)
-        SLK_RUN(name, flops, bytes, s, launch_hadamard_quantize<_Float16>(X, rows, n, lb, signs, fmt, a_codes, a_scales, flag, s));
-    else
-        SLK_RUN(name, flops, bytes, s, launch_hadamard_quantize<float>(X, rows, n, lb, signs, fmt, a_codes, a_scales, flag, s));
-    return SLK_OK;
+    const double flops = elems * (lb + 1), bytes = elems * (hd_bytes(x_dtype) + mxa_block_bytes<FMT>() / 32.0);
+    return with_dtype(x_dtype, [&](auto t) -> int {
+        typedef typename decltype(t)::T XT;
+        SLK_RUN(name, flops, bytes, s,
+                (k_hadamard_quantize<XT, FMT><<<grid, HD_THREADS, lds, s>>>(static_cast<const XT *>(X), (size_t)rows, n, lb, signs, c, a_codes, a_scales, flag)));
+        return SLK_OK;
+    });
 }
 
 extern "C" {
@@ -392,13 +368,13 @@ int slk_hadamard_rows(const void *X, int x_dtype, void *Y, int y_dtype, long lon
 int slk_mx_rotate_quantize_act(const void *X, int x_dtype, long long rows, int n, int block, const float *signs, int fmt,
                                uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
     SLK_REQUIRE(fmt == SLK_MX_ACT_FP8 || fmt == SLK_MX_ACT_FP4, "unknown fmt %d", fmt);
-    return mx_rotate_quantize("mx_rotate_quantize_act", X, x_dtype, rows, n, block, signs, fmt == SLK_MX_ACT_FP4 ? MXA_E2M1 : MXA_E4M3, a_codes,
-                              a_scales, flag, stream);
+    const auto body = fmt == SLK_MX_ACT_FP4 ? mx_rotate_quantize<MXA_E2M1> : mx_rotate_quantize<MXA_E4M3>;
+    return body("mx_rotate_quantize_act", X, x_dtype, rows, n, block, signs, a_codes, a_scales, flag, stream);
 }
 
 int slk_mx_rotate_quantize_act6(const void *X, int x_dtype, long long rows, int n, int block, const float *signs, uint8_t *a_codes,
                                 uint8_t *a_scales, int *flag, slk_stream_t stream) {
-    return mx_rotate_quantize("mx_rotate_quantize_act6", X, x_dtype, rows, n, block, signs, MXA_E2M3, a_codes, a_scales, flag, stream);
+    return mx_rotate_quantize<MXA_E2M3>("mx_rotate_quantize_act6", X, x_dtype, rows, n, block, signs, a_codes, a_scales, flag, stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mxquant.h"
 
 namespace slk {
 
@@ -45,10 +46,6 @@ __device__ __forceinline__ float e2m1_value(unsigned c, float sc) {
     const int m = (int)(c & 7u);
     const unsigned sign = m ? (c & 8u) << 28 : 0u;
     return __uint_as_float(e2m1_bits(m) | sign) * sc;
-}
-// 2^(b - 127) for a scale byte (0: the denormal 2^-127; 255 is E8M0's NaN)
-__device__ __forceinline__ float e8m0_value(unsigned b) {
-    return __uint_as_float(b == 0u ? 0x00400000u : (b == 255u ? 0x7fc00000u : b << 23));
 }
 
 // ---------------------------------------------------------------- scale selection
@@ -266,8 +263,6 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const uint8_t *__restrict
 }  // namespace slk
 
 using namespace slk;
-
-static inline bool aligned16(const void *p) { return (uintptr_t)p % 16 == 0; }
 
 extern "C" {
 

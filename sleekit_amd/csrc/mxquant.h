@@ -1,6 +1,9 @@
-// The element encoders and the block scale of the MX activation formats (include/sleekit_amd.h): shared by the plain
-// quantizers of mxgemm.hip and by the rotation's quantizing epilogue in hadamard.hip, so that both write the same bits.
+// What a kernel knows of an MX activation format (include/sleekit_amd.h): the element encoders and decoders, the block
+// scale, and how one lane's codes are packed, stored and read back.  Shared by the plain quantizer and the de-quantizer
+// of mxgemm.hip and by the rotation's quantizing epilogue in hadamard.hip, so that all of them write and read the same bits.
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -15,6 +18,14 @@ __device__ __forceinline__ unsigned e4m3_code(unsigned a) {
     const unsigned normal = min(((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - (120u << 3), 0x7eu);
     const unsigned sub = (unsigned)rintf(__uint_as_float(a) * 512.0f);
     return a >= 0x3c800000u ? normal : sub;
+}
+
+// the float32 value of a code; 0x7f / 0xff are NaN
+__device__ __forceinline__ float e4m3_value(unsigned c) {
+    const unsigned e = (c >> 3) & 15u, m = c & 7u;
+    const float mag = e ? __uint_as_float(((e + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
+    const float v = (c & 0x7fu) == 0x7fu ? __uint_as_float(0x7fc00000u) : mag;
+    return (c & 0x80u) ? -v : v;
 }
 
 // ---------------------------------------------------------------- E2M1
@@ -39,14 +50,30 @@ __device__ __forceinline__ unsigned e2m3_code(unsigned a) {
     return a >= 0x3f800000u ? normal : sub;
 }
 
+// the float32 value of a code (bias 1, subnormals m / 8, no NaN)
+__device__ __forceinline__ float e2m3_value(unsigned c) {
+    const unsigned e = (c >> 3) & 3u, m = c & 7u;
+    const float mag = e ? __uint_as_float(((e + 126u) << 23) | (m << 20)) : (float)m * 0.125f;
+    return (c & 0x20u) ? -mag : mag;
+}
+
+// ---------------------------------------------------------------- E8M0
+// 2^(b - 127) for a scale byte (0: the denormal 2^-127; 255 is E8M0's NaN)
+__device__ __forceinline__ float e8m0_value(unsigned b) {
+    return __uint_as_float(b == 0u ? 0x00400000u : (b == 255u ? 0x7fc00000u : b << 23));
+}
+
 // The formats of an activation block: the largest magnitude of its element grid divides the block's largest |x|.
 enum { MXA_E4M3 = 0, MXA_E2M1 = 1, MXA_E2M3 = 2 };
 
 template <int FMT>
 __device__ __forceinline__ constexpr float mxa_largest() { return FMT == MXA_E2M1 ? 6.0f : FMT == MXA_E2M3 ? 7.5f : 448.0f; }
-// bits a code (a block of 32 codes is four times as many bytes)
+// bits a code
 template <int FMT>
 __host__ __device__ constexpr int mxa_bits() { return FMT == MXA_E2M1 ? 4 : FMT == MXA_E2M3 ? 6 : 8; }
+// bytes a block in memory: 32 codes and the scale byte
+template <int FMT>
+__host__ __device__ constexpr int mxa_block_bytes() { return 4 * mxa_bits<FMT>() + 1; }
 
 // `top`: the largest magnitude bits of a block (an integer maximum: a NaN or an infinity is the largest).  The exponent
 // field of the smallest power of two >= max(amax / LARGEST, 1e-16): 74 (the floor) .. 247 for 448, .. 253 for 6 and 7.5.
@@ -74,6 +101,14 @@ __device__ __forceinline__ unsigned mxa_code(float x, float inv) {
     }
 }
 
+// ... and the value of a code (E2M1 is the weights' format: its decoder is mx.hip's)
+template <int FMT>
+__device__ __forceinline__ float mxa_value(unsigned c) {
+    static_assert(FMT == MXA_E4M3 || FMT == MXA_E2M3, "no decoder for this format here");
+    if constexpr (FMT == MXA_E2M3) return e2m3_value(c);
+    else return e4m3_value(c);
+}
+
 // N codes of BITS bits as a little-endian bit stream in N BITS / 32 words: code e at bits BITS e .. BITS e + BITS - 1.
 // For 4 and 8 bits a code lies inside one word; a 6-bit code may straddle two (every index here is a constant once
 // the loop is unrolled, so a lane's words are built with shifts and ors alone).
@@ -89,6 +124,59 @@ __device__ __forceinline__ void mxa_pack(const float (&x)[N], float inv, unsigne
         w[word] |= c << shift;
         if (shift + BITS > 32) w[word + 1] |= c >> (32 - shift);
     }
+}
+
+// One lane's words in memory: one, two or four of them move as one aligned vector, three (16 E2M3 codes: 12 bytes of a
+// row whose blocks are 24) as Codes12, three dwords, every one of them aligned.
+struct alignas(4) Codes12 {
+    unsigned w[3];
+};
+
+// The byte of a row-major matrix's bit stream at which element e starts, for an e whose codes before it are whole bytes
+// (a multiple of 8 / gcd(BITS, 8): 1, 2 or 4 elements -- the gcd is BITS' lowest set bit).
+template <int FMT>
+__host__ __device__ constexpr size_t mxa_byte_of(size_t e) {
+    constexpr int BITS = mxa_bits<FMT>(), G = BITS & -BITS;
+    return e / (8 / G) * (BITS / G);
+}
+
+// mxa_pack's words to `at` in one store, and back in one load.
+template <int FMT, int N>
+__device__ __forceinline__ void mxa_store(uint8_t *at, const unsigned (&w)[N * mxa_bits<FMT>() / 32]) {
+    constexpr int WORDS = N * mxa_bits<FMT>() / 32;
+    static_assert(N * mxa_bits<FMT>() % 32 == 0 && WORDS >= 1 && WORDS <= 4, "a lane stores one to four whole dwords");
+    if constexpr (WORDS == 3) {
+        *reinterpret_cast<Codes12 *>(at) = (Codes12){{w[0], w[1], w[2]}};
+    } else {
+        typedef unsigned V __attribute__((ext_vector_type(WORDS)));
+        V v;
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k) v[k] = w[k];
+        *reinterpret_cast<V *>(at) = v;
+    }
+}
+template <int FMT, int N>
+__device__ __forceinline__ void mxa_load(const uint8_t *at, unsigned (&w)[N * mxa_bits<FMT>() / 32]) {
+    constexpr int WORDS = N * mxa_bits<FMT>() / 32;
+    static_assert(N * mxa_bits<FMT>() % 32 == 0 && WORDS >= 1 && WORDS <= 4, "a lane loads one to four whole dwords");
+    typedef unsigned V __attribute__((ext_vector_type(WORDS)));
+    typedef typename std::conditional<WORDS == 3, Codes12, V>::type C;
+    const C c = *reinterpret_cast<const C *>(at);
+#pragma unroll
+    for (int k = 0; k < WORDS; ++k) {
+        if constexpr (WORDS == 3) w[k] = c.w[k];
+        else w[k] = c[k];
+    }
+}
+
+// Code e of mxa_pack's words (e a constant once the caller's loop is unrolled).
+template <int FMT, int WORDS>
+__device__ __forceinline__ unsigned mxa_code_at(const unsigned (&w)[WORDS], int e) {
+    constexpr int BITS = mxa_bits<FMT>();
+    const int at = BITS * e, word = at >> 5, shift = at & 31;
+    unsigned c = w[word] >> shift;
+    if (shift + BITS > 32) c |= w[word + 1] << (32 - shift);
+    return c & ((1u << BITS) - 1u);
 }
 
 }  // namespace slk

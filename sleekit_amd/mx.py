@@ -201,21 +201,7 @@ def decode_scales(E):
 def dequantize_mxfp4(codes, scales, dtype=torch.float32):
     """The layer rebuilt from its packed form: (R, n) of `dtype` (float32: bit for bit the Q that was packed; bfloat16 or
     float16: that value rounded to nearest even, `.to(dtype)`).  NumPy input gives a NumPy array, which has no bfloat16."""
-    if dtype not in _OUT:
-        raise ValueError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16 (got {dtype})")
-    if isinstance(codes, np.ndarray) and dtype == torch.bfloat16:
-        raise ValueError("NumPy has no bfloat16: pass the codes as a device tensor for a bfloat16 result")
-    R, half = _matrix(codes, "codes", (torch.uint8, np.uint8))
-    n = 2 * half
-    _blocks(n)
-    _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
-    _check_scale_shape(scales, R, n, "scale bytes")
-    cd, sd = _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8)
-    out = torch.empty((R, n), dtype=dtype, device=cd.device)
-    flag = torch.empty(1, dtype=torch.int32, device=cd.device)
-    _lib.check(_lib.lib.slk_mx_dequantize(dev.ptr(cd), dev.ptr(sd), R, n, _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.stream_handle()))
-    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
-    return dev.like_input(out, codes)
+    return _dequantize(codes, scales, dtype, _FORMATS["mxfp4"], "codes")
 
 
 def quantize_layer_mxfp4(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_moves=0, scales=None, min_block_size=32,
@@ -257,57 +243,28 @@ _ACT = (torch.float32, torch.bfloat16, torch.float16, np.float32, np.float16)
 _NP_OUT = {torch.float32: np.float32, torch.float16: np.float16}
 
 
-def _out_dtype(dtype, template):
+def _out_dtype(dtype, template, what="input"):
     if dtype not in _OUT:
         raise ValueError(f"dtype must be torch.float32, torch.bfloat16 or torch.float16 (got {dtype})")
     if isinstance(template, np.ndarray) and dtype == torch.bfloat16:
-        raise ValueError("NumPy has no bfloat16: pass the input as a device tensor for a bfloat16 result")
+        raise ValueError(f"NumPy has no bfloat16: pass the {what} as a device tensor for a bfloat16 result")
 
 
 def _torch_dtype(x):
     return x.dtype if isinstance(x, torch.Tensor) else {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}[x.dtype]
 
 
-def _quantize_act(Xd, M, K):
-    """(a_codes, a_scales, flag) of a contiguous device X (M, K) of float32, bfloat16 or float16; the caller reads the flag
-    (_raise_finite) once everything that follows has been launched: reading it waits for the stream."""
-    Xd = _aligned(Xd)
-    codes = torch.empty((M, K), dtype=torch.uint8, device=Xd.device)
-    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
-    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
-    _lib.check(_lib.lib.slk_mx_quantize_act(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
-    return codes, scales, flag
-
-
-def _quantize_act4(Xd, M, K):
-    """_quantize_act for MXFP4 activations: a_codes (M, K / 2)."""
-    Xd = _aligned(Xd)
-    codes = torch.empty((M, K // 2), dtype=torch.uint8, device=Xd.device)
-    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
-    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
-    _lib.check(_lib.lib.slk_mx_quantize_act4(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
-    return codes, scales, flag
-
-
-def _quantize_act6(Xd, M, K):
-    """_quantize_act for MXFP6 (E2M3) activations: a_codes (M, 3 K / 4)."""
-    Xd = _aligned(Xd)
-    codes = torch.empty((M, 3 * K // 4), dtype=torch.uint8, device=Xd.device)
-    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
-    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
-    _lib.check(_lib.lib.slk_mx_quantize_act6(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
-    return codes, scales, flag
-
-
-# An activation format: the bits of a code (a_codes is (M, K bits / 8)), its plain quantizer and its product.
-_Format = collections.namedtuple("_Format", "name bits quantize gemm")
-_FORMATS = {
-    "mxfp8": _Format("mxfp8", 8, _quantize_act, "slk_mx_gemm"),
-    "mxfp4": _Format("mxfp4", 4, _quantize_act4, "slk_mx_gemm_a4"),
-    "mxfp6_e2m3": _Format("mxfp6_e2m3", 6, _quantize_act6, "slk_mx_gemm_a6"),
-}
+# An activation format as plain data: the bits of a code (a_codes is (M, K bits / 8)), the C entries of its plain quantizer,
+# its de-quantizer (MXFP4's is the layer's own) and its product, and how the fused rotate-and-quantize entry is called: its
+# name and the `fmt` argument it takes (None: the entry takes none).
+_Format = collections.namedtuple("_Format", "name bits quantize_entry dequantize_entry gemm_entry rotate_entry rotate_fmt")
+_FORMATS = {f.name: f for f in (
+    _Format("mxfp8", 8, "slk_mx_quantize_act", "slk_mx_dequantize_act", "slk_mx_gemm", "slk_mx_rotate_quantize_act", _lib.MX_ACT_FP8),
+    _Format("mxfp4", 4, "slk_mx_quantize_act4", "slk_mx_dequantize", "slk_mx_gemm_a4", "slk_mx_rotate_quantize_act", _lib.MX_ACT_FP4),
+    _Format("mxfp6_e2m3", 6, "slk_mx_quantize_act6", "slk_mx_dequantize_act6", "slk_mx_gemm_a6", "slk_mx_rotate_quantize_act6", None),
+)}
 _ACTIVATIONS = tuple(_FORMATS)
-_ACTIVATIONS_ARE = 'activations must be "mxfp8", "mxfp4" or "mxfp6_e2m3"'
+_ACTIVATIONS_ARE = "activations must be " + ", ".join(f'"{name}"' for name in _ACTIVATIONS[:-1]) + f' or "{_ACTIVATIONS[-1]}"'
 
 
 def _activations(activations):
@@ -317,24 +274,43 @@ def _activations(activations):
     return _FORMATS[activations]
 
 
+def _act_outputs(Xd, M, K, fmt):
+    codes = torch.empty((M, K * fmt.bits // 8), dtype=torch.uint8, device=Xd.device)
+    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
+    return codes, scales, torch.empty(1, dtype=torch.int32, device=Xd.device)
+
+
+def _quantize_act(Xd, M, K, fmt=_FORMATS["mxfp8"]):
+    """(a_codes, a_scales, flag) of a contiguous device X (M, K) of float32, bfloat16 or float16 in the _Format fmt; the
+    caller reads the flag (_raise_finite) once everything that follows has been launched: reading it waits for the stream."""
+    Xd = _aligned(Xd)
+    codes, scales, flag = _act_outputs(Xd, M, K, fmt)
+    _lib.check(getattr(_lib.lib, fmt.quantize_entry)(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag),
+                                                     dev.stream_handle()))
+    return codes, scales, flag
+
+
+# The names and the call tests/test_gpu_mx_act4.py and test_gpu_mx_act6.py hold the fused kernel against (their two steps):
+# the plain quantizer of MXFP4 and of MXFP6 under a name of its own, and False / True for MXFP8 / MXFP4 below.
+def _quantize_act4(Xd, M, K):
+    return _quantize_act(Xd, M, K, _FORMATS["mxfp4"])
+
+
+def _quantize_act6(Xd, M, K):
+    return _quantize_act(Xd, M, K, _FORMATS["mxfp6_e2m3"])
+
+
 def _rotate_quantize_act(Xd, M, K, rotation, fmt):
-    """(a_codes, a_scales, flag) of (X R) without X R in memory: the transform's float32 value goes into the quantizer.
-    fmt: a _Format, or False / True for MXFP8 / MXFP4."""
+    """_quantize_act of (X R) without X R in memory: the transform's float32 value goes into the quantizer."""
     if isinstance(fmt, bool):
         fmt = _FORMATS["mxfp4" if fmt else "mxfp8"]
     Xd = _aligned(Xd)
     signs = rotation.signs if rotation.signs.device == Xd.device else rotation.signs.to(Xd.device)
     signs = _aligned(signs)
-    codes = torch.empty((M, K * fmt.bits // 8), dtype=torch.uint8, device=Xd.device)
-    scales = torch.empty((M, K // BLOCK), dtype=torch.uint8, device=Xd.device)
-    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
-    if fmt.bits == 6:
-        _lib.check(_lib.lib.slk_mx_rotate_quantize_act6(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs), dev.ptr(codes),
-                                                        dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
-    else:
-        _lib.check(_lib.lib.slk_mx_rotate_quantize_act(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs),
-                                                       _lib.MX_ACT_FP4 if fmt.bits == 4 else _lib.MX_ACT_FP8, dev.ptr(codes), dev.ptr(scales),
-                                                       dev.ptr(flag), dev.stream_handle()))
+    codes, scales, flag = _act_outputs(Xd, M, K, fmt)
+    which = () if fmt.rotate_fmt is None else (fmt.rotate_fmt,)
+    _lib.check(getattr(_lib.lib, fmt.rotate_entry)(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs), *which, dev.ptr(codes),
+                                                   dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
     return codes, scales, flag
 
 
@@ -344,8 +320,8 @@ def _raise_finite(flag):
 
 def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"]):
     out = torch.empty((M, N), dtype=dtype, device=ac.device)
-    _lib.check(getattr(_lib.lib, fmt.gemm)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _OUT[dtype],
-                                           dev.ptr(out), dev.stream_handle()))
+    _lib.check(getattr(_lib.lib, fmt.gemm_entry)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K,
+                                                 _OUT[dtype], dev.ptr(out), dev.stream_handle()))
     return out
 
 
@@ -368,72 +344,64 @@ def _bias(bias):
     return None if bias is None else dev.to_device(bias)
 
 
+def _quantize(X, fmt):
+    M, K = _matrix(X, "X", _ACT)
+    _blocks(K)
+    codes, scales, flag = _quantize_act(dev.to_device(X, _torch_dtype(X)), M, K, fmt)
+    _raise_finite(flag)
+    return dev.like_input(codes, X), dev.like_input(scales, X)
+
+
 def quantize_mxfp8(X):
     """X (M, K) float32, bfloat16 or float16 -> (a_codes uint8 (M, K), a_scales uint8 (M, K / 32)): MXFP8 E4M3 under
     non-saturating power-of-two block scales (module docstring).  A NaN or an infinity in X: ValueError."""
-    M, K = _matrix(X, "X", _ACT)
-    _blocks(K)
-    codes, scales, flag = _quantize_act(dev.to_device(X, _torch_dtype(X)), M, K)
-    _raise_finite(flag)
-    return dev.like_input(codes, X), dev.like_input(scales, X)
+    return _quantize(X, _FORMATS["mxfp8"])
 
 
 def quantize_mxfp4_act(X):
     """X (M, K) float32, bfloat16 or float16 -> (a_codes uint8 (M, K / 2), a_scales uint8 (M, K / 32)): MXFP4 activations
     (module docstring, W4A4); dequantize_mxfp4(a_codes, a_scales) is the inverse.  A NaN or an infinity in X: ValueError."""
-    M, K = _matrix(X, "X", _ACT)
-    _blocks(K)
-    codes, scales, flag = _quantize_act4(dev.to_device(X, _torch_dtype(X)), M, K)
-    _raise_finite(flag)
-    return dev.like_input(codes, X), dev.like_input(scales, X)
+    return _quantize(X, _FORMATS["mxfp4"])
 
 
 def quantize_mxfp6_act(X):
     """X (M, K) float32, bfloat16 or float16 -> (a_codes uint8 (M, 3 K / 4), a_scales uint8 (M, K / 32)): MXFP6 E2M3
     activations (module docstring, W4A6); dequantize_mxfp6_act is the inverse.  A NaN or an infinity in X: ValueError."""
-    M, K = _matrix(X, "X", _ACT)
-    _blocks(K)
-    codes, scales, flag = _quantize_act6(dev.to_device(X, _torch_dtype(X)), M, K)
-    _raise_finite(flag)
-    return dev.like_input(codes, X), dev.like_input(scales, X)
+    return _quantize(X, _FORMATS["mxfp6_e2m3"])
 
 
-def _columns6(width):
-    """K of an MXFP6 a_codes of `width` bytes a row (24 bytes a block of 32)."""
-    if width < 24 or width % 24 != 0:
-        raise ValueError(f"MXFP6 blocks of {BLOCK} columns are 24 bytes: a_codes must have a positive multiple of 24 columns (got {width})")
-    return width // 24 * BLOCK
+def _columns(width, fmt):
+    """K of codes of `width` bytes a row in the _Format fmt: a whole number of codes, and of blocks (4 bits bytes each)."""
+    if 8 * width % fmt.bits != 0:
+        raise ValueError(f"a_codes has {width} columns of bytes, which is no whole number of {fmt.bits}-bit codes")
+    return BLOCK * _blocks(8 * width // fmt.bits)
+
+
+def _dequantize(codes, scales, dtype, fmt, what):
+    """value(code) * 2^(b - 127) of codes in the _Format fmt, (M, K) of `dtype`; `what` names the codes in an error."""
+    _out_dtype(dtype, codes, "codes" if what == "codes" else "input")
+    M, width = _matrix(codes, what, (torch.uint8, np.uint8))
+    K = _columns(width, fmt)
+    _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(scales, M, K, "scale bytes")
+    cd, sd = _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8)
+    out = torch.empty((M, K), dtype=dtype, device=cd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=cd.device)
+    _lib.check(getattr(_lib.lib, fmt.dequantize_entry)(dev.ptr(cd), dev.ptr(sd), M, K, _OUT[dtype], dev.ptr(out), dev.ptr(flag),
+                                                       dev.stream_handle()))
+    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
+    return dev.like_input(out, codes)
 
 
 def dequantize_mxfp6_act(a_codes, a_scales, dtype=torch.float32):
     """value(code) * 2^(b - 127) of MXFP6 E2M3 activations, (M, K) of `dtype`: exact in float32; bfloat16 or float16: that
     value rounded to nearest even."""
-    _out_dtype(dtype, a_codes)
-    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    K = _columns6(width)
-    _matrix(a_scales, "scale bytes", (torch.uint8, np.uint8))
-    _check_scale_shape(a_scales, M, K, "scale bytes")
-    cd, sd = _aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8)
-    out = torch.empty((M, K), dtype=dtype, device=cd.device)
-    flag = torch.empty(1, dtype=torch.int32, device=cd.device)
-    _lib.check(_lib.lib.slk_mx_dequantize_act6(dev.ptr(cd), dev.ptr(sd), M, K, _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.stream_handle()))
-    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
-    return dev.like_input(out, a_codes)
+    return _dequantize(a_codes, a_scales, dtype, _FORMATS["mxfp6_e2m3"], "a_codes")
 
 
 def dequantize_mxfp8(a_codes, a_scales, dtype=torch.float32):
     """value(code) * 2^(b - 127), (M, K) of `dtype` (bfloat16 or float16: the float32 value rounded to nearest even)."""
-    _out_dtype(dtype, a_codes)
-    M, K = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    _blocks(K)
-    _matrix(a_scales, "scale bytes", (torch.uint8, np.uint8))
-    _check_scale_shape(a_scales, M, K, "scale bytes")
-    cd, sd = _aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8)
-    out = torch.empty((M, K), dtype=dtype, device=cd.device)
-    flag = torch.empty(1, dtype=torch.int32, device=cd.device)
-    _lib.check(_lib.lib.slk_mx_dequantize_act(dev.ptr(cd), dev.ptr(sd), M, K, _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.stream_handle()))
-    _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
-    return dev.like_input(out, a_codes)
+    return _dequantize(a_codes, a_scales, dtype, _FORMATS["mxfp8"], "a_codes")
 
 
 def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, activations="mxfp8"):
@@ -443,10 +411,7 @@ def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, 
     fmt = _activations(activations)
     _out_dtype(dtype, a_codes)
     M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    if 8 * width % fmt.bits != 0:
-        raise ValueError(f"a_codes has {width} columns of bytes, which is no whole number of {fmt.bits}-bit codes")
-    K = 8 * width // fmt.bits
-    _blocks(K)
+    K = _columns(width, fmt)
     _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(a_scales, M, K, "activation scale bytes")
     N, Kw = _weights(codes, scales)
@@ -492,7 +457,7 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
     if rotation is not None:
         ac, asc, flag = _rotate_quantize_act(Xd, M, K, rotation, fmt)
     else:
-        ac, asc, flag = fmt.quantize(Xd, M, K)
+        ac, asc, flag = _quantize_act(Xd, M, K, fmt)
     out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt)
     _raise_finite(flag)
     return dev.like_input(out.reshape(lead + (N,)), x)

@@ -2,7 +2,7 @@
 """MXFP4 and MXFP6 activations against MXFP8 ones, and the rotation fused into the quantizer against the two steps, on the
 MI355X.
 
-    python tools/micro_mx_act.py [--reps 20] [--m 1,16,256,4096] [--only linear|fused] [--parent-lib libsleekit_amd.so]
+    python tools/micro_mx_act.py [--reps 20] [--m 1,16,256,4096] [--only linear|fused|quantize] [--parent-lib libsleekit_amd.so]
 
 Every side runs on preallocated outputs and is timed with device events (median of `reps` after a warm-up, with
 [min, max]); the sides of a row alternate call by call in one process.
@@ -11,8 +11,8 @@ Every side runs on preallocated outputs and is timed with device events (median 
           (a8) slk_mx_quantize_act  + slk_mx_gemm      what linear_mxfp4 launches by default (W4A8)
           (a6) slk_mx_quantize_act6 + slk_mx_gemm_a6   what activations="mxfp6_e2m3" launches (W4A6)
           (a4) slk_mx_quantize_act4 + slk_mx_gemm_a4   what activations="mxfp4" launches (W4A4)
-          and, with --parent-lib (a library built from another commit), (p8) and (p4): W4A8 and W4A4 through that
-          library, in the same rotation.  Each side is in the rotation twice: the difference of the two medians of one
+          and, with --parent-lib (a library built from another commit), (p8), (p6) and (p4): W4A8, W4A6 and W4A4 through
+          that library, in the same rotation.  Each side is in the rotation twice: the difference of the two medians of one
           side is the run-to-run spread.
           M <= 16 moves the weights once and is held against HBM (6.3 TB/s); M >= 256 against the block-scaled MFMA
           peak of its format (5 PFLOP/s E4M3, 10 PFLOP/s E2M3 and E2M1).
@@ -20,6 +20,9 @@ Every side runs on preallocated outputs and is timed with device events (median 
           (two) slk_hadamard_rows to float32 + slk_mx_quantize_act / _act6 / _act4
           (one) slk_mx_rotate_quantize_act / _act6
           with the bytes each must move as a share of HBM.
+  quantize  4096 x 11008 bfloat16: each plain quantizer (slk_mx_quantize_act, _act6, _act4) and each activation
+          de-quantizer (slk_mx_dequantize_act, _act6, to bfloat16) alone, this library and --parent-lib (required) alternating,
+          each side twice; the spread is the difference of the parent's own two medians.
 One JSON line per row and side.
 """
 
@@ -75,7 +78,8 @@ def stats(t):
 
 BITS = {"a8": 8, "a6": 6, "a4": 4}
 NAMES = {"a8": "W4A8: quantize_act + mx_gemm", "a6": "W4A6: quantize_act6 + mx_gemm_a6", "a4": "W4A4: quantize_act4 + mx_gemm_a4",
-         "p8": "parent W4A8: quantize_act + mx_gemm", "p4": "parent W4A4: quantize_act4 + mx_gemm_a4"}
+         "p8": "parent W4A8: quantize_act + mx_gemm", "p6": "parent W4A6: quantize_act6 + mx_gemm_a6",
+         "p4": "parent W4A4: quantize_act4 + mx_gemm_a4"}
 
 
 def linear_rows(N, K, M, reps, parent=None):
@@ -103,6 +107,7 @@ def linear_rows(N, K, M, reps, parent=None):
              ("a4", side(L, "slk_mx_quantize_act4", "slk_mx_gemm_a4", ac["a4"]))]
     if parent is not None:
         sides += [("p8", side(parent, "slk_mx_quantize_act", "slk_mx_gemm", ac["a8"])),
+                  ("p6", side(parent, "slk_mx_quantize_act6", "slk_mx_gemm_a6", ac["a6"])),
                   ("p4", side(parent, "slk_mx_quantize_act4", "slk_mx_gemm_a4", ac["a4"]))]
     ts = timed([fn for _, fn in sides] * 2, reps)
     first, second = ts[:len(sides)], ts[len(sides):]
@@ -126,13 +131,49 @@ def linear_rows(N, K, M, reps, parent=None):
                           a6_over_a4=round(t6[0] / t4[0], 3), a6_median_at_or_below_a8=bool(max(t6[0], t6b[0]) <= min(t8[0], t8b[0])),
                           a6_median_within_a8_range=bool(min(t8[1], t8b[1]) <= min(t6[0], t6b[0]) and max(t6[0], t6b[0]) <= max(t8[2], t8b[2])),
                           spread_us=round(spread, 1))), flush=True)
-    for here, there in (("a8", "p8"), ("a4", "p4")):
+    for here, there in (("a8", "p8"), ("a6", "p6"), ("a4", "p4")):
         if there in out:
-            (t, tb), (p, pb) = out[here], out[there]
-            lo, hi = min(p[1], pb[1]), max(p[2], pb[2])
-            print(json.dumps(dict(bench="linear", size=f"{N}x{K}", M=M, side=f"{NAMES[here][:4]} against the parent's", this_us=round(t[0], 1),
-                                  parent_us=round(p[0], 1), this_over_parent=round(t[0] / p[0], 3),
-                                  this_median_within_parent_range=bool(lo <= min(t[0], tb[0]) and max(t[0], tb[0]) <= hi))), flush=True)
+            print(json.dumps(dict(bench="linear", size=f"{N}x{K}", M=M, side=f"{NAMES[here][:4]} against the parent's",
+                                  **against_parent(out[here], out[there]))), flush=True)
+
+
+def against_parent(this, parent):
+    """This library's two (median, min, max) against the parent's two, as the fields of a comparison row."""
+    (t, tb), (p, pb) = this, parent
+    lo, hi = min(p[1], pb[1]), max(p[2], pb[2])
+    return dict(this_us=round(t[0], 1), this_repeat_us=round(tb[0], 1), parent_us=round(p[0], 1), parent_repeat_us=round(pb[0], 1),
+                parent_min_us=round(lo, 1), parent_max_us=round(hi, 1), this_over_parent=round(t[0] / p[0], 3),
+                parent_spread=round(abs(p[0] - pb[0]) / p[0], 3),
+                this_median_within_parent_range=bool(lo <= min(t[0], tb[0]) and max(t[0], tb[0]) <= hi))
+
+
+def quantize_rows(M, K, reps, parent):
+    """Each plain quantizer and each activation de-quantizer alone, this library against the parent's."""
+    s = dev.stream_handle
+    gen = torch.Generator(device="cuda").manual_seed(M + K)
+    x = torch.randn((M, K), device="cuda", generator=gen).to(torch.bfloat16)
+    asc = torch.empty((M, K // 32), dtype=torch.uint8, device="cuda")
+    flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+    back = torch.empty((M, K), dtype=torch.bfloat16, device="cuda")
+    for what, bits, quantize, dequantize in (("mxfp8", 8, "slk_mx_quantize_act", "slk_mx_dequantize_act"),
+                                             ("mxfp6_e2m3", 6, "slk_mx_quantize_act6", "slk_mx_dequantize_act6"),
+                                             ("mxfp4", 4, "slk_mx_quantize_act4", None)):
+        a = torch.empty((M, K * bits // 8), dtype=torch.uint8, device="cuda")
+
+        def forth(lib):
+            return lambda: _lib.check(getattr(lib, quantize)(dev.ptr(x), _lib.DTYPE_BF16, M, K, dev.ptr(a), dev.ptr(asc), dev.ptr(flag), s()))
+
+        def and_back(lib):
+            return lambda: _lib.check(getattr(lib, dequantize)(dev.ptr(a), dev.ptr(asc), M, K, _lib.DTYPE_BF16, dev.ptr(back), dev.ptr(flag), s()))
+
+        for entry, side in ((quantize, forth), (dequantize, and_back)):
+            if entry is None:  # (MXFP4 activations are de-quantized by the layer's own slk_mx_dequantize)
+                continue
+            this, there, this2, there2 = timed([side(L), side(parent)] * 2, reps)
+            nbytes = 2 * M * K + M * K * bits // 8 + M * K // 32
+            print(json.dumps(dict(bench="quantize", shape=f"{M}x{K}", fmt=what, side=f"{entry} against the parent's", **stats(this), bytes=nbytes,
+                                  share_of_hbm=round(nbytes / HBM * 1e6 / this[0], 3), **against_parent((this, this2), (there, there2)))),
+                  flush=True)
 
 
 def fused_rows(rows, n, block, reps):
@@ -187,19 +228,22 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--m", default="1,16,256,4096")
-    ap.add_argument("--only", choices=("linear", "fused"), default=None)
-    ap.add_argument("--parent-lib", default=None, help="a libsleekit_amd.so built from another commit: its W4A8 and W4A4 join the rotation")
+    ap.add_argument("--only", choices=("linear", "fused", "quantize"), default=None)
+    ap.add_argument("--parent-lib", default=None, help="a libsleekit_amd.so built from another commit: its W4A8, W4A6 and W4A4 join the rotation")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "micro_mx_act measures the MI355X; there is no CPU path"
     torch.cuda.set_device(0)
     parent = load_library(args.parent_lib) if args.parent_lib else None
-    if args.only != "fused":
+    if args.only in (None, "linear"):
         for N, K in ((4096, 4096), (4096, 11008)):
             for M in (int(m) for m in args.m.split(",")):
                 linear_rows(N, K, M, args.reps, parent)
                 torch.cuda.empty_cache()
-    if args.only != "linear":
+    if args.only in (None, "fused"):
         fused_rows(4096, 4096, 4096, args.reps)
+    if args.only == "quantize" or (args.only is None and parent is not None):
+        assert parent is not None, "--only quantize compares against --parent-lib"
+        quantize_rows(4096, 11008, args.reps, parent)
 
 
 if __name__ == "__main__":
