@@ -88,7 +88,8 @@ typedef void *slk_stream_t;
  * pointers), then slk_packed_gemm (a linear layer computed from the packed indices; an addition within 8, nothing existing
  * changed), then slk_hadamard_rows (the block Hadamard rotation of sleekit_amd/rotation.py; likewise), then MXFP4
  * activations: slk_mx_quantize_act4, slk_mx_gemm_a4 and slk_mx_rotate_quantize_act (likewise), then MXFP6 (E2M3)
- * activations: slk_mx_quantize_act6, slk_mx_dequantize_act6, slk_mx_gemm_a6 and slk_mx_rotate_quantize_act6 (likewise). */
+ * activations: slk_mx_quantize_act6, slk_mx_dequantize_act6, slk_mx_gemm_a6 and slk_mx_rotate_quantize_act6 (likewise), then MXFP6
+ * (E2M3) layers: slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6 and slk_mx_gemm_w6 (likewise). */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -608,6 +609,37 @@ int slk_mx_gemm_a6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_
                    const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream);
 int slk_mx_rotate_quantize_act6(const void *X, int x_dtype, long long rows, int n, int block, const float *signs,
                                 uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream);
+
+/* MXFP6 layers: E2M3 weights, 6.25 bits a weight, W6A8 / W6A6 on the block-scaled MFMA (B in E2M3, blgp = 2: FP6 operands
+ * run at the FP4 rate on this chip).  Blocks and `scales` are MXFP4's (above), byte 255 included; only the elements differ.
+ *   - elements: OCP E2M3, code = sign << 5 | e << 3 | m, exactly the MXFP6 activations' values (above).
+ *   - the codebook is the 63-entry table -7.5 .. 7.5 (the 31 non-zero magnitudes on both sides of 0) whose limits are the
+ *     midpoints, a tie going upward.  Table index i < 31 is code 0x20 | (31 - i), otherwise i - 31.  Code 0x20 (-0) is
+ *     never written and reads back as index 31, value +0; an index above 62 is a caller error and is stored as code 0x1f.
+ *   - codes: uint8 R x 3 n / 4.  A row is a little-endian bit stream, element k at bits 6 k .. 6 k + 5: a block is 24 bytes
+ *     and four elements c0 .. c3 make the three bytes of c0 | c1 << 6 | c2 << 12 | c3 << 18 -- the MXFP6 activations' form,
+ *     so slk_mx_dequantize_act6(codes, scales) rebuilds Q = value(idx) / (1 / s) bit for bit.  codes must start on 16
+ *     bytes; rows then start on 8.
+ *   Known answers: indices 0, 1, 30, 31, 32, 61, 62 are codes 3f 3e 21 00 01 1e 1f; columns with codes [01, 02, 3f, 00] pack
+ *   to bytes [81, f0, 03]; indices [0, 62, 31, 32] pack to bytes [ff, 07, 04]; the scale 0.0078125 is byte 120.
+ * slk_mx_scale_search6: slk_mx_scale_search with E2M3 and 7.5 in place of E2M1 and 6: b0 = max(max / 7.5, min / -7.5, 1e-16),
+ *   base the smallest power of two >= b0, the same modes, factors, float32 row sums and first minimum.
+ * slk_mx_pack6 / slk_mx_unpack6: slk_mx_pack's / slk_mx_unpack's contracts (either pair may be NULL, the same scale checks
+ *   and flag) with the index <-> code map and the stream above.
+ * slk_mx_gemm_w6: slk_mx_gemm against such a layer (w_codes N x 3 K / 4): a_fmt SLK_MX_ACT_FP8 (a_codes M x K, W6A8) or
+ *   SLK_MX_ACT_FP6 (a_codes M x 3 K / 4, W6A6); SLK_MX_ACT_FP4 is refused.  The same contract -- exact products, float32
+ *   sums inside the MFMA over K in a fixed order, no atomics, a repeated call gives the same bits, any M, N >= 1.  Nothing
+ *   past the 3 N K / 4 bytes of w_codes is read.
+ * SLK_E_ARG as for their MXFP4 twins, and an a_fmt other than the two above.                                          */
+#define SLK_MX_ACT_FP6 2
+int slk_mx_scale_search6(const float *W, const float *hdiag, int mode, int R, int n, uint8_t *scales, float *S,
+                         slk_stream_t stream);
+int slk_mx_pack6(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag,
+                 slk_stream_t stream);
+int slk_mx_unpack6(const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag,
+                   slk_stream_t stream);
+int slk_mx_gemm_w6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                   const float *bias, int M, int N, int K, int a_fmt, int out_dtype, void *out, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

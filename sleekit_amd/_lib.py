@@ -25,6 +25,7 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2  # slk_dequantize_packed `out_dtype`,
 DTYPE_F64 = 3  # slk_hadamard_rows only
 MX_MAX, MX_MSE, MX_DIAG = 0, 1, 2  # slk_mx_scale_search `mode`
 MX_ACT_FP8, MX_ACT_FP4 = 0, 1  # slk_mx_rotate_quantize_act `fmt`
+MX_ACT_FP6 = 2  # slk_mx_gemm_w6 `a_fmt` (beside MX_ACT_FP8)
 ORDER_NONE, ORDER_DIAG, ORDER_ERR, ORDER_SQERR, ORDER_KEYS = 0, 1, 2, 3, 4
 ORDER_MODES = {"none": ORDER_NONE, "diag": ORDER_DIAG, "err": ORDER_ERR, "sqerr": ORDER_SQERR}
 
@@ -128,6 +129,10 @@ PROTOTYPES = {
     "slk_mx_dequantize_act6": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
     "slk_mx_gemm_a6": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "slk_mx_rotate_quantize_act6": (c_int, [P, c_int, c_longlong, c_int, c_int, P, P, P, P, P]),
+    "slk_mx_scale_search6": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
+    "slk_mx_pack6": (c_int, [P, P, c_int, c_int, P, P, P, P]),
+    "slk_mx_unpack6": (c_int, [P, P, c_int, c_int, P, P, P, P]),
+    "slk_mx_gemm_w6": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

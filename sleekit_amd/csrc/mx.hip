@@ -1,6 +1,7 @@
 // MXFP4: blocks of 32 consecutive columns of a row share one power-of-two scale (an E8M0 byte), the elements are FP4
 // E2M1 codes, two a byte (slk_mx_scale_search, slk_mx_pack, slk_mx_unpack, slk_mx_dequantize; the format is pinned in
-// include/sleekit_amd.h and INTEGRATION.md).
+// include/sleekit_amd.h and INTEGRATION.md).  MXFP6 layers keep E2M3 codes instead, a row as a stream of 6-bit codes
+// (slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6; slk_mx_dequantize_act6 of mxgemm.hip reads that stream back).
 //
 // n % 32 == 0, so block k of the (R, n) layer is elements [32 k, 32 k + 32) of the flat array whatever the row: every
 // kernel here runs over the R n / 32 blocks (64-bit counts) and only the diagonal of H needs a block's place in its row.
@@ -48,12 +49,34 @@ __device__ __forceinline__ float e2m1_value(unsigned c, float sc) {
     return __uint_as_float(e2m1_bits(m) | sign) * sc;
 }
 
+// ---------------------------------------------------------------- E2M3 (MXFP6 layers)
+// e2m1_round's rule on the 32 magnitudes of E2M3: `a` as there, the bits of the magnitude |x| rounds to with a tie upward.
+// The grid is the floats of 3 mantissa bits from 1 up (spacing 2^(e - 3) in binade e) and k / 8 below, which in the binades
+// 1/2, 1/4 and 1/8 is the floats of 2, 1 and 0 mantissa bits, and in the binade of 1/16 the one limit 1/16 = its lowest
+// float, above which everything goes to 1/8: 24 bits cut, the exponent's own lowest bit among them (123 + 1 = 124 is even).
+// So one rule serves all binades -- add half of the last kept bit and cut `cut` = 20 .. 24 bits -- and integer
+// arithmetic alone decides every limit; below 1/16 (-1, a negative zero, included) the answer is 0.  7.5 is the top.
+__device__ __forceinline__ unsigned e2m3_round(int a) {
+    a = min(a, 0x40f00000);  // 7.5
+    const int cut = min(max(147 - (a >> 23), 20), 24);
+    const unsigned r = (((unsigned)a + (1u << (cut - 1))) >> cut) << cut;
+    return a >= 0x3d800000 ? r : 0u;
+}
+
+// The element format of a layer as the scale search sees it: the largest magnitude, and the rounding onto the grid.
+template <int WF>
+__device__ __forceinline__ unsigned mxw_round(int a) {
+    if constexpr (WF == MXA_E2M3) return e2m3_round(a);
+    else return e2m1_round(a);
+}
+
 // ---------------------------------------------------------------- scale selection
 // 8 lanes a block, 8 blocks a wave: lane a of a block keeps elements a, 8 + a, 16 + a, 24 + a (and their diagonal
 // entries) in registers for all four candidates, which is NumPy's running sum r[a] of a 32-element row; the xor steps
 // 1, 2, 4 on DPP combine them as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)).  Nothing goes through LDS.
 // MODE 0: max (the power of two at or above the non-saturating scale), 1: mse, 2: diag (terms weighed by diag(H)).
-template <int MODE>
+// WF: the elements, MXA_E2M1 (largest magnitude 6) or MXA_E2M3 (7.5).
+template <int MODE, int WF = MXA_E2M1>
 __global__ __launch_bounds__(256) void k_mx_scale_search(const float *__restrict__ W, const float *__restrict__ hdiag, size_t blocks,
                                                          int bpr, uint8_t *__restrict__ E, float *__restrict__ S) {
     const int lane = threadIdx.x & 63, q = lane >> 3, a = lane & 7;
@@ -77,7 +100,7 @@ __global__ __launch_bounds__(256) void k_mx_scale_search(const float *__restrict
         mn = fminf(mn, dpp_f<DPP_HALF_MIRROR>(mn));
         mx = fmaxf(mx, dpp_f<DPP_HALF_MIRROR>(mx));
         // scaling.py:53-54 with codes +-6: max(max / 6, min / -6) = max(max, -min) / 6 (a division by 6 is monotonic and odd)
-        const float b0 = fmaxf(fmaxf(mx, -mn) / 6.0f, 1.0e-16f);
+        const float b0 = fmaxf(fmaxf(mx, -mn) / mxa_largest<WF>(), 1.0e-16f);
         // the smallest power of two >= b0, as its exponent field: 74 (the floor) .. 253 for finite weights
         unsigned eb = min(((__float_as_uint(b0) + 0x7fffffu) >> 23) & 0xffu, 253u);
         if constexpr (MODE != 0) {
@@ -98,7 +121,7 @@ __global__ __launch_bounds__(256) void k_mx_scale_search(const float *__restrict
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     // |x| / s, its magnitude on the grid, |v| / (1 / s) - |x|: the error but for its sign, which the square drops
-                    const float v = __uint_as_float(e2m1_round((int)__float_as_uint(ax[i] * inv) - neg[i]));
+                    const float v = __uint_as_float(mxw_round<WF>((int)__float_as_uint(ax[i] * inv) - neg[i]));
                     const float e = v * s - ax[i];
                     const float e2 = e * e;
                     const float term = MODE == 2 ? h[i] * e2 : e2;
@@ -146,20 +169,34 @@ __device__ __forceinline__ unsigned mx_indices_of(unsigned h) {
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 typedef unsigned uint2v __attribute__((ext_vector_type(2)));
 
+// float32 scales -> E8M0 bytes, and back: a block a thread, the same for every element format.
+__device__ __forceinline__ void mx_pack_scales(const float *__restrict__ S, size_t blocks, size_t gid, size_t threads,
+                                               uint8_t *__restrict__ E, int *__restrict__ flag) {
+    bool bad = false;
+    for (size_t k = gid; k < blocks; k += threads) {
+        const unsigned u = __float_as_uint(S[k]), b = u >> 23;  // a positive normal power of two: its exponent field
+        bad |= (u & 0x807fffffu) != 0u || b == 0u || b == 255u;
+        E[k] = (uint8_t)min(b & 0xffu, 254u);
+    }
+    if (bad && flag) *flag = 1;
+}
+__device__ __forceinline__ void mx_unpack_scales(const uint8_t *__restrict__ E, size_t blocks, size_t gid, size_t threads,
+                                                 float *__restrict__ S, int *__restrict__ flag) {
+    bool bad = false;
+    for (size_t k = gid; k < blocks; k += threads) {
+        const unsigned b = E[k];
+        bad |= b == 255u;
+        S[k] = e8m0_value(b);
+    }
+    if (bad && flag) *flag = 1;
+}
+
 // A unit is 16 indices <-> 8 bytes of codes (two lanes a block): one 16-byte and one 8-byte access a lane, contiguous
 // over the wave.  The scales take a loop of their own, a block a thread.
 __global__ __launch_bounds__(256) void k_mx_pack(const uint8_t *__restrict__ idx, const float *__restrict__ S, size_t blocks,
                                                  uint8_t *__restrict__ codes, uint8_t *__restrict__ E, int *__restrict__ flag) {
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
-    if (S) {
-        bool bad = false;
-        for (size_t k = gid; k < blocks; k += threads) {
-            const unsigned u = __float_as_uint(S[k]), b = u >> 23;  // a positive normal power of two: its exponent field
-            bad |= (u & 0x807fffffu) != 0u || b == 0u || b == 255u;
-            E[k] = (uint8_t)min(b & 0xffu, 254u);
-        }
-        if (bad && flag) *flag = 1;
-    }
+    if (S) mx_pack_scales(S, blocks, gid, threads, E, flag);
     if (!idx) return;
     const uint4v *src = reinterpret_cast<const uint4v *>(idx);
     uint2v *dst = reinterpret_cast<uint2v *>(codes);
@@ -186,15 +223,7 @@ __global__ __launch_bounds__(256) void k_mx_pack(const uint8_t *__restrict__ idx
 __global__ __launch_bounds__(256) void k_mx_unpack(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, size_t blocks,
                                                    uint8_t *__restrict__ idx, float *__restrict__ S, int *__restrict__ flag) {
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
-    if (S) {
-        bool bad = false;
-        for (size_t k = gid; k < blocks; k += threads) {
-            const unsigned b = E[k];
-            bad |= b == 255u;
-            S[k] = e8m0_value(b);
-        }
-        if (bad && flag) *flag = 1;
-    }
+    if (S) mx_unpack_scales(E, blocks, gid, threads, S, flag);
     if (!idx) return;
     const uint2v *src = reinterpret_cast<const uint2v *>(codes);
     uint4v *dst = reinterpret_cast<uint4v *>(idx);
@@ -215,6 +244,70 @@ __global__ __launch_bounds__(256) void k_mx_unpack(const uint8_t *__restrict__ c
             o.y = mx_indices_of(v[u].x >> 16);
             o.z = mx_indices_of(v[u].y & 0xffffu);
             o.w = mx_indices_of(v[u].y >> 16);
+            dst[i] = o;
+        }
+    }
+}
+
+// MXFP6.  Index i of the 63-entry table -> E2M3 code: min(i, 62), then i < 31 -> 0x20 | (31 - i), else i - 31; and back:
+// a set sign bit -> 31 - magnitude code (0x20, -0, -> 31), else code + 31.
+__device__ __forceinline__ unsigned mx6_code_of(unsigned i) {
+    i = min(i, 62u);
+    return i < 31u ? 0x20u | (31u - i) : i - 31u;
+}
+__device__ __forceinline__ unsigned mx6_index_of(unsigned c) { return (c & 0x20u) ? 31u - (c & 31u) : c + 31u; }
+
+// A unit is 16 indices <-> 12 bytes of the row's stream of 6-bit codes (two lanes a block, as above): one 16-byte access
+// and three aligned dwords a lane (mxquant.h: the activation quantizer's own packer, store and load).
+__global__ __launch_bounds__(256) void k_mx_pack6(const uint8_t *__restrict__ idx, const float *__restrict__ S, size_t blocks,
+                                                  uint8_t *__restrict__ codes, uint8_t *__restrict__ E, int *__restrict__ flag) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    if (S) mx_pack_scales(S, blocks, gid, threads, E, flag);
+    if (!idx) return;
+    const uint4v *src = reinterpret_cast<const uint4v *>(idx);
+    const size_t units = 2 * blocks;
+    for (size_t i0 = gid; i0 < units; i0 += threads * MX_UNROLL) {
+        uint4v v[MX_UNROLL];
+#pragma unroll
+        for (int u = 0; u < MX_UNROLL; ++u) {
+            const size_t i = i0 + u * threads;
+            if (i < units) v[u] = src[i];
+        }
+#pragma unroll
+        for (int u = 0; u < MX_UNROLL; ++u) {
+            const size_t i = i0 + u * threads;
+            if (i >= units) continue;
+            float x[16];  // the codes' values: the quantizer's packer turns them, under the scale 1, back into their codes
+            unsigned w[3];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) x[e] = e2m3_value(mx6_code_of((v[u][e >> 2] >> (8 * (e & 3))) & 0xffu));
+            mxa_pack<MXA_E2M3, 16>(x, 1.0f, w);
+            mxa_store<MXA_E2M3, 16>(codes + 12 * i, w);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mx_unpack6(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, size_t blocks,
+                                                    uint8_t *__restrict__ idx, float *__restrict__ S, int *__restrict__ flag) {
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    if (S) mx_unpack_scales(E, blocks, gid, threads, S, flag);
+    if (!idx) return;
+    uint4v *dst = reinterpret_cast<uint4v *>(idx);
+    const size_t units = 2 * blocks;
+    for (size_t i0 = gid; i0 < units; i0 += threads * MX_UNROLL) {
+        unsigned w[MX_UNROLL][3];
+#pragma unroll
+        for (int u = 0; u < MX_UNROLL; ++u) {
+            const size_t i = i0 + u * threads;
+            if (i < units) mxa_load<MXA_E2M3, 16>(codes + 12 * i, w[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < MX_UNROLL; ++u) {
+            const size_t i = i0 + u * threads;
+            if (i >= units) continue;
+            uint4v o = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int e = 0; e < 16; ++e) o[e >> 2] |= mx6_index_of(mxa_code_at<MXA_E2M3>(w[u], e)) << (8 * (e & 3));
             dst[i] = o;
         }
     }
@@ -264,9 +357,10 @@ __global__ __launch_bounds__(256) void k_mx_dequantize(const uint8_t *__restrict
 
 using namespace slk;
 
-extern "C" {
-
-int slk_mx_scale_search(const float *W, const float *hdiag, int mode, int R, int n, uint8_t *scales, float *S, slk_stream_t stream) {
+// slk_mx_scale_search (WF MXA_E2M1) and slk_mx_scale_search6 (MXA_E2M3)
+template <int WF>
+static int mx_scale_search(const char *name, const float *W, const float *hdiag, int mode, int R, int n, uint8_t *scales, float *S,
+                           slk_stream_t stream) {
     SLK_REQUIRE(R > 0 && n > 0 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (R = %d, n = %d)", R, n);
     SLK_REQUIRE(mode >= SLK_MX_MAX && mode <= SLK_MX_DIAG, "unknown scale mode %d", mode);
     SLK_REQUIRE(W && (scales || S), "null pointer");
@@ -279,15 +373,18 @@ int slk_mx_scale_search(const float *W, const float *hdiag, int mode, int R, int
     const int grid = (int)(wgs < 8192 ? wgs : 8192);
     const double bytes = 4.0 * R * n + 5.0 * blocks;
     if (mode == SLK_MX_MAX)
-        SLK_RUN("mx_scale_search", 0, bytes, s, k_mx_scale_search<0><<<grid, 256, 0, s>>>(W, hdiag, blocks, bpr, scales, S));
+        SLK_RUN(name, 0, bytes, s, (k_mx_scale_search<0, WF><<<grid, 256, 0, s>>>(W, hdiag, blocks, bpr, scales, S)));
     else if (mode == SLK_MX_MSE)
-        SLK_RUN("mx_scale_search", 0, bytes, s, k_mx_scale_search<1><<<grid, 256, 0, s>>>(W, hdiag, blocks, bpr, scales, S));
+        SLK_RUN(name, 0, bytes, s, (k_mx_scale_search<1, WF><<<grid, 256, 0, s>>>(W, hdiag, blocks, bpr, scales, S)));
     else
-        SLK_RUN("mx_scale_search", 0, bytes, s, k_mx_scale_search<2><<<grid, 256, 0, s>>>(W, hdiag, blocks, bpr, scales, S));
+        SLK_RUN(name, 0, bytes, s, (k_mx_scale_search<2, WF><<<grid, 256, 0, s>>>(W, hdiag, blocks, bpr, scales, S)));
     return SLK_OK;
 }
 
-int slk_mx_pack(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag, slk_stream_t stream) {
+// slk_mx_pack, slk_mx_unpack (BITS 4) and slk_mx_pack6, slk_mx_unpack6 (6): one contract
+template <int BITS>
+static int mx_pack(const char *name, const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag,
+                   slk_stream_t stream) {
     SLK_REQUIRE(R > 0 && n > 0 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (R = %d, n = %d)", R, n);
     SLK_REQUIRE((idx != nullptr) == (codes != nullptr) && (S != nullptr) == (scales != nullptr) && (idx || S),
                 "null pointer: idx goes with codes, S with scales, and one pair is needed");
@@ -295,12 +392,15 @@ int slk_mx_pack(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes
     hipStream_t s = as_stream(stream);
     const size_t blocks = (size_t)R * (n / 32);
     if (flag) zero_async(flag, sizeof(int), s);
-    const double bytes = (idx ? 48.0 : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
-    SLK_RUN("mx_pack", 0, bytes, s, k_mx_pack<<<mx_grid(2 * blocks), 256, 0, s>>>(idx, S, blocks, codes, scales, flag));
+    const double bytes = (idx ? 32.0 + 4.0 * BITS : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
+    if constexpr (BITS == 6) SLK_RUN(name, 0, bytes, s, k_mx_pack6<<<mx_grid(2 * blocks), 256, 0, s>>>(idx, S, blocks, codes, scales, flag));
+    else SLK_RUN(name, 0, bytes, s, k_mx_pack<<<mx_grid(2 * blocks), 256, 0, s>>>(idx, S, blocks, codes, scales, flag));
     return SLK_OK;
 }
 
-int slk_mx_unpack(const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag, slk_stream_t stream) {
+template <int BITS>
+static int mx_unpack(const char *name, const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag,
+                     slk_stream_t stream) {
     SLK_REQUIRE(R > 0 && n > 0 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (R = %d, n = %d)", R, n);
     SLK_REQUIRE((idx != nullptr) == (codes != nullptr) && (S != nullptr) == (scales != nullptr) && (idx || S),
                 "null pointer: codes go with idx, scales with S, and one pair is needed");
@@ -308,9 +408,36 @@ int slk_mx_unpack(const uint8_t *codes, const uint8_t *scales, int R, int n, uin
     hipStream_t s = as_stream(stream);
     const size_t blocks = (size_t)R * (n / 32);
     if (flag) zero_async(flag, sizeof(int), s);
-    const double bytes = (idx ? 48.0 : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
-    SLK_RUN("mx_unpack", 0, bytes, s, k_mx_unpack<<<mx_grid(2 * blocks), 256, 0, s>>>(codes, scales, blocks, idx, S, flag));
+    const double bytes = (idx ? 32.0 + 4.0 * BITS : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
+    if constexpr (BITS == 6) SLK_RUN(name, 0, bytes, s, k_mx_unpack6<<<mx_grid(2 * blocks), 256, 0, s>>>(codes, scales, blocks, idx, S, flag));
+    else SLK_RUN(name, 0, bytes, s, k_mx_unpack<<<mx_grid(2 * blocks), 256, 0, s>>>(codes, scales, blocks, idx, S, flag));
     return SLK_OK;
+}
+
+extern "C" {
+
+int slk_mx_scale_search(const float *W, const float *hdiag, int mode, int R, int n, uint8_t *scales, float *S, slk_stream_t stream) {
+    return mx_scale_search<MXA_E2M1>("mx_scale_search", W, hdiag, mode, R, n, scales, S, stream);
+}
+
+int slk_mx_scale_search6(const float *W, const float *hdiag, int mode, int R, int n, uint8_t *scales, float *S, slk_stream_t stream) {
+    return mx_scale_search<MXA_E2M3>("mx_scale_search6", W, hdiag, mode, R, n, scales, S, stream);
+}
+
+int slk_mx_pack(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag, slk_stream_t stream) {
+    return mx_pack<4>("mx_pack", idx, S, R, n, codes, scales, flag, stream);
+}
+
+int slk_mx_pack6(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag, slk_stream_t stream) {
+    return mx_pack<6>("mx_pack6", idx, S, R, n, codes, scales, flag, stream);
+}
+
+int slk_mx_unpack(const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag, slk_stream_t stream) {
+    return mx_unpack<4>("mx_unpack", codes, scales, R, n, idx, S, flag, stream);
+}
+
+int slk_mx_unpack6(const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag, slk_stream_t stream) {
+    return mx_unpack<6>("mx_unpack6", codes, scales, R, n, idx, S, flag, stream);
 }
 
 int slk_mx_dequantize(const uint8_t *codes, const uint8_t *scales, int R, int n, int out_dtype, void *out, int *flag,

@@ -1,7 +1,8 @@
 // A linear layer computed from the packed MXFP4 form on the block-scaled MFMA (slk_mx_quantize_act, _act4, _act6,
-// slk_mx_dequantize_act, _act6, slk_mx_gemm, _a4, _a6; the formats are pinned in include/sleekit_amd.h and INTEGRATION.md).
+// slk_mx_dequantize_act, _act6, slk_mx_gemm, _a4, _a6, _w6; the formats are pinned in include/sleekit_amd.h and INTEGRATION.md).
 //
-// Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns.
+// Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns -- or, for
+// an MXFP6 layer (slk_mx_gemm_w6), as slk_mx_pack6 left them: E2M3 codes, 24 bytes a block.
 // Activations are quantized on the fly to MXFP8: E4M3 codes, one a byte, under the same kind of block scale -- or to
 // MXFP4, in the weights' own form, or to MXFP6 (E2M3, 24 bytes a block).
 //
@@ -16,6 +17,8 @@
 //   A, E2M3 (6 VGPRs; slk_mx_gemm_a6, MXFP6 activations): the 32 consecutive k of block q as one little-endian stream of
 //      192 bits, element j of the block at bits 6 j .. 6 j + 5 of VGPRs 0-5 -- not cut in halves, the stored form as it is
 //      (held by the one-hot test of tests/test_gpu_mx_act6.py).
+//   B, E2M3 (6 VGPRs, blgp = 2; slk_mx_gemm_w6, MXFP6 layers): that map mirrored -- lane i + 16 q carries column i and the 32
+//      consecutive k of block q as the stored stream in VGPRs 0-5 (held by the one-hot test of tests/test_gpu_mx6.py).
 // The stored forms feed the instruction with plain loads (16 bytes a piece; three of 8 for E2M3): no shuffle, no pre-swizzle, no LDS.
 // D: lane l holds column l & 15, rows 4 (l >> 4) + 0 .. 3.
 #include "common.h"
@@ -131,21 +134,40 @@ struct FragA {
     int v[mxa_bits<AF>()];  // 8, 4 or 6 VGPRs
     int sc;
 };
-struct FragB {
+template <int WF = MXA_E2M1>
+struct FragB;
+template <>
+struct FragB<MXA_E2M1> {
     v4i v;
     int sc;
 };
-__device__ __forceinline__ FragB load_b(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, int row, int rows, int kb,
-                                        int bpr) {
-    FragB f;
-    f.v = (v4i){0, 0, 0, 0};
-    f.sc = 127;
-    if (row < rows && kb < bpr) {
-        const size_t blk = (size_t)row * bpr + kb;
-        f.v = *reinterpret_cast<const v4i *>(codes + 16 * blk);
-        f.sc = E[blk];
+template <>
+struct FragB<MXA_E2M3> {
+    int v[6];
+    int sc;
+};
+template <int AF>
+__device__ __forceinline__ FragA<AF> load_a_block(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, int row, int rows, int kb,
+                                                  int bpr);
+// The B fragment: the lane's block of the layer, 16 bytes of E2M1 in one load, or 24 bytes of E2M3 as three 8-byte loads
+// (load_a_block below: exactly 24 bytes, so the last block of the last row reads nothing past the layer's 3 N K / 4 bytes).
+template <int WF = MXA_E2M1>
+__device__ __forceinline__ FragB<WF> load_b(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, int row, int rows, int kb,
+                                            int bpr) {
+    if constexpr (WF == MXA_E2M1) {
+        FragB<WF> f;
+        f.v = (v4i){0, 0, 0, 0};
+        f.sc = 127;
+        if (row < rows && kb < bpr) {
+            const size_t blk = (size_t)row * bpr + kb;
+            f.v = *reinterpret_cast<const v4i *>(codes + 16 * blk);
+            f.sc = E[blk];
+        }
+        return f;
+    } else {
+        const FragA<WF> a = load_a_block<WF>(codes, E, row, rows, kb, bpr);
+        return {{a.v[0], a.v[1], a.v[2], a.v[3], a.v[4], a.v[5]}, a.sc};
     }
-    return f;
 }
 // The A fragment of each activation format (load_a).  E4M3: two 16-byte pieces of the row, from two blocks (the two halves
 // of the map above).  E2M1 activations are stored like the weights and map like them (held by the one-hot test of
@@ -194,23 +216,25 @@ __device__ __forceinline__ FragA<AF> load_a(const uint8_t *__restrict__ codes, c
         for (int i = 0; i < 8; ++i) f.v[i] = i < 4 ? lo[i] : hi[i - 4];
         return f;
     } else if constexpr (AF == MXA_E2M1) {
-        const FragB b = load_b(codes, E, row, rows, 4 * step + q, bpr);
+        const FragB<> b = load_b(codes, E, row, rows, 4 * step + q, bpr);
         return {{b.v.x, b.v.y, b.v.z, b.v.w}, b.sc};
     } else {
         return load_a_block<AF>(codes, E, row, rows, 4 * step + q, bpr);
     }
 }
-// acc += A (16 x 128) B^T (E2M1, 16 x 128), each lane's block under its own scale.  The instruction takes eight VGPRs a
+// acc += A (16 x 128) B^T (E2M1 or E2M3, 16 x 128), each lane's block under its own scale.  The instruction takes eight VGPRs a
 // side and reads as many of them as the format has; with A in E2M1 or E2M3 it runs at twice the E4M3 rate.
 template <int AF>
 __host__ __device__ constexpr int mx_cbsz() { return AF == MXA_E2M1 ? 4 : AF == MXA_E2M3 ? 2 : 0; }
-template <int AF>
-__device__ __forceinline__ v4f mx_mfma(const FragA<AF> a, const FragB b, v4f acc) {
+template <int AF, int WF = MXA_E2M1>
+__device__ __forceinline__ v4f mx_mfma(const FragA<AF> a, const FragB<WF> b, v4f acc) {
     v8i av = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < mxa_bits<AF>(); ++i) av[i] = a.v[i];
-    const v8i bv = {b.v.x, b.v.y, b.v.z, b.v.w, 0, 0, 0, 0};
-    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, mx_cbsz<AF>(), 4 /* B: E2M1 */, 0, a.sc, 0, b.sc);
+    v8i bv = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < mxa_bits<WF>(); ++i) bv[i] = b.v[i];
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, mx_cbsz<AF>(), mx_cbsz<WF>() /* blgp: B's format */, 0, a.sc, 0, b.sc);
 }
 
 template <int OUT>
@@ -230,7 +254,7 @@ __device__ __forceinline__ void store_tile(v4f acc, const float *__restrict__ bi
 // the SK partial tiles in wave order.  Both orders are fixed, so a result does not depend on timing.
 constexpr int MXG_SK = 8;
 constexpr int MXG_SPLIT_MAX_M = 64;
-template <int OUT, int AF = MXA_E4M3>
+template <int OUT, int AF = MXA_E4M3, int WF = MXA_E2M1>
 __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                                 const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                                 const float *__restrict__ bias, int M, int N, int K,
@@ -242,9 +266,9 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *_
     v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int s = wave; s < steps; s += 2 * MXG_SK) {  // two steps' loads in flight; a step past the end loads zeros
         const FragA<AF> a0 = load_a<AF>(Ac, As, m, M, s, q, bpr), a1 = load_a<AF>(Ac, As, m, M, s + MXG_SK, q, bpr);
-        const FragB b0 = load_b(Wc, Ws, n, N, 4 * s + q, bpr), b1 = load_b(Wc, Ws, n, N, 4 * (s + MXG_SK) + q, bpr);
-        acc = mx_mfma<AF>(a0, b0, acc);
-        acc = mx_mfma<AF>(a1, b1, acc);
+        const FragB<WF> b0 = load_b<WF>(Wc, Ws, n, N, 4 * s + q, bpr), b1 = load_b<WF>(Wc, Ws, n, N, 4 * (s + MXG_SK) + q, bpr);
+        acc = mx_mfma<AF, WF>(a0, b0, acc);
+        acc = mx_mfma<AF, WF>(a1, b1, acc);
     }
     if (wave) part[wave - 1][lane] = acc;
     __syncthreads();
@@ -256,7 +280,7 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *_
 
 // Many rows: a wave holds a 32 x 32 tile of Y as 2 x 2 MFMA tiles, so each fragment it loads feeds two MFMAs, and the four
 // waves of a workgroup cover 64 x 64; the fragments two waves share come to the second of them from the cache.
-template <int OUT, int AF = MXA_E4M3>
+template <int OUT, int AF = MXA_E4M3, int WF = MXA_E2M1>
 __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                        const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                        const float *__restrict__ bias, int M, int N, int K,
@@ -271,16 +295,16 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
         for (int j = 0; j < 2; ++j) acc[i][j] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
     for (int s = 0; s < steps; ++s) {
         FragA<AF> a[2];
-        FragB b[2];
+        FragB<WF> b[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             a[i] = load_a<AF>(Ac, As, m0 + 16 * i + (lane & 15), M, s, q, bpr);
-            b[i] = load_b(Wc, Ws, n0 + 16 * i + (lane & 15), N, 4 * s + q, bpr);
+            b[i] = load_b<WF>(Wc, Ws, n0 + 16 * i + (lane & 15), N, 4 * s + q, bpr);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = mx_mfma<AF>(a[i], b[j], acc[i][j]);
+            for (int j = 0; j < 2; ++j) acc[i][j] = mx_mfma<AF, WF>(a[i], b[j], acc[i][j]);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -340,8 +364,8 @@ static int mx_dequantize_act(const char *name, const uint8_t *a_codes, const uin
     });
 }
 
-// slk_mx_gemm (AF MXA_E4M3), _a4 (MXA_E2M1) and _a6 (MXA_E2M3)
-template <int AF>
+// slk_mx_gemm (AF MXA_E4M3), _a4 (MXA_E2M1) and _a6 (MXA_E2M3) against an MXFP4 layer; _w6 (WF MXA_E2M3) against an MXFP6 one
+template <int AF, int WF = MXA_E2M1>
 static int mx_gemm(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
                    const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
     SLK_REQUIRE(M > 0 && N > 0, "M and N must be at least 1 (M = %d, N = %d)", M, N);
@@ -356,14 +380,14 @@ static int mx_gemm(const char *name, const uint8_t *a_codes, const uint8_t *a_sc
         constexpr int OUT = decltype(t)::OUT;
         T *Y = static_cast<T *>(out);
         const double flops = 2.0 * M * N * K;
-        const double bytes = ((double)M * mxa_block_bytes<AF>() + (double)N * mxa_block_bytes<MXA_E2M1>()) * K / 32.0 + (double)M * N * sizeof(T);
+        const double bytes = ((double)M * mxa_block_bytes<AF>() + (double)N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * N * sizeof(T);
         if (M <= MXG_SPLIT_MAX_M) {
             const dim3 grid((N + 15) / 16, (M + 15) / 16);
             SLK_RUN(name, flops, bytes, s,
-                    (k_mx_gemm_splitk<OUT, AF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
+                    (k_mx_gemm_splitk<OUT, AF, WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
         } else {
             const dim3 grid((N + 63) / 64, (M + 63) / 64);
-            SLK_RUN(name, flops, bytes, s, (k_mx_gemm_tiled<OUT, AF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
+            SLK_RUN(name, flops, bytes, s, (k_mx_gemm_tiled<OUT, AF, WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
         }
         return SLK_OK;
     });
@@ -406,6 +430,15 @@ int slk_mx_gemm_a4(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_
 int slk_mx_gemm_a6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
                    int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
     return mx_gemm<MXA_E2M3>("mx_gemm_a6", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
+}
+
+int slk_mx_gemm_w6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
+                   int M, int N, int K, int a_fmt, int out_dtype, void *out, slk_stream_t stream) {
+    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP6,
+                "an MXFP6 layer takes MXFP8 (SLK_MX_ACT_FP8) or MXFP6 (SLK_MX_ACT_FP6) activations (a_fmt = %d)", a_fmt);
+    if (a_fmt == SLK_MX_ACT_FP6)
+        return mx_gemm<MXA_E2M3, MXA_E2M3>("mx_gemm_w6a6", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
+    return mx_gemm<MXA_E4M3, MXA_E2M3>("mx_gemm_w6", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
 }
 
 }  // extern "C"

@@ -67,6 +67,21 @@ Known answers: amax 7.5 gives byte 127 and 7.5, -0.3, 0.0625, 0.1875 the codes 1
 byte 125 and 1.0, -1.0, 0.3, 0.0625 the codes 18 38 0a 02, bytes 18 ae 08.
 `rotation=R` works as for the other formats (slk_mx_rotate_quantize_act6).
 
+MXFP6 LAYERS.  `weights="mxfp6_e2m3"` (compute_mx_scales, matmul_mx, MXLinear) and quantize_mxfp6, pack_mxfp6, unpack_mxfp6,
+dequantize_mxfp6, linear_mxfp6 are the same pipeline with E2M3 elements: 6.25 bits a weight for about a sixteenth of MXFP4's
+squared rounding error, on the same MFMA at the FP4 rate (W6A8 with "mxfp8" activations, W6A6 with "mxfp6_e2m3"; "mxfp4"
+activations against such a layer are refused).  The usual recipe: MXFP6 for the few sensitive layers, MXFP4 for the rest.
+  elements  OCP E2M3, code = sign << 5 | e << 3 | m, the activation format's values.  The codebook E2M3 is the 63-entry table
+            -7.5 .. 7.5 whose limits are the midpoints (a tie goes upward); table index i < 31 is code 0x20 | (31 - i),
+            otherwise i - 31.  Code 0x20 (-0) is never written and reads back as index 31; an index above 62 is a caller
+            error and is stored as code 0x1f.
+  codes     uint8 (R, 3 n / 4): a row is a little-endian stream of 6-bit codes, element k at bits 6 k .. 6 k + 5, 24 bytes a
+            block -- the MXFP6 activations' form, so dequantize_mxfp6 is dequantize_mxfp6_act's kernel.
+  scales    as MXFP4's; the scale rule is the one above with E2M3 and 7.5 in place of E2M1 and 6.
+Known answers: indices 0, 1, 30, 31, 32, 61, 62 are codes 3f 3e 21 00 01 1e 1f; indices [0, 62, 31, 32] pack to bytes ff 07 04.
+    res = quantize_mxfp6(W, H, nb_ls_moves=10);  y = linear_mxfp6(x, res.codes, res.scales, bias, activations="mxfp6_e2m3")
+    layer = MXLinear.from_result(nn_linear, res)          # the format is read off the widths of res.codes and res.scales
+
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
 everything runs on the GPU on the current stream, and there is no CPU fallback.
 """
@@ -83,11 +98,29 @@ from .codebook import Codebook
 
 BLOCK = 32
 E2M1 = Codebook([-6, -4, -3, -2, -1.5, -1, -0.5, 0, 0.5, 1, 1.5, 2, 3, 4, 6])
+_E2M3_MAGNITUDES = [m / 8 for m in range(1, 8)] + [2.0 ** (e - 1) * (1 + m / 8) for e in (1, 2, 3) for m in range(8)]
+E2M3 = Codebook([-v for v in reversed(_E2M3_MAGNITUDES)] + [0.0] + _E2M3_MAGNITUDES)
 
 MXResult = collections.namedtuple("MXResult", "Q idx S codes scales")
 
 _MODES = {"max": _lib.MX_MAX, "mse": _lib.MX_MSE, "diag": _lib.MX_DIAG}
 _OUT = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+# A weight format as plain data: the bits of a code (codes is (R, n bits / 8)), the codebook of the loop, its largest
+# magnitude, and the C entries of the scale search, the pack, the unpack and the de-quantizer (MXFP6's is the activations').
+_Weights = collections.namedtuple("_Weights", "name bits codebook largest scale_entry pack_entry unpack_entry dequantize_entry")
+_WEIGHTS = {f.name: f for f in (
+    _Weights("mxfp4", 4, E2M1, 6.0, "slk_mx_scale_search", "slk_mx_pack", "slk_mx_unpack", "slk_mx_dequantize"),
+    _Weights("mxfp6_e2m3", 6, E2M3, 7.5, "slk_mx_scale_search6", "slk_mx_pack6", "slk_mx_unpack6", "slk_mx_dequantize_act6"),
+)}
+_FP4, _FP6 = _WEIGHTS["mxfp4"], _WEIGHTS["mxfp6_e2m3"]
+
+
+def _weight_format(weights):
+    """The _Weights of a `weights` value.  (The bare "mxfp6" names two element formats and is refused.)"""
+    if not isinstance(weights, str) or weights not in _WEIGHTS:
+        raise ValueError(f'weights must be "mxfp4" or "mxfp6_e2m3" (got {weights!r})')
+    return _WEIGHTS[weights]
 
 
 def _blocks(n):
@@ -116,9 +149,11 @@ def _raise_flag(flag, message):
         raise ValueError(message)
 
 
-def compute_mx_scales(W, H=None, mode="mse"):
+def compute_mx_scales(W, H=None, mode="mse", weights="mxfp4"):
     """(S, E): the blocks' power-of-two scales as float32 and as E8M0 bytes, (R, n / 32) each (module docstring).
-    mode "max", "mse" or "diag"; "diag" weighs the errors with diag(H) and needs H."""
+    mode "max", "mse" or "diag"; "diag" weighs the errors with diag(H) and needs H.  weights: the element format the scales
+    are chosen for, "mxfp4" (E2M1) or "mxfp6_e2m3"."""
+    wf = _weight_format(weights)
     if mode not in _MODES:
         raise ValueError(f'MX scale modes are "max", "mse" and "diag" (got "{mode}")')
     if mode == "diag" and H is None:
@@ -134,27 +169,27 @@ def compute_mx_scales(W, H=None, mode="mse"):
         hd = Hd.diagonal().contiguous()
     S = torch.empty((R, G), dtype=torch.float32, device=Wd.device)
     E = torch.empty((R, G), dtype=torch.uint8, device=Wd.device)
-    _lib.check(_lib.lib.slk_mx_scale_search(dev.ptr(Wd), dev.ptr(hd), _MODES[mode], R, n, dev.ptr(E), dev.ptr(S), dev.stream_handle()))
+    _lib.check(getattr(_lib.lib, wf.scale_entry)(dev.ptr(Wd), dev.ptr(hd), _MODES[mode], R, n, dev.ptr(E), dev.ptr(S), dev.stream_handle()))
     return dev.like_input(S, W), dev.like_input(E, W)
 
 
-def _pack(idx_d, S_d, R, n):
+def _pack(idx_d, S_d, R, n, wf=_FP4):
     """(codes, scales) of device idx (R, n) and / or S (R, n / 32); either may be None."""
     device = (idx_d if idx_d is not None else S_d).device
-    codes = torch.empty((R, n // 2), dtype=torch.uint8, device=device) if idx_d is not None else None
+    codes = torch.empty((R, n * wf.bits // 8), dtype=torch.uint8, device=device) if idx_d is not None else None
     scales = torch.empty((R, n // BLOCK), dtype=torch.uint8, device=device) if S_d is not None else None
     flag = torch.empty(1, dtype=torch.int32, device=device) if S_d is not None else None
-    _lib.check(_lib.lib.slk_mx_pack(dev.ptr(idx_d), dev.ptr(S_d), R, n, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
+    _lib.check(getattr(_lib.lib, wf.pack_entry)(dev.ptr(idx_d), dev.ptr(S_d), R, n, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
     _raise_flag(flag, "MX scales must be positive powers of two in 2^-126 .. 2^127 (E8M0)")
     return codes, scales
 
 
-def _unpack(codes_d, scales_d, R, n):
+def _unpack(codes_d, scales_d, R, n, wf=_FP4):
     device = (codes_d if codes_d is not None else scales_d).device
     idx = torch.empty((R, n), dtype=torch.uint8, device=device) if codes_d is not None else None
     S = torch.empty((R, n // BLOCK), dtype=torch.float32, device=device) if scales_d is not None else None
     flag = torch.empty(1, dtype=torch.int32, device=device) if scales_d is not None else None
-    _lib.check(_lib.lib.slk_mx_unpack(dev.ptr(codes_d), dev.ptr(scales_d), R, n, dev.ptr(idx), dev.ptr(S), dev.ptr(flag), dev.stream_handle()))
+    _lib.check(getattr(_lib.lib, wf.unpack_entry)(dev.ptr(codes_d), dev.ptr(scales_d), R, n, dev.ptr(idx), dev.ptr(S), dev.ptr(flag), dev.stream_handle()))
     _raise_flag(flag, "scale byte 255 is E8M0's NaN, not a scale")
     return idx, S
 
@@ -164,26 +199,41 @@ def _check_scale_shape(x, R, n, what):
         raise ValueError(f"{what} must be ({R}, {n // BLOCK}) for a ({R}, {n}) layer; got {tuple(x.shape)}")
 
 
-def pack_mxfp4(idx, S):
-    """uint8 table indices (R, n) and float32 power-of-two scales (R, n / 32) -> (codes uint8 (R, n / 2), scales uint8
-    (R, n / 32)).  A scale that is not a power of two E8M0 holds: ValueError."""
+def _pack_layer(idx, S, wf):
     R, n = _matrix(idx, "indices", (torch.uint8, np.uint8))
     _blocks(n)
     _matrix(S, "scales", (torch.float32, np.float32))
     _check_scale_shape(S, R, n, "scales")
-    codes, scales = _pack(_aligned(dev.to_device(idx, torch.uint8)), dev.to_device(S), R, n)
+    codes, scales = _pack(_aligned(dev.to_device(idx, torch.uint8)), dev.to_device(S), R, n, wf)
     return dev.like_input(codes, idx), dev.like_input(scales, idx)
+
+
+def _unpack_layer(codes, scales, wf):
+    R, n = _weights(codes, scales, wf)
+    idx, S = _unpack(_aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), R, n, wf)
+    return dev.like_input(idx, codes), dev.like_input(S, codes)
+
+
+def pack_mxfp4(idx, S):
+    """uint8 table indices (R, n) and float32 power-of-two scales (R, n / 32) -> (codes uint8 (R, n / 2), scales uint8
+    (R, n / 32)).  A scale that is not a power of two E8M0 holds: ValueError."""
+    return _pack_layer(idx, S, _FP4)
 
 
 def unpack_mxfp4(codes, scales):
     """(codes (R, n / 2), scales (R, n / 32)) -> (idx uint8 (R, n), S float32 (R, n / 32))."""
-    R, half = _matrix(codes, "codes", (torch.uint8, np.uint8))
-    n = 2 * half
-    _blocks(n)
-    _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
-    _check_scale_shape(scales, R, n, "scale bytes")
-    idx, S = _unpack(_aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), R, n)
-    return dev.like_input(idx, codes), dev.like_input(S, codes)
+    return _unpack_layer(codes, scales, _FP4)
+
+
+def pack_mxfp6(idx, S):
+    """pack_mxfp4 for an MXFP6 layer: indices into the 63-entry E2M3 table -> (codes uint8 (R, 3 n / 4), scales uint8
+    (R, n / 32)) (module docstring, MXFP6 LAYERS)."""
+    return _pack_layer(idx, S, _FP6)
+
+
+def unpack_mxfp6(codes, scales):
+    """(codes (R, 3 n / 4), scales (R, n / 32)) -> (idx uint8 (R, n), S float32 (R, n / 32))."""
+    return _unpack_layer(codes, scales, _FP6)
 
 
 def encode_scales(S):
@@ -201,24 +251,51 @@ def decode_scales(E):
 def dequantize_mxfp4(codes, scales, dtype=torch.float32):
     """The layer rebuilt from its packed form: (R, n) of `dtype` (float32: bit for bit the Q that was packed; bfloat16 or
     float16: that value rounded to nearest even, `.to(dtype)`).  NumPy input gives a NumPy array, which has no bfloat16."""
-    return _dequantize(codes, scales, dtype, _FORMATS["mxfp4"], "codes")
+    return _dequantize(codes, scales, dtype, _FP4, "codes")
+
+
+def dequantize_mxfp6(codes, scales, dtype=torch.float32):
+    """dequantize_mxfp4 for an MXFP6 layer (codes (R, 3 n / 4)): float32 is bit for bit the Q that was packed."""
+    return _dequantize(codes, scales, dtype, _FP6, "codes")
+
+
+def _quantize_layer(wf, W, H, act_order, damp, scale_mode, nb_ls_moves, scales, min_block_size, num_blocks, want_ls_trace):
+    R, n = W.shape
+    _blocks(n)
+    if scales is None:
+        S = compute_mx_scales(W, H, scale_mode, wf.name)[0]
+    else:
+        S = dev.to_device(scales)
+        _check_scale_shape(S, R, n, "scales")
+    res = groups.quantize_layer_grouped(W, S, wf.codebook, H, BLOCK, act_order, damp, min_block_size, num_blocks, nb_ls_moves=nb_ls_moves,
+                                        want_ls_trace=want_ls_trace)
+    codes, E = _pack(res.idx, S, R, n, wf)  # (scales given by the caller are checked here: not a power of two, ValueError)
+    return MXResult(res.Q, res.idx, S, codes, E), res
+
+
+def _quantize_checked(wf, W, H, act_order, damp, scale_mode, nb_ls_moves, scales, min_block_size, num_blocks):
+    _matrix(W, "W", (torch.float32, np.float32))
+    if H is None or H.ndim != 2 or tuple(H.shape) != (W.shape[1], W.shape[1]):
+        raise ValueError(f"H must be ({W.shape[1]}, {W.shape[1]})")
+    if scale_mode not in _MODES:
+        raise ValueError(f'MX scale modes are "max", "mse" and "diag" (got "{scale_mode}")')
+    _blocks(int(W.shape[1]))
+    out, _ = _quantize_layer(wf, dev.to_device(W), dev.to_device(H), act_order, damp, scale_mode, nb_ls_moves, scales, min_block_size,
+                             num_blocks, False)
+    return MXResult(*(dev.like_input(t, W) for t in out))
 
 
 def quantize_layer_mxfp4(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_moves=0, scales=None, min_block_size=32,
                          num_blocks=8, want_ls_trace=False):
     """quantize_mxfp4 on device tensors (W (R, n), H (n, n), float32): (MXResult of device tensors, the grouped loop's
     engine.LayerResult; want_ls_trace: with the moves taken in its ls_trace)."""
-    R, n = W.shape
-    _blocks(n)
-    if scales is None:
-        S = compute_mx_scales(W, H, scale_mode)[0]
-    else:
-        S = dev.to_device(scales)
-        _check_scale_shape(S, R, n, "scales")
-    res = groups.quantize_layer_grouped(W, S, E2M1, H, BLOCK, act_order, damp, min_block_size, num_blocks, nb_ls_moves=nb_ls_moves,
-                                        want_ls_trace=want_ls_trace)
-    codes, E = _pack(res.idx, S, R, n)  # (scales given by the caller are checked here: not a power of two, ValueError)
-    return MXResult(res.Q, res.idx, S, codes, E), res
+    return _quantize_layer(_FP4, W, H, act_order, damp, scale_mode, nb_ls_moves, scales, min_block_size, num_blocks, want_ls_trace)
+
+
+def quantize_layer_mxfp6(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_moves=0, scales=None, min_block_size=32,
+                         num_blocks=8, want_ls_trace=False):
+    """quantize_layer_mxfp4 with the E2M3 codebook: the MXResult's codes are (R, 3 n / 4)."""
+    return _quantize_layer(_FP6, W, H, act_order, damp, scale_mode, nb_ls_moves, scales, min_block_size, num_blocks, want_ls_trace)
 
 
 def quantize_mxfp4(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_moves=0, scales=None, min_block_size=32,
@@ -227,15 +304,15 @@ def quantize_mxfp4(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_mo
     float32 powers of two (R, n / 32)), groups.quantize_layer_grouped with the E2M1 codebook and groups of 32 (nb_ls_moves of
     its local search after the loop, up to 16384 columns), then the pack.  Returns MXResult(Q, idx, S, codes, scales):
     Q float32 de-scaled like W, idx the uint8 table indices, S the float32 scales, codes and scales the packed form."""
-    _matrix(W, "W", (torch.float32, np.float32))
-    if H is None or H.ndim != 2 or tuple(H.shape) != (W.shape[1], W.shape[1]):
-        raise ValueError(f"H must be ({W.shape[1]}, {W.shape[1]})")
-    if scale_mode not in _MODES:
-        raise ValueError(f'MX scale modes are "max", "mse" and "diag" (got "{scale_mode}")')
-    _blocks(int(W.shape[1]))
-    out, _ = quantize_layer_mxfp4(dev.to_device(W), dev.to_device(H), act_order, damp, scale_mode, nb_ls_moves, scales,
-                                  min_block_size, num_blocks)
-    return MXResult(*(dev.like_input(t, W) for t in out))
+    return _quantize_checked(_FP4, W, H, act_order, damp, scale_mode, nb_ls_moves, scales, min_block_size, num_blocks)
+
+
+def quantize_mxfp6(W, H, act_order="diag", damp=0.01, scale_mode="mse", nb_ls_moves=0, scales=None, min_block_size=32,
+                   num_blocks=8):
+    """quantize_mxfp4 to MXFP6: the scales of compute_mx_scales(..., weights="mxfp6_e2m3"), the grouped loop and its local
+    search with the 63-entry E2M3 codebook, then pack_mxfp6.  The same MXResult fields; codes are (R, 3 n / 4) and
+    dequantize_mxfp6(codes, scales) is Q bit for bit."""
+    return _quantize_checked(_FP6, W, H, act_order, damp, scale_mode, nb_ls_moves, scales, min_block_size, num_blocks)
 
 
 # ---------------------------------------------------------------------------------------------------------------- linear
@@ -318,17 +395,32 @@ def _raise_finite(flag):
     _raise_flag(flag, "activations must be finite: X holds a NaN or an infinity")
 
 
-def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"]):
+# slk_mx_gemm_w6's `a_fmt` of the activation formats an MXFP6 layer takes
+_W6_ACT = {"mxfp8": _lib.MX_ACT_FP8, "mxfp6_e2m3": _lib.MX_ACT_FP6}
+
+
+def _check_pair(fmt, wf):
+    if wf is _FP6 and fmt.name not in _W6_ACT:
+        raise ValueError(f'an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations (got "{fmt.name}")')
+
+
+def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"], wf=_FP4):
     out = torch.empty((M, N), dtype=dtype, device=ac.device)
+    if wf is _FP6:
+        _lib.check(_lib.lib.slk_mx_gemm_w6(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _W6_ACT[fmt.name],
+                                           _OUT[dtype], dev.ptr(out), dev.stream_handle()))
+        return out
     _lib.check(getattr(_lib.lib, fmt.gemm_entry)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K,
                                                  _OUT[dtype], dev.ptr(out), dev.stream_handle()))
     return out
 
 
-def _weights(codes, scales):
-    """(N, K) of a packed layer, its shapes and dtypes checked."""
-    N, half = _matrix(codes, "codes", (torch.uint8, np.uint8))
-    K = 2 * half
+def _weights(codes, scales, wf=_FP4):
+    """(N, K) of a packed layer in the _Weights wf, its shapes and dtypes checked."""
+    N, width = _matrix(codes, "codes", (torch.uint8, np.uint8))
+    if 8 * width % wf.bits != 0:
+        raise ValueError(f"codes has {width} columns of bytes, which is no whole number of {wf.bits}-bit codes")
+    K = 8 * width // wf.bits
     _blocks(K)
     _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(scales, N, K, "scale bytes")
@@ -404,22 +496,24 @@ def dequantize_mxfp8(a_codes, a_scales, dtype=torch.float32):
     return _dequantize(a_codes, a_scales, dtype, _FORMATS["mxfp8"], "a_codes")
 
 
-def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, activations="mxfp8"):
+def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, activations="mxfp8", weights="mxfp4"):
     """Y (M, N) = deq(a_codes, a_scales) @ deq(codes, scales).T + bias on the block-scaled MFMA: MXFP8 activations (M, K)
     -- or, with activations="mxfp4", MXFP4 activations (M, K / 2), or, with "mxfp6_e2m3", MXFP6 ones (M, 3 K / 4) -- against
-    an MXFP4 layer (N, K), float32 sums in a fixed order, the result rounded once to `dtype`."""
-    fmt = _activations(activations)
+    an MXFP4 layer (N, K), float32 sums in a fixed order, the result rounded once to `dtype`.  weights="mxfp6_e2m3": against
+    an MXFP6 layer, codes (N, 3 K / 4), with "mxfp8" or "mxfp6_e2m3" activations."""
+    fmt, wf = _activations(activations), _weight_format(weights)
+    _check_pair(fmt, wf)
     _out_dtype(dtype, a_codes)
     M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
     K = _columns(width, fmt)
     _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(a_scales, M, K, "activation scale bytes")
-    N, Kw = _weights(codes, scales)
+    N, Kw = _weights(codes, scales, wf)
     if Kw != K:
         raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
     _check_bias(bias, N)
     out = _gemm(_aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), _aligned(dev.to_device(codes, torch.uint8)),
-                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt)
+                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt, wf)
     return dev.like_input(out, a_codes)
 
 
@@ -430,7 +524,18 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
     in matmul_mx and the float32 bias (N,) added; the result is (..., N) in `dtype`, or in x's dtype when `dtype` is None.
     rotation (a rotation.Rotation over K features): x R is quantized instead of x, the rotation running inside the
     quantizer -- bit for bit linear_mxfp4(rotation.apply(x, dtype=torch.float32), ...) with the same `dtype` result."""
+    return _linear(x, codes, scales, bias, dtype, activations, rotation, _FP4)
+
+
+def linear_mxfp6(x, codes, scales, bias=None, dtype=None, activations="mxfp8", rotation=None):
+    """linear_mxfp4 with a packed MXFP6 weight, codes (N, 3 K / 4): W6A8 with activations="mxfp8", W6A6 with "mxfp6_e2m3"
+    ("mxfp4": ValueError).  The activation quantizers, the fused rotation and the result's dtype are linear_mxfp4's."""
+    return _linear(x, codes, scales, bias, dtype, activations, rotation, _FP6)
+
+
+def _linear(x, codes, scales, bias, dtype, activations, rotation, wf):
     fmt = _activations(activations)
+    _check_pair(fmt, wf)
     if rotation is not None:
         from .rotation import Rotation
 
@@ -443,7 +548,7 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
     if dtype is None:
         dtype = _torch_dtype(x)
     _out_dtype(dtype, x)
-    N, K = _weights(codes, scales)
+    N, K = _weights(codes, scales, wf)
     if x.shape[-1] != K:
         raise ValueError(f"x has {x.shape[-1]} columns but the layer has {K}")
     if rotation is not None and rotation.n != K:
@@ -458,58 +563,79 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
         ac, asc, flag = _rotate_quantize_act(Xd, M, K, rotation, fmt)
     else:
         ac, asc, flag = _quantize_act(Xd, M, K, fmt)
-    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt)
+    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt, wf)
     _raise_finite(flag)
     return dev.like_input(out.reshape(lead + (N,)), x)
 
 
 class MXLinear(torch.nn.Module):
-    """A linear layer kept in its packed MXFP4 form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
+    """A linear layer kept in its packed MX form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
     or None; forward(x) = linear_mxfp4(x, codes, scales, bias, activations=activations).  `activations` ("mxfp8", the
-    default, "mxfp4" or "mxfp6_e2m3") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8"."""
+    default, "mxfp4" or "mxfp6_e2m3") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8".
+    weights="mxfp6_e2m3": an MXFP6 layer, `codes` (N, 3 K / 4), forward through linear_mxfp6; it refuses "mxfp4" activations.
+    `weights` is extra state too, written only when it is not "mxfp4"; a state of the other weight format is an error."""
 
-    def __init__(self, in_features, out_features, bias=True, device=None, activations="mxfp8"):
+    def __init__(self, in_features, out_features, bias=True, device=None, activations="mxfp8", weights="mxfp4"):
         super().__init__()
         _blocks(int(in_features))
-        _activations(activations)
-        self.activations = activations
+        _check_pair(_activations(activations), _weight_format(weights))
+        self.activations, self.weights = activations, weights
         self.in_features, self.out_features = int(in_features), int(out_features)
-        self.register_buffer("codes", torch.zeros((self.out_features, self.in_features // 2), dtype=torch.uint8, device=device))
+        width = self.in_features * _WEIGHTS[weights].bits // 8
+        self.register_buffer("codes", torch.zeros((self.out_features, width), dtype=torch.uint8, device=device))
         self.register_buffer("scales", torch.full((self.out_features, self.in_features // BLOCK), 127, dtype=torch.uint8, device=device))
         self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=device) if bias else None)
 
-    # `activations` travels as the module's extra state, written only when it is not the default: the state dict of a
-    # default module has the keys it always had, and a state dict without the key -- every one saved before -- means "mxfp8"
+    # `activations` and `weights` travel as the module's extra state, each written only when it is not the default: the state
+    # dict of a default module has the keys it always had, and a state dict without the key -- every one saved before --
+    # means "mxfp8" activations and "mxfp4" weights
     _STATE_KEY = torch.nn.modules.module._EXTRA_STATE_KEY_SUFFIX
 
     def _save_to_state_dict(self, destination, prefix, keep_vars):
         super()._save_to_state_dict(destination, prefix, keep_vars)
+        state = {}
         if self.activations != "mxfp8":
-            destination[prefix + self._STATE_KEY] = {"activations": self.activations}
+            state["activations"] = self.activations
+        if self.weights != "mxfp4":
+            state["weights"] = self.weights
+        if state:
+            destination[prefix + self._STATE_KEY] = state
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         key = prefix + self._STATE_KEY
-        activations = "mxfp8"
+        activations, weights = "mxfp8", "mxfp4"
         if key in state_dict:
             state = state_dict[key]
             activations = state.get("activations", "mxfp8") if isinstance(state, dict) else None
+            weights = state.get("weights", "mxfp4") if isinstance(state, dict) else None
             if not isinstance(activations, str) or activations not in _ACTIVATIONS:
                 error_msgs.append(f"{key}: {_ACTIVATIONS_ARE} (got {activations!r})")
                 activations = self.activations
             state_dict = {k: v for k, v in state_dict.items() if k != key}  # (the base class knows no such key)
+        if weights != self.weights:  # (the buffers have the module's shape: another format is never read into them)
+            error_msgs.append(f"{key}: the state is of an {weights!r} layer, this module holds {self.weights!r} weights")
+        elif self.weights == "mxfp6_e2m3" and activations not in _W6_ACT:
+            error_msgs.append(f'{key}: an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations (got {activations!r})')
+            activations = self.activations
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
         self.activations = activations
 
     @classmethod
     def from_result(cls, layer, result, activations="mxfp8"):
-        """The module of a torch.nn.Linear and the MXResult that Sleekit(layer).quantize_mxfp4() returned (taken after the
-        call, so that a corrected bias comes along)."""
+        """The module of a torch.nn.Linear and the MXResult that Sleekit(layer).quantize_mxfp4() or quantize_mxfp6() returned
+        (taken after the call, so that a corrected bias comes along).  The weight format is read off the result's widths:
+        bits a code = 8 * codes width / (32 * scales width), 4 or 6."""
         if not isinstance(layer, torch.nn.Linear):
             raise ValueError(f"MXLinear.from_result takes a torch.nn.Linear (got {type(layer).__name__})")
-        N, K = _weights(result.codes, result.scales)
+        wide, blocks = int(result.codes.shape[-1]), int(result.scales.shape[-1])
+        by_bits = {wf.bits * BLOCK * blocks: wf for wf in _WEIGHTS.values()}
+        if result.codes.ndim != 2 or result.scales.ndim != 2 or blocks < 1 or 8 * wide not in by_bits:
+            raise ValueError(f"codes of {wide} bytes a row under {blocks} scale bytes are neither 4 nor 6 bits a weight")
+        wf = by_bits[8 * wide]
+        N, K = _weights(result.codes, result.scales, wf)
         if (N, K) != (layer.out_features, layer.in_features):
             raise ValueError(f"the result is of a ({N}, {K}) layer, not of this ({layer.out_features}, {layer.in_features}) one")
-        self = cls(K, N, layer.bias is not None, layer.weight.device, activations)
+        self = cls(K, N, layer.bias is not None, layer.weight.device, activations, wf.name)
         self.codes.copy_(torch.as_tensor(result.codes))
         self.scales.copy_(torch.as_tensor(result.scales))
         if layer.bias is not None:
@@ -517,8 +643,8 @@ class MXLinear(torch.nn.Module):
         return self
 
     def forward(self, x, rotation=None):
-        return linear_mxfp4(x, self.codes, self.scales, self.bias, activations=self.activations, rotation=rotation)
+        return _linear(x, self.codes, self.scales, self.bias, None, self.activations, rotation, _WEIGHTS[self.weights])
 
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
-                f"activations={self.activations}")
+                f"activations={self.activations}" + ("" if self.weights == "mxfp4" else f", weights={self.weights}"))

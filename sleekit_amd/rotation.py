@@ -199,7 +199,7 @@ class RotatedLinear(torch.nn.Module):
 
     @classmethod
     def from_result(cls, layer, result, codebook=None, fused=False, activations="mxfp8", **kw):
-        """The module of a torch.nn.Linear and the result of Sleekit(layer).quantize_packed / quantize_mxfp4(..., rotation=):
+        """The module of a torch.nn.Linear and the result of Sleekit(layer).quantize_packed / quantize_mxfp4 / quantize_mxfp6 (rotation=):
         MXLinear.from_result(layer, result) inside when the result carries `codes`, else PackedLinear.from_result(layer,
         result, codebook, **kw).  fused and activations ("mxfp8" | "mxfp4" | "mxfp6_e2m3") are the MXLinear's (class docstring, mx.MXLinear)."""
         rotation = getattr(result, "rotation", None)

@@ -266,6 +266,17 @@ class Sleekit:
         result.S, result.codes, result.scales = packed.S, packed.codes, packed.scales
         return self._store(result, weight, bias_correction, rotation)
 
+    def quantize_mxfp6(self, scale_mode="mse", order_mode="diag", bias_correction=False, damp=0.01, nb_ls_moves=0):
+        """quantize_mxfp4's twin for MXFP6 (sleekit_amd.mx, MXFP6 LAYERS): FP6 E2M3 elements, 6.25 bits a weight, the same scale
+        modes, loop, local search, bias correction and rotation.  result.codes is uint8 (out, 3 features / 4)."""
+        from . import mx
+
+        rotation = self._check_rotation(self.rotation)
+        weight, H = self._weight_and_hessian(bias_correction, rotation)
+        packed, result = mx.quantize_layer_mxfp6(weight, H, order_mode, damp, scale_mode, nb_ls_moves)
+        result.S, result.codes, result.scales = packed.S, packed.codes, packed.scales
+        return self._store(result, weight, bias_correction, rotation)
+
     def free(self):
         self.layer = self.mean = self.hessian = None
         self.count = 0

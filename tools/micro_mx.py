@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MXFP4: kernel times and HBM rates of the scale search, pack, unpack and dequantize, on the MI355X.
 
-    python tools/micro_mx.py [--reps 20] [--no-layer]
+    python tools/micro_mx.py [--reps 20] [--no-layer] [--fp6]
 
 Sizes: 4096 x 4096 and 4096 x 11008.  Each C entry is timed alone on preallocated outputs with device events (median of
 `reps` after a warm-up; min and max are printed as the spread), the two sides of a comparison alternating call by call.
@@ -15,6 +15,9 @@ MI355X_MICROARCH.md measured as achievable for HBM.
   pack / unpack  slk_mx_pack / slk_mx_unpack against slk_pack_indices / slk_unpack_indices at 4 bits.
   layer          quantize_mxfp4 (scales, loop, pack) against groups.quantize_grouped with NF4, g = 32, given S, at 4096 x 4096
                  (host clock around a device synchronise), and its parts.
+--fp6: the MXFP6 (E2M3) entries against their MXFP4 twins instead, alternating call by call -- slk_mx_scale_search6 against
+slk_mx_scale_search (mse, diag), slk_mx_pack6 / slk_mx_unpack6 against slk_mx_pack / slk_mx_unpack, and at 4096 x 4096 a
+whole quantize_mxfp6 against quantize_mxfp4 (the loop's search over 63 entries is two levels deeper than over 15).
 One JSON line per row.
 """
 
@@ -154,15 +157,60 @@ def layer_rows(W, H, reps):
         print(json.dumps(dict(size="4096x4096", call=name, **wall(fn, reps))), flush=True)
 
 
+def fp6_rows(size, W, H, reps, layer):
+    R, n = W.shape
+    G = n // 32
+    s = dev.stream_handle
+    hd = H.diagonal().contiguous()
+    E = torch.empty((R, G), dtype=torch.uint8, device="cuda")
+    S = torch.empty((R, G), dtype=torch.float32, device="cuda")
+    for mode, code, h in (("mse", _lib.MX_MSE, None), ("diag", _lib.MX_DIAG, hd)):
+        fp6 = lambda: _lib.check(L.slk_mx_scale_search6(dev.ptr(W), dev.ptr(h), code, R, n, dev.ptr(E), dev.ptr(S), s()))  # noqa: E731
+        fp4 = lambda: _lib.check(L.slk_mx_scale_search(dev.ptr(W), dev.ptr(h), code, R, n, dev.ptr(E), dev.ptr(S), s()))  # noqa: E731
+        t6, t4 = timed_pair([fp6, fp4], reps)
+        row(size, f"mx_scale_search6 {mode}", t6, 4 * R * n + 5 * R * G, over_fp4=round(t6[0] / t4[0], 3))
+        row(size, f"mx_scale_search {mode}", t4, 4 * R * n + 5 * R * G)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    idx = torch.randint(0, 15, (R, n), dtype=torch.uint8, device="cuda", generator=gen)
+    Sb = mx.decode_scales(torch.randint(100, 140, (R, G), dtype=torch.uint8, device="cuda", generator=gen))
+    c4, e4 = mx.pack_mxfp4(idx, Sb)
+    c6, e6 = mx.pack_mxfp6(idx, Sb)
+    idx_out, S_out = torch.empty_like(idx), torch.empty_like(Sb)
+    P = dev.ptr
+    sides = (("pack", lambda: L.slk_mx_pack6(P(idx), P(Sb), R, n, P(c6), P(e6), None, s()),
+              lambda: L.slk_mx_pack(P(idx), P(Sb), R, n, P(c4), P(e4), None, s())),
+             ("unpack", lambda: L.slk_mx_unpack6(P(c6), P(e6), R, n, P(idx_out), P(S_out), None, s()),
+              lambda: L.slk_mx_unpack(P(c4), P(e4), R, n, P(idx_out), P(S_out), None, s())))
+    for what, fp6, fp4 in sides:
+        t6, t4 = timed_pair([lambda: _lib.check(fp6()), lambda: _lib.check(fp4())], reps)
+        row(size, f"mx_{what}6", t6, R * n + 3 * R * n // 4 + 5 * R * G, over_fp4=round(t6[0] / t4[0], 3))
+        row(size, f"mx_{what}", t4, R * n + R * n // 2 + 5 * R * G)
+    if layer:
+        S4, S6 = mx.compute_mx_scales(W, H, "mse")[0], mx.compute_mx_scales(W, H, "mse", weights="mxfp6_e2m3")[0]
+        for name, fn in (("quantize_mxfp6 (mse scales, loop, pack)", lambda: mx.quantize_mxfp6(W, H)),
+                         ("quantize_mxfp4 (mse scales, loop, pack)", lambda: mx.quantize_mxfp4(W, H)),
+                         ("quantize_mxfp6 given scales (loop, pack)", lambda: mx.quantize_mxfp6(W, H, scales=S6)),
+                         ("quantize_mxfp4 given scales (loop, pack)", lambda: mx.quantize_mxfp4(W, H, scales=S4)),
+                         ("quantize_mxfp6 (mse scales, loop, pack) again", lambda: mx.quantize_mxfp6(W, H)),
+                         ("quantize_mxfp4 (mse scales, loop, pack) again", lambda: mx.quantize_mxfp4(W, H))):
+            print(json.dumps(dict(size=size, call=name, **wall(fn, max(3, reps // 4)))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-layer", action="store_true")
+    ap.add_argument("--fp6", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "micro_mx measures the MI355X; there is no CPU path"
     torch.cuda.set_device(0)
     for size, (R, n) in (("4096x4096", (4096, 4096)), ("4096x11008", (4096, 11008))):
         layer = synth.make_layer_device(R, n, 31, "cuda")
+        if args.fp6:
+            fp6_rows(size, layer["W"], layer["H"], args.reps, n == 4096 and not args.no_layer)
+            del layer
+            torch.cuda.empty_cache()
+            continue
         scale_rows(size, layer["W"], layer["H"], args.reps)
         pack_rows(size, R, n, args.reps)
         if n == 4096 and not args.no_layer:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The packed MXFP4 linear layer against the routes a user had before it, on the MI355X.
 
-    python tools/micro_mx_gemm.py [--reps 20] [--m 1,16,256,4096]
+    python tools/micro_mx_gemm.py [--reps 20] [--m 1,16,256,4096] [--w6]
 
 Layers N x K = 4096 x 4096 and 4096 x 11008, M rows of bfloat16 activations, bfloat16 output.  Every side runs on
 preallocated outputs and is timed with device events (median of `reps` after a warm-up, with [min, max]); the sides of a
@@ -16,6 +16,8 @@ one side is the run-to-run spread the verdict allows for.
 
 M <= 16 moves the weights once and is held against HBM: bytes the algorithm must move over 6.3 TB/s.  M >= 256 is held
 against the E4M3 block-scaled MFMA peak (5 PFLOP/s dense).  `bound` names the larger of the two shares' times.
+--w6: the MXFP6 layer instead -- slk_mx_gemm_w6 with MXFP8 and MXFP6 activations (W6A8, W6A6) against slk_mx_gemm and
+slk_mx_gemm_a6 on an MXFP4 layer of the same shape (W4A8, W4A6), activations quantized beforehand, the four sides alternating.
 One JSON line per row.
 """
 
@@ -116,16 +118,54 @@ def rows(N, K, M, reps):
     emit("c as mx.dequantize_mxfp4 + torch.matmul", t_cpy, w_bytes + 4 * N * K + 2 * M * K + 2 * M * N)
 
 
+def rows_w6(N, K, M, reps):
+    s = dev.stream_handle
+    gen = torch.Generator(device="cuda").manual_seed(N + K + M)
+    w4 = torch.randint(0, 256, (N, K // 2), dtype=torch.uint8, device="cuda", generator=gen) & 0x77
+    idx6 = torch.randint(0, 63, (N, K), dtype=torch.uint8, device="cuda", generator=gen)
+    scales = torch.randint(118, 124, (N, K // 32), dtype=torch.uint8, device="cuda", generator=gen)
+    w6 = mx.pack_mxfp6(idx6, mx.decode_scales(scales))[0]
+    del idx6
+    x = torch.randn((M, K), device="cuda", generator=gen).to(torch.bfloat16)
+    a8, a8s = mx.quantize_mxfp8(x)
+    a6, a6s = mx.quantize_mxfp6_act(x)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device="cuda")
+    P = dev.ptr
+
+    def w4a8():
+        _lib.check(L.slk_mx_gemm(P(a8), P(a8s), P(w4), P(scales), None, M, N, K, _lib.DTYPE_BF16, P(y), s()))
+
+    def w6a8():
+        _lib.check(L.slk_mx_gemm_w6(P(a8), P(a8s), P(w6), P(scales), None, M, N, K, _lib.MX_ACT_FP8, _lib.DTYPE_BF16, P(y), s()))
+
+    def w4a6():
+        _lib.check(L.slk_mx_gemm_a6(P(a6), P(a6s), P(w4), P(scales), None, M, N, K, _lib.DTYPE_BF16, P(y), s()))
+
+    def w6a6():
+        _lib.check(L.slk_mx_gemm_w6(P(a6), P(a6s), P(w6), P(scales), None, M, N, K, _lib.MX_ACT_FP6, _lib.DTYPE_BF16, P(y), s()))
+
+    sides = (("W4A8 slk_mx_gemm", w4a8, 4, 8), ("W6A8 slk_mx_gemm_w6", w6a8, 6, 8), ("W4A6 slk_mx_gemm_a6", w4a6, 4, 6),
+             ("W6A6 slk_mx_gemm_w6", w6a6, 6, 6), ("W4A8 again", w4a8, 4, 8))
+    ts = timed([fn for _, fn, _, _ in sides], reps)
+    flops = 2.0 * M * N * K
+    for (name, _, wb, ab), (us, lo, hi) in zip(sides, ts):
+        nbytes = (N * wb + M * ab) * K // 8 + (N + M) * K // 32 + 2 * M * N
+        t_hbm, t_mfma = nbytes / HBM * 1e6, flops / PEAK * 1e6
+        print(json.dumps(dict(size=f"{N}x{K}", M=M, side=name, us=round(us, 1), min_us=round(lo, 1), max_us=round(hi, 1), bytes=int(nbytes),
+                              share_of_hbm=round(t_hbm / us, 3), tflops=round(flops / us * 1e-6, 1), over_w4a8=round(us / ts[0][0], 3))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--m", default="1,16,256,4096")
+    ap.add_argument("--w6", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "micro_mx_gemm measures the MI355X; there is no CPU path"
     torch.cuda.set_device(0)
     for N, K in ((4096, 4096), (4096, 11008)):
         for M in (int(m) for m in args.m.split(",")):
-            rows(N, K, M, args.reps)
+            (rows_w6 if args.w6 else rows)(N, K, M, args.reps)
             torch.cuda.empty_cache()
 
 
