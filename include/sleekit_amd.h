@@ -89,7 +89,8 @@ typedef void *slk_stream_t;
  * changed), then slk_hadamard_rows (the block Hadamard rotation of sleekit_amd/rotation.py; likewise), then MXFP4
  * activations: slk_mx_quantize_act4, slk_mx_gemm_a4 and slk_mx_rotate_quantize_act (likewise), then MXFP6 (E2M3)
  * activations: slk_mx_quantize_act6, slk_mx_dequantize_act6, slk_mx_gemm_a6 and slk_mx_rotate_quantize_act6 (likewise), then MXFP6
- * (E2M3) layers: slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6 and slk_mx_gemm_w6 (likewise). */
+ * (E2M3) layers: slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6 and slk_mx_gemm_w6 (likewise), then the expert-grouped
+ * product: slk_mx_experts_workspace_bytes and slk_mx_gemm_experts (likewise). */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -640,6 +641,38 @@ int slk_mx_unpack6(const uint8_t *codes, const uint8_t *scales, int R, int n, ui
                    slk_stream_t stream);
 int slk_mx_gemm_w6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
                    const float *bias, int M, int N, int K, int a_fmt, int out_dtype, void *out, slk_stream_t stream);
+
+/* A mixture-of-experts layer in one call: E packed layers of one shape N x K, every row of A multiplied with the layer of
+ * its expert.  The rows are sorted by expert, and `offsets` -- E + 1 ints in DEVICE memory, never read by the host -- says
+ * where each expert's rows are: rows offsets[e] .. offsets[e + 1] - 1 of A and of out (M x N) belong to expert e.
+ *   - w_codes: the E layers one after the other, E x N x (K bits / 8) bytes, expert e's at byte e * N * (K / 32) * 16
+ *     (SLK_MX_W_FP4, E2M1) or * 24 (SLK_MX_W_FP6, E2M3); w_scales E x N x K / 32; bias E x N float32, may be NULL.
+ *   - a_codes / a_scales: M rows as the activation quantizers write them; a_fmt SLK_MX_ACT_FP8, _FP4 or _FP6.  The pairs
+ *     are the dense entries': the three activation formats against SLK_MX_W_FP4, and SLK_MX_ACT_FP8 or SLK_MX_ACT_FP6
+ *     against SLK_MX_W_FP6; SLK_MX_ACT_FP4 against SLK_MX_W_FP6 is refused.
+ *   - for the rows of expert e, out[m][n] = sum_k A[m][k] W_e[n][k] (+ bias[e][n]) under slk_mx_gemm's contract -- exact
+ *     products, float32 sums inside the MFMA over K in a fixed order, no atomics, a repeated call gives the same bits --
+ *     and BIT FOR BIT what slk_mx_gemm / _a4 / _a6 / _w6 gives for that slice of A alone against that expert's layer: an
+ *     expert with up to 64 rows takes the dense entries' few-rows form, one with more their many-rows form.
+ *   - offsets rule: offsets[0] == 0, offsets[e] <= offsets[e + 1], offsets[E] == M (an expert may have no rows).  It is
+ *     checked on the device before any address is made from an offset: if it does not hold, flag[0] = 1 and out is not
+ *     written.  flag: DEVICE int, required, written by the call (0 where the rule holds).
+ *   - workspace: slk_mx_experts_workspace_bytes(E, M) bytes, aligned to 4; it holds the row tiles of the call (as ints:
+ *     the number of 16-row and of 64-row tiles at [0] and [1], from [4] the M / 16 + E entries (expert, first row, row
+ *     bound) of the 16-row tiles, after them the M / 64 + E entries of the 64-row tiles).
+ *   Everything runs in order on `stream`: nothing waits on another workgroup, and the host reads nothing.  Nothing is read
+ *   past a_codes, w_codes, w_scales or bias of exactly the sizes above.
+ * SLK_E_ARG, before any launch, slk_last_error() naming the offender: E < 1 or E > SLK_MX_MAX_EXPERTS, M or N < 1, K % 32
+ *   != 0 or K < 32, a NULL pointer other than bias, an unknown dtype, a_fmt or w_fmt, the refused pair, a_codes, w_codes or
+ *   out off 16-byte alignment, a workspace off 4 bytes or below slk_mx_experts_workspace_bytes(E, M), M / 64 + E above the
+ *   65535 row tiles of one launch.  slk_mx_experts_workspace_bytes is 0 for E or M < 1.                                */
+#define SLK_MX_W_FP4 0
+#define SLK_MX_W_FP6 1
+#define SLK_MX_MAX_EXPERTS 1024
+size_t slk_mx_experts_workspace_bytes(int E, int M);
+int slk_mx_gemm_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                        const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, int out_dtype,
+                        void *out, int *flag, void *workspace, size_t ws_bytes, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -26,6 +26,8 @@ DTYPE_F64 = 3  # slk_hadamard_rows only
 MX_MAX, MX_MSE, MX_DIAG = 0, 1, 2  # slk_mx_scale_search `mode`
 MX_ACT_FP8, MX_ACT_FP4 = 0, 1  # slk_mx_rotate_quantize_act `fmt`
 MX_ACT_FP6 = 2  # slk_mx_gemm_w6 `a_fmt` (beside MX_ACT_FP8)
+MX_W_FP4, MX_W_FP6 = 0, 1  # slk_mx_gemm_experts `w_fmt`
+MX_MAX_EXPERTS = 1024
 ORDER_NONE, ORDER_DIAG, ORDER_ERR, ORDER_SQERR, ORDER_KEYS = 0, 1, 2, 3, 4
 ORDER_MODES = {"none": ORDER_NONE, "diag": ORDER_DIAG, "err": ORDER_ERR, "sqerr": ORDER_SQERR}
 
@@ -133,6 +135,8 @@ PROTOTYPES = {
     "slk_mx_pack6": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "slk_mx_unpack6": (c_int, [P, P, c_int, c_int, P, P, P, P]),
     "slk_mx_gemm_w6": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "slk_mx_experts_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "slk_mx_gemm_experts": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

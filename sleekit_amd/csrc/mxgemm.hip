@@ -1,5 +1,6 @@
 // A linear layer computed from the packed MXFP4 form on the block-scaled MFMA (slk_mx_quantize_act, _act4, _act6,
-// slk_mx_dequantize_act, _act6, slk_mx_gemm, _a4, _a6, _w6; the formats are pinned in include/sleekit_amd.h and INTEGRATION.md).
+// slk_mx_dequantize_act, _act6, slk_mx_gemm, _a4, _a6, _w6, slk_mx_gemm_experts; the formats are pinned in include/sleekit_amd.h and
+// INTEGRATION.md).
 //
 // Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns -- or, for
 // an MXFP6 layer (slk_mx_gemm_w6), as slk_mx_pack6 left them: E2M3 codes, 24 bytes a block.
@@ -254,18 +255,20 @@ __device__ __forceinline__ void store_tile(v4f acc, const float *__restrict__ bi
 // the SK partial tiles in wave order.  Both orders are fixed, so a result does not depend on timing.
 constexpr int MXG_SK = 8;
 constexpr int MXG_SPLIT_MAX_M = 64;
-template <int OUT, int AF = MXA_E4M3, int WF = MXA_E2M1>
-__global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
-                                                                const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
-                                                                const float *__restrict__ bias, int M, int N, int K,
-                                                                typename PkOut<OUT>::T *__restrict__ Y) {
+// (The body is shared with the expert-grouped kernel below: row0 / rows are the tile's first row and the row bound of the
+// matrix -- or of the expert --, n0 the tile's first column.)
+template <int OUT, int AF, int WF>
+__device__ __forceinline__ void mx_gemm_splitk_tile(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                    const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                    const float *__restrict__ bias, int row0, int rows, int n0, int N, int K,
+                                                    typename PkOut<OUT>::T *__restrict__ Y) {
     __shared__ v4f part[MXG_SK - 1][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bpr = K / 32, steps = (bpr + 3) / 4;
-    const int m = blockIdx.y * 16 + (lane & 15), n = blockIdx.x * 16 + (lane & 15), q = lane >> 4;
+    const int m = row0 + (lane & 15), n = n0 + (lane & 15), q = lane >> 4;
     v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int s = wave; s < steps; s += 2 * MXG_SK) {  // two steps' loads in flight; a step past the end loads zeros
-        const FragA<AF> a0 = load_a<AF>(Ac, As, m, M, s, q, bpr), a1 = load_a<AF>(Ac, As, m, M, s + MXG_SK, q, bpr);
+        const FragA<AF> a0 = load_a<AF>(Ac, As, m, rows, s, q, bpr), a1 = load_a<AF>(Ac, As, m, rows, s + MXG_SK, q, bpr);
         const FragB<WF> b0 = load_b<WF>(Wc, Ws, n, N, 4 * s + q, bpr), b1 = load_b<WF>(Wc, Ws, n, N, 4 * (s + MXG_SK) + q, bpr);
         acc = mx_mfma<AF, WF>(a0, b0, acc);
         acc = mx_mfma<AF, WF>(a1, b1, acc);
@@ -275,19 +278,26 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *_
     if (wave) return;
 #pragma unroll
     for (int w = 0; w < MXG_SK - 1; ++w) acc += part[w][lane];
-    store_tile<OUT>(acc, bias, blockIdx.y * 16 + 4 * q, n, M, N, Y);
+    store_tile<OUT>(acc, bias, row0 + 4 * q, n, rows, N, Y);
+}
+template <int OUT, int AF = MXA_E4M3, int WF = MXA_E2M1>
+__global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                const float *__restrict__ bias, int M, int N, int K,
+                                                                typename PkOut<OUT>::T *__restrict__ Y) {
+    mx_gemm_splitk_tile<OUT, AF, WF>(Ac, As, Wc, Ws, bias, blockIdx.y * 16, M, blockIdx.x * 16, N, K, Y);
 }
 
 // Many rows: a wave holds a 32 x 32 tile of Y as 2 x 2 MFMA tiles, so each fragment it loads feeds two MFMAs, and the four
 // waves of a workgroup cover 64 x 64; the fragments two waves share come to the second of them from the cache.
-template <int OUT, int AF = MXA_E4M3, int WF = MXA_E2M1>
-__global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
-                                                       const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
-                                                       const float *__restrict__ bias, int M, int N, int K,
-                                                       typename PkOut<OUT>::T *__restrict__ Y) {
+template <int OUT, int AF, int WF>
+__device__ __forceinline__ void mx_gemm_tiled_tile(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                   const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                   const float *__restrict__ bias, int row0, int rows, int col0, int N, int K,
+                                                   typename PkOut<OUT>::T *__restrict__ Y) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bpr = K / 32, steps = (bpr + 3) / 4;
-    const int m0 = blockIdx.y * 64 + (wave >> 1) * 32, n0 = blockIdx.x * 64 + (wave & 1) * 32, q = lane >> 4;
+    const int m0 = row0 + (wave >> 1) * 32, n0 = col0 + (wave & 1) * 32, q = lane >> 4;
     v4f acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -298,7 +308,7 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
         FragB<WF> b[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            a[i] = load_a<AF>(Ac, As, m0 + 16 * i + (lane & 15), M, s, q, bpr);
+            a[i] = load_a<AF>(Ac, As, m0 + 16 * i + (lane & 15), rows, s, q, bpr);
             b[i] = load_b<WF>(Wc, Ws, n0 + 16 * i + (lane & 15), N, 4 * s + q, bpr);
         }
 #pragma unroll
@@ -309,7 +319,109 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) store_tile<OUT>(acc[i][j], bias, m0 + 16 * i + 4 * q, n0 + 16 * j + (lane & 15), M, N, Y);
+        for (int j = 0; j < 2; ++j) store_tile<OUT>(acc[i][j], bias, m0 + 16 * i + 4 * q, n0 + 16 * j + (lane & 15), rows, N, Y);
+}
+template <int OUT, int AF = MXA_E4M3, int WF = MXA_E2M1>
+__global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                       const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                       const float *__restrict__ bias, int M, int N, int K,
+                                                       typename PkOut<OUT>::T *__restrict__ Y) {
+    mx_gemm_tiled_tile<OUT, AF, WF>(Ac, As, Wc, Ws, bias, blockIdx.y * 64, M, blockIdx.x * 64, N, K, Y);
+}
+
+// ---------------------------------------------------------------- a mixture-of-experts layer in one call
+// slk_mx_gemm_experts: the rows of A are sorted by expert and `offsets` (device memory, E + 1 ints) says where each expert's
+// rows begin.  The host never reads it.  k_mx_expert_tiles, one workgroup, checks the offsets and turns them into two
+// tables of row tiles in the workspace: 16-row tiles of the experts with 1 .. MXG_SPLIT_MAX_M rows, for the split-K form, and
+// 64-row tiles of the others, for the 2 x 2 tiled form -- the form mx_gemm would choose for that expert's rows alone, so the
+// result is that call's bit for bit.  The two products are launched over host-computable upper bounds of the tile counts;
+// a workgroup at or past its table's count returns at once.  Invalid offsets raise the flag and leave both counts 0: no
+// address is ever made from an offset that was not checked.
+//
+// The workspace, as ints: [0] the number of 16-row tiles, [1] of 64-row tiles, [2], [3] unused; from [4] the 16-row table,
+// M / 16 + E entries of (expert, first row, row bound); after it the 64-row table, M / 64 + E entries of the same.
+// An expert of m rows has at most m / 16 + 1 (m / 64 + 1) tiles, so the tables cannot overflow when the offsets are valid.
+constexpr int MXE_MAX_EXPERTS = SLK_MX_MAX_EXPERTS;
+constexpr int MXE_HEAD = 4;
+static inline size_t mxe_cap16(int E, int M) { return (size_t)M / 16 + E; }
+static inline size_t mxe_cap64(int E, int M) { return (size_t)M / 64 + E; }
+
+__global__ __launch_bounds__(256) void k_mx_expert_tiles(const int *__restrict__ offsets, int E, int M, int *__restrict__ ws,
+                                                         int cap16, int *__restrict__ flag) {
+    __shared__ int scan16[256], scan64[256];
+    __shared__ int base[2];
+    const int t = threadIdx.x;
+    // 1. the rule: offsets[0] == 0, non-decreasing, offsets[E] == M (so every offset lies in 0 .. M)
+    int bad = 0;
+    for (int e = t; e < E; e += 256) {
+        const int o0 = offsets[e], o1 = offsets[e + 1];
+        bad |= o1 < o0 || (e == 0 && o0 != 0) || (e == E - 1 && o1 != M);
+    }
+    bad = __syncthreads_or(bad);
+    if (t == 0) flag[0] = bad ? 1 : 0;
+    if (bad) {
+        if (t < 2) ws[t] = 0;
+        return;
+    }
+    // 2. the tables, in expert order: 256 experts a round, each thread its expert's tiles behind an exclusive scan
+    if (t < 2) base[t] = 0;
+    int *const t16 = ws + MXE_HEAD, *const t64 = ws + MXE_HEAD + 3 * (size_t)cap16;
+    for (int e0 = 0; e0 < E; e0 += 256) {
+        const int e = e0 + t;
+        const int o0 = e < E ? offsets[e] : 0, o1 = e < E ? offsets[e + 1] : 0, m = o1 - o0;
+        const int n16 = m >= 1 && m <= MXG_SPLIT_MAX_M ? (m + 15) / 16 : 0, n64 = m > MXG_SPLIT_MAX_M ? (m + 63) / 64 : 0;
+        scan16[t] = n16, scan64[t] = n64;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {  // (inclusive, Hillis-Steele)
+            const int a = t >= d ? scan16[t - d] : 0, b = t >= d ? scan64[t - d] : 0;
+            __syncthreads();
+            scan16[t] += a, scan64[t] += b;
+            __syncthreads();
+        }
+        int at16 = base[0] + scan16[t] - n16, at64 = base[1] + scan64[t] - n64;
+        for (int i = 0; i < n16; ++i, ++at16) t16[3 * at16] = e, t16[3 * at16 + 1] = o0 + 16 * i, t16[3 * at16 + 2] = o1;
+        for (int i = 0; i < n64; ++i, ++at64) t64[3 * at64] = e, t64[3 * at64 + 1] = o0 + 64 * i, t64[3 * at64 + 2] = o1;
+        __syncthreads();
+        if (t == 255) base[0] += scan16[255], base[1] += scan64[255];
+        __syncthreads();
+    }
+    if (t < 2) ws[t] = base[t];
+}
+
+// One row tile of one expert: the dense kernels' bodies on that expert's layer, bias and row bound.
+template <int WF>
+struct ExpertTile {
+    const uint8_t *Wc, *Ws;
+    const float *bias;
+    int row0, rows;
+    __device__ __forceinline__ ExpertTile(const int *__restrict__ table, const uint8_t *__restrict__ w_codes,
+                                          const uint8_t *__restrict__ w_scales, const float *__restrict__ b, int N, int K) {
+        const int *entry = table + 3 * (size_t)blockIdx.y;
+        const size_t e = (size_t)entry[0], blocks = (size_t)N * (K / 32);
+        Wc = w_codes + e * blocks * (4 * mxa_bits<WF>()), Ws = w_scales + e * blocks;  // 16 or 24 bytes of codes a block
+        bias = b ? b + e * N : nullptr;
+        row0 = entry[1], rows = entry[2];
+    }
+};
+template <int OUT, int AF, int WF>
+__global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_experts_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                        const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                        const float *__restrict__ bias, const int *__restrict__ count,
+                                                                        const int *__restrict__ table, int N, int K,
+                                                                        typename PkOut<OUT>::T *__restrict__ Y) {
+    if ((int)blockIdx.y >= *count) return;
+    const ExpertTile<WF> x(table, Wc, Ws, bias, N, K);
+    mx_gemm_splitk_tile<OUT, AF, WF>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x * 16, N, K, Y);
+}
+template <int OUT, int AF, int WF>
+__global__ __launch_bounds__(256) void k_mx_gemm_experts_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                               const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                               const float *__restrict__ bias, const int *__restrict__ count,
+                                                               const int *__restrict__ table, int N, int K,
+                                                               typename PkOut<OUT>::T *__restrict__ Y) {
+    if ((int)blockIdx.y >= *count) return;
+    const ExpertTile<WF> x(table, Wc, Ws, bias, N, K);
+    mx_gemm_tiled_tile<OUT, AF, WF>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x * 64, N, K, Y);
 }
 
 static inline int mxg_grid(size_t units) {
@@ -393,7 +505,71 @@ static int mx_gemm(const char *name, const uint8_t *a_codes, const uint8_t *a_sc
     });
 }
 
+// slk_mx_gemm_experts of one format pair: the prologue, the split-K product over the 16-row table and, where an expert can
+// have more than MXG_SPLIT_MAX_M rows at all, the tiled product over the 64-row table; in order on the stream
+template <int AF, int WF>
+static int mx_gemm_experts(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                           const float *bias, const int *offsets, int E, int M, int N, int K, int out_dtype, void *out, int *flag, int *ws,
+                           hipStream_t s) {
+    const int cap16 = (int)mxe_cap16(E, M), cap64 = (int)mxe_cap64(E, M);
+    // an expert of the split-K form has at most MXG_SPLIT_MAX_M / 16 tiles, so 4 E bounds the first launch as well
+    const int rows16 = cap16 < 4 * E ? cap16 : 4 * E, rows64 = cap64;
+    SLK_RUN("mx_expert_tiles", 0, 4.0 * (E + 1), s, (k_mx_expert_tiles<<<1, 256, 0, s>>>(offsets, E, M, ws, cap16, flag)));
+    const int *t16 = ws + MXE_HEAD, *t64 = ws + MXE_HEAD + 3 * (size_t)cap16;
+    return with_dtype(out_dtype, [&](auto t) -> int {
+        typedef typename decltype(t)::T T;
+        constexpr int OUT = decltype(t)::OUT;
+        T *Y = static_cast<T *>(out);
+        const double flops = 2.0 * M * N * K;
+        const double bytes = ((double)M * mxa_block_bytes<AF>() + (double)E * N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * N * sizeof(T);
+        const dim3 grid16((N + 15) / 16, rows16), grid64((N + 63) / 64, rows64);
+        SLK_RUN(name, flops, bytes, s,
+                (k_mx_gemm_experts_splitk<OUT, AF, WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, t16, N, K, Y)));
+        if (M > MXG_SPLIT_MAX_M)
+            SLK_RUN(name, 0, 0, s,
+                    (k_mx_gemm_experts_tiled<OUT, AF, WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, t64, N, K, Y)));
+        return SLK_OK;
+    });
+}
+
 extern "C" {
+
+size_t slk_mx_experts_workspace_bytes(int E, int M) {
+    if (E < 1 || M < 1) return 0;
+    return sizeof(int) * (MXE_HEAD + 3 * (mxe_cap16(E, M) + mxe_cap64(E, M)));
+}
+
+int slk_mx_gemm_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
+                        const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, int out_dtype, void *out, int *flag,
+                        void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    SLK_REQUIRE(E >= 1 && E <= MXE_MAX_EXPERTS, "E must be 1 .. %d experts (E = %d)", MXE_MAX_EXPERTS, E);
+    SLK_REQUIRE(M > 0 && N > 0, "M and N must be at least 1 (M = %d, N = %d)", M, N);
+    SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);
+    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
+    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP4 || a_fmt == SLK_MX_ACT_FP6, "unknown a_fmt %d", a_fmt);
+    SLK_REQUIRE(w_fmt == SLK_MX_W_FP4 || w_fmt == SLK_MX_W_FP6, "unknown w_fmt %d", w_fmt);
+    SLK_REQUIRE(!(w_fmt == SLK_MX_W_FP6 && a_fmt == SLK_MX_ACT_FP4),
+                "an MXFP6 layer takes MXFP8 (SLK_MX_ACT_FP8) or MXFP6 (SLK_MX_ACT_FP6) activations (a_fmt = %d)", a_fmt);
+    SLK_REQUIRE(a_codes && a_scales && w_codes && w_scales && out, "null pointer");
+    SLK_REQUIRE(offsets, "null offsets");
+    SLK_REQUIRE(flag, "null flag");
+    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(out), "a_codes, w_codes and out must be aligned to 16 bytes");
+    SLK_REQUIRE(workspace && (uintptr_t)workspace % sizeof(int) == 0, "the workspace must be non-null and aligned to 4 bytes");
+    SLK_REQUIRE(ws_bytes >= slk_mx_experts_workspace_bytes(E, M), "the workspace is too small: %zu bytes, slk_mx_experts_workspace_bytes(%d, %d) = %zu",
+                ws_bytes, E, M, slk_mx_experts_workspace_bytes(E, M));
+    SLK_REQUIRE(mxe_cap64(E, M) <= 65535, "M / 64 + E is above the 65535 row tiles of one launch (M = %d, E = %d)", M, E);
+    hipStream_t s = as_stream(stream);
+    int *ws = static_cast<int *>(workspace);
+#define SLK_MXE_PAIR(AF, WF, NAME) return mx_gemm_experts<AF, WF>(NAME, a_codes, a_scales, w_codes, w_scales, bias, offsets, E, M, N, K, out_dtype, out, flag, ws, s)
+    if (w_fmt == SLK_MX_W_FP6) {
+        if (a_fmt == SLK_MX_ACT_FP6) SLK_MXE_PAIR(MXA_E2M3, MXA_E2M3, "mx_gemm_experts_w6a6");
+        SLK_MXE_PAIR(MXA_E4M3, MXA_E2M3, "mx_gemm_experts_w6");
+    }
+    if (a_fmt == SLK_MX_ACT_FP4) SLK_MXE_PAIR(MXA_E2M1, MXA_E2M1, "mx_gemm_experts_a4");
+    if (a_fmt == SLK_MX_ACT_FP6) SLK_MXE_PAIR(MXA_E2M3, MXA_E2M1, "mx_gemm_experts_a6");
+    SLK_MXE_PAIR(MXA_E4M3, MXA_E2M1, "mx_gemm_experts");
+#undef SLK_MXE_PAIR
+}
 
 int slk_mx_quantize_act(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
     return mx_quantize_act<MXA_E4M3>("mx_quantize_act", X, x_dtype, M, K, a_codes, a_scales, flag, stream);

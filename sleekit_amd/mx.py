@@ -82,6 +82,16 @@ Known answers: indices 0, 1, 30, 31, 32, 61, 62 are codes 3f 3e 21 00 01 1e 1f; 
     res = quantize_mxfp6(W, H, nb_ls_moves=10);  y = linear_mxfp6(x, res.codes, res.scales, bias, activations="mxfp6_e2m3")
     layer = MXLinear.from_result(nn_linear, res)          # the format is read off the widths of res.codes and res.scales
 
+EXPERTS.  A mixture-of-experts layer is E packed layers of one shape, stacked: codes (E, N, K bits / 8), scales (E, N, K / 32),
+bias (E, N).  One call multiplies every row with the layer of its expert (slk_mx_gemm_experts): the rows are sorted by expert
+and `offsets`, int32 (E + 1,) on the device, says where each expert's rows begin -- offsets[0] == 0, never decreasing,
+offsets[E] == M; the host never reads it, and offsets that break the rule are a ValueError after the launches.  Each expert's
+rows are bit for bit matmul_mx of that slice.  Every format pair of matmul_mx is taken.
+    results = quantize_experts(Ws, Hs)                         # E MXResults, each quantize_mxfp4(W, H)'s bit for bit
+    experts = MXExperts.from_results(results, biases)          # buffers codes, scales, bias
+    y = experts.forward_tokens(x, expert_ids, gates)           # x (T, K), expert_ids and gates (T, k) -> (T, N)
+    order, offsets = sort_by_expert(expert_ids, E);  Y = linear_mx_experts(x[order // k], codes, scales, offsets, bias)
+
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
 everything runs on the GPU on the current stream, and there is no CPU fallback.
 """
@@ -568,23 +578,8 @@ def _linear(x, codes, scales, bias, dtype, activations, rotation, wf):
     return dev.like_input(out.reshape(lead + (N,)), x)
 
 
-class MXLinear(torch.nn.Module):
-    """A linear layer kept in its packed MX form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
-    or None; forward(x) = linear_mxfp4(x, codes, scales, bias, activations=activations).  `activations` ("mxfp8", the
-    default, "mxfp4" or "mxfp6_e2m3") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8".
-    weights="mxfp6_e2m3": an MXFP6 layer, `codes` (N, 3 K / 4), forward through linear_mxfp6; it refuses "mxfp4" activations.
-    `weights` is extra state too, written only when it is not "mxfp4"; a state of the other weight format is an error."""
-
-    def __init__(self, in_features, out_features, bias=True, device=None, activations="mxfp8", weights="mxfp4"):
-        super().__init__()
-        _blocks(int(in_features))
-        _check_pair(_activations(activations), _weight_format(weights))
-        self.activations, self.weights = activations, weights
-        self.in_features, self.out_features = int(in_features), int(out_features)
-        width = self.in_features * _WEIGHTS[weights].bits // 8
-        self.register_buffer("codes", torch.zeros((self.out_features, width), dtype=torch.uint8, device=device))
-        self.register_buffer("scales", torch.full((self.out_features, self.in_features // BLOCK), 127, dtype=torch.uint8, device=device))
-        self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=device) if bias else None)
+class _MXModule(torch.nn.Module):
+    """What MXLinear and MXExperts share: `activations` and `weights` as the module's extra state."""
 
     # `activations` and `weights` travel as the module's extra state, each written only when it is not the default: the state
     # dict of a default module has the keys it always had, and a state dict without the key -- every one saved before --
@@ -620,6 +615,25 @@ class MXLinear(torch.nn.Module):
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
         self.activations = activations
 
+
+class MXLinear(_MXModule):
+    """A linear layer kept in its packed MX form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
+    or None; forward(x) = linear_mxfp4(x, codes, scales, bias, activations=activations).  `activations` ("mxfp8", the
+    default, "mxfp4" or "mxfp6_e2m3") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8".
+    weights="mxfp6_e2m3": an MXFP6 layer, `codes` (N, 3 K / 4), forward through linear_mxfp6; it refuses "mxfp4" activations.
+    `weights` is extra state too, written only when it is not "mxfp4"; a state of the other weight format is an error."""
+
+    def __init__(self, in_features, out_features, bias=True, device=None, activations="mxfp8", weights="mxfp4"):
+        super().__init__()
+        _blocks(int(in_features))
+        _check_pair(_activations(activations), _weight_format(weights))
+        self.activations, self.weights = activations, weights
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        width = self.in_features * _WEIGHTS[weights].bits // 8
+        self.register_buffer("codes", torch.zeros((self.out_features, width), dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.full((self.out_features, self.in_features // BLOCK), 127, dtype=torch.uint8, device=device))
+        self.register_buffer("bias", torch.zeros(self.out_features, dtype=torch.float32, device=device) if bias else None)
+
     @classmethod
     def from_result(cls, layer, result, activations="mxfp8"):
         """The module of a torch.nn.Linear and the MXResult that Sleekit(layer).quantize_mxfp4() or quantize_mxfp6() returned
@@ -648,3 +662,284 @@ class MXLinear(torch.nn.Module):
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
                 f"activations={self.activations}" + ("" if self.weights == "mxfp4" else f", weights={self.weights}"))
+
+
+# --------------------------------------------------------------------------------------------------------------- experts
+# A mixture-of-experts layer: E packed layers of one shape, every row of x against the layer of its expert, in one call
+# (slk_mx_gemm_experts; module docstring, EXPERTS).
+_A_FMT = {"mxfp8": _lib.MX_ACT_FP8, "mxfp4": _lib.MX_ACT_FP4, "mxfp6_e2m3": _lib.MX_ACT_FP6}
+_W_FMT = {"mxfp4": _lib.MX_W_FP4, "mxfp6_e2m3": _lib.MX_W_FP6}
+_OFFSETS_RULE = ("offsets must start at 0, never decrease and end at the number of rows: "
+                 "offsets[0] == 0, offsets[e] <= offsets[e + 1], offsets[E] == M")
+
+
+def _raise_flags(*checks):
+    """(device flag or None, message) pairs read in ONE device -> host transfer, the first raised flag's message raised."""
+    checks = [(f, m) for f, m in checks if f is not None]
+    if not checks:
+        return
+    for v, (_, message) in zip(torch.cat([f.reshape(1).to(torch.int32) for f, _ in checks]).tolist(), checks):
+        if v:
+            raise ValueError(message)
+
+
+def _expert_weights(codes, scales, wf):
+    """(E, N, K) of stacked packed layers, codes (E, N, K bits / 8) and scales (E, N, K / 32), shapes and dtypes checked."""
+    for x, what in ((codes, "codes"), (scales, "scale bytes")):
+        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 3:
+            raise ValueError(f"{what} of stacked experts must be a 3-D NumPy array or torch tensor (experts, rows, bytes)")
+        if x.dtype not in (torch.uint8, np.uint8):
+            raise ValueError(f"{what} must be torch.uint8 (got {x.dtype})")
+    E, N, width = (int(v) for v in codes.shape)
+    if E < 1 or E > _lib.MX_MAX_EXPERTS or N < 1:
+        raise ValueError(f"codes must hold 1 .. {_lib.MX_MAX_EXPERTS} experts of at least one row (got {tuple(codes.shape)})")
+    if 8 * width % wf.bits != 0:
+        raise ValueError(f"codes has {width} columns of bytes, which is no whole number of {wf.bits}-bit codes")
+    K = 8 * width // wf.bits
+    _blocks(K)
+    if tuple(scales.shape) != (E, N, K // BLOCK):
+        raise ValueError(f"scale bytes must be ({E}, {N}, {K // BLOCK}) for {E} ({N}, {K}) layers; got {tuple(scales.shape)}")
+    return E, N, K
+
+
+def _check_expert_bias(bias, E, N):
+    if bias is not None and (not isinstance(bias, (np.ndarray, torch.Tensor)) or tuple(bias.shape) != (E, N)):
+        raise ValueError(f"bias must be ({E}, {N}); got {tuple(getattr(bias, 'shape', ()))}")
+
+
+def _check_offsets(offsets, E):
+    if not isinstance(offsets, (np.ndarray, torch.Tensor)) or offsets.dtype not in (torch.int32, np.int32) or tuple(offsets.shape) != (E + 1,):
+        raise ValueError(f"offsets must be int32 ({E + 1},): one more than the {E} experts "
+                         f"(got {getattr(offsets, 'dtype', type(offsets).__name__)} {tuple(getattr(offsets, 'shape', ()))})")
+
+
+def _gemm_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, dtype, fmt, wf):
+    """(out (M, N), flag) of device operands: the caller reads the flag (_OFFSETS_RULE) once everything is launched."""
+    out = torch.empty((M, N), dtype=dtype, device=ac.device)
+    flag = torch.empty(1, dtype=torch.int32, device=ac.device)
+    ws, ws_bytes = dev.scratch(_lib.lib.slk_mx_experts_workspace_bytes(E, M), "mx_experts")
+    _lib.check(_lib.lib.slk_mx_gemm_experts(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), dev.ptr(offsets), E, M, N, K,
+                                            _A_FMT[fmt.name], _W_FMT[wf.name], _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.ptr(ws), ws_bytes,
+                                            dev.stream_handle()))
+    return out, flag
+
+
+def _expert_tile_tables(E, M):
+    """The two tile tables the last grouped product of (E, M) on this stream left in its workspace, as NumPy arrays (tiles, 3)
+    of (expert, first row, row bound): 16-row tiles, then 64-row tiles (tests/test_gpu_mx_experts.py holds them to a model)."""
+    ws = dev.scratch(_lib.lib.slk_mx_experts_workspace_bytes(E, M), "mx_experts")[0]
+    words = ws[:_lib.lib.slk_mx_experts_workspace_bytes(E, M)].view(torch.int32).cpu().numpy()
+    n16, n64, cap16 = int(words[0]), int(words[1]), M // 16 + E
+    return words[4:4 + 3 * n16].reshape(n16, 3).copy(), words[4 + 3 * cap16:4 + 3 * cap16 + 3 * n64].reshape(n64, 3).copy()
+
+
+def matmul_mx_experts(a_codes, a_scales, codes, scales, offsets, bias=None, dtype=torch.float32, activations="mxfp8", weights="mxfp4"):
+    """matmul_mx for a stack of E experts in one call: rows offsets[e] .. offsets[e + 1] - 1 of the quantized activations
+    (M rows, sorted by expert) are multiplied with expert e's layer, codes (E, N, K bits / 8) and scales (E, N, K / 32), and
+    bias (E, N) float32 added: Y (M, N), each expert's rows bit for bit matmul_mx of that slice against that layer.
+    offsets is int32 (E + 1,) and stays on the device; it must start at 0, never decrease and end at M (an expert may have
+    no rows).  The rule is checked on the device: where it does not hold nothing is computed and a ValueError is raised --
+    after the launches, by one read of the call's flag (which waits for the stream)."""
+    fmt, wf = _activations(activations), _weight_format(weights)
+    _check_pair(fmt, wf)
+    _out_dtype(dtype, a_codes)
+    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    K = _columns(width, fmt)
+    _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(a_scales, M, K, "activation scale bytes")
+    E, N, Kw = _expert_weights(codes, scales, wf)
+    if Kw != K:
+        raise ValueError(f"a_codes has {K} columns but the experts' layers have {Kw}")
+    _check_expert_bias(bias, E, N)
+    _check_offsets(offsets, E)
+    out, flag = _gemm_experts(_aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8),
+                              _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
+                              dev.to_device(offsets, torch.int32), E, M, N, K, dtype, fmt, wf)
+    _raise_flags((flag, _OFFSETS_RULE))
+    return dev.like_input(out, a_codes)
+
+
+def _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotation, wf, also=()):
+    fmt = _activations(activations)
+    _check_pair(fmt, wf)
+    if rotation is not None:
+        from .rotation import Rotation
+
+        if not isinstance(rotation, Rotation):
+            raise ValueError(f"rotation must be a Rotation (got {type(rotation).__name__})")
+    M, Kx = _matrix(x, "x", _ACT)
+    if dtype is None:
+        dtype = _torch_dtype(x)
+    _out_dtype(dtype, x)
+    E, N, K = _expert_weights(codes, scales, wf)
+    if Kx != K:
+        raise ValueError(f"x has {Kx} columns but the experts' layers have {K}")
+    if rotation is not None and rotation.n != K:
+        raise ValueError(f"the rotation has {rotation.n} features but the layers have {K}")
+    _check_expert_bias(bias, E, N)
+    _check_offsets(offsets, E)
+    Xd = dev.to_device(x, _torch_dtype(x))
+    if rotation is not None:
+        ac, asc, finite = _rotate_quantize_act(Xd, M, K, rotation, fmt)
+    else:
+        ac, asc, finite = _quantize_act(Xd, M, K, fmt)
+    out, flag = _gemm_experts(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
+                              dev.to_device(offsets, torch.int32), E, M, N, K, dtype, fmt, wf)
+    _raise_flags(*also, (finite, "activations must be finite: X holds a NaN or an infinity"), (flag, _OFFSETS_RULE))
+    return dev.like_input(out, x)
+
+
+def linear_mx_experts(x, codes, scales, offsets, bias=None, dtype=None, activations="mxfp8", weights="mxfp4", rotation=None):
+    """linear_mxfp4 / linear_mxfp6 for a stack of experts: x (M, K) float32, bfloat16 or float16, its rows sorted by expert
+    as `offsets` says (matmul_mx_experts), is quantized by ONE launch of the activation quantizer over all rows (with
+    `rotation`, of the fused rotate-and-quantize kernel), then multiplied by one grouped product; (M, N) in `dtype`, or in
+    x's dtype when `dtype` is None.  The two flags -- finite activations, the offsets rule -- are read together after the
+    launches: one wait for the stream a call.  With rotation= the result is the call on rotation.apply(x,
+    dtype=torch.float32) bit for bit."""
+    return _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotation, _weight_format(weights))
+
+
+def _sorted_by_expert(ids, E):
+    """(order, offsets, bad) of a flat device tensor of expert ids: all three stay on the device.  Ids outside 0 .. E - 1 are
+    clamped for the sort, so the offsets always follow the rule, and `bad` (one int32) says whether there were any."""
+    bad = ((ids < 0) | (ids >= E)).any().to(torch.int32)
+    key, order = torch.sort(ids.clamp(0, E - 1), stable=True)
+    offsets = torch.searchsorted(key, torch.arange(E + 1, device=ids.device, dtype=key.dtype), out_int32=True)
+    return order, offsets, bad
+
+
+def _expert_ids(expert_ids, E):
+    if not isinstance(expert_ids, (np.ndarray, torch.Tensor)) or expert_ids.dtype not in (torch.int32, torch.int64, np.int32, np.int64):
+        raise ValueError(f"expert_ids must be an int32 or int64 NumPy array or torch tensor (got {getattr(expert_ids, 'dtype', type(expert_ids).__name__)})")
+    if isinstance(E, bool) or not isinstance(E, int) or E < 1 or E > _lib.MX_MAX_EXPERTS:
+        raise ValueError(f"E must be an int in 1 .. {_lib.MX_MAX_EXPERTS} (got {E!r})")
+    if expert_ids.size == 0 if isinstance(expert_ids, np.ndarray) else expert_ids.numel() == 0:
+        raise ValueError("expert_ids is empty")
+    return dev.to_device(expert_ids, torch.int64).reshape(-1)
+
+
+def _ids_message(E):
+    return f"expert ids must lie in 0 .. {E - 1}"
+
+
+def sort_by_expert(expert_ids, E):
+    """(order, offsets) of expert ids of any shape, flattened: `order` (int64) is the stable sort of the ids -- rows
+    x[order] are sorted by expert, equal ids in their original order -- and `offsets` the int32 (E + 1,) table
+    matmul_mx_experts takes.  Built from torch ops on the device; the offsets are never read by the host.  An id outside
+    0 .. E - 1 is a ValueError: that check is one reduction whose single int is read before returning, which is this
+    function's only synchronisation (MXExperts.forward_tokens reads it together with its product's flags instead)."""
+    ids = _expert_ids(expert_ids, E)
+    order, offsets, bad = _sorted_by_expert(ids, E)
+    _raise_flags((bad, _ids_message(E)))
+    return dev.like_input(order, expert_ids), dev.like_input(offsets, expert_ids)
+
+
+class MXExperts(_MXModule):
+    """The experts of a mixture-of-experts layer kept in their packed MX form: buffers `codes` (E, N, K bits / 8), `scales`
+    (E, N, K / 32) and `bias` (E, N) float32 or None; `activations` and `weights` are extra state as in MXLinear.
+    forward(x, offsets) = linear_mx_experts(x, codes, scales, offsets, bias, ...) for rows sorted by expert;
+    forward_tokens(x, expert_ids, gates) routes, runs and combines."""
+
+    def __init__(self, num_experts, in_features, out_features, bias=True, device=None, activations="mxfp8", weights="mxfp4"):
+        super().__init__()
+        _blocks(int(in_features))
+        _check_pair(_activations(activations), _weight_format(weights))
+        if not 1 <= int(num_experts) <= _lib.MX_MAX_EXPERTS:
+            raise ValueError(f"num_experts must be 1 .. {_lib.MX_MAX_EXPERTS} (got {num_experts})")
+        self.activations, self.weights = activations, weights
+        self.num_experts, self.in_features, self.out_features = int(num_experts), int(in_features), int(out_features)
+        shape = (self.num_experts, self.out_features)
+        self.register_buffer("codes", torch.zeros(shape + (self.in_features * _WEIGHTS[weights].bits // 8,), dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.full(shape + (self.in_features // BLOCK,), 127, dtype=torch.uint8, device=device))
+        self.register_buffer("bias", torch.zeros(shape, dtype=torch.float32, device=device) if bias else None)
+
+    @classmethod
+    def from_results(cls, results, biases=None, activations="mxfp8", device=None):
+        """The module of a list of MXResults of one shape and format (quantize_experts) and, optionally, `biases` (E, N).
+        The weight format is read off the widths, as in MXLinear.from_result."""
+        results = list(results)
+        if not results:
+            raise ValueError("MXExperts.from_results takes at least one MXResult")
+        first = results[0]
+        wide, blocks = int(first.codes.shape[-1]), int(first.scales.shape[-1])
+        by_bits = {wf.bits * BLOCK * blocks: wf for wf in _WEIGHTS.values()}
+        if first.codes.ndim != 2 or first.scales.ndim != 2 or blocks < 1 or 8 * wide not in by_bits:
+            raise ValueError(f"codes of {wide} bytes a row under {blocks} scale bytes are neither 4 nor 6 bits a weight")
+        wf = by_bits[8 * wide]
+        N, K = _weights(first.codes, first.scales, wf)
+        for e, r in enumerate(results):
+            if tuple(r.codes.shape) != tuple(first.codes.shape) or tuple(r.scales.shape) != tuple(first.scales.shape):
+                raise ValueError(f"expert {e} is not a ({N}, {K}) layer of the first expert's format")
+        _check_expert_bias(biases, len(results), N)
+        if device is None:
+            device = first.codes.device if isinstance(first.codes, torch.Tensor) else dev.require_gpu()
+        self = cls(len(results), K, N, biases is not None, device, activations, wf.name)
+        for e, r in enumerate(results):
+            self.codes[e].copy_(torch.as_tensor(r.codes))
+            self.scales[e].copy_(torch.as_tensor(r.scales))
+        if biases is not None:
+            self.bias.copy_(torch.as_tensor(biases).float())
+        return self
+
+    def forward(self, x, offsets, rotation=None):
+        return _linear_experts(x, self.codes, self.scales, offsets, self.bias, None, self.activations, rotation, _WEIGHTS[self.weights])
+
+    def forward_tokens(self, x, expert_ids, gates=None, rotation=None):
+        """x (T, K), expert_ids (T, k) -- token t goes to its k experts -- and gates (T, k), None meaning ones: (T, N) in x's
+        dtype, sum_j gates[t][j] * expert expert_ids[t][j] (x[t]).  The T k rows x[order // k] are sorted by expert
+        (sort_by_expert's order and offsets, on the device), run through forward, put back in (T, k) order by a gather, and
+        added up in float32 in the order j = 0, 1, ..., k - 1 (product, then sum: no atomics, no index_add_), so a repeated
+        call gives the same bits.  The id check and the product's two flags are read together: one wait for the stream."""
+        T, _ = _matrix(x, "x", _ACT)
+        if not isinstance(expert_ids, (np.ndarray, torch.Tensor)) or expert_ids.ndim != 2 or expert_ids.shape[0] != T or expert_ids.shape[1] < 1:
+            raise ValueError(f"expert_ids must be ({T}, k) for x of {T} rows; got {tuple(getattr(expert_ids, 'shape', ()))}")
+        k = int(expert_ids.shape[1])
+        if gates is not None and (not isinstance(gates, (np.ndarray, torch.Tensor)) or tuple(gates.shape) != (T, k)):
+            raise ValueError(f"gates must be ({T}, {k}); got {tuple(getattr(gates, 'shape', ()))}")
+        ids = _expert_ids(expert_ids, self.num_experts)
+        order, offsets, bad = _sorted_by_expert(ids, self.num_experts)
+        Xd = dev.to_device(x, _torch_dtype(x))
+        y = _linear_experts(Xd[order // k], self.codes, self.scales, offsets, self.bias, None, self.activations, rotation,
+                            _WEIGHTS[self.weights], also=((bad, _ids_message(self.num_experts)),))
+        back = torch.empty_like(order)
+        back[order] = torch.arange(order.numel(), device=order.device)
+        y = y[back].reshape(T, k, self.out_features).float()
+        g = None if gates is None else dev.to_device(gates, torch.float32)
+        total = y[:, 0] if g is None else y[:, 0] * g[:, 0:1]
+        for j in range(1, k):
+            total = total + (y[:, j] if g is None else y[:, j] * g[:, j:j + 1])
+        return dev.like_input(total.to(_torch_dtype(x)), x)
+
+    def extra_repr(self):
+        return (f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, "
+                f"bias={self.bias is not None}, activations={self.activations}" + ("" if self.weights == "mxfp4" else f", weights={self.weights}"))
+
+
+def quantize_experts(Ws, Hs, weights="mxfp4", act_order="diag", damp=0.01, scale_mode="mse"):
+    """quantize_mxfp4 / quantize_mxfp6 (nb_ls_moves = 0) for the E experts of a layer: Ws (E, R, n) or a list of (R, n),
+    Hs one (n, n) Hessian per expert.  Returns a list of E MXResults, each bit for bit the single call's.  The loops go
+    through dist.quantize_stream -- same-shaped small layers are factored and looped in launches that cover them all -- and
+    the indices of all experts are packed by one call (rows are independent).  The stream has no local search."""
+    from . import dist
+
+    wf = _weight_format(weights)
+    if scale_mode not in _MODES:
+        raise ValueError(f'MX scale modes are "max", "mse" and "diag" (got "{scale_mode}")')
+    Ws, Hs = list(Ws), list(Hs)
+    if not Ws or len(Ws) != len(Hs):
+        raise ValueError(f"quantize_experts takes one Hessian per expert (got {len(Ws)} layers and {len(Hs)} Hessians)")
+    R, n = _matrix(Ws[0], "W", (torch.float32, np.float32))
+    _blocks(n)
+    for W, H in zip(Ws, Hs):
+        if _matrix(W, "W", (torch.float32, np.float32)) != (R, n):
+            raise ValueError(f"every expert must be ({R}, {n}); got {tuple(W.shape)}")
+        if H is None or H.ndim != 2 or tuple(H.shape) != (n, n):
+            raise ValueError(f"H must be ({n}, {n})")
+    Wd, Hd = [dev.to_device(W) for W in Ws], [dev.to_device(H) for H in Hs]
+    S = [compute_mx_scales(W, H, scale_mode, wf.name)[0] for W, H in zip(Wd, Hd)]
+    layers = [dict(W=W, H=H, gscale=s, group_size=BLOCK) for W, H, s in zip(Wd, Hd, S)]
+    shards = dist.quantize_stream(layers, dist.HipBackend(wf.codebook, act_order, damp, 0, with_error=False))
+    E = len(layers)
+    codes, scales = _pack(_aligned(torch.cat([sh["idx"] for sh in shards])), torch.cat(S), E * R, n, wf)
+    codes, scales = codes.reshape(E, R, -1), scales.reshape(E, R, -1)
+    return [MXResult(*(dev.like_input(t, Ws[e]) for t in (shards[e]["Q"], shards[e]["idx"], S[e], codes[e], scales[e]))) for e in range(E)]
