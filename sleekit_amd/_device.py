@@ -68,6 +68,11 @@ def ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def aligned(t):
+    """The MX and packed-index kernels move 16 bytes a lane: a contiguous view that starts off such a boundary is copied."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def workspace(R, n, batch=1, grouped=False):
     """(tensor, bytes): grow-only scratch per (device, stream) sized by slk_workspace_bytes(_batch); `grouped`: for the
     grouped batch loop, whose workspace is slk_workspace_bytes_batch at every batch size."""

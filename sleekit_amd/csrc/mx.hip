@@ -1,7 +1,10 @@
-// MXFP4: blocks of 32 consecutive columns of a row share one power-of-two scale (an E8M0 byte), the elements are FP4
-// E2M1 codes, two a byte (slk_mx_scale_search, slk_mx_pack, slk_mx_unpack, slk_mx_dequantize; the format is pinned in
-// include/sleekit_amd.h and INTEGRATION.md).  MXFP6 layers keep E2M3 codes instead, a row as a stream of 6-bit codes
-// (slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6; slk_mx_dequantize_act6 of mxgemm.hip reads that stream back).
+// Every kernel that turns a matrix into an MX form or back (the forms are pinned in include/sleekit_amd.h and
+// INTEGRATION.md; what a kernel knows of an element format is mxquant.h's).  Blocks of 32 consecutive columns of a row
+// share one power-of-two scale (an E8M0 byte); the elements are E2M1 codes, two a byte (MXFP4), E2M3 codes, a row as a
+// stream of 6-bit codes (MXFP6), or E4M3 codes, one a byte (MXFP8).
+//   a layer:      slk_mx_scale_search, slk_mx_pack, slk_mx_unpack (E2M1); slk_mx_scale_search6, _pack6, _unpack6 (E2M3)
+//   activations:  slk_mx_quantize_act (E4M3), _act4 (E2M1), _act6 (E2M3)
+//   either, back: slk_mx_dequantize (E2M1), slk_mx_dequantize_act (E4M3), _act6 (E2M3): one kernel, whatever wrote the codes
 //
 // n % 32 == 0, so block k of the (R, n) layer is elements [32 k, 32 k + 32) of the flat array whatever the row: every
 // kernel here runs over the R n / 32 blocks (64-bit counts) and only the diagonal of H needs a block's place in its row.
@@ -18,56 +21,11 @@ namespace slk {
 
 static constexpr int MX_UNROLL = 4;  // units per thread and step, a whole grid apart: enough loads in flight
 
-static inline int mx_grid(size_t units) {
-    size_t b = (units + 256 * MX_UNROLL - 1) / (256 * MX_UNROLL);
+// workgroups of 256 lanes for `units` of work, `per` of them a thread and step
+static inline int mx_grid(size_t units, int per) {
+    size_t b = (units + 256 * per - 1) / (256 * per);
     if (b > 4096) b = 4096;  // 16 workgroups a CU, grid-stride beyond
     return b < 1 ? 1 : (int)b;
-}
-
-// ---------------------------------------------------------------- E2M1
-// The codebook's midpoints send a tie upward (np.digitize counts the limits <= x): |x| on a limit rounds away from
-// zero for x > 0 and towards zero for x < 0.  On the bits of |x| as an integer that is one rule for both signs: a
-// negative x is moved one float down first (|x| > L  <=>  the float below |x| is >= L; -0.0 becomes -1, below every
-// limit).  `a`: those bits, `neg` (0 or 1) already taken off.  Returns the bits of the magnitude |x| rounds to:
-// from 1 up the grid is the floats of one mantissa bit, so adding half of that bit and cutting the rest rounds with ties
-// up (6 is the top); below 1 it is 0, 0.5, 1 with the limits 0.25 and 0.75.
-__device__ __forceinline__ unsigned e2m1_round(int a) {
-    a = min(a, 0x40c00000);  // 6
-    const unsigned high = ((unsigned)a + 0x00200000u) & 0xffc00000u;
-    const unsigned low = a >= 0x3f400000 ? 0x3f800000u : (a >= 0x3e800000 ? 0x3f000000u : 0u);
-    return a >= 0x3f800000 ? high : low;
-}
-// the float32 bits of magnitude m: 0, 0.5, then (1 + (m & 1) / 2) 2^((m >> 1) - 1)
-__device__ __forceinline__ unsigned e2m1_bits(int m) {
-    const unsigned normal = ((126u + (unsigned)(m >> 1)) << 23) | ((unsigned)(m & 1) << 22);
-    return m >= 2 ? normal : (m ? 0x3f000000u : 0u);
-}
-// the value of code c (sign << 3 | m) times `sc`; code 0x8 reads as +0
-__device__ __forceinline__ float e2m1_value(unsigned c, float sc) {
-    const int m = (int)(c & 7u);
-    const unsigned sign = m ? (c & 8u) << 28 : 0u;
-    return __uint_as_float(e2m1_bits(m) | sign) * sc;
-}
-
-// ---------------------------------------------------------------- E2M3 (MXFP6 layers)
-// e2m1_round's rule on the 32 magnitudes of E2M3: `a` as there, the bits of the magnitude |x| rounds to with a tie upward.
-// The grid is the floats of 3 mantissa bits from 1 up (spacing 2^(e - 3) in binade e) and k / 8 below, which in the binades
-// 1/2, 1/4 and 1/8 is the floats of 2, 1 and 0 mantissa bits, and in the binade of 1/16 the one limit 1/16 = its lowest
-// float, above which everything goes to 1/8: 24 bits cut, the exponent's own lowest bit among them (123 + 1 = 124 is even).
-// So one rule serves all binades -- add half of the last kept bit and cut `cut` = 20 .. 24 bits -- and integer
-// arithmetic alone decides every limit; below 1/16 (-1, a negative zero, included) the answer is 0.  7.5 is the top.
-__device__ __forceinline__ unsigned e2m3_round(int a) {
-    a = min(a, 0x40f00000);  // 7.5
-    const int cut = min(max(147 - (a >> 23), 20), 24);
-    const unsigned r = (((unsigned)a + (1u << (cut - 1))) >> cut) << cut;
-    return a >= 0x3d800000 ? r : 0u;
-}
-
-// The element format of a layer as the scale search sees it: the largest magnitude, and the rounding onto the grid.
-template <int WF>
-__device__ __forceinline__ unsigned mxw_round(int a) {
-    if constexpr (WF == MXA_E2M3) return e2m3_round(a);
-    else return e2m1_round(a);
 }
 
 // ---------------------------------------------------------------- scale selection
@@ -145,30 +103,6 @@ __global__ __launch_bounds__(256) void k_mx_scale_search(const float *__restrict
 }
 
 // ---------------------------------------------------------------- pack / unpack
-// Four index bytes in a word: min(i, 14), then i < 7 -> 15 - i (= 8 | (7 - i)), else i - 7; no byte carries into the next.
-__device__ __forceinline__ unsigned mx_codes_of(unsigned x) {
-    const unsigned over = (((x & 0x7f7f7f7fu) + 0x71717171u) | x) & 0x80808080u;  // bytes >= 15
-    const unsigned om = (over >> 7) * 0xffu;
-    x = (x & ~om) | (0x0e0e0e0eu & om);
-    const unsigned gm = (((x + 0x79797979u) >> 7) & 0x01010101u) * 0xffu;  // bytes >= 7
-    return (gm & ((x + 0x09090909u) & 0x0f0f0f0fu)) | (~gm & (x ^ 0x0f0f0f0fu));
-}
-// ... their four nibbles as 16 bits, the first index lowest
-__device__ __forceinline__ unsigned mx_nibbles(unsigned c) {
-    const unsigned y = c | (c >> 4);
-    return (y & 0xffu) | ((y >> 8) & 0xff00u);
-}
-// 16 bits of codes -> four index bytes: code >= 8 -> 15 - code (0x8 -> 7), else code + 7
-__device__ __forceinline__ unsigned mx_indices_of(unsigned h) {
-    unsigned x = (h & 0xffu) | ((h & 0xff00u) << 8);
-    x = (x | (x << 4)) & 0x0f0f0f0fu;
-    const unsigned m = ((x >> 3) & 0x01010101u) * 0xffu;
-    return (m & (x ^ 0x0f0f0f0fu)) | (~m & (x + 0x07070707u));
-}
-
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-typedef unsigned uint2v __attribute__((ext_vector_type(2)));
-
 // float32 scales -> E8M0 bytes, and back: a block a thread, the same for every element format.
 __device__ __forceinline__ void mx_pack_scales(const float *__restrict__ S, size_t blocks, size_t gid, size_t threads,
                                                uint8_t *__restrict__ E, int *__restrict__ flag) {
@@ -191,15 +125,17 @@ __device__ __forceinline__ void mx_unpack_scales(const uint8_t *__restrict__ E, 
     if (bad && flag) *flag = 1;
 }
 
-// A unit is 16 indices <-> 8 bytes of codes (two lanes a block): one 16-byte and one 8-byte access a lane, contiguous
-// over the wave.  The scales take a loop of their own, a block a thread.
+// A unit is 16 indices <-> their codes, 8 bytes of E2M1 or 12 of E2M3 (two lanes a block): one 16-byte access and two or
+// three aligned dwords a lane (mxquant.h: the quantizer's own placing, store and load), contiguous over the wave.  The
+// scales take a loop of their own, a block a thread.
+template <int WF>
 __global__ __launch_bounds__(256) void k_mx_pack(const uint8_t *__restrict__ idx, const float *__restrict__ S, size_t blocks,
                                                  uint8_t *__restrict__ codes, uint8_t *__restrict__ E, int *__restrict__ flag) {
+    constexpr int WORDS = mxa_bits<WF>() / 2;
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
     if (S) mx_pack_scales(S, blocks, gid, threads, E, flag);
     if (!idx) return;
     const uint4v *src = reinterpret_cast<const uint4v *>(idx);
-    uint2v *dst = reinterpret_cast<uint2v *>(codes);
     const size_t units = 2 * blocks;
     for (size_t i0 = gid; i0 < units; i0 += threads * MX_UNROLL) {
         uint4v v[MX_UNROLL];
@@ -212,142 +148,145 @@ __global__ __launch_bounds__(256) void k_mx_pack(const uint8_t *__restrict__ idx
         for (int u = 0; u < MX_UNROLL; ++u) {
             const size_t i = i0 + u * threads;
             if (i >= units) continue;
-            uint2v o;
-            o.x = mx_nibbles(mx_codes_of(v[u].x)) | (mx_nibbles(mx_codes_of(v[u].y)) << 16);
-            o.y = mx_nibbles(mx_codes_of(v[u].z)) | (mx_nibbles(mx_codes_of(v[u].w)) << 16);
-            dst[i] = o;
+            unsigned w[WORDS];
+            mxw_words_of<WF>(v[u], w);
+            mxa_store<WF, 16>(codes + 4 * WORDS * i, w);
         }
     }
 }
 
+template <int WF>
 __global__ __launch_bounds__(256) void k_mx_unpack(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, size_t blocks,
                                                    uint8_t *__restrict__ idx, float *__restrict__ S, int *__restrict__ flag) {
-    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
-    if (S) mx_unpack_scales(E, blocks, gid, threads, S, flag);
-    if (!idx) return;
-    const uint2v *src = reinterpret_cast<const uint2v *>(codes);
-    uint4v *dst = reinterpret_cast<uint4v *>(idx);
-    const size_t units = 2 * blocks;
-    for (size_t i0 = gid; i0 < units; i0 += threads * MX_UNROLL) {
-        uint2v v[MX_UNROLL];
-#pragma unroll
-        for (int u = 0; u < MX_UNROLL; ++u) {
-            const size_t i = i0 + u * threads;
-            if (i < units) v[u] = src[i];
-        }
-#pragma unroll
-        for (int u = 0; u < MX_UNROLL; ++u) {
-            const size_t i = i0 + u * threads;
-            if (i >= units) continue;
-            uint4v o;
-            o.x = mx_indices_of(v[u].x & 0xffffu);
-            o.y = mx_indices_of(v[u].x >> 16);
-            o.z = mx_indices_of(v[u].y & 0xffffu);
-            o.w = mx_indices_of(v[u].y >> 16);
-            dst[i] = o;
-        }
-    }
-}
-
-// MXFP6.  Index i of the 63-entry table -> E2M3 code: min(i, 62), then i < 31 -> 0x20 | (31 - i), else i - 31; and back:
-// a set sign bit -> 31 - magnitude code (0x20, -0, -> 31), else code + 31.
-__device__ __forceinline__ unsigned mx6_code_of(unsigned i) {
-    i = min(i, 62u);
-    return i < 31u ? 0x20u | (31u - i) : i - 31u;
-}
-__device__ __forceinline__ unsigned mx6_index_of(unsigned c) { return (c & 0x20u) ? 31u - (c & 31u) : c + 31u; }
-
-// A unit is 16 indices <-> 12 bytes of the row's stream of 6-bit codes (two lanes a block, as above): one 16-byte access
-// and three aligned dwords a lane (mxquant.h: the activation quantizer's own packer, store and load).
-__global__ __launch_bounds__(256) void k_mx_pack6(const uint8_t *__restrict__ idx, const float *__restrict__ S, size_t blocks,
-                                                  uint8_t *__restrict__ codes, uint8_t *__restrict__ E, int *__restrict__ flag) {
-    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
-    if (S) mx_pack_scales(S, blocks, gid, threads, E, flag);
-    if (!idx) return;
-    const uint4v *src = reinterpret_cast<const uint4v *>(idx);
-    const size_t units = 2 * blocks;
-    for (size_t i0 = gid; i0 < units; i0 += threads * MX_UNROLL) {
-        uint4v v[MX_UNROLL];
-#pragma unroll
-        for (int u = 0; u < MX_UNROLL; ++u) {
-            const size_t i = i0 + u * threads;
-            if (i < units) v[u] = src[i];
-        }
-#pragma unroll
-        for (int u = 0; u < MX_UNROLL; ++u) {
-            const size_t i = i0 + u * threads;
-            if (i >= units) continue;
-            float x[16];  // the codes' values: the quantizer's packer turns them, under the scale 1, back into their codes
-            unsigned w[3];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) x[e] = e2m3_value(mx6_code_of((v[u][e >> 2] >> (8 * (e & 3))) & 0xffu));
-            mxa_pack<MXA_E2M3, 16>(x, 1.0f, w);
-            mxa_store<MXA_E2M3, 16>(codes + 12 * i, w);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_mx_unpack6(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, size_t blocks,
-                                                    uint8_t *__restrict__ idx, float *__restrict__ S, int *__restrict__ flag) {
+    constexpr int WORDS = mxa_bits<WF>() / 2;
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
     if (S) mx_unpack_scales(E, blocks, gid, threads, S, flag);
     if (!idx) return;
     uint4v *dst = reinterpret_cast<uint4v *>(idx);
     const size_t units = 2 * blocks;
     for (size_t i0 = gid; i0 < units; i0 += threads * MX_UNROLL) {
-        unsigned w[MX_UNROLL][3];
+        unsigned w[MX_UNROLL][WORDS];
 #pragma unroll
         for (int u = 0; u < MX_UNROLL; ++u) {
             const size_t i = i0 + u * threads;
-            if (i < units) mxa_load<MXA_E2M3, 16>(codes + 12 * i, w[u]);
+            if (i < units) mxa_load<WF, 16>(codes + 4 * WORDS * i, w[u]);
         }
 #pragma unroll
         for (int u = 0; u < MX_UNROLL; ++u) {
             const size_t i = i0 + u * threads;
-            if (i >= units) continue;
-            uint4v o = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[e >> 2] |= mx6_index_of(mxa_code_at<MXA_E2M3>(w[u], e)) << (8 * (e & 3));
-            dst[i] = o;
+            if (i < units) dst[i] = mxw_indices_of<WF>(w[u]);
         }
     }
+}
+
+// ---------------------------------------------------------------- quantize activations
+template <class T>
+__device__ __forceinline__ float act_f32(T x);
+template <>
+__device__ __forceinline__ float act_f32<float>(float x) { return x; }
+template <>
+__device__ __forceinline__ float act_f32<unsigned short>(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
+template <>
+__device__ __forceinline__ float act_f32<_Float16>(_Float16 x) { return (float)x; }
+
+// The plain quantizer.  LPB lanes a block, 32 / LPB elements a lane, read in 16-byte pieces: the block's largest |x| over
+// its lanes on DPP, the scale byte from the block's first lane, and every lane's codes as whole dwords of the row's
+// little-endian bit stream (mxa_pack, mxa_store).  E4M3 and E2M1 take four lanes a block: 8 bytes a lane, or one dword of
+// nibbles, the even k in the low ones, which is the weights' own layout.  Eight 6-bit codes are 6 bytes, which no lane can
+// store as whole dwords at a 6-byte stride, so E2M3 takes two: 12 bytes a lane, three dwords at a 12-byte stride, every one
+// of them aligned (a row is 24 bytes a block; DESIGN.md section 20 has this shape measured against a lane a block).
+// A NaN or an infinity has the largest magnitude bits of its block, so the integer maximum finds it and raises the flag.
+template <int FMT>
+__host__ __device__ constexpr int mxq_lanes() { return FMT == MXA_E2M3 ? 2 : 4; }
+
+template <class T, int FMT, int LPB>
+__global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X, size_t blocks, uint8_t *__restrict__ codes,
+                                                         uint8_t *__restrict__ E, int *__restrict__ flag) {
+    static_assert(LPB == 2 || LPB == 4, "the maximum takes one or two DPP steps");
+    constexpr int EPL = 32 / LPB, BYTES = EPL * mxa_bits<FMT>() / 8;  // elements and bytes of codes a lane
+    static_assert(BYTES % 4 == 0, "a lane stores whole dwords: fewer lanes a block for this format");
+    constexpr int PER = 16 / (int)sizeof(T), PIECES = EPL / PER;      // elements a 16-byte piece, pieces a lane
+    typedef T V __attribute__((ext_vector_type(PER)));
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    const size_t units = LPB * blocks, rounds = (units + threads - 1) / threads;
+    const V *src = reinterpret_cast<const V *>(X);
+    bool bad = false;
+    for (size_t r = 0; r < rounds; ++r) {  // (every lane of a block takes every round: units is a multiple of LPB, and so is threads)
+        const size_t i = r * threads + gid;
+        const bool live = i < units;
+        float x[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) x[e] = 0.0f;
+        if (live) {
+#pragma unroll
+            for (int p = 0; p < PIECES; ++p) {
+                const V v = src[PIECES * i + p];
+#pragma unroll
+                for (int e = 0; e < PER; ++e) x[p * PER + e] = act_f32<T>(v[e]);
+            }
+        }
+        int top = 0;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) top = max(top, (int)(__float_as_uint(x[e]) & 0x7fffffffu));
+        top = max(top, dpp_i<DPP_XOR1>(top));
+        if constexpr (LPB == 4) top = max(top, dpp_i<DPP_XOR2>(top));
+        bad |= top >= 0x7f800000;
+        const unsigned eb = mxa_scale_byte<FMT>(top);
+        unsigned w[BYTES / 4];
+        mxa_pack<FMT>(x, mxa_inverse(eb), w);
+        if (live) {
+            mxa_store<FMT, EPL>(codes + BYTES * i, w);
+            if (i % LPB == 0) E[i / LPB] = (uint8_t)eb;
+        }
+    }
+    if (bad) *flag = 1;
 }
 
 // ---------------------------------------------------------------- de-quantize
-// A unit is the 16 bytes a lane stores: 4 float32 values from 2 bytes of codes, or 8 16-bit values from 4 bytes.  OUT as
+// value(code) 2^(b - 127) of any format's codes, whoever wrote them.  A lane stores 16 bytes of E4M3's or E2M1's values (4
+// float32 values from 4 codes, 8 16-bit ones from 8: for E2M1 half a dword of codes, or one), or the sixteen values of the 12
+// bytes an E2M3 lane wrote (64 or 32 bytes, 16 at a time).  E2M1's lanes keep MX_UNROLL units in flight, a whole grid
+// apart, as the layer's other kernels do; the others take a unit a step (DESIGN.md section 24 has both measured).  OUT as
 // in pack.hip: the 16-bit results are the float32 value rounded to nearest even.
-template <int OUT>
+template <int FMT, class T>
+__host__ __device__ constexpr int mxd_elements() { return FMT == MXA_E2M3 ? 16 : 16 / (int)sizeof(T); }
+template <int FMT>
+__host__ __device__ constexpr int mxd_unroll() { return FMT == MXA_E2M1 ? MX_UNROLL : 1; }
+
+template <int OUT, int FMT>
 __global__ __launch_bounds__(256) void k_mx_dequantize(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E, size_t blocks,
                                                        typename PkOut<OUT>::T *__restrict__ out, int *__restrict__ flag) {
     typedef typename PkOut<OUT>::T T;
-    constexpr int EPL = 16 / (int)sizeof(T), UPB = 32 / EPL;  // elements a unit, units a block
-    typedef T V __attribute__((ext_vector_type(EPL)));
-    typedef typename std::conditional<EPL == 4, unsigned short, unsigned>::type C;
+    constexpr int EPL = mxd_elements<FMT, T>(), LPB = 32 / EPL, BYTES = EPL * mxa_bits<FMT>() / 8, UNROLL = mxd_unroll<FMT>();
+    constexpr int PER = 16 / (int)sizeof(T), PIECES = EPL / PER;
+    typedef T V __attribute__((ext_vector_type(PER)));
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
-    const C *src = reinterpret_cast<const C *>(codes);
     V *dst = reinterpret_cast<V *>(out);
-    const size_t units = UPB * blocks;
+    const size_t units = LPB * blocks;
     bool bad = false;
-    for (size_t i0 = gid; i0 < units; i0 += threads * MX_UNROLL) {
-        unsigned c[MX_UNROLL], b[MX_UNROLL];
+    for (size_t i0 = gid; i0 < units; i0 += threads * UNROLL) {
+        unsigned w[UNROLL][(BYTES + 3) / 4], b[UNROLL];
 #pragma unroll
-        for (int u = 0; u < MX_UNROLL; ++u) {
+        for (int u = 0; u < UNROLL; ++u) {
             const size_t i = i0 + u * threads;
             if (i < units) {
-                c[u] = src[i];
-                b[u] = E[i / UPB];
+                mxa_load<FMT, EPL>(codes + BYTES * i, w[u]);
+                b[u] = E[i / LPB];
             }
         }
 #pragma unroll
-        for (int u = 0; u < MX_UNROLL; ++u) {
+        for (int u = 0; u < UNROLL; ++u) {
             const size_t i = i0 + u * threads;
             if (i >= units) continue;
             bad |= b[u] == 255u;
             const float sc = e8m0_value(b[u]);
-            V v;
 #pragma unroll
-            for (int e = 0; e < EPL; ++e) v[e] = PkOut<OUT>::cvt(e2m1_value(c[u] >> (4 * e), sc));
-            dst[i] = v;
+            for (int p = 0; p < PIECES; ++p) {
+                V v;
+#pragma unroll
+                for (int e = 0; e < PER; ++e) v[e] = PkOut<OUT>::cvt(mxa_value<FMT>(mxa_code_at<FMT>(w[u], p * PER + e)) * sc);
+                dst[PIECES * i + p] = v;
+            }
         }
     }
     if (bad && flag) *flag = 1;
@@ -381,8 +320,8 @@ static int mx_scale_search(const char *name, const float *W, const float *hdiag,
     return SLK_OK;
 }
 
-// slk_mx_pack, slk_mx_unpack (BITS 4) and slk_mx_pack6, slk_mx_unpack6 (6): one contract
-template <int BITS>
+// slk_mx_pack, slk_mx_unpack (WF MXA_E2M1) and slk_mx_pack6, slk_mx_unpack6 (MXA_E2M3): one contract
+template <int WF>
 static int mx_pack(const char *name, const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag,
                    slk_stream_t stream) {
     SLK_REQUIRE(R > 0 && n > 0 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (R = %d, n = %d)", R, n);
@@ -392,13 +331,12 @@ static int mx_pack(const char *name, const uint8_t *idx, const float *S, int R, 
     hipStream_t s = as_stream(stream);
     const size_t blocks = (size_t)R * (n / 32);
     if (flag) zero_async(flag, sizeof(int), s);
-    const double bytes = (idx ? 32.0 + 4.0 * BITS : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
-    if constexpr (BITS == 6) SLK_RUN(name, 0, bytes, s, k_mx_pack6<<<mx_grid(2 * blocks), 256, 0, s>>>(idx, S, blocks, codes, scales, flag));
-    else SLK_RUN(name, 0, bytes, s, k_mx_pack<<<mx_grid(2 * blocks), 256, 0, s>>>(idx, S, blocks, codes, scales, flag));
+    const double bytes = (idx ? 32.0 + 4.0 * mxa_bits<WF>() : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
+    SLK_RUN(name, 0, bytes, s, k_mx_pack<WF><<<mx_grid(2 * blocks, MX_UNROLL), 256, 0, s>>>(idx, S, blocks, codes, scales, flag));
     return SLK_OK;
 }
 
-template <int BITS>
+template <int WF>
 static int mx_unpack(const char *name, const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag,
                      slk_stream_t stream) {
     SLK_REQUIRE(R > 0 && n > 0 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (R = %d, n = %d)", R, n);
@@ -408,10 +346,50 @@ static int mx_unpack(const char *name, const uint8_t *codes, const uint8_t *scal
     hipStream_t s = as_stream(stream);
     const size_t blocks = (size_t)R * (n / 32);
     if (flag) zero_async(flag, sizeof(int), s);
-    const double bytes = (idx ? 32.0 + 4.0 * BITS : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
-    if constexpr (BITS == 6) SLK_RUN(name, 0, bytes, s, k_mx_unpack6<<<mx_grid(2 * blocks), 256, 0, s>>>(codes, scales, blocks, idx, S, flag));
-    else SLK_RUN(name, 0, bytes, s, k_mx_unpack<<<mx_grid(2 * blocks), 256, 0, s>>>(codes, scales, blocks, idx, S, flag));
+    const double bytes = (idx ? 32.0 + 4.0 * mxa_bits<WF>() : 0.0) * blocks + (S ? 5.0 : 0.0) * blocks;
+    SLK_RUN(name, 0, bytes, s, k_mx_unpack<WF><<<mx_grid(2 * blocks, MX_UNROLL), 256, 0, s>>>(codes, scales, blocks, idx, S, flag));
     return SLK_OK;
+}
+
+// slk_mx_quantize_act (MXA_E4M3), _act4 (MXA_E2M1) and _act6 (MXA_E2M3)
+template <int FMT>
+static int mx_quantize_act(const char *name, const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag,
+                           slk_stream_t stream) {
+    SLK_REQUIRE(M > 0 && K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (M = %d, K = %d)", M, K);
+    SLK_REQUIRE(known_dtype(x_dtype), "unknown x_dtype %d", x_dtype);
+    SLK_REQUIRE(X && a_codes && a_scales && flag, "null pointer");
+    SLK_REQUIRE(aligned16(X) && aligned16(a_codes), "X and a_codes must be aligned to 16 bytes");
+    hipStream_t s = as_stream(stream);
+    const size_t blocks = (size_t)M * (K / 32);
+    zero_async(flag, sizeof(int), s);
+    constexpr int LPB = mxq_lanes<FMT>();
+    const int grid = mx_grid(LPB * blocks, 1);
+    return with_dtype(x_dtype, [&](auto t) -> int {
+        typedef typename decltype(t)::T T;
+        const double bytes = (mxa_block_bytes<FMT>() + 32.0 * sizeof(T)) * blocks;
+        SLK_RUN(name, 0, bytes, s, (k_mx_quantize_act<T, FMT, LPB><<<grid, 256, 0, s>>>(static_cast<const T *>(X), blocks, a_codes, a_scales, flag)));
+        return SLK_OK;
+    });
+}
+
+// slk_mx_dequantize (MXA_E2M1), slk_mx_dequantize_act (MXA_E4M3) and _act6 (MXA_E2M3)
+template <int FMT>
+static int mx_dequantize(const char *name, const uint8_t *codes, const uint8_t *scales, int M, int K, int out_dtype, void *out, int *flag,
+                         slk_stream_t stream) {
+    SLK_REQUIRE(M > 0 && K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (M = %d, K = %d)", M, K);
+    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
+    SLK_REQUIRE(codes && scales && out, "null pointer");
+    SLK_REQUIRE(aligned16(codes) && aligned16(out), "codes and out must be aligned to 16 bytes");
+    hipStream_t s = as_stream(stream);
+    const size_t blocks = (size_t)M * (K / 32);
+    if (flag) zero_async(flag, sizeof(int), s);
+    return with_dtype(out_dtype, [&](auto t) -> int {
+        typedef typename decltype(t)::T T;
+        const double bytes = (mxa_block_bytes<FMT>() + 32.0 * sizeof(T)) * blocks;
+        const int grid = mx_grid(32 / mxd_elements<FMT, T>() * blocks, mxd_unroll<FMT>());
+        SLK_RUN(name, 0, bytes, s, (k_mx_dequantize<decltype(t)::OUT, FMT><<<grid, 256, 0, s>>>(codes, scales, blocks, static_cast<T *>(out), flag)));
+        return SLK_OK;
+    });
 }
 
 extern "C" {
@@ -425,42 +403,46 @@ int slk_mx_scale_search6(const float *W, const float *hdiag, int mode, int R, in
 }
 
 int slk_mx_pack(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag, slk_stream_t stream) {
-    return mx_pack<4>("mx_pack", idx, S, R, n, codes, scales, flag, stream);
+    return mx_pack<MXA_E2M1>("mx_pack", idx, S, R, n, codes, scales, flag, stream);
 }
 
 int slk_mx_pack6(const uint8_t *idx, const float *S, int R, int n, uint8_t *codes, uint8_t *scales, int *flag, slk_stream_t stream) {
-    return mx_pack<6>("mx_pack6", idx, S, R, n, codes, scales, flag, stream);
+    return mx_pack<MXA_E2M3>("mx_pack6", idx, S, R, n, codes, scales, flag, stream);
 }
 
 int slk_mx_unpack(const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag, slk_stream_t stream) {
-    return mx_unpack<4>("mx_unpack", codes, scales, R, n, idx, S, flag, stream);
+    return mx_unpack<MXA_E2M1>("mx_unpack", codes, scales, R, n, idx, S, flag, stream);
 }
 
 int slk_mx_unpack6(const uint8_t *codes, const uint8_t *scales, int R, int n, uint8_t *idx, float *S, int *flag, slk_stream_t stream) {
-    return mx_unpack<6>("mx_unpack6", codes, scales, R, n, idx, S, flag, stream);
+    return mx_unpack<MXA_E2M3>("mx_unpack6", codes, scales, R, n, idx, S, flag, stream);
+}
+
+int slk_mx_quantize_act(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    return mx_quantize_act<MXA_E4M3>("mx_quantize_act", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
+}
+
+int slk_mx_quantize_act4(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    return mx_quantize_act<MXA_E2M1>("mx_quantize_act4", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
+}
+
+int slk_mx_quantize_act6(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    return mx_quantize_act<MXA_E2M3>("mx_quantize_act6", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
 }
 
 int slk_mx_dequantize(const uint8_t *codes, const uint8_t *scales, int R, int n, int out_dtype, void *out, int *flag,
                       slk_stream_t stream) {
-    SLK_REQUIRE(R > 0 && n > 0 && n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (R = %d, n = %d)", R, n);
-    SLK_REQUIRE(codes && scales && out, "null pointer");
-    SLK_REQUIRE(out_dtype == SLK_DTYPE_F32 || out_dtype == SLK_DTYPE_BF16 || out_dtype == SLK_DTYPE_F16, "unknown out_dtype %d",
-                out_dtype);
-    SLK_REQUIRE(aligned16(codes) && aligned16(out), "codes and out must be aligned to 16 bytes");
-    hipStream_t s = as_stream(stream);
-    const size_t blocks = (size_t)R * (n / 32);
-    if (flag) zero_async(flag, sizeof(int), s);
-    const double bytes = (17.0 + 32.0 * (out_dtype == SLK_DTYPE_F32 ? 4.0 : 2.0)) * blocks;
-    if (out_dtype == SLK_DTYPE_BF16)
-        SLK_RUN("mx_dequantize", 0, bytes, s,
-                k_mx_dequantize<PK_BF16><<<mx_grid(4 * blocks), 256, 0, s>>>(codes, scales, blocks, static_cast<unsigned short *>(out), flag));
-    else if (out_dtype == SLK_DTYPE_F16)
-        SLK_RUN("mx_dequantize", 0, bytes, s,
-                k_mx_dequantize<PK_F16><<<mx_grid(4 * blocks), 256, 0, s>>>(codes, scales, blocks, static_cast<_Float16 *>(out), flag));
-    else
-        SLK_RUN("mx_dequantize", 0, bytes, s,
-                k_mx_dequantize<PK_F32><<<mx_grid(8 * blocks), 256, 0, s>>>(codes, scales, blocks, static_cast<float *>(out), flag));
-    return SLK_OK;
+    return mx_dequantize<MXA_E2M1>("mx_dequantize", codes, scales, R, n, out_dtype, out, flag, stream);
+}
+
+int slk_mx_dequantize_act(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
+                          slk_stream_t stream) {
+    return mx_dequantize<MXA_E4M3>("mx_dequantize_act", a_codes, a_scales, M, K, out_dtype, out, flag, stream);
+}
+
+int slk_mx_dequantize_act6(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
+                           slk_stream_t stream) {
+    return mx_dequantize<MXA_E2M3>("mx_dequantize_act6", a_codes, a_scales, M, K, out_dtype, out, flag, stream);
 }
 
 }  // extern "C"

@@ -1,11 +1,11 @@
-// A linear layer computed from the packed MXFP4 form on the block-scaled MFMA (slk_mx_quantize_act, _act4, _act6,
-// slk_mx_dequantize_act, _act6, slk_mx_gemm, _a4, _a6, _w6, slk_mx_gemm_experts; the formats are pinned in include/sleekit_amd.h and
-// INTEGRATION.md).
+// The product of a linear layer in a packed MX form on the block-scaled MFMA, and that product over the experts of a
+// mixture-of-experts layer (slk_mx_gemm, _a4, _a6, _w6, slk_mx_gemm_experts; the formats are pinned in include/sleekit_amd.h
+// and INTEGRATION.md).  Nothing here converts: the kernels that write and read back these forms are mx.hip's.
 //
 // Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns -- or, for
 // an MXFP6 layer (slk_mx_gemm_w6), as slk_mx_pack6 left them: E2M3 codes, 24 bytes a block.
-// Activations are quantized on the fly to MXFP8: E4M3 codes, one a byte, under the same kind of block scale -- or to
-// MXFP4, in the weights' own form, or to MXFP6 (E2M3, 24 bytes a block).
+// Activations come as slk_mx_quantize_act left them, MXFP8: E4M3 codes, one a byte, under the same kind of block scale -- or
+// as MXFP4 (_act4), in the weights' own form, or as MXFP6 (_act6: E2M3, 24 bytes a block).
 //
 // v_mfma_scale_f32_16x16x128_f8f6f4, as found on the hardware and held by the one-hot test of
 // tests/test_gpu_mx_gemm.py.  Lane l = i + 16 q carries row (A) or column (B) i.
@@ -30,102 +30,6 @@ namespace slk {
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-template <class T>
-__device__ __forceinline__ float act_f32(T x);
-template <>
-__device__ __forceinline__ float act_f32<float>(float x) { return x; }
-template <>
-__device__ __forceinline__ float act_f32<unsigned short>(unsigned short x) { return __uint_as_float((unsigned)x << 16); }
-template <>
-__device__ __forceinline__ float act_f32<_Float16>(_Float16 x) { return (float)x; }
-
-// The plain quantizer.  LPB lanes a block, 32 / LPB elements a lane, read in 16-byte pieces: the block's largest |x| over
-// its lanes on DPP, the scale byte from the block's first lane, and every lane's codes as whole dwords of the row's
-// little-endian bit stream (mxa_pack, mxa_store).  E4M3 and E2M1 take four lanes a block: 8 bytes a lane, or one dword of
-// nibbles, the even k in the low ones, which is the weights' own layout.  Eight 6-bit codes are 6 bytes, which no lane can
-// store as whole dwords at a 6-byte stride, so E2M3 takes two: 12 bytes a lane, three dwords at a 12-byte stride, every one
-// of them aligned (a row is 24 bytes a block; DESIGN.md section 20 has this shape measured against a lane a block).
-// A NaN or an infinity has the largest magnitude bits of its block, so the integer maximum finds it and raises the flag.
-template <int FMT>
-__host__ __device__ constexpr int mxq_lanes() { return FMT == MXA_E2M3 ? 2 : 4; }
-
-template <class T, int FMT, int LPB>
-__global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X, size_t blocks, uint8_t *__restrict__ codes,
-                                                         uint8_t *__restrict__ E, int *__restrict__ flag) {
-    static_assert(LPB == 2 || LPB == 4, "the maximum takes one or two DPP steps");
-    constexpr int EPL = 32 / LPB, BYTES = EPL * mxa_bits<FMT>() / 8;  // elements and bytes of codes a lane
-    static_assert(BYTES % 4 == 0, "a lane stores whole dwords: fewer lanes a block for this format");
-    constexpr int PER = 16 / (int)sizeof(T), PIECES = EPL / PER;      // elements a 16-byte piece, pieces a lane
-    typedef T V __attribute__((ext_vector_type(PER)));
-    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
-    const size_t units = LPB * blocks, rounds = (units + threads - 1) / threads;
-    const V *src = reinterpret_cast<const V *>(X);
-    bool bad = false;
-    for (size_t r = 0; r < rounds; ++r) {  // (every lane of a block takes every round: units is a multiple of LPB, and so is threads)
-        const size_t i = r * threads + gid;
-        const bool live = i < units;
-        float x[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) x[e] = 0.0f;
-        if (live) {
-#pragma unroll
-            for (int p = 0; p < PIECES; ++p) {
-                const V v = src[PIECES * i + p];
-#pragma unroll
-                for (int e = 0; e < PER; ++e) x[p * PER + e] = act_f32<T>(v[e]);
-            }
-        }
-        int top = 0;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) top = max(top, (int)(__float_as_uint(x[e]) & 0x7fffffffu));
-        top = max(top, dpp_i<DPP_XOR1>(top));
-        if constexpr (LPB == 4) top = max(top, dpp_i<DPP_XOR2>(top));
-        bad |= top >= 0x7f800000;
-        const unsigned eb = mxa_scale_byte<FMT>(top);
-        unsigned w[BYTES / 4];
-        mxa_pack<FMT>(x, mxa_inverse(eb), w);
-        if (live) {
-            mxa_store<FMT, EPL>(codes + BYTES * i, w);
-            if (i % LPB == 0) E[i / LPB] = (uint8_t)eb;
-        }
-    }
-    if (bad) *flag = 1;
-}
-
-// ... and back.  A lane stores 16 bytes of E4M3's values (4 float32 values from 4 codes, 8 16-bit ones from 8), or the
-// sixteen values of the 12 bytes an E2M3 lane wrote (64 or 32 bytes, 16 at a time).
-template <int FMT, class T>
-__host__ __device__ constexpr int mxd_elements() { return FMT == MXA_E2M3 ? 16 : 16 / (int)sizeof(T); }
-
-template <int OUT, int FMT>
-__global__ __launch_bounds__(256) void k_mx_dequantize_act(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ E,
-                                                           size_t blocks, typename PkOut<OUT>::T *__restrict__ out,
-                                                           int *__restrict__ flag) {
-    typedef typename PkOut<OUT>::T T;
-    constexpr int EPL = mxd_elements<FMT, T>(), LPB = 32 / EPL, BYTES = EPL * mxa_bits<FMT>() / 8;
-    constexpr int PER = 16 / (int)sizeof(T), PIECES = EPL / PER;
-    typedef T V __attribute__((ext_vector_type(PER)));
-    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
-    V *dst = reinterpret_cast<V *>(out);
-    const size_t units = LPB * blocks;
-    bool bad = false;
-    for (size_t i = gid; i < units; i += threads) {
-        unsigned w[BYTES / 4];
-        mxa_load<FMT, EPL>(codes + BYTES * i, w);
-        const unsigned b = E[i / LPB];
-        bad |= b == 255u;
-        const float sc = e8m0_value(b);
-#pragma unroll
-        for (int p = 0; p < PIECES; ++p) {
-            V v;
-#pragma unroll
-            for (int e = 0; e < PER; ++e) v[e] = PkOut<OUT>::cvt(mxa_value<FMT>(mxa_code_at<FMT>(w, p * PER + e)) * sc);
-            dst[PIECES * i + p] = v;
-        }
-    }
-    if (bad && flag) *flag = 1;
-}
 
 // ---------------------------------------------------------------- the product
 // One lane's share of a 16 x 128 operand step (the map above), or zeros (and the scale 1) past the rows or past the
@@ -424,57 +328,9 @@ __global__ __launch_bounds__(256) void k_mx_gemm_experts_tiled(const uint8_t *__
     mx_gemm_tiled_tile<OUT, AF, WF>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x * 64, N, K, Y);
 }
 
-static inline int mxg_grid(size_t units) {
-    size_t b = (units + 255) / 256;
-    if (b > 4096) b = 4096;  // 16 workgroups a CU, grid-stride beyond
-    return b < 1 ? 1 : (int)b;
-}
-
 }  // namespace slk
 
 using namespace slk;
-
-// slk_mx_quantize_act (MXA_E4M3), _act4 (MXA_E2M1) and _act6 (MXA_E2M3)
-template <int FMT>
-static int mx_quantize_act(const char *name, const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag,
-                           slk_stream_t stream) {
-    SLK_REQUIRE(M > 0 && K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (M = %d, K = %d)", M, K);
-    SLK_REQUIRE(known_dtype(x_dtype), "unknown x_dtype %d", x_dtype);
-    SLK_REQUIRE(X && a_codes && a_scales && flag, "null pointer");
-    SLK_REQUIRE(aligned16(X) && aligned16(a_codes), "X and a_codes must be aligned to 16 bytes");
-    hipStream_t s = as_stream(stream);
-    const size_t blocks = (size_t)M * (K / 32);
-    zero_async(flag, sizeof(int), s);
-    constexpr int LPB = mxq_lanes<FMT>();
-    const int grid = mxg_grid(LPB * blocks);
-    return with_dtype(x_dtype, [&](auto t) -> int {
-        typedef typename decltype(t)::T T;
-        const double bytes = (mxa_block_bytes<FMT>() + 32.0 * sizeof(T)) * blocks;
-        SLK_RUN(name, 0, bytes, s, (k_mx_quantize_act<T, FMT, LPB><<<grid, 256, 0, s>>>(static_cast<const T *>(X), blocks, a_codes, a_scales, flag)));
-        return SLK_OK;
-    });
-}
-
-// slk_mx_dequantize_act (MXA_E4M3) and _act6 (MXA_E2M3)
-template <int FMT>
-static int mx_dequantize_act(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out,
-                             int *flag, slk_stream_t stream) {
-    SLK_REQUIRE(M > 0 && K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (M = %d, K = %d)", M, K);
-    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
-    SLK_REQUIRE(a_codes && a_scales && out, "null pointer");
-    SLK_REQUIRE(aligned16(a_codes) && aligned16(out), "a_codes and out must be aligned to 16 bytes");
-    hipStream_t s = as_stream(stream);
-    const size_t blocks = (size_t)M * (K / 32);
-    if (flag) zero_async(flag, sizeof(int), s);
-    return with_dtype(out_dtype, [&](auto t) -> int {
-        typedef typename decltype(t)::T T;
-        const double bytes = (mxa_block_bytes<FMT>() + 32.0 * sizeof(T)) * blocks;
-        const int grid = mxg_grid(32 / mxd_elements<FMT, T>() * blocks);
-        SLK_RUN(name, 0, bytes, s,
-                (k_mx_dequantize_act<decltype(t)::OUT, FMT><<<grid, 256, 0, s>>>(a_codes, a_scales, blocks, static_cast<T *>(out), flag)));
-        return SLK_OK;
-    });
-}
 
 // slk_mx_gemm (AF MXA_E4M3), _a4 (MXA_E2M1) and _a6 (MXA_E2M3) against an MXFP4 layer; _w6 (WF MXA_E2M3) against an MXFP6 one
 template <int AF, int WF = MXA_E2M1>
@@ -569,28 +425,6 @@ int slk_mx_gemm_experts(const uint8_t *a_codes, const uint8_t *a_scales, const u
     if (a_fmt == SLK_MX_ACT_FP6) SLK_MXE_PAIR(MXA_E2M3, MXA_E2M1, "mx_gemm_experts_a6");
     SLK_MXE_PAIR(MXA_E4M3, MXA_E2M1, "mx_gemm_experts");
 #undef SLK_MXE_PAIR
-}
-
-int slk_mx_quantize_act(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
-    return mx_quantize_act<MXA_E4M3>("mx_quantize_act", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
-}
-
-int slk_mx_quantize_act4(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
-    return mx_quantize_act<MXA_E2M1>("mx_quantize_act4", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
-}
-
-int slk_mx_quantize_act6(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
-    return mx_quantize_act<MXA_E2M3>("mx_quantize_act6", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
-}
-
-int slk_mx_dequantize_act(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
-                          slk_stream_t stream) {
-    return mx_dequantize_act<MXA_E4M3>("mx_dequantize_act", a_codes, a_scales, M, K, out_dtype, out, flag, stream);
-}
-
-int slk_mx_dequantize_act6(const uint8_t *a_codes, const uint8_t *a_scales, int M, int K, int out_dtype, void *out, int *flag,
-                           slk_stream_t stream) {
-    return mx_dequantize_act<MXA_E2M3>("mx_dequantize_act6", a_codes, a_scales, M, K, out_dtype, out, flag, stream);
 }
 
 int slk_mx_gemm(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,

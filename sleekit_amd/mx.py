@@ -116,12 +116,15 @@ MXResult = collections.namedtuple("MXResult", "Q idx S codes scales")
 _MODES = {"max": _lib.MX_MAX, "mse": _lib.MX_MSE, "diag": _lib.MX_DIAG}
 _OUT = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
 
-# A weight format as plain data: the bits of a code (codes is (R, n bits / 8)), the codebook of the loop, its largest
-# magnitude, and the C entries of the scale search, the pack, the unpack and the de-quantizer (MXFP6's is the activations').
-_Weights = collections.namedtuple("_Weights", "name bits codebook largest scale_entry pack_entry unpack_entry dequantize_entry")
+# A weight format as plain data: the bits of a code (codes is (R, n bits / 8)), its C constant, the codebook of the loop, its
+# largest magnitude, the activation formats its product takes, and the C entries of the scale search, the pack, the unpack
+# and the de-quantizer.
+_Weights = collections.namedtuple("_Weights", "name bits c_fmt codebook largest activations scale_entry pack_entry unpack_entry dequantize_entry")
 _WEIGHTS = {f.name: f for f in (
-    _Weights("mxfp4", 4, E2M1, 6.0, "slk_mx_scale_search", "slk_mx_pack", "slk_mx_unpack", "slk_mx_dequantize"),
-    _Weights("mxfp6_e2m3", 6, E2M3, 7.5, "slk_mx_scale_search6", "slk_mx_pack6", "slk_mx_unpack6", "slk_mx_dequantize_act6"),
+    _Weights("mxfp4", 4, _lib.MX_W_FP4, E2M1, 6.0, ("mxfp8", "mxfp4", "mxfp6_e2m3"),
+             "slk_mx_scale_search", "slk_mx_pack", "slk_mx_unpack", "slk_mx_dequantize"),
+    _Weights("mxfp6_e2m3", 6, _lib.MX_W_FP6, E2M3, 7.5, ("mxfp8", "mxfp6_e2m3"),
+             "slk_mx_scale_search6", "slk_mx_pack6", "slk_mx_unpack6", "slk_mx_dequantize_act6"),
 )}
 _FP4, _FP6 = _WEIGHTS["mxfp4"], _WEIGHTS["mxfp6_e2m3"]
 
@@ -147,11 +150,6 @@ def _matrix(x, what, dtypes):
     if x.shape[0] < 1 or x.shape[0] >= 1 << 31 or x.shape[1] >= 1 << 31:
         raise ValueError(f"{what} must have 1 <= rows, columns < 2^31 (got {tuple(x.shape)})")
     return int(x.shape[0]), int(x.shape[1])
-
-
-def _aligned(t):
-    """The kernels move 16 bytes a lane: a contiguous view that starts off such a boundary is copied."""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 def _raise_flag(flag, message):
@@ -214,13 +212,13 @@ def _pack_layer(idx, S, wf):
     _blocks(n)
     _matrix(S, "scales", (torch.float32, np.float32))
     _check_scale_shape(S, R, n, "scales")
-    codes, scales = _pack(_aligned(dev.to_device(idx, torch.uint8)), dev.to_device(S), R, n, wf)
+    codes, scales = _pack(dev.aligned(dev.to_device(idx, torch.uint8)), dev.to_device(S), R, n, wf)
     return dev.like_input(codes, idx), dev.like_input(scales, idx)
 
 
 def _unpack_layer(codes, scales, wf):
     R, n = _weights(codes, scales, wf)
-    idx, S = _unpack(_aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), R, n, wf)
+    idx, S = _unpack(dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), R, n, wf)
     return dev.like_input(idx, codes), dev.like_input(S, codes)
 
 
@@ -341,14 +339,15 @@ def _torch_dtype(x):
     return x.dtype if isinstance(x, torch.Tensor) else {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}[x.dtype]
 
 
-# An activation format as plain data: the bits of a code (a_codes is (M, K bits / 8)), the C entries of its plain quantizer,
-# its de-quantizer (MXFP4's is the layer's own) and its product, and how the fused rotate-and-quantize entry is called: its
-# name and the `fmt` argument it takes (None: the entry takes none).
-_Format = collections.namedtuple("_Format", "name bits quantize_entry dequantize_entry gemm_entry rotate_entry rotate_fmt")
+# An activation format as plain data: the bits of a code (a_codes is (M, K bits / 8)), its C constant, the C entries of its
+# plain quantizer, its de-quantizer and its product, and how the fused rotate-and-quantize entry is called: its name and
+# whether it takes the constant as its `fmt` argument.
+_Format = collections.namedtuple("_Format", "name bits c_fmt quantize_entry dequantize_entry gemm_entry rotate_entry rotate_takes_fmt")
 _FORMATS = {f.name: f for f in (
-    _Format("mxfp8", 8, "slk_mx_quantize_act", "slk_mx_dequantize_act", "slk_mx_gemm", "slk_mx_rotate_quantize_act", _lib.MX_ACT_FP8),
-    _Format("mxfp4", 4, "slk_mx_quantize_act4", "slk_mx_dequantize", "slk_mx_gemm_a4", "slk_mx_rotate_quantize_act", _lib.MX_ACT_FP4),
-    _Format("mxfp6_e2m3", 6, "slk_mx_quantize_act6", "slk_mx_dequantize_act6", "slk_mx_gemm_a6", "slk_mx_rotate_quantize_act6", None),
+    _Format("mxfp8", 8, _lib.MX_ACT_FP8, "slk_mx_quantize_act", "slk_mx_dequantize_act", "slk_mx_gemm", "slk_mx_rotate_quantize_act", True),
+    _Format("mxfp4", 4, _lib.MX_ACT_FP4, "slk_mx_quantize_act4", "slk_mx_dequantize", "slk_mx_gemm_a4", "slk_mx_rotate_quantize_act", True),
+    _Format("mxfp6_e2m3", 6, _lib.MX_ACT_FP6, "slk_mx_quantize_act6", "slk_mx_dequantize_act6", "slk_mx_gemm_a6", "slk_mx_rotate_quantize_act6",
+            False),
 )}
 _ACTIVATIONS = tuple(_FORMATS)
 _ACTIVATIONS_ARE = "activations must be " + ", ".join(f'"{name}"' for name in _ACTIVATIONS[:-1]) + f' or "{_ACTIVATIONS[-1]}"'
@@ -370,7 +369,7 @@ def _act_outputs(Xd, M, K, fmt):
 def _quantize_act(Xd, M, K, fmt=_FORMATS["mxfp8"]):
     """(a_codes, a_scales, flag) of a contiguous device X (M, K) of float32, bfloat16 or float16 in the _Format fmt; the
     caller reads the flag (_raise_finite) once everything that follows has been launched: reading it waits for the stream."""
-    Xd = _aligned(Xd)
+    Xd = dev.aligned(Xd)
     codes, scales, flag = _act_outputs(Xd, M, K, fmt)
     _lib.check(getattr(_lib.lib, fmt.quantize_entry)(dev.ptr(Xd), _OUT[Xd.dtype], M, K, dev.ptr(codes), dev.ptr(scales), dev.ptr(flag),
                                                      dev.stream_handle()))
@@ -391,11 +390,11 @@ def _rotate_quantize_act(Xd, M, K, rotation, fmt):
     """_quantize_act of (X R) without X R in memory: the transform's float32 value goes into the quantizer."""
     if isinstance(fmt, bool):
         fmt = _FORMATS["mxfp4" if fmt else "mxfp8"]
-    Xd = _aligned(Xd)
+    Xd = dev.aligned(Xd)
     signs = rotation.signs if rotation.signs.device == Xd.device else rotation.signs.to(Xd.device)
-    signs = _aligned(signs)
+    signs = dev.aligned(signs)
     codes, scales, flag = _act_outputs(Xd, M, K, fmt)
-    which = () if fmt.rotate_fmt is None else (fmt.rotate_fmt,)
+    which = (fmt.c_fmt,) if fmt.rotate_takes_fmt else ()
     _lib.check(getattr(_lib.lib, fmt.rotate_entry)(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs), *which, dev.ptr(codes),
                                                    dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
     return codes, scales, flag
@@ -405,19 +404,18 @@ def _raise_finite(flag):
     _raise_flag(flag, "activations must be finite: X holds a NaN or an infinity")
 
 
-# slk_mx_gemm_w6's `a_fmt` of the activation formats an MXFP6 layer takes
-_W6_ACT = {"mxfp8": _lib.MX_ACT_FP8, "mxfp6_e2m3": _lib.MX_ACT_FP6}
+_MXFP6_TAKES = 'an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations'  # (the one weight format that refuses any)
 
 
 def _check_pair(fmt, wf):
-    if wf is _FP6 and fmt.name not in _W6_ACT:
-        raise ValueError(f'an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations (got "{fmt.name}")')
+    if fmt.name not in wf.activations:
+        raise ValueError(f'{_MXFP6_TAKES} (got "{fmt.name}")')
 
 
 def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"], wf=_FP4):
     out = torch.empty((M, N), dtype=dtype, device=ac.device)
     if wf is _FP6:
-        _lib.check(_lib.lib.slk_mx_gemm_w6(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, _W6_ACT[fmt.name],
+        _lib.check(_lib.lib.slk_mx_gemm_w6(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, fmt.c_fmt,
                                            _OUT[dtype], dev.ptr(out), dev.stream_handle()))
         return out
     _lib.check(getattr(_lib.lib, fmt.gemm_entry)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K,
@@ -425,13 +423,17 @@ def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"], wf=_FP4
     return out
 
 
+def _columns(width, bits, what):
+    """K of `what`, `width` bytes a row of `bits`-bit codes: a whole number of codes, and of blocks (4 bits bytes each)."""
+    if 8 * width % bits != 0:
+        raise ValueError(f"{what} has {width} columns of bytes, which is no whole number of {bits}-bit codes")
+    return BLOCK * _blocks(8 * width // bits)
+
+
 def _weights(codes, scales, wf=_FP4):
     """(N, K) of a packed layer in the _Weights wf, its shapes and dtypes checked."""
     N, width = _matrix(codes, "codes", (torch.uint8, np.uint8))
-    if 8 * width % wf.bits != 0:
-        raise ValueError(f"codes has {width} columns of bytes, which is no whole number of {wf.bits}-bit codes")
-    K = 8 * width // wf.bits
-    _blocks(K)
+    K = _columns(width, wf.bits, "codes")
     _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(scales, N, K, "scale bytes")
     return N, K
@@ -472,21 +474,14 @@ def quantize_mxfp6_act(X):
     return _quantize(X, _FORMATS["mxfp6_e2m3"])
 
 
-def _columns(width, fmt):
-    """K of codes of `width` bytes a row in the _Format fmt: a whole number of codes, and of blocks (4 bits bytes each)."""
-    if 8 * width % fmt.bits != 0:
-        raise ValueError(f"a_codes has {width} columns of bytes, which is no whole number of {fmt.bits}-bit codes")
-    return BLOCK * _blocks(8 * width // fmt.bits)
-
-
 def _dequantize(codes, scales, dtype, fmt, what):
     """value(code) * 2^(b - 127) of codes in the _Format fmt, (M, K) of `dtype`; `what` names the codes in an error."""
     _out_dtype(dtype, codes, "codes" if what == "codes" else "input")
     M, width = _matrix(codes, what, (torch.uint8, np.uint8))
-    K = _columns(width, fmt)
+    K = _columns(width, fmt.bits, "a_codes")
     _matrix(scales, "scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(scales, M, K, "scale bytes")
-    cd, sd = _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8)
+    cd, sd = dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8)
     out = torch.empty((M, K), dtype=dtype, device=cd.device)
     flag = torch.empty(1, dtype=torch.int32, device=cd.device)
     _lib.check(getattr(_lib.lib, fmt.dequantize_entry)(dev.ptr(cd), dev.ptr(sd), M, K, _OUT[dtype], dev.ptr(out), dev.ptr(flag),
@@ -515,14 +510,14 @@ def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, 
     _check_pair(fmt, wf)
     _out_dtype(dtype, a_codes)
     M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    K = _columns(width, fmt)
+    K = _columns(width, fmt.bits, "a_codes")
     _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(a_scales, M, K, "activation scale bytes")
     N, Kw = _weights(codes, scales, wf)
     if Kw != K:
         raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
     _check_bias(bias, N)
-    out = _gemm(_aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), _aligned(dev.to_device(codes, torch.uint8)),
+    out = _gemm(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), dev.aligned(dev.to_device(codes, torch.uint8)),
                 dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt, wf)
     return dev.like_input(out, a_codes)
 
@@ -573,7 +568,7 @@ def _linear(x, codes, scales, bias, dtype, activations, rotation, wf):
         ac, asc, flag = _rotate_quantize_act(Xd, M, K, rotation, fmt)
     else:
         ac, asc, flag = _quantize_act(Xd, M, K, fmt)
-    out = _gemm(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt, wf)
+    out = _gemm(ac, asc, dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt, wf)
     _raise_finite(flag)
     return dev.like_input(out.reshape(lead + (N,)), x)
 
@@ -609,8 +604,8 @@ class _MXModule(torch.nn.Module):
             state_dict = {k: v for k, v in state_dict.items() if k != key}  # (the base class knows no such key)
         if weights != self.weights:  # (the buffers have the module's shape: another format is never read into them)
             error_msgs.append(f"{key}: the state is of an {weights!r} layer, this module holds {self.weights!r} weights")
-        elif self.weights == "mxfp6_e2m3" and activations not in _W6_ACT:
-            error_msgs.append(f'{key}: an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations (got {activations!r})')
+        elif activations not in _WEIGHTS[self.weights].activations:
+            error_msgs.append(f"{key}: {_MXFP6_TAKES} (got {activations!r})")
             activations = self.activations
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
         self.activations = activations
@@ -667,8 +662,6 @@ class MXLinear(_MXModule):
 # --------------------------------------------------------------------------------------------------------------- experts
 # A mixture-of-experts layer: E packed layers of one shape, every row of x against the layer of its expert, in one call
 # (slk_mx_gemm_experts; module docstring, EXPERTS).
-_A_FMT = {"mxfp8": _lib.MX_ACT_FP8, "mxfp4": _lib.MX_ACT_FP4, "mxfp6_e2m3": _lib.MX_ACT_FP6}
-_W_FMT = {"mxfp4": _lib.MX_W_FP4, "mxfp6_e2m3": _lib.MX_W_FP6}
 _OFFSETS_RULE = ("offsets must start at 0, never decrease and end at the number of rows: "
                  "offsets[0] == 0, offsets[e] <= offsets[e + 1], offsets[E] == M")
 
@@ -693,10 +686,7 @@ def _expert_weights(codes, scales, wf):
     E, N, width = (int(v) for v in codes.shape)
     if E < 1 or E > _lib.MX_MAX_EXPERTS or N < 1:
         raise ValueError(f"codes must hold 1 .. {_lib.MX_MAX_EXPERTS} experts of at least one row (got {tuple(codes.shape)})")
-    if 8 * width % wf.bits != 0:
-        raise ValueError(f"codes has {width} columns of bytes, which is no whole number of {wf.bits}-bit codes")
-    K = 8 * width // wf.bits
-    _blocks(K)
+    K = _columns(width, wf.bits, "codes")
     if tuple(scales.shape) != (E, N, K // BLOCK):
         raise ValueError(f"scale bytes must be ({E}, {N}, {K // BLOCK}) for {E} ({N}, {K}) layers; got {tuple(scales.shape)}")
     return E, N, K
@@ -719,7 +709,7 @@ def _gemm_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, dtype, fmt, wf):
     flag = torch.empty(1, dtype=torch.int32, device=ac.device)
     ws, ws_bytes = dev.scratch(_lib.lib.slk_mx_experts_workspace_bytes(E, M), "mx_experts")
     _lib.check(_lib.lib.slk_mx_gemm_experts(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), dev.ptr(offsets), E, M, N, K,
-                                            _A_FMT[fmt.name], _W_FMT[wf.name], _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.ptr(ws), ws_bytes,
+                                            fmt.c_fmt, wf.c_fmt, _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.ptr(ws), ws_bytes,
                                             dev.stream_handle()))
     return out, flag
 
@@ -744,7 +734,7 @@ def matmul_mx_experts(a_codes, a_scales, codes, scales, offsets, bias=None, dtyp
     _check_pair(fmt, wf)
     _out_dtype(dtype, a_codes)
     M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    K = _columns(width, fmt)
+    K = _columns(width, fmt.bits, "a_codes")
     _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
     _check_scale_shape(a_scales, M, K, "activation scale bytes")
     E, N, Kw = _expert_weights(codes, scales, wf)
@@ -752,8 +742,8 @@ def matmul_mx_experts(a_codes, a_scales, codes, scales, offsets, bias=None, dtyp
         raise ValueError(f"a_codes has {K} columns but the experts' layers have {Kw}")
     _check_expert_bias(bias, E, N)
     _check_offsets(offsets, E)
-    out, flag = _gemm_experts(_aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8),
-                              _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
+    out, flag = _gemm_experts(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8),
+                              dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
                               dev.to_device(offsets, torch.int32), E, M, N, K, dtype, fmt, wf)
     _raise_flags((flag, _OFFSETS_RULE))
     return dev.like_input(out, a_codes)
@@ -783,7 +773,7 @@ def _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotatio
         ac, asc, finite = _rotate_quantize_act(Xd, M, K, rotation, fmt)
     else:
         ac, asc, finite = _quantize_act(Xd, M, K, fmt)
-    out, flag = _gemm_experts(ac, asc, _aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
+    out, flag = _gemm_experts(ac, asc, dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
                               dev.to_device(offsets, torch.int32), E, M, N, K, dtype, fmt, wf)
     _raise_flags(*also, (finite, "activations must be finite: X holds a NaN or an infinity"), (flag, _OFFSETS_RULE))
     return dev.like_input(out, x)
@@ -940,6 +930,6 @@ def quantize_experts(Ws, Hs, weights="mxfp4", act_order="diag", damp=0.01, scale
     layers = [dict(W=W, H=H, gscale=s, group_size=BLOCK) for W, H, s in zip(Wd, Hd, S)]
     shards = dist.quantize_stream(layers, dist.HipBackend(wf.codebook, act_order, damp, 0, with_error=False))
     E = len(layers)
-    codes, scales = _pack(_aligned(torch.cat([sh["idx"] for sh in shards])), torch.cat(S), E * R, n, wf)
+    codes, scales = _pack(dev.aligned(torch.cat([sh["idx"] for sh in shards])), torch.cat(S), E * R, n, wf)
     codes, scales = codes.reshape(E, R, -1), scales.reshape(E, R, -1)
     return [MXResult(*(dev.like_input(t, Ws[e]) for t in (shards[e]["Q"], shards[e]["idx"], S[e], codes[e], scales[e]))) for e in range(E)]

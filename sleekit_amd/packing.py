@@ -181,11 +181,6 @@ def _torch_dtype(x):
     return x.dtype if isinstance(x, torch.Tensor) else {np.dtype(np.float32): torch.float32, np.dtype(np.float16): torch.float16}[x.dtype]
 
 
-def _aligned(t):
-    """The kernels move 16 bytes a lane: a contiguous view that starts off such a boundary is copied."""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
-
-
 def _check_shape(x, shape, what):
     if not isinstance(x, (np.ndarray, torch.Tensor)) or tuple(x.shape) != shape:
         raise ValueError(f"{what} must be {shape}; got {tuple(getattr(x, 'shape', ()))}")
@@ -272,7 +267,7 @@ def linear_packed(x, P, codebook, bits=None, scale=None, group_scales=None, grou
     if M < 1 or M >= 1 << 31:
         raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
     levels, lo, hi, table = engine.require_uniform(codebook)
-    Xd = _aligned(dev.to_device(x, _torch_dtype(x)).reshape(M, K))
+    Xd = dev.aligned(dev.to_device(x, _torch_dtype(x)).reshape(M, K))
     Pd = dev.to_device(P.view(np.int32) if isinstance(P, np.ndarray) else P, torch.int32)
     Sd = dev.to_device(scale) if scale is not None else None
     Gd = dev.to_device(group_scales) if group_scales is not None else None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MXFP4: kernel times and HBM rates of the scale search, pack, unpack and dequantize, on the MI355X.
 
-    python tools/micro_mx.py [--reps 20] [--no-layer] [--fp6]
+    python tools/micro_mx.py [--reps 20] [--no-layer] [--fp6] [--parent-lib libsleekit_amd.so]
 
 Sizes: 4096 x 4096 and 4096 x 11008.  Each C entry is timed alone on preallocated outputs with device events (median of
 `reps` after a warm-up; min and max are printed as the spread), the two sides of a comparison alternating call by call.
@@ -18,6 +18,10 @@ MI355X_MICROARCH.md measured as achievable for HBM.
 --fp6: the MXFP6 (E2M3) entries against their MXFP4 twins instead, alternating call by call -- slk_mx_scale_search6 against
 slk_mx_scale_search (mse, diag), slk_mx_pack6 / slk_mx_unpack6 against slk_mx_pack / slk_mx_unpack, and at 4096 x 4096 a
 whole quantize_mxfp6 against quantize_mxfp4 (the loop's search over 63 entries is two levels deeper than over 15).
+--parent-lib (a library built from another commit): only the converters, each against that library's -- slk_mx_pack, _unpack,
+_pack6, _unpack6, slk_mx_dequantize to float32, bfloat16 and float16, slk_mx_dequantize_act6 and _act to bfloat16 -- the two
+libraries alternating call by call, each side twice (micro_mx_act.py's loader and comparison row).  `passes`: both medians of
+this library at or below the parent's largest time, or the ratio of the first medians at most 1 + the parent's own spread.
 One JSON line per row.
 """
 
@@ -34,6 +38,8 @@ import torch  # noqa: E402
 
 from sleekit_amd import _device as dev, _lib, engine, groups, mx, packing, synth  # noqa: E402
 from sleekit_amd.codebook import Codebook  # noqa: E402
+
+from micro_mx_act import against_parent, load_library, timed  # noqa: E402
 
 HBM = 6.3e12  # bytes/s
 L = _lib.lib
@@ -196,8 +202,45 @@ def fp6_rows(size, W, H, reps, layer):
             print(json.dumps(dict(size=size, call=name, **wall(fn, max(3, reps // 4)))), flush=True)
 
 
+def parent_rows(size, R, n, reps, parent):
+    """Every converter of this library against the parent's, on the same buffers."""
+    G = n // 32
+    P, s = dev.ptr, dev.stream_handle
+    gen = torch.Generator(device="cuda").manual_seed(R + n)
+    Eb = torch.randint(100, 140, (R, G), dtype=torch.uint8, device="cuda", generator=gen)
+    S = mx.decode_scales(Eb)
+    S_out, e_out = torch.empty_like(S), torch.empty_like(Eb)
+    out = torch.empty((R, n), dtype=torch.float32, device="cuda")  # (every dtype's result: the 16-bit ones fill half of it)
+    rows = []
+    for six, bits, entries in (("", 4, 15), ("6", 6, 63)):
+        idx = torch.randint(0, entries, (R, n), dtype=torch.uint8, device="cuda", generator=gen)
+        codes = (mx.pack_mxfp6 if six else mx.pack_mxfp4)(idx, S)[0]
+        c_out, idx_out = torch.empty_like(codes), torch.empty_like(idx)
+        moved = R * n + R * n * bits // 8 + 5 * R * G
+        rows.append((f"slk_mx_pack{six}", moved, lambda lib, six=six, idx=idx, c_out=c_out: getattr(lib, "slk_mx_pack" + six)(
+            P(idx), P(S), R, n, P(c_out), P(e_out), None, s())))
+        rows.append((f"slk_mx_unpack{six}", moved, lambda lib, six=six, codes=codes, idx_out=idx_out: getattr(lib, "slk_mx_unpack" + six)(
+            P(codes), P(Eb), R, n, P(idx_out), P(S_out), None, s())))
+        if six:
+            rows.append(("slk_mx_dequantize_act6 bfloat16", R * n * bits // 8 + R * G + 2 * R * n, lambda lib, codes=codes: lib.slk_mx_dequantize_act6(
+                P(codes), P(Eb), R, n, _lib.DTYPE_BF16, P(out), None, s())))
+            continue
+        for name, code, osz in (("float32", _lib.DTYPE_F32, 4), ("bfloat16", _lib.DTYPE_BF16, 2), ("float16", _lib.DTYPE_F16, 2)):
+            rows.append((f"slk_mx_dequantize {name}", R * n // 2 + R * G + osz * R * n, lambda lib, codes=codes, code=code: lib.slk_mx_dequantize(
+                P(codes), P(Eb), R, n, code, P(out), None, s())))
+    c8 = torch.randint(0, 0x7F, (R, n), dtype=torch.uint8, device="cuda", generator=gen)  # (E4M3 codes, no NaN)
+    rows.append(("slk_mx_dequantize_act bfloat16", R * n + R * G + 2 * R * n, lambda lib: lib.slk_mx_dequantize_act(
+        P(c8), P(Eb), R, n, _lib.DTYPE_BF16, P(out), None, s())))
+    for entry, nbytes, call in rows:
+        this, there, this2, there2 = timed([lambda: _lib.check(call(L)), lambda: _lib.check(call(parent))] * 2, reps)
+        cmp = against_parent((this, this2), (there, there2))
+        passes = max(this[0], this2[0]) <= cmp["parent_max_us"] or this[0] / there[0] <= 1.0 + abs(there[0] - there2[0]) / there[0]
+        row(size, f"{entry} against the parent's", this, nbytes, passes=bool(passes), **cmp)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", default=None, help="a libsleekit_amd.so built from another commit: only the converters, against its")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-layer", action="store_true")
     ap.add_argument("--fp6", action="store_true")
@@ -205,6 +248,10 @@ def main():
     assert torch.cuda.is_available(), "micro_mx measures the MI355X; there is no CPU path"
     torch.cuda.set_device(0)
     for size, (R, n) in (("4096x4096", (4096, 4096)), ("4096x11008", (4096, 11008))):
+        if args.parent_lib:
+            parent_rows(size, R, n, args.reps, load_library(args.parent_lib))
+            torch.cuda.empty_cache()
+            continue
         layer = synth.make_layer_device(R, n, 31, "cuda")
         if args.fp6:
             fp6_rows(size, layer["W"], layer["H"], args.reps, n == 4096 and not args.no_layer)
