@@ -12,12 +12,16 @@ is RCCL on ROCm).  The exchange is one asynchronous all-gather per round of G la
 simultaneous broadcasts, one root each), issued up front so the loops of round g overlap the
 factorisations and the transfer of round g+1; on a single rank nothing is communicated.
 
-The module is engine-agnostic: `backend` supplies factorize / run_rows, which lets the CPU
-test-suite drive the same scheduling code over gloo with a stand-in backend.
+The module is engine-agnostic: `backend` supplies factorize / run_rows (class Backend below is the whole contract, with
+every optional hook's default), which lets the CPU test-suite drive the same scheduling code over gloo with a stand-in backend.
 """
 
+import collections
+import contextlib
+import ctypes
 import operator
 import os
+import types
 
 import torch
 import torch.distributed as dist
@@ -138,22 +142,63 @@ def plan_rounds(layers, size, bucket=True):
     return rounds, root
 
 
-class HipBackend:
+class Backend:
+    """What quantize_stream asks of an engine.  Required: payload_words(n), alloc_payload(words, device), pack(factor, words),
+    unpack(payload, n), factorize(layer), run_rows(layer, lo, hi, factor).  Everything optional is below with the default the
+    scheduler sees -- it probes nothing, and looks every method up on the instance at call time (tests put counters there).
+    The defaults are the plainest schedule: in order on the caller's stream, a layer per factorisation, a layer per loop."""
+
+    moves = 0                        # local-search moves (check_layers: none with group scales)
+    exchange_log = None              # a list: every all-gather is timed between two events and appended (measurement)
+    bucket_by_shape = True           # several ranks: rounds of one shape (plan_rounds)
+    rounds_on_factor_streams = True  # a batched round runs on the stream that factored this rank's layer of it
+    factor_chains = False            # factorize_many is ONE launch chain: a rank's layers of a group of rounds form one job on
+    #                                  one stream (up to _chain_cap of them), not a job each on rotating streams
+    group_bytes = 1 << 32            # bytes the factorisations of one chain may hold (_chain_cap)
+    local_batch = 1                  # one rank: small layers per batched round (run_round_local); also caps a short round
+    short_rows = 4096                # one rank: stacked rows of a round of short-wide layers (_short_rounds) ...
+    short_factor_batch = 1           # ... and how many of its factorisations share a chain
+    tall_stack = 1                   # one rank: full-height layers per loop (run_tall)
+    _factor_rotation = _loop_rotation = 0  # where the rotation over the factor / loop streams stands (_Lanes)
+
+    def streams(self):  # (factor streams, comm stream, loop streams), or no side streams
+        return None, None, None
+
+    def group_limit(self, layer, rows):  # layers of this shape, `rows` per rank, in one loop batch (0: round by round)
+        return 0
+
+    def can_batch(self, round_layers, lo, hi):  # run_round(round_layers, lo, hi, payloads) takes these shards as one batch
+        return False
+
+    def wants_local_batch(self, layer):  # one rank: in rounds of its shape through run_round_local(round_layers)
+        return False
+
+    def wants_stacked_loop(self, layer):  # one rank: factored in chains, looped by run_round_stacked(round_layers, factors)
+        return False
+
+    def wants_tall_stack(self, layer):  # one rank: its loop shares launches with its neighbours', run_tall(stack_layers, factors)
+        return False
+
+    def factorize_many(self, layers):
+        return [self.factorize(lay) for lay in layers]
+
+    def note_statuses(self, infos, layers, defer=False):  # every layer's factorisation status word, once per call
+        pass
+
+
+class HipBackend(Backend):
     """The real thing: sleekit_amd.engine on the current device."""
+
+    factor_chains = True
 
     def __init__(self, quantizer, act_order="diag", damp=0.01, nb_ls_moves=0, with_error=True, overlap=True):
         from . import engine
 
         self.engine, self.quantizer, self.overlap = engine, quantizer, overlap
         self.act_order, self.damp, self.moves, self.with_error = act_order, damp, nb_ls_moves, with_error
-        self.local_batch = int(os.environ.get("SLK_LOCAL_BATCH", self.local_batch))            # (measurement knobs)
-        self.local_batch_cols = int(os.environ.get("SLK_LOCAL_BATCH_COLS", self.local_batch_cols))
-        self.group_rows = int(os.environ.get("SLK_GROUP_ROWS", self.group_rows))
-        self.short_factor_batch = int(os.environ.get("SLK_SHORT_FACTOR_BATCH", self.short_factor_batch))
-        self.short_rows = int(os.environ.get("SLK_SHORT_ROWS", self.short_rows))
-        self.tall_stack = int(os.environ.get("SLK_TALL_STACK", self.tall_stack))
-        self.group_wide_rows = int(os.environ.get("SLK_GROUP_WIDE_ROWS", self.group_wide_rows))
-        self.group_bytes = int(os.environ.get("SLK_GROUP_BYTES", self.group_bytes))
+        for knob in ("local_batch", "local_batch_cols", "group_rows", "short_factor_batch", "short_rows", "tall_stack", "group_wide_rows",
+                     "group_bytes"):  # (measurement knobs: SLK_LOCAL_BATCH ...)
+            setattr(self, knob, int(os.environ.get("SLK_" + knob.upper(), getattr(self, knob))))
 
     def streams(self):
         """(factor streams, comm stream, loop streams), created once; (None, None, None) = everything in order."""
@@ -377,8 +422,6 @@ class HipBackend:
         if U is None or U.shape[0] < B:
             U = self._ustacks[key] = torch.zeros((B, n, n), dtype=torch.float64, device=device)
         U = U[:B]
-        import ctypes
-
         order = torch.empty((B, n), dtype=torch.int64, device=device)
         info = torch.empty(B, dtype=torch.int32, device=device)
         # (every rank runs the same backend settings, so with_error here means the roots packed real verdicts)
@@ -530,17 +573,89 @@ class HipBackend:
 LOOP_LAYERS = 16  # layers one loop takes as a list of tensors (slk_gptq_quantize_layers)
 
 
-def _guard_inputs(layers, stream):
-    """The caller's tensors of `layers` (W, H, scale, gscale, mean) are read on the side stream `stream`: tell the caching allocator,
-    so that a caller who drops them right after a join=False call does not hand memory the side streams still read back for
-    reuse (the allocator then holds the block until `stream` has passed this point)."""
-    if stream is None:
-        return
-    for lay in layers:
-        for key in ("W", "H", "scale", "gscale", "mean"):
-            t = lay.get(key)
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                t.record_stream(stream)
+class _Lanes:
+    """The streams of ONE quantize_stream call and every operation the scheduler makes on them: the only code of the module
+    that touches torch.cuda's streams and events or Tensor.record_stream (but for _all_gather_words and its rehearsal handle).
+    With no side streams (overlap=False, the CPU stand-ins) every stream it hands out is None and every verb does nothing."""
+
+    def __init__(self, backend=None, join=True):
+        self.backend, self.joins = backend, join
+        fs, self.comm, ls = backend.streams() if backend is not None else (None, None, None)
+        self.factor, self.loop, self.side = fs or [], ls or [], fs is not None
+        self.here = torch.cuda.current_stream() if self.side else None
+        self.pool = (self.factor + self.loop) or [None]  # what the one-rank rounds of small layers alternate over
+        self._forked = set()
+
+    def _take(self, counter, streams):
+        if not self.side:
+            return None
+        k = getattr(self.backend, counter)  # the rotation lives on the backend: it carries on from one call to the next
+        setattr(self.backend, counter, (k + 1) % len(streams))
+        return streams[k % len(streams)]
+
+    def next_factor(self):
+        """Factorisations are latency-bound chains: consecutive ones alternate between the factor streams (across calls too:
+        with one layer per rank and call, consecutive calls would otherwise queue one chain behind the other)."""
+        return self._take("_factor_rotation", self.factor)
+
+    def next_loop(self):  # batched rounds rotate over the loop streams across calls, like the factorisations
+        return self._take("_loop_rotation", self.loop)
+
+    def loop_of(self, l):  # layer by layer: consecutive layers alternate
+        return self.loop[l % len(self.loop)] if self.side else None
+
+    def fork(self, *streams):
+        """Each of `streams` behind the caller's stream, once per call (before its first use)."""
+        for st in streams:
+            if st is not None and id(st) not in self._forked:
+                self._forked.add(id(st))
+                st.wait_stream(self.here)
+
+    def on(self, stream, layers=()):
+        """Context: what is enqueued inside goes to `stream` and reads the caller's tensors of `layers`.  Unjoined, the caching
+        allocator is told so: a caller who drops them right after a join=False call does not hand memory the side streams
+        still read back for reuse (the allocator holds the block until `stream` has passed this point)."""
+        if stream is None:
+            return contextlib.nullcontext()
+        if not self.joins:
+            for lay in layers:
+                for key in ("W", "H", "scale", "gscale", "mean"):
+                    t = lay.get(key)
+                    if isinstance(t, torch.Tensor) and t.is_cuda:
+                        t.record_stream(stream)
+        return torch.cuda.stream(stream)
+
+    def mark(self, stream):
+        """An event at this point of `stream` (None: none)."""
+        if stream is None:
+            return None
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        return ev
+
+    @staticmethod
+    def stamp():
+        """Measurement (exchange_log): a timing event at this point of the current stream, side streams or not."""
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record(torch.cuda.current_stream())
+        return ev
+
+    def wait(self, stream, event):
+        if event is not None:
+            stream.wait_event(event)
+
+    def moved(self, tensors, stream):
+        """`tensors` were made on one stream and are read on `stream` (lanes.here: the caller's): keep the allocator honest."""
+        if stream is not None:
+            for t in tensors:
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(stream)
+
+    def join(self, streams):
+        """join=True: the caller's stream waits for `streams`, so the results can be used on it at once."""
+        if self.joins and self.here is not None:
+            for st in streams:
+                self.here.wait_stream(st)
 
 
 def _stack_views(tensors):
@@ -553,14 +668,6 @@ def _stack_views(tensors):
                                   and t.storage_offset() == t0.storage_offset() + i * step for i, t in enumerate(tensors)):
         return t0.as_strided((len(tensors),) + tuple(t0.shape), (step,) + tuple(t0.stride()))
     return torch.stack(tensors)
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 def _all_gather_words(payload, size):
@@ -579,100 +686,84 @@ def _all_gather_words(payload, size):
     return outs, dist.all_gather(outs, payload, async_op=True)
 
 
+def _shape_kind(layer):
+    """The key of short rounds, groups of rounds and tall stacks: layers of one key may share a loop."""
+    return tuple(layer["W"].shape), _layer_kind(layer)
+
+
+def _chain_cap(backend, n):
+    """How many n-column factorisations may share one launch chain (factorize_many): a chain of B holds B x (A, U and two
+    workspace images) of n x n doubles, capped at backend.group_bytes."""
+    return max(1, int(backend.group_bytes) // (32 * n * n))
+
+
+def _factor_job(lanes, backend, job):
+    """The factors of a job's layers on the next factor stream -- one launch chain for several (factorize_many), the plain
+    call for one -- with the event behind them and the stream they went to."""
+    fs = lanes.next_factor()
+    lanes.fork(fs)
+    with lanes.on(fs, job):
+        made = backend.factorize_many(job) if len(job) > 1 else [backend.factorize(job[0])]
+        return made, lanes.mark(fs), fs
+
+
+def _run_layer(backend, layer, factor, rank=0, size=1):
+    """A single layer's rows of `rank` from its factor: the shard, with the factorisation's status word."""
+    return dict(backend.run_rows(layer, *row_range(layer["W"].shape[0], rank, size), factor), info=factor[2])
+
+
 def _quantize_stream_local(layers, small, short, backend, join):
     """One rank, a stream with small or short layers in it (quantize_stream).  `small` layers go in batched rounds by
     shape -- factored AND looped together -- one round after the other on alternating streams (a round is a chain of short
     launches: two or three in flight fill the gaps); `short` ones (wide, few rows) go in rounds whose factorisations share
     one launch chain on a factor stream (HipBackend.short_factor_batch) and whose rows are looped as one stack; the rest
     through the usual route."""
-    n_layers = len(layers)
-    out = [None] * n_layers
-    fstreams, _, lstreams = backend.streams()
-    side = fstreams is not None
-    pool = (fstreams + lstreams) if side else [None]
-    here = torch.cuda.current_stream() if side else None
-
-    def on(st):
-        return torch.cuda.stream(st) if st is not None else _NullCtx()
+    out = [None] * len(layers)
+    lanes = _Lanes(backend, join)
+    lanes.fork(*lanes.pool)
 
     def keep(shards, idxs):
         for l, shard in zip(idxs, shards):
             out[l] = shard
-            if here is not None:
-                for t in shard.values():
-                    if isinstance(t, torch.Tensor):
-                        t.record_stream(here)
+        lanes.moved([t for shard in shards for t in shard.values()], lanes.here)  # made on a side stream, consumed on the caller's
 
-    for st in pool:
-        if st is not None:
-            st.wait_stream(here)
-    if small:
-        rounds, _ = plan_rounds([layers[l] for l in small], backend.local_batch)
-        for i, members in enumerate(rounds):
-            st = pool[i % len(pool)]
-            idxs = [small[m] for m in members]
-            if not join:
-                _guard_inputs([layers[l] for l in idxs], st)
-            with on(st):
-                if len(idxs) == 1:
-                    lay = layers[idxs[0]]
-                    fac = backend.factorize(lay)
-                    shards = [dict(backend.run_rows(lay, 0, lay["W"].shape[0], fac), info=fac[2])]
-                else:
-                    shards = backend.run_round_local([layers[l] for l in idxs])
-            keep(shards, idxs)
-    if short:
-        # a round's factorisations in one launch chain (chains rotate over the factor streams), its stacked loop on the loop
-        # stream behind them
-        ls = lstreams[0] if side else None
-        rotation = getattr(backend, "_factor_rotation", 0) if side else 0
-        for members in _short_rounds(layers, short, backend):
-            facs, events = [], []
-            n_ = layers[members[0]]["H"].shape[0]
-            # (a chain of B factorisations holds B x (A, U and two workspace images) of n x n doubles: capped at group_bytes)
-            fb = max(1, min(int(getattr(backend, "short_factor_batch", 1)), int(getattr(backend, "group_bytes", 1 << 32)) // (32 * n_ * n_)))
-            for i in range(0, len(members), fb):
-                job = members[i:i + fb]
-                fs = fstreams[rotation % len(fstreams)] if side else None
-                rotation += 1
-                if not join:
-                    _guard_inputs([layers[l] for l in job], fs)
-                with on(fs):
-                    if len(job) > 1 and hasattr(backend, "factorize_many"):
-                        facs.extend(backend.factorize_many([layers[l] for l in job]))
-                    elif len(job) > 1:
-                        facs.extend(backend.factorize(layers[l]) for l in job)
-                    else:
-                        facs.append(backend.factorize(layers[job[0]]))
-                    if side:
-                        ev = torch.cuda.Event()
-                        ev.record(fs)
-                        events.append(ev)
-            if not join:
-                _guard_inputs([layers[l] for l in members], ls)
-            with on(ls):
-                for ev in events:
-                    ls.wait_event(ev)
-                if len(members) == 1:
-                    lay = layers[members[0]]
-                    shards = [dict(backend.run_rows(lay, 0, lay["W"].shape[0], facs[0]), info=facs[0][2])]
-                else:
-                    shards = backend.run_round_stacked([layers[l] for l in members], facs)
-                if side:
-                    for f in facs:
-                        for t in f:
-                            t.record_stream(ls)
-            keep(shards, members)
-        if side:
-            backend._factor_rotation = rotation % len(fstreams)
+    for i, members in enumerate(plan_rounds([layers[l] for l in small], backend.local_batch)[0] if small else []):
+        st = lanes.pool[i % len(lanes.pool)]
+        idxs = [small[m] for m in members]
+        round_layers = [layers[l] for l in idxs]
+        with lanes.on(st, round_layers):
+            if len(idxs) == 1:
+                shards = [_run_layer(backend, round_layers[0], backend.factorize(round_layers[0]))]
+            else:
+                shards = backend.run_round_local(round_layers)
+        keep(shards, idxs)
+    # a short round's factorisations in launch chains (the chains rotate over the factor streams), its stacked loop on the
+    # loop stream behind them
+    ls = lanes.loop_of(0)
+    for members in _short_rounds(layers, short, backend):
+        round_layers = [layers[l] for l in members]
+        per_chain = max(1, min(int(backend.short_factor_batch), _chain_cap(backend, round_layers[0]["H"].shape[0])))
+        facs, events = [], []
+        for i in range(0, len(members), per_chain):
+            made, ev, _ = _factor_job(lanes, backend, round_layers[i:i + per_chain])
+            facs.extend(made)
+            events.append(ev)
+        with lanes.on(ls, round_layers):
+            for ev in events:
+                lanes.wait(ls, ev)
+            if len(members) == 1:
+                shards = [_run_layer(backend, round_layers[0], facs[0])]
+            else:
+                shards = backend.run_round_stacked(round_layers, facs)
+            for f in facs:
+                lanes.moved(f, ls)
+        keep(shards, members)
     taken = set(small) | set(short)
-    rest = [l for l in range(n_layers) if l not in taken]
+    rest = [l for l in range(len(layers)) if l not in taken]
     if rest:
         for l, shard in zip(rest, _quantize_stream([layers[l] for l in rest], backend, join=join, _local=False)):
             out[l] = shard
-    if join and here is not None:
-        for st in pool:
-            here.wait_stream(st)
+    lanes.join(lanes.pool)
     return out
 
 
@@ -680,10 +771,10 @@ def _short_rounds(layers, short, backend):
     """Rounds of same-shaped `short` layers whose stacked rows come to about a full layer's worth (4096)."""
     by_shape = {}
     for l in short:
-        by_shape.setdefault((tuple(layers[l]["W"].shape), _layer_kind(layers[l])), []).append(l)
+        by_shape.setdefault(_shape_kind(layers[l]), []).append(l)
     rounds = []
     for (shape, _), members in by_shape.items():
-        per = max(2, min(backend.local_batch, int(getattr(backend, "short_rows", 4096)) // max(shape[0], 1)))
+        per = max(2, min(backend.local_batch, int(backend.short_rows) // max(shape[0], 1)))
         rounds.extend(members[i:i + per] for i in range(0, len(members), per))
     return rounds
 
@@ -700,31 +791,27 @@ def quantize_stream(layers, backend, comm_device=None, join=True):
 
     join=True ends in ONE blocking device -> host read of the status words (a host synchronisation per call).  join=False
     blocks nowhere: `_device.raise_pending()` is then REQUIRED, after synchronising, to see the statuses (the list it reads is
-    bounded: _device.PENDING_LIMIT); the inputs may be dropped at once (_guard_inputs).
+    bounded: _device.PENDING_LIMIT); the inputs may be dropped at once (_Lanes.on).
 
     Group scales: a layer dict may carry `gscale` (R, n / group_size) float32 and `group_size` instead of `scale`; its shards
     are then those of sleekit_amd.groups (Q de-scaled, idx the codebook indices of Q / s).  check_layers refuses bad keys
     (ValueError) and grouped layers under a local search (NotImplementedError) before anything runs.
     """
-    check_layers(layers, getattr(backend, "moves", 0))
+    check_layers(layers, backend.moves)
     out = _quantize_stream(layers, backend, comm_device, join, True)
-    note = getattr(backend, "note_statuses", None)
-    if note is not None:
-        note([None if shard is None else shard.get("info") for shard in out], layers, defer=not join)
+    backend.note_statuses([None if shard is None else shard.get("info") for shard in out], layers, defer=not join)
     return out
 
 
 def _group_rounds(rounds, layers, backend, rank, size):
     """Consecutive rounds of one shape joined into groups of at most backend.group_limit(layer, shard rows) layers (the
-    loop batch the backend wants for such shards); without that hook, or for big layers (limit below two rounds), every
-    round is a group of its own."""
-    limit_of = getattr(backend, "group_limit", None)
+    loop batch the backend wants for such shards); for a backend that wants none (Backend.group_limit: 0), or for big layers
+    (limit below two rounds), every round is a group of its own."""
     groups, key_now, count, limit = [], None, 0, 0
     for g, members in enumerate(rounds):
         first = layers[members[0]]
-        same = len({(tuple(layers[l]["W"].shape), _layer_kind(layers[l])) for l in members}) == 1
-        key = (tuple(first["W"].shape), _layer_kind(first)) if same else None
-        if limit_of is not None and key is not None and key == key_now and count + len(members) <= limit:
+        key = _shape_kind(first) if len({_shape_kind(layers[l]) for l in members}) == 1 else None
+        if key is not None and key == key_now and count + len(members) <= limit:
             groups[-1].append(g)
             count += len(members)
             continue
@@ -734,8 +821,208 @@ def _group_rounds(rounds, layers, backend, rank, size):
         # differ by one when R % size != 0 (1030 rows on 8 ranks: 129 / 128, on either side of the 128-row padding), so every
         # rank asks with the TALLEST shard, rank 0's = ceil(R / size) -- also for a rank that has no rows of the layer at all.
         lo, hi = row_range(first["W"].shape[0], 0, size)
-        limit = int(limit_of(first, hi - lo)) if (limit_of is not None and key is not None) else 0
+        limit = int(backend.group_limit(first, hi - lo)) if key is not None else 0
     return groups
+
+
+def _factor_jobs(groups, rounds, root, rank, layers, backend):
+    """The factorisations `rank` owes -- the layers it is the root of, in processing order -- as lists of layers factored
+    together: its layers of a GROUP of rounds share one launch chain (up to _chain_cap of them) when the backend factors in
+    chains, everything else goes one by one."""
+    jobs = []
+    for members_g in groups:
+        own = [l for g in members_g for l in rounds[g] if root[l] == rank]
+        if len(members_g) > 1 and len(own) > 1 and backend.factor_chains:
+            cap = _chain_cap(backend, layers[own[0]]["H"].shape[0])
+            jobs.extend(own[i:i + cap] for i in range(0, len(own), cap))
+        else:
+            jobs.extend([l] for l in own)
+    return jobs
+
+
+def _tall_stacks(order, layers, backend):
+    """One rank: consecutive full-height layers of one shape and kind share one loop (backend.tall_stack at a time; a
+    remainder goes through the same call with fewer).  Returns tall[first member] = the stack, tall[later member] = ()."""
+    tall = {}
+    per = min(int(backend.tall_stack), LOOP_LAYERS)
+    run, run_key = [], None
+    for l in list(order) + [None]:
+        key = None if l is None or not backend.wants_tall_stack(layers[l]) else _shape_kind(layers[l])
+        if key != run_key or len(run) == per:
+            for m in run:
+                tall[m] = run if m == run[0] else ()
+            run = []
+        run_key = key
+        if key is not None:
+            run.append(l)
+    return tall
+
+
+_Plan = collections.namedtuple("_Plan", "rank size exchange rounds root groups slot jobs tall")
+
+
+def _plan_stream(layers, backend, rank, size):
+    """Who does what, from the layers, the world and the backend's policy alone (no stream, no tensor is touched).
+
+    rounds of one shape each and root[l] = the rank that factors layer l (plan_rounds).  Rounds of SMALL layers are taken in
+    GROUPS (the backend says how many layers it wants in one loop batch: group_limit): a rank factors all its layers of a
+    group in one batched factorisation (jobs), the group's payloads cross in ONE all-gather (slot[l]: the slot of l's round in
+    every rank's buffer) and its row shards go through the loop as ONE stack.  The shards of a small layer on several ranks
+    are a chain of short launches whatever their height (one rank of 8 on OPT-125M: 10 rounds x 15 loop launches and 9
+    factorisations x 45 launches per step, as long as the whole model on one GPU); groups make it 3 x 15 and 3 x 45.  A group
+    of one round is the plain scheme."""
+    exchange = size > 1 or always_exchange
+    rounds, root = plan_rounds(layers, size, bucket=exchange and backend.bucket_by_shape)
+    groups = _group_rounds(rounds, layers, backend, rank, size) if exchange else [[g] for g in range(len(rounds))]
+    slot = {l: j for members_g in groups for j, g in enumerate(members_g) for l in rounds[g]}
+    jobs = _factor_jobs(groups, rounds, root, rank, layers, backend)
+    tall = {} if exchange else _tall_stacks([l for g in rounds for l in g], layers, backend)
+    return _Plan(rank, size, exchange, rounds, root, groups, slot, jobs, tall)
+
+
+def _factor_phase(run):
+    """1. every rank factors the layers it is the root of (concurrently across ranks), job by job on rotating factor
+    streams; factors[l], the event behind it (ready[l]) and the stream it went to (stream_of[l])."""
+    for job in run.plan.jobs:
+        made, ev, fs = _factor_job(run.lanes, run.backend, [run.layers[l] for l in job])
+        for l, fac in zip(job, made):
+            run.factors[l], run.ready[l], run.stream_of[l] = fac, ev, fs
+
+
+def _exchange_group(layers, group_rounds, root, rank, size, backend, lanes, factors, ready, device):
+    """The all-gather of one group of rounds (lists of layers), asynchronous: this rank's payload of every round -- its own
+    layer's packed factor, behind that factor's event -- in the round's slot of one buffer of equal-sized contributions.
+    Returns (buffer, (per-rank buffers, work, words per payload, words per slot))."""
+    # equal-sized contributions: a group's layers share one shape (a lone round of mixed shapes: the widest)
+    words = max(backend.payload_words(layers[l]["H"].shape[0]) for members in group_rounds for l in members)
+    stride = (words + 1) // 2 * 2 if len(group_rounds) > 1 else words
+    buffer = None if len(group_rounds) == 1 else backend.alloc_payload(stride * len(group_rounds), device)
+    for j, members in enumerate(group_rounds):
+        own = [l for l in members if root[l] == rank]  # at most one: a round has at most `size` layers
+        if own:
+            l = own[0]
+            lanes.wait(lanes.comm, ready[l])
+            payload = backend.pack(factors[l], words)
+            lanes.moved(factors[l], lanes.comm)  # made on a factor stream, read here
+        elif rehearse is not None:
+            # rehearsal: a real factor of the right shape must stand in for the peers' (a blank one is not a
+            # permutation + triangle the kernels can run on); made once per shape, outside what is measured
+            first = layers[members[0]]
+            key = (first["H"].shape[0], words)
+            if key not in _rehearsal_payloads:
+                _rehearsal_payloads[key] = backend.pack(backend.factorize(first), words)
+            payload = _rehearsal_payloads[key]
+        elif buffer is None:  # no layer of this round is this rank's: contribute a blank
+            payload = backend.alloc_payload(words, device).zero_()
+        else:
+            payload = None  # (a slot nobody reads)
+        if buffer is None:
+            buffer = payload
+        elif payload is not None:
+            buffer[j * stride:j * stride + words].copy_(payload)
+    log = backend.exchange_log
+    if log is not None and buffer.is_cuda:
+        # measurement (bench.py's pass with events): the comm stream brackets the collective with two events
+        # and waits for it, so that their distance is the exchange itself
+        e0 = lanes.stamp()
+        parts, work = _all_gather_words(buffer, size)
+        work.wait()
+        log.append((e0, lanes.stamp(), buffer.numel() * buffer.element_size() * (size - 1)))
+    else:
+        parts, work = _all_gather_words(buffer, size)
+    return buffer, (parts, work, words, stride)
+
+
+def _exchange_phase(run, comm_device):
+    """2. one asynchronous all-gather per group of rounds, issued in order on the comm stream."""
+    plan, lanes = run.plan, run.lanes
+    lanes.fork(lanes.comm)
+    with lanes.on(lanes.comm):
+        for gi, members_g in enumerate(plan.groups):
+            device = comm_device if comm_device is not None else run.layers[0]["H"].device
+            buffer, run.gathered[gi] = _exchange_group(run.layers, [plan.rounds[g] for g in members_g], plan.root, plan.rank, plan.size,
+                                                       run.backend, lanes, run.factors, run.ready, device)
+            run.buffers.append(buffer)
+
+
+def _payload_of(run, gi, l):
+    parts, _, words, stride = run.gathered[gi]
+    at = run.plan.slot[l] * stride
+    return parts[run.plan.root[l]][at:at + words]
+
+
+def _loop_phase(run):
+    """3. every rank runs its rows of every layer as the factors land, group by group.  A group goes through the
+    kernels as ONE batch when the backend can do that (run_round): the shards are R / G rows each, too few to
+    fill the chip alone.  Otherwise layer by layer, consecutive ones on alternating streams (their leaf chains
+    are latency-bound) -- on one rank in stacks where the backend wants them (run_tall)."""
+    plan = run.plan
+    run.lanes.fork(*run.lanes.loop)
+    for gi, members_g in enumerate(plan.groups):
+        members = [l for g in members_g for l in plan.rounds[g]]
+        round_layers = [run.layers[l] for l in members]
+        lo, hi = row_range(round_layers[0]["W"].shape[0], plan.rank, plan.size)
+        if plan.exchange and run.backend.can_batch(round_layers, lo, hi):
+            _loop_round(run, gi, members, round_layers, lo, hi)
+            continue
+        for l in members:
+            if l not in plan.tall:
+                _loop_layer(run, gi, l)
+            elif plan.tall[l]:  # (a later member went with the first)
+                _loop_tall(run, plan.tall[l])
+
+
+def _loop_round(run, gi, members, round_layers, lo, hi):
+    """A group's shards as one batch, from the payloads of its all-gather."""
+    lanes = run.lanes
+    ls = lanes.next_loop()
+    own = [l for l in members if l in run.stream_of]
+    if own and run.backend.rounds_on_factor_streams:
+        # The round runs on the stream that factored this rank's layer of it: one stream fewer to pair badly.
+        # HIP multiplexes all streams of a process onto a few in-order hardware queues; a loop stream that shares
+        # its queue with the factor stream of the NEXT round puts that factorisation behind this round's loops and
+        # the pipeline collapses into factor -> loop -> factor (4.4 ... 7.0 ms per step at N = 8 depending on how
+        # the streams fell).
+        ls = run.stream_of[own[0]]
+    with lanes.on(ls, round_layers):
+        parts, work = run.gathered[gi][:2]
+        work.wait()  # orders the stream behind the transfer; no host block on GPU
+        shards = run.backend.run_round(round_layers, lo, hi, [_payload_of(run, gi, l) for l in members])
+        lanes.moved(parts, ls)
+    for l, shard in zip(members, shards):
+        run.out[l] = shard
+
+
+def _loop_tall(run, stack):
+    """One rank: a stack of full-height layers through one loop, behind EVERY member's factorisation."""
+    lanes = run.lanes
+    ls = lanes.loop_of(stack[0])
+    stack_layers = [run.layers[m] for m in stack]
+    with lanes.on(ls, stack_layers):
+        for m in stack:
+            lanes.wait(ls, run.ready[m])
+        for m, shard in zip(stack, run.backend.run_tall(stack_layers, [run.factors[m] for m in stack])):
+            run.out[m] = shard
+        for m in stack:
+            lanes.moved(run.factors[m], ls)  # made on the factor streams, read on this one
+
+
+def _loop_layer(run, gi, l):
+    """A single layer's rows: from its factor made here, or from the payload of its round's all-gather."""
+    plan, lanes, layer = run.plan, run.lanes, run.layers[l]
+    ls = lanes.loop_of(l)
+    with lanes.on(ls, [layer]):
+        if plan.exchange:
+            parts, work = run.gathered[gi][:2]
+            work.wait()
+            if run.factors[l] is None or always_exchange:
+                run.factors[l] = run.backend.unpack(_payload_of(run, gi, l), layer["H"].shape[0])
+        else:
+            lanes.wait(ls, run.ready[l])
+        run.out[l] = _run_layer(run.backend, layer, run.factors[l], plan.rank, plan.size)
+        lanes.moved(run.factors[l], ls)  # made on a factor / comm stream, read on this one
+        if plan.exchange:
+            lanes.moved(parts, ls)
 
 
 def _quantize_stream(layers, backend, comm_device=None, join=True, _local=True):
@@ -752,252 +1039,40 @@ def _quantize_stream(layers, backend, comm_device=None, join=True, _local=True):
     broadcasts -- because xGMI is a point-to-point mesh: every rank then receives over all of its
     7 links at once, where G separate ring broadcasts would each crawl through one link per hop.
 
-    Three kinds of queues per rank when the backend provides device streams (`backend.streams()`):
-      factor streams : the n x n factorisations this rank owns (latency-bound chains)
-      comm stream    : pack + all-gather of each round, behind that round's factor event
-      loop streams   : the row loops, each behind its round's collective
+    Three kinds of queues per rank when the backend provides device streams (`backend.streams()`, held by _Lanes):
+      factor streams : the n x n factorisations this rank owns (latency-bound chains)            _factor_phase
+      comm stream    : pack + all-gather of each round, behind that round's factor event         _exchange_phase
+      loop streams   : the row loops, each behind its round's collective                         _loop_phase
     so the factorisation of round g+1 runs under the loops and errors of round g.
 
     `join` (default): the caller's stream waits for the loop streams before this returns, so the results can
     be used on it at once.  With join=False nothing waits: the NEXT call's factorisations then start under
     this call's loops (a throughput loop over independent batches, bench.py) -- synchronise the device, or
     the loop streams, before reading the results.  The INPUT tensors may be dropped when the call returns: every side
-    stream that reads them is recorded on them (_guard_inputs), so their memory is not reused before those streams pass.
+    stream that reads them is recorded on them (_Lanes.on), so their memory is not reused before those streams pass.
     """
     rank, size = world()
     n_layers = len(layers)
-    if size == 1 and not always_exchange and _local and hasattr(backend, "run_round_local"):
+    if size == 1 and not always_exchange and _local:
         # one rank: small layers go in rounds of one shape, factored and looped in launches that cover the round
         small = [l for l in range(n_layers) if backend.wants_local_batch(layers[l])]
         short = [l for l in range(n_layers) if backend.wants_stacked_loop(layers[l])]
         small, short = (small if len(small) > 1 else []), (short if len(short) > 1 else [])
         if small or short:
             return _quantize_stream_local(layers, small, short, backend, join)
-    fstreams, cstream, lstreams = backend.streams() if hasattr(backend, "streams") else (None, None, None)
-    side = fstreams is not None
-    here = torch.cuda.current_stream() if side else None
-    exchange = size > 1 or always_exchange
-    # rounds of one shape each; root[l] = the rank that factors layer l (plan_rounds)
-    rounds, root = plan_rounds(layers, size, bucket=exchange and getattr(backend, "bucket_by_shape", True))
-    n_rounds = len(rounds)
-    factors = [None] * n_layers
-    ready = [None] * n_layers
-
-    def on(stream):
-        return torch.cuda.stream(stream) if stream is not None else _NullCtx()
-
-    # Rounds of SMALL layers are taken in GROUPS (the backend says how many layers it wants in one loop batch:
-    # group_limit): a rank factors all its layers of a group in one batched factorisation, the group's payloads cross in ONE
-    # all-gather (a slot per round in every rank's buffer) and its row shards go through the loop as ONE stack.  The shards
-    # of a small layer on several ranks are a chain of short launches whatever their height (one rank of 8 on OPT-125M: 10
-    # rounds x 15 loop launches and 9 factorisations x 45 launches per step, as long as the whole model on one GPU);
-    # groups make it 3 x 15 and 3 x 45.  A group of one round is the plain scheme.
-    groups = _group_rounds(rounds, layers, backend, rank, size) if exchange else [[g] for g in range(n_rounds)]
-    slot = {}  # layer -> its round's slot in the group's buffers
-    for members_g in groups:
-        for j, g in enumerate(members_g):
-            for l in rounds[g]:
-                slot[l] = j
-
-    # 1. every rank factors the layers it is the root of (concurrently across ranks), in processing order; the
-    #    factorisations are latency-bound chains, so consecutive ones alternate between streams
-    #    (the rotation carries on from the previous call: with one layer per rank and call -- a round of G
-    #    layers on G ranks -- consecutive calls would otherwise queue on the same stream, one chain behind the other)
-    jobs = []  # lists of layers factored together
-    for members_g in groups:
-        own = [l for g in members_g for l in rounds[g] if root[l] == rank]
-        if len(members_g) > 1 and len(own) > 1 and hasattr(backend, "factorize_many"):
-            # (a chain of B factorisations holds B x (A, U and two workspace images) of n x n doubles: capped like the one-rank
-            # path's chains, _quantize_stream_local)
-            n_ = layers[own[0]]["H"].shape[0]
-            cap = max(1, int(getattr(backend, "group_bytes", 1 << 32)) // (32 * n_ * n_))
-            jobs.extend(own[i:i + cap] for i in range(0, len(own), cap))
-        else:
-            jobs.extend([l] for l in own)
-    first = getattr(backend, "_factor_rotation", 0) if side else 0
-    if side:
-        backend._factor_rotation = (first + len(jobs)) % len(fstreams)
-    stream_of = {}  # layer -> the stream its factorisation went to
-    for k, job in enumerate(jobs):
-        fs = fstreams[(first + k) % len(fstreams)] if side else None
-        if side and k < len(fstreams):
-            fs.wait_stream(here)
-        if not join:
-            _guard_inputs([layers[l] for l in job], fs)
-        with on(fs):
-            made = backend.factorize_many([layers[l] for l in job]) if len(job) > 1 else [backend.factorize(layers[job[0]])]
-            ev = None
-            if side:
-                ev = torch.cuda.Event()
-                ev.record(fs)
-        for l, fac in zip(job, made):
-            factors[l], ready[l], stream_of[l] = fac, ev, fs
-    # 2. one asynchronous all-gather per group of rounds, issued in order
-    gathered = [None] * len(groups)  # (per-rank buffers, work, words per payload, words per slot)
-    keep = []
-    if exchange:
-        if cstream is not None:
-            cstream.wait_stream(here)
-        with on(cstream):
-            for gi, members_g in enumerate(groups):
-                members = [l for g in members_g for l in rounds[g]]
-                # equal-sized contributions: a group's layers share one shape (a lone round of mixed shapes: the widest)
-                words = max(backend.payload_words(layers[j]["H"].shape[0]) for j in members)
-                stride = (words + 1) // 2 * 2 if len(members_g) > 1 else words
-                dev_ = comm_device if comm_device is not None else layers[0]["H"].device
-                buffer = None if len(members_g) == 1 else backend.alloc_payload(stride * len(members_g), dev_)
-                for j, g in enumerate(members_g):
-                    own = [l for l in rounds[g] if root[l] == rank]  # at most one: a round has at most `size` layers
-                    if own:
-                        l = own[0]
-                        if ready[l] is not None:
-                            cstream.wait_event(ready[l])
-                        payload = backend.pack(factors[l], words)
-                        if side:
-                            for t in factors[l]:
-                                t.record_stream(cstream)  # made on a factor stream, read here
-                    elif rehearse is not None:
-                        # rehearsal: a real factor of the right shape must stand in for the peers' (a blank one is not a
-                        # permutation + triangle the kernels can run on); made once per shape, outside what is measured
-                        n_ = layers[rounds[g][0]]["H"].shape[0]
-                        if (n_, words) not in _rehearsal_payloads:
-                            _rehearsal_payloads[(n_, words)] = backend.pack(backend.factorize(layers[rounds[g][0]]), words)
-                        payload = _rehearsal_payloads[(n_, words)]
-                    elif buffer is None:  # no layer of this round is this rank's: contribute a blank
-                        payload = backend.alloc_payload(words, dev_).zero_()
-                    else:
-                        payload = None  # (a slot nobody reads)
-                    if buffer is None:
-                        buffer = payload
-                    elif payload is not None:
-                        buffer[j * stride:j * stride + words].copy_(payload)
-                log = getattr(backend, "exchange_log", None)
-                if log is not None and buffer.is_cuda:
-                    # measurement (bench.py's pass with events): the comm stream brackets the collective with two events
-                    # and waits for it, so that their distance is the exchange itself
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(torch.cuda.current_stream())
-                    parts, work = _all_gather_words(buffer, size)
-                    work.wait()
-                    e1.record(torch.cuda.current_stream())
-                    log.append((e0, e1, buffer.numel() * buffer.element_size() * (size - 1)))
-                else:
-                    parts, work = _all_gather_words(buffer, size)
-                gathered[gi] = (parts, work, words, stride)
-                keep.append(buffer)
-
-    def payload_of(gi, l):
-        parts, _, words, stride = gathered[gi]
-        return parts[root[l]][slot[l] * stride:slot[l] * stride + words]
-
-    # 3. every rank runs its rows of every layer as the factors land, group by group.  A group goes through the
-    #    kernels as ONE batch when the backend can do that (run_round): the shards are R / G rows each, too few to
-    #    fill the chip alone.  Otherwise layer by layer, consecutive ones on alternating streams (their leaf chains
-    #    are latency-bound).
-    out = [None] * n_layers
-    if side:
-        for st in lstreams:
-            st.wait_stream(here)
-    # (batched rounds rotate over the loop streams across calls, like the factorisations above)
-    batched_rounds = getattr(backend, "_loop_rotation", 0) if side else 0
-    # one rank: consecutive full-height layers of one shape and kind share one loop (HipBackend.tall_stack at a time; a
-    # remainder goes through the same call with fewer): tall[first member] = the stack, tall[later member] = ()
-    tall = {}
-    if not exchange and hasattr(backend, "run_tall"):
-        per = min(int(backend.tall_stack), LOOP_LAYERS)
-        run, run_key = [], None
-        for l in [l for g in rounds for l in g] + [None]:
-            key = None if l is None or not backend.wants_tall_stack(layers[l]) else (tuple(layers[l]["W"].shape), _layer_kind(layers[l]))
-            if key != run_key or len(run) == per:
-                for m in run:
-                    tall[m] = run if m == run[0] else ()
-                run = []
-            run_key = key
-            if key is not None:
-                run.append(l)
-    for gi, members_g in enumerate(groups):
-        members = [l for g in members_g for l in rounds[g]]
-        lo, hi = row_range(layers[members[0]]["W"].shape[0], rank, size)
-        if exchange and hasattr(backend, "run_round") and backend.can_batch([layers[l] for l in members], lo, hi):
-            ls = lstreams[batched_rounds % len(lstreams)] if side else None
-            own = [l for l in members if l in stream_of]
-            if side and own and getattr(backend, "rounds_on_factor_streams", True):
-                # The round runs on the stream that factored this rank's layer of it: one stream fewer to pair badly.
-                # HIP multiplexes all streams of a process onto a few in-order hardware queues; a loop stream that shares
-                # its queue with the factor stream of the NEXT round puts that factorisation behind this round's loops and
-                # the pipeline collapses into factor -> loop -> factor (4.4 ... 7.0 ms per step at N = 8 depending on how
-                # the streams fell).
-                ls = stream_of[own[0]]
-            batched_rounds += 1
-            if side:
-                backend._loop_rotation = batched_rounds % len(lstreams)
-            if not join:
-                _guard_inputs([layers[l] for l in members], ls)
-            with on(ls):
-                parts, work = gathered[gi][:2]
-                work.wait()  # orders the stream behind the transfer; no host block on GPU
-                shards = backend.run_round([layers[l] for l in members], lo, hi, [payload_of(gi, l) for l in members])
-                if side:
-                    for t in parts:
-                        t.record_stream(ls)
-            for l, shard in zip(members, shards):
-                out[l] = shard
-            continue
-        for l in members:
-            if l in tall:
-                stack = tall[l]
-                if not stack:  # a later member: it went with the first
-                    continue
-                ls = lstreams[l % len(lstreams)] if side else None
-                if not join:
-                    _guard_inputs([layers[m] for m in stack], ls)
-                with on(ls):
-                    for m in stack:
-                        if ready[m] is not None:
-                            ls.wait_event(ready[m])  # behind EVERY member's factorisation
-                    for m, shard in zip(stack, backend.run_tall([layers[m] for m in stack], [factors[m] for m in stack])):
-                        out[m] = shard
-                    if side:  # made on the factor streams, read on this one
-                        for m in stack:
-                            for t in factors[m]:
-                                t.record_stream(ls)
-                continue
-            layer = layers[l]
-            ls = lstreams[l % len(lstreams)] if side else None
-            if not join:
-                _guard_inputs([layer], ls)
-            with on(ls):
-                if exchange:
-                    parts, work = gathered[gi][:2]
-                    work.wait()
-                    if factors[l] is None or always_exchange:
-                        factors[l] = backend.unpack(payload_of(gi, l), layer["H"].shape[0])
-                elif ready[l] is not None:
-                    ls.wait_event(ready[l])
-                lo, hi = row_range(layer["W"].shape[0], rank, size)
-                shard = backend.run_rows(layer, lo, hi, factors[l])
-                if side:  # made on a factor / comm stream, read on this one
-                    for t in factors[l]:
-                        t.record_stream(ls)
-                    if exchange:
-                        for t in gathered[gi][0]:
-                            t.record_stream(ls)
-            shard["info"] = factors[l][2]
-            out[l] = shard
-    if side:
-        if join:
-            for st in lstreams + fstreams:  # (batched rounds run on factor streams)
-                here.wait_stream(st)
-        # tensors made on the side streams are consumed on the caller's stream: keep the allocator honest
-        extra = [(p,) for p in keep if p is not None] + [tuple(g[0]) for g in gathered if g is not None]
-        for f in factors + extra:
-            for t in f or ():
-                t.record_stream(here)
-        for shard in out:
-            for t in shard.values():
-                if isinstance(t, torch.Tensor):
-                    t.record_stream(here)
-    return out
+    plan = _plan_stream(layers, backend, rank, size)
+    lanes = _Lanes(backend, join)
+    run = types.SimpleNamespace(layers=layers, backend=backend, plan=plan, lanes=lanes, factors=[None] * n_layers, ready=[None] * n_layers,
+                                stream_of={}, gathered=[None] * len(plan.groups), buffers=[], out=[None] * n_layers)
+    _factor_phase(run)
+    if plan.exchange:
+        _exchange_phase(run, comm_device)
+    _loop_phase(run)
+    lanes.join(lanes.loop + lanes.factor)  # (batched rounds run on factor streams)
+    # tensors made on the side streams are consumed on the caller's stream
+    lanes.moved([t for f in run.factors if f is not None for t in f] + [b for b in run.buffers if b is not None]
+                + [t for got in run.gathered if got is not None for t in got[0]] + [t for shard in run.out for t in shard.values()], lanes.here)
+    return run.out
 
 
 def verify_exchange(layers, backend, max_rounds=2):
@@ -1012,10 +1087,10 @@ def verify_exchange(layers, backend, max_rounds=2):
         return out
     rounds, root = plan_rounds(layers, size)
     for members in rounds[:max_rounds]:
-        words = max(backend.payload_words(layers[j]["H"].shape[0]) for j in members)
-        own = [l for l in members if root[l] == rank]
-        payload = backend.pack(backend.factorize(layers[own[0]]), words) if own else backend.alloc_payload(words, layers[0]["H"].device).zero_()
-        parts, work = _all_gather_words(payload, size)
+        # this rank's payload of the round and its all-gather, by the scheduler's own function (on the current stream)
+        factors = {l: backend.factorize(layers[l]) for l in members if root[l] == rank}
+        payload, (parts, work, words, _) = _exchange_group(layers, [members], root, rank, size, backend, _Lanes(), factors,
+                                                           dict.fromkeys(factors), layers[0]["H"].device)
         work.wait()
         weight = torch.arange(1, words + 1, dtype=torch.int64, device=payload.device)
 

@@ -19,7 +19,7 @@ import torch.multiprocessing as mp
 from sleekit_amd import dist as sdist
 
 
-class FakeBackend:
+class FakeBackend(sdist.Backend):
     def __init__(self):
         self.factored = []
 
@@ -155,6 +155,8 @@ class StatusBackend(FakeBatchBackend):
 
 class GroupingBackend(FakeBatchBackend):
     """+ the hooks that let quantize_stream take rounds of small layers in GROUPS (HipBackend.group_limit / factorize_many)."""
+
+    factor_chains = True
 
     def __init__(self, limit):
         super().__init__()

@@ -112,7 +112,7 @@ def test_plan_rounds_keeps_kinds_apart():
 
 
 def test_short_rounds_keep_kinds_apart():
-    class Backend:
+    class Backend(sdist.Backend):
         local_batch, short_rows = 8, 6144
 
     layers = _mixed(1024, 4096, copies=3)
@@ -124,7 +124,7 @@ def test_short_rounds_keep_kinds_apart():
 
 
 def test_group_rounds_keep_kinds_apart():
-    class Backend:
+    class Backend(sdist.Backend):
         def group_limit(self, layer, rows):
             return 64
 
