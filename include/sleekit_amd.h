@@ -90,7 +90,8 @@ typedef void *slk_stream_t;
  * activations: slk_mx_quantize_act4, slk_mx_gemm_a4 and slk_mx_rotate_quantize_act (likewise), then MXFP6 (E2M3)
  * activations: slk_mx_quantize_act6, slk_mx_dequantize_act6, slk_mx_gemm_a6 and slk_mx_rotate_quantize_act6 (likewise), then MXFP6
  * (E2M3) layers: slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6 and slk_mx_gemm_w6 (likewise), then the expert-grouped
- * product: slk_mx_experts_workspace_bytes and slk_mx_gemm_experts (likewise). */
+ * product: slk_mx_experts_workspace_bytes and slk_mx_gemm_experts (likewise), then the gated MLP: slk_mx_glu, slk_mx_gemm_glu
+ * and slk_mx_gemm_glu_experts (likewise). */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -673,6 +674,47 @@ size_t slk_mx_experts_workspace_bytes(int E, int M);
 int slk_mx_gemm_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
                         const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, int out_dtype,
                         void *out, int *flag, void *workspace, size_t ws_bytes, slk_stream_t stream);
+
+/* A gated MLP, down(act(gate(x)) * up(x)), between its two products.  The gate, all float32, every operation rounded once
+ * (no multiply contracted with an add), the same exp at every site:
+ *     g' = g > limit ? limit : g                          (a NaN passes through; limit = +inf: no clamp)
+ *     u' = u > limit ? limit : (u < -limit ? -limit : u)
+ *     s  = 1 / (1 + exp(-(alpha g')))
+ *     h  = (u' + shift) (g' s)
+ *   alpha = 1, limit = +inf, shift = 0: SwiGLU (Llama, Mixtral, Qwen); alpha = 1.702, limit = 7, shift = 1: gpt-oss.
+ *   `interleaved` says where gate and up of hidden column j are among 2 N columns (of Y) or rows (of the layer, of its bias):
+ *   0: gate j, up N + j;  1: gate 2 j, up 2 j + 1 (gpt-oss).
+ *
+ * slk_mx_glu: H (M x N, out_dtype) = h of Y (M x 2 N; float32, bfloat16 or float16 by x_dtype), the float32 h rounded once.
+ *
+ * slk_mx_gemm_glu: the product of a_codes / a_scales (M x K, format a_fmt, as slk_mx_quantize_act* writes them) with a layer of
+ *   2 N rows (w_codes, w_scales; w_fmt; the pairs of slk_mx_gemm_experts), + bias (2 N float32, may be NULL) in float32, the
+ *   gate, and the quantizer of a_fmt on h, in one launch: h_codes (M x N bits / 8) and h_scales (M x N / 32) are bit for bit
+ *   what slk_mx_gemm* to float32, slk_mx_glu to float32 and slk_mx_quantize_act* of that format write.  The gate and up sums
+ *   are slk_mx_gemm's to float32 bit for bit (M <= 64: its few-rows form, above: its many-rows form).  N % 32 == 0.
+ *   flag: DEVICE int that the CALLER zeroes; the call sets it to 1, and never clears it, when a block of h holds a NaN or an
+ *   infinity (the quantizers' rule).  Rows >= M and everything outside h_codes / h_scales of exactly these sizes are neither
+ *   read nor written.
+ *
+ * slk_mx_gemm_glu_experts: the same over rows sorted by expert (slk_mx_gemm_experts: offsets, workspace of
+ *   slk_mx_experts_workspace_bytes(E, M), the same prologue); w_codes E x 2 N x (K bits / 8), w_scales E x 2 N x K / 32, bias
+ *   E x 2 N.  flag: TWO device ints: flag[0] the offsets rule, written by the call; flag[1] the non-finite rule, zeroed by the
+ *   caller.  Offsets that break the rule leave h_codes and h_scales untouched.  Each expert's rows are bit for bit
+ *   slk_mx_gemm_glu of that slice.
+ *
+ * SLK_E_ARG, before any launch: M < 1, N no positive multiple of 32 (slk_mx_glu: N < 1), K as in slk_mx_gemm, a NULL pointer
+ *   other than bias, an unknown dtype, a_fmt or w_fmt, the refused pair, Y, H, a_codes, w_codes or h_codes off 16-byte
+ *   alignment, limit not above 0 (a NaN included), alpha or shift not finite, interleaved not 0 or 1, and for the experts
+ *   what slk_mx_gemm_experts refuses.                                                                                   */
+int slk_mx_glu(const void *Y, int x_dtype, int M, int N, float alpha, float limit, float shift, int interleaved, int out_dtype,
+               void *H, slk_stream_t stream);
+int slk_mx_gemm_glu(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                    const float *bias, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift,
+                    int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag, slk_stream_t stream);
+int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                            const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha,
+                            float limit, float shift, int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag,
+                            void *workspace, size_t ws_bytes, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

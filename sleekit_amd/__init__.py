@@ -1,6 +1,7 @@
 """sleekit_amd: MI355X-native GPTQ/OBQ layer quantization behind the sleekit function surface.
 
     from sleekit_amd import obq, scaling, codebook, groups, packing, mx, rotation, Sleekit, MXLinear, MXExperts, PackedLinear
+    from sleekit_amd import MXGatedMLP, MXExpertsMLP
     from sleekit_amd import Rotation, RotatedLinear
 
 mirrors `sleekit.obq`, `sleekit.scaling`, `sleekit.codebook` and `sleekit.Sleekit` of
@@ -23,7 +24,7 @@ def __getattr__(name):
         return importlib.import_module(f"{__name__}.{name}")
     if name == "Sleekit":
         return importlib.import_module(f"{__name__}.statistics").Sleekit
-    if name in ("MXLinear", "MXExperts"):
+    if name in ("MXLinear", "MXExperts", "MXGatedMLP", "MXExpertsMLP"):
         return getattr(importlib.import_module(f"{__name__}.mx"), name)
     if name == "PackedLinear":
         return importlib.import_module(f"{__name__}.packing").PackedLinear

@@ -137,6 +137,11 @@ PROTOTYPES = {
     "slk_mx_gemm_w6": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "slk_mx_experts_workspace_bytes": (c_size_t, [c_int, c_int]),
     "slk_mx_gemm_experts": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "slk_mx_glu": (c_int, [P, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_int, P, P]),
+    "slk_mx_gemm_glu": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, P, P, P, P]),
+    "slk_mx_gemm_glu_experts": (
+        c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, P, P, P, P, c_size_t, P],
+    ),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

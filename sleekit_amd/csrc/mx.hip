@@ -5,6 +5,7 @@
 //   a layer:      slk_mx_scale_search, slk_mx_pack, slk_mx_unpack (E2M1); slk_mx_scale_search6, _pack6, _unpack6 (E2M3)
 //   activations:  slk_mx_quantize_act (E4M3), _act4 (E2M1), _act6 (E2M3)
 //   either, back: slk_mx_dequantize (E2M1), slk_mx_dequantize_act (E4M3), _act6 (E2M3): one kernel, whatever wrote the codes
+//   between two layers of a gated MLP: slk_mx_glu, the gate (mxglu.h) over a (M, 2 N) matrix, elementwise
 //
 // n % 32 == 0, so block k of the (R, n) layer is elements [32 k, 32 k + 32) of the flat array whatever the row: every
 // kernel here runs over the R n / 32 blocks (64-bit counts) and only the diagonal of H needs a block's place in its row.
@@ -15,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mxglu.h"
 #include "mxquant.h"
 
 namespace slk {
@@ -196,9 +198,7 @@ __device__ __forceinline__ float act_f32<_Float16>(_Float16 x) { return (float)x
 // store as whole dwords at a 6-byte stride, so E2M3 takes two: 12 bytes a lane, three dwords at a 12-byte stride, every one
 // of them aligned (a row is 24 bytes a block; DESIGN.md section 20 has this shape measured against a lane a block).
 // A NaN or an infinity has the largest magnitude bits of its block, so the integer maximum finds it and raises the flag.
-template <int FMT>
-__host__ __device__ constexpr int mxq_lanes() { return FMT == MXA_E2M3 ? 2 : 4; }
-
+// (mxq_lanes, the lanes a block of each format, is mxquant.h's: the fused product's epilogue re-reads its tile in this shape.)
 template <class T, int FMT, int LPB>
 __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X, size_t blocks, uint8_t *__restrict__ codes,
                                                          uint8_t *__restrict__ E, int *__restrict__ flag) {
@@ -240,6 +240,42 @@ __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X
         }
     }
     if (bad) *flag = 1;
+}
+
+// ---------------------------------------------------------------- the gate, elementwise
+// H (M, N) = mx_glu(gate, up) of Y (M, 2 N): VEC hidden columns a thread (4 where N % 4 == 0, so that every piece is one
+// aligned vector: 16 bytes of float32, 8 of a 16-bit type), a unit a step, a whole grid apart.  Not interleaved, a thread reads
+// VEC gates at column j and VEC ups at N + j; interleaved, the 2 VEC consecutive elements from column 2 j, gate first.
+template <class T, int OUT, int VEC>
+__global__ __launch_bounds__(256) void k_mx_glu(const T *__restrict__ Y, size_t units, int N, const GluParams p,
+                                                typename PkOut<OUT>::T *__restrict__ H) {
+    typedef typename PkOut<OUT>::T O;
+    typedef T VI __attribute__((ext_vector_type(VEC)));
+    typedef O VO __attribute__((ext_vector_type(VEC)));
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    const size_t per_row = (size_t)N / VEC;
+    for (size_t i = gid; i < units; i += threads) {
+        const size_t m = i / per_row, j = (i - m * per_row) * VEC;
+        const T *row = Y + m * 2 * (size_t)N;
+        float g[VEC], u[VEC];
+        if (p.interleaved) {
+            const VI v0 = *reinterpret_cast<const VI *>(row + 2 * j), v1 = *reinterpret_cast<const VI *>(row + 2 * j + VEC);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const T a = 2 * e < VEC ? v0[(2 * e) % VEC] : v1[(2 * e) % VEC];
+                const T b = 2 * e + 1 < VEC ? v0[(2 * e + 1) % VEC] : v1[(2 * e + 1) % VEC];
+                g[e] = act_f32<T>(a), u[e] = act_f32<T>(b);
+            }
+        } else {
+            const VI vg = *reinterpret_cast<const VI *>(row + j), vu = *reinterpret_cast<const VI *>(row + N + j);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) g[e] = act_f32<T>(vg[e]), u[e] = act_f32<T>(vu[e]);
+        }
+        VO o;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) o[e] = PkOut<OUT>::cvt(mx_glu(g[e], u[e], p));
+        *reinterpret_cast<VO *>(H + m * (size_t)N + j) = o;
+    }
 }
 
 // ---------------------------------------------------------------- de-quantize
@@ -393,6 +429,37 @@ static int mx_dequantize(const char *name, const uint8_t *codes, const uint8_t *
 }
 
 extern "C" {
+
+int slk_mx_glu(const void *Y, int x_dtype, int M, int N, float alpha, float limit, float shift, int interleaved, int out_dtype, void *H,
+               slk_stream_t stream) {
+    SLK_REQUIRE(M > 0 && N > 0, "M and N must be at least 1 (M = %d, N = %d)", M, N);
+    SLK_REQUIRE(N <= 0x3fffffff, "Y has 2 N columns: N must be below 2^30 (N = %d)", N);
+    SLK_REQUIRE(known_dtype(x_dtype), "unknown x_dtype %d", x_dtype);
+    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
+    SLK_REQUIRE(Y && H, "null pointer");
+    SLK_REQUIRE(aligned16(Y) && aligned16(H), "Y and H must be aligned to 16 bytes");
+    SLK_REQUIRE(limit > 0.0f, "limit must be above 0, +inf meaning no clamp (limit = %g)", (double)limit);
+    SLK_REQUIRE(glu_finite(alpha) && glu_finite(shift), "alpha and shift must be finite (alpha = %g, shift = %g)", (double)alpha, (double)shift);
+    SLK_REQUIRE(interleaved == 0 || interleaved == 1, "interleaved must be 0 or 1 (got %d)", interleaved);
+    hipStream_t s = as_stream(stream);
+    const GluParams p = {alpha, limit, shift, interleaved};
+    return with_dtype(x_dtype, [&](auto ti) -> int {
+        typedef typename decltype(ti)::T T;
+        return with_dtype(out_dtype, [&](auto to) -> int {
+            typedef typename decltype(to)::T O;
+            constexpr int OUT = decltype(to)::OUT;
+            const double bytes = (double)M * N * (2.0 * sizeof(T) + sizeof(O));
+            if (N % 4 == 0) {
+                const size_t units = (size_t)M * N / 4;
+                SLK_RUN("mx_glu", 0, bytes, s, (k_mx_glu<T, OUT, 4><<<mx_grid(units, 1), 256, 0, s>>>(static_cast<const T *>(Y), units, N, p, static_cast<O *>(H))));
+            } else {
+                const size_t units = (size_t)M * N;
+                SLK_RUN("mx_glu", 0, bytes, s, (k_mx_glu<T, OUT, 1><<<mx_grid(units, 1), 256, 0, s>>>(static_cast<const T *>(Y), units, N, p, static_cast<O *>(H))));
+            }
+            return SLK_OK;
+        });
+    });
+}
 
 int slk_mx_scale_search(const float *W, const float *hdiag, int mode, int R, int n, uint8_t *scales, float *S, slk_stream_t stream) {
     return mx_scale_search<MXA_E2M1>("mx_scale_search", W, hdiag, mode, R, n, scales, S, stream);

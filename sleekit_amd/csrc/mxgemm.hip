@@ -1,6 +1,8 @@
 // The product of a linear layer in a packed MX form on the block-scaled MFMA, and that product over the experts of a
 // mixture-of-experts layer (slk_mx_gemm, _a4, _a6, _w6, slk_mx_gemm_experts; the formats are pinned in include/sleekit_amd.h
-// and INTEGRATION.md).  Nothing here converts: the kernels that write and read back these forms are mx.hip's.
+// and INTEGRATION.md).  Nothing here converts: the kernels that write and read back these forms are mx.hip's.  The one
+// exception is the fused gate/up product of a gated MLP (slk_mx_gemm_glu, _experts), whose epilogue ends in the plain
+// quantizer's own functions (mxquant.h) and writes the next layer's activations.
 //
 // Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns -- or, for
 // an MXFP6 layer (slk_mx_gemm_w6), as slk_mx_pack6 left them: E2M3 codes, 24 bytes a block.
@@ -23,6 +25,7 @@
 // The stored forms feed the instruction with plain loads (16 bytes a piece; three of 8 for E2M3): no shuffle, no pre-swizzle, no LDS.
 // D: lane l holds column l & 15, rows 4 (l >> 4) + 0 .. 3.
 #include "common.h"
+#include "mxglu.h"
 #include "mxquant.h"
 
 namespace slk {
@@ -233,6 +236,178 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
     mx_gemm_tiled_tile<OUT, AF, WF>(Ac, As, Wc, Ws, bias, blockIdx.y * 64, M, blockIdx.x * 64, N, K, Y);
 }
 
+// ---------------------------------------------------------------- the fused gate/up product of a gated MLP
+// slk_mx_gemm_glu: A against a layer of 2 N rows, gate and up, and instead of Y (M, 2 N) the next layer's activations:
+// h = mx_glu(gate + bias, up + bias) (mxglu.h), quantized per (row, block of 32 hidden columns) to A's own format exactly as
+// the plain quantizer of mx.hip would have done it -- the integer maximum of the magnitude bits, mxa_scale_byte, mxa_pack
+// with mxa_inverse, mxa_store, the scale byte.  Every accumulator keeps the order over K of the kernels above (the split-K
+// form: wave w the steps w, w + SK, ..., two in flight, wave 0 adds in wave order; the tiled form: the steps in order), so the
+// gate and up sums are slk_mx_gemm's float32 values bit for bit, and the codes are those of the three-step route
+// slk_mx_gemm to float32, slk_mx_glu to float32, slk_mx_quantize_act*.
+//
+// A block of h must lie inside one workgroup.  The accumulator layout (lane l: column l & 15, rows 4 (l >> 4) + 0 .. 3) is
+// not the packer's (contiguous elements a lane), so the float32 tile of h goes through LDS: rows of GLU_LD = 36 floats (the
+// pad keeps a row on 16 bytes for the re-read in 16-byte pieces; a 32-lane group's dword stores fall on 32 distinct banks:
+// lanes of q = 0 on 0 .. 15, of q = 1 on 4 * 36 % 32 + 0 .. 15), re-read in the quantizer's lane shape, mxq_lanes lanes a block.
+constexpr int GLU_LD = 36;
+
+// One MFMA tile of gate and up sums -> h in the staged tile: rows r0 .. r0 + 3, column c.
+__device__ __forceinline__ void glu_stage(float *__restrict__ tile, v4f g, v4f u, const float *__restrict__ bias, int gate, int up, int r0,
+                                          int c, const GluParams p) {
+    const float bg = bias ? bias[gate] : 0.0f, bu = bias ? bias[up] : 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tile[(r0 + r) * GLU_LD + c] = mx_glu(bias ? g[r] + bg : g[r], bias ? u[r] + bu : u[r], p);
+}
+// The staged ROWS x 32 tile -> codes and scale bytes of hidden block `blk` of rows row0 .. (below `rows`), by one wave:
+// k_mx_quantize_act's body.  Returns whether a live block holds a NaN or an infinity.
+template <int AF, int ROWS>
+__device__ __forceinline__ bool glu_quantize_tile(const float *__restrict__ tile, int lane, int row0, int rows, int N, int blk, bool blk_live,
+                                                  uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs) {
+    constexpr int LPB = mxq_lanes<AF>(), EPL = 32 / LPB, BYTES = EPL * mxa_bits<AF>() / 8;
+    bool bad = false;
+#pragma unroll
+    for (int i0 = 0; i0 < ROWS * LPB; i0 += 64) {  // (every lane of a block takes the round: 64 is a multiple of LPB)
+        const int i = i0 + lane, r = i / LPB, piece = i % LPB, m = row0 + r;
+        const bool staged = r < ROWS, live = staged && blk_live && m < rows;
+        float x[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) x[e] = staged ? tile[r * GLU_LD + piece * EPL + e] : 0.0f;
+        int top = 0;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) top = max(top, (int)(__float_as_uint(x[e]) & 0x7fffffffu));
+        top = max(top, dpp_i<DPP_XOR1>(top));
+        if constexpr (LPB == 4) top = max(top, dpp_i<DPP_XOR2>(top));
+        bad |= live && top >= 0x7f800000;
+        const unsigned eb = mxa_scale_byte<AF>(top);
+        unsigned w[BYTES / 4];
+        mxa_pack<AF>(x, mxa_inverse(eb), w);
+        if (live) {
+            mxa_store<AF, EPL>(Hc + (size_t)m * mxa_byte_of<AF>((size_t)N) + (size_t)blk * (4 * mxa_bits<AF>()) + piece * BYTES, w);
+            if (piece == 0) Hs[(size_t)m * (N / 32) + blk] = (uint8_t)eb;
+        }
+    }
+    return bad;
+}
+
+// Few rows: a workgroup is 16 rows x one block of 32 hidden columns -- four accumulators a wave, gate and up times two
+// 16-column tiles -- and each A fragment meets four B fragments.  (row0 / rows as in mx_gemm_splitk_tile; blk the block.)
+template <int AF, int WF>
+__device__ __forceinline__ void mx_gemm_glu_splitk_tile(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                        const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                        const float *__restrict__ bias, int row0, int rows, int blk, int N, int K,
+                                                        const GluParams p, uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs,
+                                                        int *__restrict__ flag) {
+    __shared__ v4f part[MXG_SK - 1][4][64];
+    __shared__ float tile[16 * GLU_LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bpr = K / 32, steps = (bpr + 3) / 4;
+    const int m = row0 + (lane & 15), q = lane >> 4;
+    int wrow[4];  // the layer's rows of this lane's column: gate and up of tile 0, gate and up of tile 1
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int j = 32 * blk + 16 * t + (lane & 15);  // (N % 32 == 0: every hidden column of the block exists)
+        wrow[2 * t] = glu_gate_of(j, N, p.interleaved), wrow[2 * t + 1] = glu_up_of(j, N, p.interleaved);
+    }
+    v4f acc[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[c] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = wave; s < steps; s += 2 * MXG_SK) {  // two steps' loads in flight; a step past the end loads zeros
+        const FragA<AF> a0 = load_a<AF>(Ac, As, m, rows, s, q, bpr), a1 = load_a<AF>(Ac, As, m, rows, s + MXG_SK, q, bpr);
+        FragB<WF> b0[4], b1[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            b0[c] = load_b<WF>(Wc, Ws, wrow[c], 2 * N, 4 * s + q, bpr);
+            b1[c] = load_b<WF>(Wc, Ws, wrow[c], 2 * N, 4 * (s + MXG_SK) + q, bpr);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = mx_mfma<AF, WF>(a0, b0[c], acc[c]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = mx_mfma<AF, WF>(a1, b1[c], acc[c]);
+    }
+    if (wave) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) part[wave - 1][c][lane] = acc[c];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int w = 0; w < MXG_SK - 1; ++w) acc[c] += part[w][c][lane];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) glu_stage(tile, acc[2 * t], acc[2 * t + 1], bias, wrow[2 * t], wrow[2 * t + 1], 4 * q, 16 * t + (lane & 15), p);
+    }
+    __syncthreads();
+    if (wave == 0 && glu_quantize_tile<AF, 16>(tile, lane, row0, rows, N, blk, true, Hc, Hs)) *flag = 1;
+}
+template <int AF, int WF>
+__global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_glu_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                    const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                    const float *__restrict__ bias, int M, int N, int K, const GluParams p,
+                                                                    uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag) {
+    mx_gemm_glu_splitk_tile<AF, WF>(Ac, As, Wc, Ws, bias, blockIdx.y * 16, M, blockIdx.x, N, K, p, Hc, Hs, flag);
+}
+
+// Many rows: a wave keeps its 32 x 32 tile of h, one block a row, as eight accumulators -- gate and up times 2 x 2 -- and the
+// four waves of a workgroup cover 64 x 64.  N % 32 == 0, so a wave's block is whole or past the end; a wave past the end
+// loads zeros, stores nothing and keeps the barrier.
+template <int AF, int WF>
+__device__ __forceinline__ void mx_gemm_glu_tiled_tile(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                       const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                       const float *__restrict__ bias, int row0, int rows, int col0, int N, int K,
+                                                       const GluParams p, uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs,
+                                                       int *__restrict__ flag) {
+    __shared__ float tile[4][32 * GLU_LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bpr = K / 32, steps = (bpr + 3) / 4;
+    const int m0 = row0 + (wave >> 1) * 32, n0 = col0 + (wave & 1) * 32, q = lane >> 4;
+    const bool blk_live = n0 < N;
+    int wrow[2][2];  // [gate, up][column tile]: the layer's row, or 2 N (no row: zeros) past the end
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = n0 + 16 * j + (lane & 15);
+        wrow[0][j] = blk_live ? glu_gate_of(col, N, p.interleaved) : 2 * N;
+        wrow[1][j] = blk_live ? glu_up_of(col, N, p.interleaved) : 2 * N;
+    }
+    v4f acc[2][2][2];  // [gate, up][row tile][column tile]
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[h][i][j] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = 0; s < steps; ++s) {
+        FragA<AF> a[2];
+        FragB<WF> b[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            a[i] = load_a<AF>(Ac, As, m0 + 16 * i + (lane & 15), rows, s, q, bpr);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) b[h][i] = load_b<WF>(Wc, Ws, wrow[h][i], 2 * N, 4 * s + q, bpr);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[h][i][j] = mx_mfma<AF, WF>(a[i], b[h][j], acc[h][i][j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            glu_stage(tile[wave], acc[0][i][j], acc[1][i][j], blk_live ? bias : nullptr, wrow[0][j], wrow[1][j], 16 * i + 4 * q, 16 * j + (lane & 15), p);
+    __syncthreads();
+    if (glu_quantize_tile<AF, 32>(tile[wave], lane, m0, rows, N, n0 / 32, blk_live, Hc, Hs)) *flag = 1;
+}
+template <int AF, int WF>
+__global__ __launch_bounds__(256) void k_mx_gemm_glu_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                           const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                           const float *__restrict__ bias, int M, int N, int K, const GluParams p,
+                                                           uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag) {
+    mx_gemm_glu_tiled_tile<AF, WF>(Ac, As, Wc, Ws, bias, blockIdx.y * 64, M, blockIdx.x * 64, N, K, p, Hc, Hs, flag);
+}
+
 // ---------------------------------------------------------------- a mixture-of-experts layer in one call
 // slk_mx_gemm_experts: the rows of A are sorted by expert and `offsets` (device memory, E + 1 ints) says where each expert's
 // rows begin.  The host never reads it.  k_mx_expert_tiles, one workgroup, checks the offsets and turns them into two
@@ -328,6 +503,29 @@ __global__ __launch_bounds__(256) void k_mx_gemm_experts_tiled(const uint8_t *__
     mx_gemm_tiled_tile<OUT, AF, WF>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x * 64, N, K, Y);
 }
 
+// ... and of the fused gate/up product: the layers have 2 N rows and the biases 2 N entries an expert
+template <int AF, int WF>
+__global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_glu_experts_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                            const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                            const float *__restrict__ bias, const int *__restrict__ count,
+                                                                            const int *__restrict__ table, int N, int K, const GluParams p,
+                                                                            uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs,
+                                                                            int *__restrict__ flag) {
+    if ((int)blockIdx.y >= *count) return;
+    const ExpertTile<WF> x(table, Wc, Ws, bias, 2 * N, K);
+    mx_gemm_glu_splitk_tile<AF, WF>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x, N, K, p, Hc, Hs, flag);
+}
+template <int AF, int WF>
+__global__ __launch_bounds__(256) void k_mx_gemm_glu_experts_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                   const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                   const float *__restrict__ bias, const int *__restrict__ count,
+                                                                   const int *__restrict__ table, int N, int K, const GluParams p,
+                                                                   uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag) {
+    if ((int)blockIdx.y >= *count) return;
+    const ExpertTile<WF> x(table, Wc, Ws, bias, 2 * N, K);
+    mx_gemm_glu_tiled_tile<AF, WF>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x * 64, N, K, p, Hc, Hs, flag);
+}
+
 }  // namespace slk
 
 using namespace slk;
@@ -388,7 +586,105 @@ static int mx_gemm_experts(const char *name, const uint8_t *a_codes, const uint8
     });
 }
 
+// slk_mx_gemm_glu and slk_mx_gemm_glu_experts: what the two share of their argument lists
+#define SLK_GLU_REQUIRE()                                                                                                                     \
+    SLK_REQUIRE(M > 0 && N >= 32 && N % 32 == 0, "a block of h is 32 hidden columns: N must be a positive multiple of 32 (M = %d, N = %d)", M, N); \
+    SLK_REQUIRE(N <= 0x3fffffff, "the layer has 2 N rows: N must be below 2^30 (N = %d)", N);                                               \
+    SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);                        \
+    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP4 || a_fmt == SLK_MX_ACT_FP6, "unknown a_fmt %d", a_fmt);                   \
+    SLK_REQUIRE(w_fmt == SLK_MX_W_FP4 || w_fmt == SLK_MX_W_FP6, "unknown w_fmt %d", w_fmt);                                                  \
+    SLK_REQUIRE(!(w_fmt == SLK_MX_W_FP6 && a_fmt == SLK_MX_ACT_FP4),                                                                         \
+                "an MXFP6 layer takes MXFP8 (SLK_MX_ACT_FP8) or MXFP6 (SLK_MX_ACT_FP6) activations (a_fmt = %d)", a_fmt);                    \
+    SLK_REQUIRE(a_codes && a_scales && w_codes && w_scales && h_codes && h_scales, "null pointer");                                          \
+    SLK_REQUIRE(flag, "null flag");                                                                                                          \
+    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(h_codes), "a_codes, w_codes and h_codes must be aligned to 16 bytes"); \
+    SLK_REQUIRE(limit > 0.0f, "limit must be above 0, +inf meaning no clamp (limit = %g)", (double)limit);                                   \
+    SLK_REQUIRE(glu_finite(alpha) && glu_finite(shift), "alpha and shift must be finite (alpha = %g, shift = %g)", (double)alpha, (double)shift); \
+    SLK_REQUIRE(interleaved == 0 || interleaved == 1, "interleaved must be 0 or 1 (got %d)", interleaved)
+
+// the format pair of (a_fmt, w_fmt), checked, as template arguments: CALL(AF, WF, name suffix)
+#define SLK_GLU_PAIRS(CALL)                                          \
+    if (w_fmt == SLK_MX_W_FP6) {                                     \
+        if (a_fmt == SLK_MX_ACT_FP6) CALL(MXA_E2M3, MXA_E2M3, "_w6a6"); \
+        CALL(MXA_E4M3, MXA_E2M3, "_w6");                             \
+    }                                                                \
+    if (a_fmt == SLK_MX_ACT_FP4) CALL(MXA_E2M1, MXA_E2M1, "_a4");    \
+    if (a_fmt == SLK_MX_ACT_FP6) CALL(MXA_E2M3, MXA_E2M1, "_a6");    \
+    CALL(MXA_E4M3, MXA_E2M1, "")
+
+template <int AF, int WF>
+static int mx_gemm_glu(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                       const float *bias, int M, int N, int K, const GluParams p, uint8_t *h_codes, uint8_t *h_scales, int *flag, hipStream_t s) {
+    const double flops = 4.0 * M * N * K;
+    const double bytes = ((double)M * mxa_block_bytes<AF>() + 2.0 * N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * mxa_block_bytes<AF>() * N / 32.0;
+    if (M <= MXG_SPLIT_MAX_M) {
+        const dim3 grid(N / 32, (M + 15) / 16);
+        SLK_RUN(name, flops, bytes, s,
+                (k_mx_gemm_glu_splitk<AF, WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
+    } else {
+        const dim3 grid((N + 63) / 64, (M + 63) / 64);
+        SLK_RUN(name, flops, bytes, s,
+                (k_mx_gemm_glu_tiled<AF, WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
+    }
+    return SLK_OK;
+}
+
+// mx_gemm_experts' three launches with the fused tile bodies; flag[0] is the prologue's, flag[1] the non-finite rule's
+template <int AF, int WF>
+static int mx_gemm_glu_experts(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                               const float *bias, const int *offsets, int E, int M, int N, int K, const GluParams p, uint8_t *h_codes,
+                               uint8_t *h_scales, int *flag, int *ws, hipStream_t s) {
+    const int cap16 = (int)mxe_cap16(E, M), cap64 = (int)mxe_cap64(E, M);
+    const int rows16 = cap16 < 4 * E ? cap16 : 4 * E, rows64 = cap64;
+    SLK_RUN("mx_expert_tiles", 0, 4.0 * (E + 1), s, (k_mx_expert_tiles<<<1, 256, 0, s>>>(offsets, E, M, ws, cap16, flag)));
+    const int *t16 = ws + MXE_HEAD, *t64 = ws + MXE_HEAD + 3 * (size_t)cap16;
+    const double flops = 4.0 * M * N * K;
+    const double bytes = ((double)M * mxa_block_bytes<AF>() + 2.0 * E * N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * mxa_block_bytes<AF>() * N / 32.0;
+    const dim3 grid16(N / 32, rows16), grid64((N + 63) / 64, rows64);
+    SLK_RUN(name, flops, bytes, s,
+            (k_mx_gemm_glu_experts_splitk<AF, WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, t16, N, K, p, h_codes,
+                                                                                 h_scales, flag + 1)));
+    if (M > MXG_SPLIT_MAX_M)
+        SLK_RUN(name, 0, 0, s,
+                (k_mx_gemm_glu_experts_tiled<AF, WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, t64, N, K, p, h_codes,
+                                                                            h_scales, flag + 1)));
+    return SLK_OK;
+}
+
 extern "C" {
+
+int slk_mx_gemm_glu(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias, int M,
+                    int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift, int interleaved, uint8_t *h_codes,
+                    uint8_t *h_scales, int *flag, slk_stream_t stream) {
+    SLK_GLU_REQUIRE();
+    SLK_REQUIRE((M + 63) / 64 <= 65535, "M is above the 65535 row tiles of one launch (M = %d)", M);
+    SLK_REQUIRE(N / 32 <= 0x7fffffff / 64, "N is above the column tiles of one launch (N = %d)", N);
+    hipStream_t s = as_stream(stream);
+    const GluParams p = {alpha, limit, shift, interleaved};
+#define SLK_GLU_PAIR(AF, WF, SUFFIX) return mx_gemm_glu<AF, WF>("mx_gemm_glu" SUFFIX, a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag, s)
+    SLK_GLU_PAIRS(SLK_GLU_PAIR);
+#undef SLK_GLU_PAIR
+}
+
+int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
+                            const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift,
+                            int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag, void *workspace, size_t ws_bytes,
+                            slk_stream_t stream) {
+    SLK_REQUIRE(E >= 1 && E <= MXE_MAX_EXPERTS, "E must be 1 .. %d experts (E = %d)", MXE_MAX_EXPERTS, E);
+    SLK_GLU_REQUIRE();
+    SLK_REQUIRE(offsets, "null offsets");
+    SLK_REQUIRE(workspace && (uintptr_t)workspace % sizeof(int) == 0, "the workspace must be non-null and aligned to 4 bytes");
+    SLK_REQUIRE(ws_bytes >= slk_mx_experts_workspace_bytes(E, M), "the workspace is too small: %zu bytes, slk_mx_experts_workspace_bytes(%d, %d) = %zu",
+                ws_bytes, E, M, slk_mx_experts_workspace_bytes(E, M));
+    SLK_REQUIRE(mxe_cap64(E, M) <= 65535, "M / 64 + E is above the 65535 row tiles of one launch (M = %d, E = %d)", M, E);
+    hipStream_t s = as_stream(stream);
+    int *ws = static_cast<int *>(workspace);
+    const GluParams p = {alpha, limit, shift, interleaved};
+#define SLK_GLU_PAIR(AF, WF, SUFFIX) \
+    return mx_gemm_glu_experts<AF, WF>("mx_gemm_glu_experts" SUFFIX, a_codes, a_scales, w_codes, w_scales, bias, offsets, E, M, N, K, p, h_codes, h_scales, flag, ws, s)
+    SLK_GLU_PAIRS(SLK_GLU_PAIR);
+#undef SLK_GLU_PAIR
+}
 
 size_t slk_mx_experts_workspace_bytes(int E, int M) {
     if (E < 1 || M < 1) return 0;

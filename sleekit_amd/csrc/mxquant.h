@@ -183,6 +183,11 @@ __device__ __forceinline__ void mxa_pack(const float (&x)[N], float inv, unsigne
     for (int e = 0; e < N; ++e) mxa_put<FMT>(w, e, mxa_code<FMT>(x[e], inv));
 }
 
+// Lanes a block in a quantizer: each lane's codes must be whole dwords, so 8 elements a lane for E4M3 and E2M1 and 16 for E2M3
+// (mx.hip, k_mx_quantize_act).
+template <int FMT>
+__host__ __device__ constexpr int mxq_lanes() { return FMT == MXA_E2M3 ? 2 : 4; }
+
 // One lane's words in memory: one, two or four of them move as one aligned vector, three (16 E2M3 codes: 12 bytes of a
 // row whose blocks are 24) as Codes12, three dwords, every one of them aligned.
 struct alignas(4) Codes12 {

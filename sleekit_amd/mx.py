@@ -92,6 +92,13 @@ rows are bit for bit matmul_mx of that slice.  Every format pair of matmul_mx is
     y = experts.forward_tokens(x, expert_ids, gates)           # x (T, K), expert_ids and gates (T, k) -> (T, N)
     order, offsets = sort_by_expert(expert_ids, E);  Y = linear_mx_experts(x[order // k], codes, scales, offsets, bias)
 
+GATED MLP.  down(act(gate(x)) * up(x)) in three launches: the up layer holds gate and up (2 N rows), and the fused product
+(slk_mx_gemm_glu) applies the gate in float32 and writes h as the down layer's a_codes / a_scales -- the section "gated MLP"
+at the end of this file has the gate, the two layouts and the calls.
+    h_codes, h_scales = matmul_mx_glu(a_codes, a_scales, up_codes, up_scales, up_bias)      # (M, N bits / 8), (M, N / 32)
+    y = gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales);  y = MXGatedMLP(up, down)(x)
+    y = MXExpertsMLP(up_experts, down_experts).forward_tokens(x, expert_ids, gates)
+
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
 everything runs on the GPU on the current stream, and there is no CPU fallback.
 """
@@ -824,6 +831,30 @@ def sort_by_expert(expert_ids, E):
     return dev.like_input(order, expert_ids), dev.like_input(offsets, expert_ids)
 
 
+def _route_tokens(x, expert_ids, gates, num_experts, out_features, run):
+    """What MXExperts.forward_tokens and MXExpertsMLP.forward_tokens share: the T k rows x[order // k] sorted by expert,
+    run(rows, offsets, also) -- a grouped layer or MLP on sorted rows, which reads `also` (the id check) together with its own
+    flags -- the gather back into (T, k) order, and the gate-weighted float32 sum in the order j = 0, 1, ..., k - 1."""
+    T, _ = _matrix(x, "x", _ACT)
+    if not isinstance(expert_ids, (np.ndarray, torch.Tensor)) or expert_ids.ndim != 2 or expert_ids.shape[0] != T or expert_ids.shape[1] < 1:
+        raise ValueError(f"expert_ids must be ({T}, k) for x of {T} rows; got {tuple(getattr(expert_ids, 'shape', ()))}")
+    k = int(expert_ids.shape[1])
+    if gates is not None and (not isinstance(gates, (np.ndarray, torch.Tensor)) or tuple(gates.shape) != (T, k)):
+        raise ValueError(f"gates must be ({T}, {k}); got {tuple(getattr(gates, 'shape', ()))}")
+    ids = _expert_ids(expert_ids, num_experts)
+    order, offsets, bad = _sorted_by_expert(ids, num_experts)
+    Xd = dev.to_device(x, _torch_dtype(x))
+    y = run(Xd[order // k], offsets, ((bad, _ids_message(num_experts)),))
+    back = torch.empty_like(order)
+    back[order] = torch.arange(order.numel(), device=order.device)
+    y = y[back].reshape(T, k, out_features).float()
+    g = None if gates is None else dev.to_device(gates, torch.float32)
+    total = y[:, 0] if g is None else y[:, 0] * g[:, 0:1]
+    for j in range(1, k):
+        total = total + (y[:, j] if g is None else y[:, j] * g[:, j:j + 1])
+    return dev.like_input(total.to(_torch_dtype(x)), x)
+
+
 class MXExperts(_MXModule):
     """The experts of a mixture-of-experts layer kept in their packed MX form: buffers `codes` (E, N, K bits / 8), `scales`
     (E, N, K / 32) and `bias` (E, N) float32 or None; `activations` and `weights` are extra state as in MXLinear.
@@ -880,25 +911,10 @@ class MXExperts(_MXModule):
         (sort_by_expert's order and offsets, on the device), run through forward, put back in (T, k) order by a gather, and
         added up in float32 in the order j = 0, 1, ..., k - 1 (product, then sum: no atomics, no index_add_), so a repeated
         call gives the same bits.  The id check and the product's two flags are read together: one wait for the stream."""
-        T, _ = _matrix(x, "x", _ACT)
-        if not isinstance(expert_ids, (np.ndarray, torch.Tensor)) or expert_ids.ndim != 2 or expert_ids.shape[0] != T or expert_ids.shape[1] < 1:
-            raise ValueError(f"expert_ids must be ({T}, k) for x of {T} rows; got {tuple(getattr(expert_ids, 'shape', ()))}")
-        k = int(expert_ids.shape[1])
-        if gates is not None and (not isinstance(gates, (np.ndarray, torch.Tensor)) or tuple(gates.shape) != (T, k)):
-            raise ValueError(f"gates must be ({T}, {k}); got {tuple(getattr(gates, 'shape', ()))}")
-        ids = _expert_ids(expert_ids, self.num_experts)
-        order, offsets, bad = _sorted_by_expert(ids, self.num_experts)
-        Xd = dev.to_device(x, _torch_dtype(x))
-        y = _linear_experts(Xd[order // k], self.codes, self.scales, offsets, self.bias, None, self.activations, rotation,
-                            _WEIGHTS[self.weights], also=((bad, _ids_message(self.num_experts)),))
-        back = torch.empty_like(order)
-        back[order] = torch.arange(order.numel(), device=order.device)
-        y = y[back].reshape(T, k, self.out_features).float()
-        g = None if gates is None else dev.to_device(gates, torch.float32)
-        total = y[:, 0] if g is None else y[:, 0] * g[:, 0:1]
-        for j in range(1, k):
-            total = total + (y[:, j] if g is None else y[:, j] * g[:, j:j + 1])
-        return dev.like_input(total.to(_torch_dtype(x)), x)
+        def run(rows, offsets, also):
+            return _linear_experts(rows, self.codes, self.scales, offsets, self.bias, None, self.activations, rotation, _WEIGHTS[self.weights], also=also)
+
+        return _route_tokens(x, expert_ids, gates, self.num_experts, self.out_features, run)
 
     def extra_repr(self):
         return (f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, "
@@ -933,3 +949,371 @@ def quantize_experts(Ws, Hs, weights="mxfp4", act_order="diag", damp=0.01, scale
     codes, scales = _pack(dev.aligned(torch.cat([sh["idx"] for sh in shards])), torch.cat(S), E * R, n, wf)
     codes, scales = codes.reshape(E, R, -1), scales.reshape(E, R, -1)
     return [MXResult(*(dev.like_input(t, Ws[e]) for t in (shards[e]["Q"], shards[e]["idx"], S[e], codes[e], scales[e]))) for e in range(E)]
+
+
+# ------------------------------------------------------------------------------------------------------------ gated MLP
+# down(act(gate(x)) * up(x)): the fused gate/up product writes the down layer's activations directly (slk_mx_gemm_glu).
+#
+# GATED MLP.  The up layer holds gate and up, 2 N rows; hidden column j takes gate = row j and up = row N + j, or, with
+# interleaved=True (gpt-oss), gate = row 2 j and up = row 2 j + 1.  The gate, all float32, each operation rounded once:
+#     g' = min(g, limit);  u' = clamp(u, -limit, limit);  h = (u' + shift) * (g' * (1 / (1 + exp(-(alpha * g')))))
+# alpha=1, limit=None, shift=0 (the defaults) is SwiGLU, silu(g) * u; alpha=1.702, limit=7, shift=1 is gpt-oss.
+#     h_codes, h_scales = matmul_mx_glu(a_codes, a_scales, up_codes, up_scales, up_bias)   # (M, N bits / 8), (M, N / 32)
+#     y = gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales)                     # quantizer, fused product, product
+#     mlp = MXGatedMLP.from_results(up_linear, up_result, down_linear, down_result);  y = mlp(x)
+# h_codes / h_scales are in the activations' own format, exactly as that format's quantizer writes them, and bit for bit
+# those of the three-step route matmul_mx(..., dtype=float32), glu(..., dtype=float32), quantize_mxfp8 / _mxfp4_act / _mxfp6_act.
+_H_FINITE = "activations must be finite: X holds a NaN or an infinity"  # (the quantizers' message: h is the down layer's X)
+_Gate = collections.namedtuple("_Gate", "alpha limit shift interleaved")
+_GATE_DEFAULT = _Gate(1.0, None, 0.0, False)
+
+
+def _gate(alpha, limit, shift, interleaved):
+    """The checked gate parameters as a _Gate (limit None: no clamp)."""
+    for v, what in ((alpha, "alpha"), (shift, "shift")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+            raise ValueError(f"{what} must be a finite number (got {v!r})")
+    if limit is not None and (isinstance(limit, bool) or not isinstance(limit, (int, float)) or not limit > 0):
+        raise ValueError(f"limit must be above 0, or None for no clamp (got {limit!r})")
+    if not isinstance(interleaved, (bool, np.bool_)):
+        raise ValueError(f"interleaved must be True or False (got {interleaved!r})")
+    return _Gate(float(alpha), None if limit is None or limit == float("inf") else float(limit), float(shift), bool(interleaved))
+
+
+def _gate_args(gate):
+    return gate.alpha, float("inf") if gate.limit is None else gate.limit, gate.shift, int(gate.interleaved)
+
+
+def _hidden(rows, what="the up layer"):
+    """N of an up layer of `rows` = 2 N rows: gate and up, and whole blocks of 32 hidden columns."""
+    if rows % 2 != 0:
+        raise ValueError(f"{what} holds gate and up: its row count must be even (got {rows})")
+    if rows // 2 < BLOCK or rows // 2 % BLOCK != 0:
+        raise ValueError(f"{what} must have 2 N rows with N a positive multiple of {BLOCK} (got {rows} rows)")
+    return rows // 2
+
+
+def _glu(Yd, M, N, gate, dtype):
+    """H (M, N) of `dtype` from a contiguous device Y (M, 2 N)."""
+    Yd = dev.aligned(Yd)
+    out = torch.empty((M, N), dtype=dtype, device=Yd.device)
+    _lib.check(_lib.lib.slk_mx_glu(dev.ptr(Yd), _OUT[Yd.dtype], M, N, *_gate_args(gate), _OUT[dtype], dev.ptr(out), dev.stream_handle()))
+    return out
+
+
+def glu(y, alpha=1.0, limit=None, shift=0.0, interleaved=False, dtype=None):
+    """The gate, elementwise (slk_mx_glu): y (..., 2 N) float32, bfloat16 or float16 -> h (..., N) in `dtype` (None: y's),
+    the float32 h rounded once.  Column j of h takes gate = y[..., j] and up = y[..., N + j]; interleaved=True: gate =
+    y[..., 2 j] and up = y[..., 2 j + 1].  alpha, limit (None: no clamp) and shift as in the section's header."""
+    gate = _gate(alpha, limit, shift, interleaved)
+    if not isinstance(y, (np.ndarray, torch.Tensor)) or y.ndim < 1:
+        raise ValueError("y must be a NumPy array or torch tensor of at least one dimension")
+    if y.dtype not in _ACT:
+        raise ValueError(f"y must be {_ACT[0]}, torch.bfloat16 or torch.float16 (got {y.dtype})")
+    if dtype is None:
+        dtype = _torch_dtype(y)
+    _out_dtype(dtype, y)
+    if y.shape[-1] < 2 or y.shape[-1] % 2 != 0 or y.shape[-1] >= 1 << 31:
+        raise ValueError(f"y holds gate and up: its last dimension must be even and at least 2 (got {y.shape[-1]})")
+    N, lead = int(y.shape[-1]) // 2, tuple(y.shape[:-1])
+    M = int(np.prod(lead, dtype=np.int64))
+    if M < 1 or M >= 1 << 31:
+        raise ValueError(f"y must have 1 <= rows < 2^31 (got {tuple(y.shape)})")
+    out = _glu(dev.to_device(y, _torch_dtype(y)).reshape(M, 2 * N), M, N, gate, dtype)
+    return dev.like_input(out.reshape(lead + (N,)), y)
+
+
+def _gemm_glu(ac, asc, wc, wsc, bias, M, N, K, fmt, wf, gate, fused=True, rotation=None):
+    """(h_codes, h_scales, flag) of device operands: the fused product, or (fused=False, or with a `rotation` of the N hidden
+    features, which spans more than a tile) the three-step route -- the product to float32, slk_mx_glu to float32, the plain
+    or the rotating quantizer.  The caller reads the flag (_H_FINITE) once everything that follows has been launched."""
+    if fused and rotation is None:
+        codes, scales, _ = _act_outputs(ac, M, N, fmt)
+        flag = torch.zeros(1, dtype=torch.int32, device=ac.device)
+        _lib.check(_lib.lib.slk_mx_gemm_glu(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, fmt.c_fmt, wf.c_fmt,
+                                            *_gate_args(gate), dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
+        return codes, scales, flag
+    h = _glu(_gemm(ac, asc, wc, wsc, bias, M, 2 * N, K, torch.float32, fmt, wf), M, N, gate, torch.float32)
+    return _rotate_quantize_act(h, M, N, rotation, fmt) if rotation is not None else _quantize_act(h, M, N, fmt)
+
+
+def _gemm_glu_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, fmt, wf, gate, fused=True, rotation=None):
+    """(h_codes, h_scales, offsets flag, finite flag): _gemm_glu over rows sorted by expert.  (Unfused under invalid offsets,
+    the product writes nothing and the next two steps run on an unwritten matrix: the offsets flag is the one to read first.)"""
+    if fused and rotation is None:
+        codes, scales, _ = _act_outputs(ac, M, N, fmt)
+        flags = torch.zeros(2, dtype=torch.int32, device=ac.device)
+        ws, ws_bytes = dev.scratch(_lib.lib.slk_mx_experts_workspace_bytes(E, M), "mx_experts")
+        _lib.check(_lib.lib.slk_mx_gemm_glu_experts(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), dev.ptr(offsets), E, M, N, K,
+                                                    fmt.c_fmt, wf.c_fmt, *_gate_args(gate), dev.ptr(codes), dev.ptr(scales), dev.ptr(flags),
+                                                    dev.ptr(ws), ws_bytes, dev.stream_handle()))
+        return codes, scales, flags[0], flags[1]
+    y, bad = _gemm_experts(ac, asc, wc, wsc, bias, offsets, E, M, 2 * N, K, torch.float32, fmt, wf)
+    h = _glu(y, M, N, gate, torch.float32)
+    codes, scales, flag = _rotate_quantize_act(h, M, N, rotation, fmt) if rotation is not None else _quantize_act(h, M, N, fmt)
+    return codes, scales, bad, flag
+
+
+def _act_operands(a_codes, a_scales, fmt):
+    """(M, K) of quantized activations in the _Format fmt, shapes and dtypes checked."""
+    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    K = _columns(width, fmt.bits, "a_codes")
+    _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(a_scales, M, K, "activation scale bytes")
+    return M, K
+
+
+def _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved, fused=True):
+    """matmul_mx_glu before its flag is read: (h_codes, h_scales, flag), device tensors."""
+    fmt, wf = _activations(activations), _weight_format(weights)
+    _check_pair(fmt, wf)
+    gate = _gate(alpha, limit, shift, interleaved)
+    M, K = _act_operands(a_codes, a_scales, fmt)
+    rows, Kw = _weights(codes, scales, wf)
+    N = _hidden(rows)
+    if Kw != K:
+        raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
+    _check_bias(bias, 2 * N)
+    return _gemm_glu(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), dev.aligned(dev.to_device(codes, torch.uint8)),
+                     dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, fmt, wf, gate, fused)
+
+
+def matmul_mx_glu(a_codes, a_scales, codes, scales, bias=None, activations="mxfp8", weights="mxfp4", alpha=1.0, limit=None, shift=0.0,
+                  interleaved=False):
+    """(h_codes (M, N bits / 8), h_scales (M, N / 32)): quantized activations (M, K) against an up layer of 2 N rows (codes
+    (2 N, K bits / 8), scales (2 N, K / 32), bias (2 N,) float32), the gate applied to the float32 sums, and h quantized to
+    the activations' own format -- one launch, and the bits of matmul_mx(dtype=float32), glu(dtype=float32) and that format's
+    quantizer.  N must be a multiple of 32.  A NaN or an infinity in h: ValueError, as from the quantizers."""
+    hc, hs, flag = _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved)
+    _raise_flags((flag, _H_FINITE))
+    return dev.like_input(hc, a_codes), dev.like_input(hs, a_codes)
+
+
+def _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, activations, weights, alpha, limit, shift, interleaved, fused=True):
+    """matmul_mx_glu_experts before its flags are read: (h_codes, h_scales, offsets flag, finite flag), device tensors."""
+    fmt, wf = _activations(activations), _weight_format(weights)
+    _check_pair(fmt, wf)
+    gate = _gate(alpha, limit, shift, interleaved)
+    M, K = _act_operands(a_codes, a_scales, fmt)
+    E, rows, Kw = _expert_weights(codes, scales, wf)
+    N = _hidden(rows, "every expert's up layer")
+    if Kw != K:
+        raise ValueError(f"a_codes has {K} columns but the experts' layers have {Kw}")
+    _check_expert_bias(bias, E, 2 * N)
+    _check_offsets(offsets, E)
+    return _gemm_glu_experts(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8),
+                             dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
+                             dev.to_device(offsets, torch.int32), E, M, N, K, fmt, wf, gate, fused)
+
+
+def matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias=None, activations="mxfp8", weights="mxfp4", alpha=1.0, limit=None,
+                          shift=0.0, interleaved=False):
+    """matmul_mx_glu for a stack of E experts in one call (slk_mx_gemm_glu_experts): rows sorted by expert under `offsets`
+    (matmul_mx_experts' rule and its ValueError), codes (E, 2 N, K bits / 8), scales (E, 2 N, K / 32), bias (E, 2 N).  Each
+    expert's rows are bit for bit matmul_mx_glu of that slice.  Offsets that break the rule leave nothing computed."""
+    hc, hs, bad, flag = _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, activations, weights, alpha, limit, shift, interleaved)
+    _raise_flags((bad, _OFFSETS_RULE), (flag, _H_FINITE))
+    return dev.like_input(hc, a_codes), dev.like_input(hs, a_codes)
+
+
+def _check_rotation(rotation, features, what):
+    if rotation is not None:
+        from .rotation import Rotation
+
+        if not isinstance(rotation, Rotation):
+            raise ValueError(f"{what} must be a Rotation (got {type(rotation).__name__})")
+        if rotation.n != features:
+            raise ValueError(f"the {what} has {rotation.n} features but the layer has {features}")
+
+
+def _gated_mlp(x, up, down, dtype, activations, gate, rotation, down_rotation, fused, wf_up, wf_down):
+    """gated_mlp_mx on up = (codes, scales, bias) and down = the same, each layer in its own weight format."""
+    fmt = _activations(activations)
+    _check_pair(fmt, wf_up)
+    _check_pair(fmt, wf_down)
+    if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim < 1:
+        raise ValueError("x must be a NumPy array or torch tensor of at least one dimension")
+    if x.dtype not in _ACT:
+        raise ValueError(f"x must be {_ACT[0]}, torch.bfloat16 or torch.float16 (got {x.dtype})")
+    if dtype is None:
+        dtype = _torch_dtype(x)
+    _out_dtype(dtype, x)
+    rows, K = _weights(up[0], up[1], wf_up)
+    N = _hidden(rows)
+    Nd, Kd = _weights(down[0], down[1], wf_down)
+    if Kd != N:
+        raise ValueError(f"the down layer has {Kd} columns but the up layer gives {N} hidden columns")
+    if x.shape[-1] != K:
+        raise ValueError(f"x has {x.shape[-1]} columns but the up layer has {K}")
+    _check_rotation(rotation, K, "rotation")
+    _check_rotation(down_rotation, N, "down_rotation")
+    _check_bias(up[2], 2 * N)
+    _check_bias(down[2], Nd)
+    lead = tuple(x.shape[:-1])
+    M = int(np.prod(lead, dtype=np.int64))
+    if M < 1 or M >= 1 << 31:
+        raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
+    Xd = dev.to_device(x, _torch_dtype(x)).reshape(M, K)
+    ac, asc, finite = _rotate_quantize_act(Xd, M, K, rotation, fmt) if rotation is not None else _quantize_act(Xd, M, K, fmt)
+    hc, hs, h_finite = _gemm_glu(ac, asc, dev.aligned(dev.to_device(up[0], torch.uint8)), dev.to_device(up[1], torch.uint8), _bias(up[2]), M, N, K,
+                                 fmt, wf_up, gate, fused, down_rotation)
+    out = _gemm(hc, hs, dev.aligned(dev.to_device(down[0], torch.uint8)), dev.to_device(down[1], torch.uint8), _bias(down[2]), M, Nd, N, dtype,
+                fmt, wf_down)
+    _raise_flags((finite, _H_FINITE), (h_finite, _H_FINITE))
+    return dev.like_input(out.reshape(lead + (Nd,)), x)
+
+
+def gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales, up_bias=None, down_bias=None, dtype=None, activations="mxfp8", weights="mxfp4",
+                 alpha=1.0, limit=None, shift=0.0, interleaved=False, rotation=None, fused=True, down_rotation=None):
+    """down(act(gate(x)) * up(x)) with both layers packed, in three launches: x (..., K) is quantized (with `rotation` inside
+    the quantizer, as in linear_mxfp4), the fused product writes the hidden activations h as codes (matmul_mx_glu: up layer
+    (2 N, K), up_bias (2 N,)), and matmul_mx runs the down layer (Nd, N) on them, + down_bias (Nd,): (..., Nd) in `dtype`, or
+    in x's dtype when it is None.  The flags of x and of h are read together after the launches: one wait for the stream.
+    fused=False runs the three-step route between the products instead -- the up product to float32, glu to float32, the plain
+    quantizer -- with the same bits.  That route is also the one taken when the down layer sits behind a rotation
+    (down_rotation, a Rotation over the N hidden features): a Hadamard block of h spans more than one tile of the product, so
+    the fused product is not asked to rotate h, and glu's float32 h feeds the fused rotate-and-quantize kernel instead."""
+    wf = _weight_format(weights)
+    gate = _gate(alpha, limit, shift, interleaved)
+    return _gated_mlp(x, (up_codes, up_scales, up_bias), (down_codes, down_scales, down_bias), dtype, activations, gate, rotation, down_rotation,
+                      fused, wf, wf)
+
+
+def _gated_mlp_experts(x, up, down, offsets, dtype, activations, gate, rotation, down_rotation, fused, wf_up, wf_down, also=()):
+    fmt = _activations(activations)
+    _check_pair(fmt, wf_up)
+    _check_pair(fmt, wf_down)
+    M, Kx = _matrix(x, "x", _ACT)
+    if dtype is None:
+        dtype = _torch_dtype(x)
+    _out_dtype(dtype, x)
+    E, rows, K = _expert_weights(up[0], up[1], wf_up)
+    N = _hidden(rows, "every expert's up layer")
+    Ed, Nd, Kd = _expert_weights(down[0], down[1], wf_down)
+    if Ed != E:
+        raise ValueError(f"the up layers are of {E} experts but the down layers of {Ed}")
+    if Kd != N:
+        raise ValueError(f"the down layers have {Kd} columns but the up layers give {N} hidden columns")
+    if Kx != K:
+        raise ValueError(f"x has {Kx} columns but the experts' up layers have {K}")
+    _check_rotation(rotation, K, "rotation")
+    _check_rotation(down_rotation, N, "down_rotation")
+    _check_expert_bias(up[2], E, 2 * N)
+    _check_expert_bias(down[2], E, Nd)
+    _check_offsets(offsets, E)
+    Xd = dev.to_device(x, _torch_dtype(x))
+    od = dev.to_device(offsets, torch.int32)
+    ac, asc, finite = _rotate_quantize_act(Xd, M, K, rotation, fmt) if rotation is not None else _quantize_act(Xd, M, K, fmt)
+    hc, hs, bad, h_finite = _gemm_glu_experts(ac, asc, dev.aligned(dev.to_device(up[0], torch.uint8)), dev.to_device(up[1], torch.uint8), _bias(up[2]),
+                                              od, E, M, N, K, fmt, wf_up, gate, fused, down_rotation)
+    out, _ = _gemm_experts(hc, hs, dev.aligned(dev.to_device(down[0], torch.uint8)), dev.to_device(down[1], torch.uint8), _bias(down[2]), od, E, M,
+                           Nd, N, dtype, fmt, wf_down)
+    _raise_flags(*also, (finite, _H_FINITE), (bad, _OFFSETS_RULE), (h_finite, _H_FINITE))
+    return dev.like_input(out, x)
+
+
+class _GatedModule(torch.nn.Module):
+    """What MXGatedMLP and MXExpertsMLP share: the sub-modules `up` and `down` and the four gate parameters, which travel as
+    the module's extra state -- written only when they are not the defaults (SwiGLU, not interleaved), as in _MXModule."""
+
+    _STATE_KEY = torch.nn.modules.module._EXTRA_STATE_KEY_SUFFIX
+
+    def _init_gate(self, up, down, kind, alpha, limit, shift, interleaved):
+        if not isinstance(up, kind) or not isinstance(down, kind):
+            raise ValueError(f"up and down must be {kind.__name__} modules (got {type(up).__name__} and {type(down).__name__})")
+        self.gate = _gate(alpha, limit, shift, interleaved)
+        N = _hidden(up.out_features)
+        if down.in_features != N:
+            raise ValueError(f"the down layer has {down.in_features} columns but the up layer gives {N} hidden columns")
+        if up.activations != down.activations:
+            raise ValueError(f"up and down must take the same activations: h is written in x's format (got {up.activations!r} and {down.activations!r})")
+        self.up, self.down = up, down
+        self.in_features, self.hidden_features, self.out_features = up.in_features, N, down.out_features
+
+    alpha, limit, shift, interleaved = (property(lambda self, i=i: self.gate[i]) for i in range(4))
+
+    @property
+    def activations(self):
+        return self.up.activations
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        state = {k: v for k, v, d in zip(_Gate._fields, self.gate, _GATE_DEFAULT) if v != d}
+        if state:
+            destination[prefix + self._STATE_KEY] = state
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        key = prefix + self._STATE_KEY
+        gate = _GATE_DEFAULT
+        if key in state_dict:
+            state = state_dict[key]
+            try:
+                gate = _gate(**{**_GATE_DEFAULT._asdict(), **state})
+            except (TypeError, ValueError) as e:
+                error_msgs.append(f"{key}: {e}")
+                gate = self.gate
+            state_dict = {k: v for k, v in state_dict.items() if k != key}  # (the base class knows no such key)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        self.gate = gate
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, hidden_features={self.hidden_features}, out_features={self.out_features}, "
+                + ", ".join(f"{k}={v}" for k, v in self.gate._asdict().items()))
+
+
+class MXGatedMLP(_GatedModule):
+    """A gated MLP kept in its packed MX form: `up` an MXLinear of 2 N rows (gate and up), `down` an MXLinear over the N
+    hidden features, and the gate parameters alpha, limit, shift, interleaved (gated_mlp_mx).  forward(x) = gated_mlp_mx(x,
+    up.codes, up.scales, down.codes, down.scales, up.bias, down.bias, ...): three launches.  The two layers may differ in
+    their weight format and must take the same activations.  The state dict is the two sub-modules' (`up.codes`, ...,
+    `down.bias`) plus the gate parameters as extra state, written only when they are not the defaults."""
+
+    def __init__(self, up, down, alpha=1.0, limit=None, shift=0.0, interleaved=False):
+        super().__init__()
+        self._init_gate(up, down, MXLinear, alpha, limit, shift, interleaved)
+
+    @classmethod
+    def from_results(cls, up_layer, up_result, down_layer, down_result, activations="mxfp8", alpha=1.0, limit=None, shift=0.0, interleaved=False):
+        """The module of two torch.nn.Linear layers and their MXResults (MXLinear.from_result of each)."""
+        return cls(MXLinear.from_result(up_layer, up_result, activations), MXLinear.from_result(down_layer, down_result, activations),
+                   alpha, limit, shift, interleaved)
+
+    def forward(self, x, rotation=None, fused=True, down_rotation=None):
+        return _gated_mlp(x, (self.up.codes, self.up.scales, self.up.bias), (self.down.codes, self.down.scales, self.down.bias), None,
+                          self.activations, self.gate, rotation, down_rotation, fused, _WEIGHTS[self.up.weights], _WEIGHTS[self.down.weights])
+
+
+class MXExpertsMLP(_GatedModule):
+    """The gated MLPs of a mixture-of-experts layer: `up` an MXExperts of E layers of 2 N rows, `down` an MXExperts of E layers
+    over the N hidden features, and the gate parameters.  forward(x, offsets) runs rows sorted by expert -- the quantizer, the
+    fused grouped product (slk_mx_gemm_glu_experts), the grouped down product: three launches and the prologues --;
+    forward_tokens(x, expert_ids, gates) routes, runs and combines as MXExperts.forward_tokens does.  The id check and every
+    device flag of a call are read together: one wait for the stream.  State dict as MXGatedMLP's."""
+
+    def __init__(self, up, down, alpha=1.0, limit=None, shift=0.0, interleaved=False):
+        super().__init__()
+        self._init_gate(up, down, MXExperts, alpha, limit, shift, interleaved)
+        if up.num_experts != down.num_experts:
+            raise ValueError(f"the up layers are of {up.num_experts} experts but the down layers of {down.num_experts}")
+        self.num_experts = up.num_experts
+
+    @classmethod
+    def from_results(cls, up_results, down_results, up_biases=None, down_biases=None, activations="mxfp8", device=None, alpha=1.0, limit=None,
+                     shift=0.0, interleaved=False):
+        """The module of two lists of E MXResults and, optionally, biases (E, 2 N) and (E, Nd) (MXExperts.from_results of each)."""
+        return cls(MXExperts.from_results(up_results, up_biases, activations, device), MXExperts.from_results(down_results, down_biases, activations, device),
+                   alpha, limit, shift, interleaved)
+
+    def _run(self, x, offsets, rotation, fused, down_rotation, also=()):
+        return _gated_mlp_experts(x, (self.up.codes, self.up.scales, self.up.bias), (self.down.codes, self.down.scales, self.down.bias), offsets, None,
+                                  self.activations, self.gate, rotation, down_rotation, fused, _WEIGHTS[self.up.weights], _WEIGHTS[self.down.weights],
+                                  also)
+
+    def forward(self, x, offsets, rotation=None, fused=True, down_rotation=None):
+        return self._run(x, offsets, rotation, fused, down_rotation)
+
+    def forward_tokens(self, x, expert_ids, gates=None, rotation=None, fused=True, down_rotation=None):
+        """x (T, K), expert_ids (T, k) and gates (T, k) or None -> (T, Nd) in x's dtype: sum_j gates[t][j] * MLP of expert
+        expert_ids[t][j] (x[t]), the routing, the gather back and the ordered float32 sum of MXExperts.forward_tokens."""
+        return _route_tokens(x, expert_ids, gates, self.num_experts, self.out_features,
+                             lambda rows, offsets, also: self._run(rows, offsets, rotation, fused, down_rotation, also))
