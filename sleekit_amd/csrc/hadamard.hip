@@ -232,7 +232,7 @@ __global__ __launch_bounds__(HD_THREADS) static void k_hadamard_rows(const XT *X
 // slk_mx_rotate_quantize_act: steps 1 to 3 of the transform (transposed == 0) with the MX activation quantizer as the
 // epilogue, applied to the float32 value -- the bits of slk_hadamard_rows to float32 followed by slk_mx_quantize_act /
 // _act4, without the float32 matrix in between.  n % 32 == 0, so a block of 32 is the chunks of an even lane and its right
-// neighbour in one row: one DPP step joins their maxima, the even lane stores the scale byte, and each lane its 16 codes
+// neighbour in one row: mxq_encode (mxquant.h) with 16 elements a lane, the even lane stores the scale byte, and each lane its 16 codes
 // (16 bytes of E4M3, 8 of E2M1; 12 of E2M3, three aligned dwords of the row's bit stream: slk_mx_rotate_quantize_act6).
 // Lanes past the matrix come in pairs too (rows * n / 16 is even) and carry zeros.
 template <class XT, int FMT>
@@ -249,17 +249,10 @@ __global__ __launch_bounds__(HD_THREADS) static void k_hadamard_quantize(const X
 #pragma unroll
     for (int e = 0; e < HD_CHUNK; ++e) v[e] = s[e] * v[e];
     hd_butterfly(v, lb, t, xch);
-    int top = 0;
 #pragma unroll
-    for (int e = 0; e < HD_CHUNK; ++e) {
-        v[e] = v[e] * c;
-        top = max(top, (int)(__float_as_uint(v[e]) & 0x7fffffffu));
-    }
-    top = max(top, dpp_i<DPP_XOR1>(top));
-    const unsigned eb = mxa_scale_byte<FMT>(top);
-    const float inv = mxa_inverse(eb);
-    unsigned w[HD_CHUNK * mxa_bits<FMT>() / 32];
-    mxa_pack<FMT>(v, inv, w);
+    for (int e = 0; e < HD_CHUNK; ++e) v[e] = v[e] * c;
+    unsigned eb, w[HD_CHUNK * mxa_bits<FMT>() / 32];
+    const int top = mxq_encode<FMT>(v, eb, w);
     if (k.live) {
         const size_t at = k.row * n + k.col;  // a multiple of 16
         mxa_store<FMT, HD_CHUNK>(codes + mxa_byte_of<FMT>(at), w);

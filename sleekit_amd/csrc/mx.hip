@@ -191,20 +191,19 @@ __device__ __forceinline__ float act_f32<unsigned short>(unsigned short x) { ret
 template <>
 __device__ __forceinline__ float act_f32<_Float16>(_Float16 x) { return (float)x; }
 
-// The plain quantizer.  LPB lanes a block, 32 / LPB elements a lane, read in 16-byte pieces: the block's largest |x| over
-// its lanes on DPP, the scale byte from the block's first lane, and every lane's codes as whole dwords of the row's
-// little-endian bit stream (mxa_pack, mxa_store).  E4M3 and E2M1 take four lanes a block: 8 bytes a lane, or one dword of
+// The plain quantizer.  LPB lanes a block, 32 / LPB elements a lane, read in 16-byte pieces; mxq_encode (mxquant.h) turns
+// them into the block's scale byte, stored by the block's first lane, and every lane's codes as whole dwords of the row's
+// little-endian bit stream (mxa_store).  E4M3 and E2M1 take four lanes a block: 8 bytes a lane, or one dword of
 // nibbles, the even k in the low ones, which is the weights' own layout.  Eight 6-bit codes are 6 bytes, which no lane can
 // store as whole dwords at a 6-byte stride, so E2M3 takes two: 12 bytes a lane, three dwords at a 12-byte stride, every one
 // of them aligned (a row is 24 bytes a block; DESIGN.md section 20 has this shape measured against a lane a block).
 // A NaN or an infinity has the largest magnitude bits of its block, so the integer maximum finds it and raises the flag.
-// (mxq_lanes, the lanes a block of each format, is mxquant.h's: the fused product's epilogue re-reads its tile in this shape.)
+// (mxq_lanes, the lanes a block of each format, is mxquant.h's: the fused product's epilogue stages its tile for mxq_encode
+// in the same lane shape.)
 template <class T, int FMT, int LPB>
 __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X, size_t blocks, uint8_t *__restrict__ codes,
                                                          uint8_t *__restrict__ E, int *__restrict__ flag) {
-    static_assert(LPB == 2 || LPB == 4, "the maximum takes one or two DPP steps");
     constexpr int EPL = 32 / LPB, BYTES = EPL * mxa_bits<FMT>() / 8;  // elements and bytes of codes a lane
-    static_assert(BYTES % 4 == 0, "a lane stores whole dwords: fewer lanes a block for this format");
     constexpr int PER = 16 / (int)sizeof(T), PIECES = EPL / PER;      // elements a 16-byte piece, pieces a lane
     typedef T V __attribute__((ext_vector_type(PER)));
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
@@ -225,15 +224,8 @@ __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X
                 for (int e = 0; e < PER; ++e) x[p * PER + e] = act_f32<T>(v[e]);
             }
         }
-        int top = 0;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) top = max(top, (int)(__float_as_uint(x[e]) & 0x7fffffffu));
-        top = max(top, dpp_i<DPP_XOR1>(top));
-        if constexpr (LPB == 4) top = max(top, dpp_i<DPP_XOR2>(top));
-        bad |= top >= 0x7f800000;
-        const unsigned eb = mxa_scale_byte<FMT>(top);
-        unsigned w[BYTES / 4];
-        mxa_pack<FMT>(x, mxa_inverse(eb), w);
+        unsigned eb, w[BYTES / 4];
+        bad |= mxq_encode<FMT>(x, eb, w) >= 0x7f800000;
         if (live) {
             mxa_store<FMT, EPL>(codes + BYTES * i, w);
             if (i % LPB == 0) E[i / LPB] = (uint8_t)eb;

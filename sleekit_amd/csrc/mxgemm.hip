@@ -2,7 +2,10 @@
 // mixture-of-experts layer (slk_mx_gemm, _a4, _a6, _w6, slk_mx_gemm_experts; the formats are pinned in include/sleekit_amd.h
 // and INTEGRATION.md).  Nothing here converts: the kernels that write and read back these forms are mx.hip's.  The one
 // exception is the fused gate/up product of a gated MLP (slk_mx_gemm_glu, _experts), whose epilogue ends in the plain
-// quantizer's own functions (mxquant.h) and writes the next layer's activations.
+// quantizer's own block encoder (mxq_encode, mxquant.h) and writes the next layer's activations.
+// The entries at the end share one dispatcher from (a_fmt, w_fmt) to a pair of template arguments (with_pair), one list of
+// what a product requires of its operands (mx_check_operands; the gated and the expert-grouped entries add theirs) and one
+// prologue for the two expert-grouped products (mx_expert_prologue).
 //
 // Weights stay as slk_mx_pack left them: FP4 E2M1 codes, two a byte, and one E8M0 byte per block of 32 columns -- or, for
 // an MXFP6 layer (slk_mx_gemm_w6), as slk_mx_pack6 left them: E2M3 codes, 24 bytes a block.
@@ -239,8 +242,8 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
 // ---------------------------------------------------------------- the fused gate/up product of a gated MLP
 // slk_mx_gemm_glu: A against a layer of 2 N rows, gate and up, and instead of Y (M, 2 N) the next layer's activations:
 // h = mx_glu(gate + bias, up + bias) (mxglu.h), quantized per (row, block of 32 hidden columns) to A's own format exactly as
-// the plain quantizer of mx.hip would have done it -- the integer maximum of the magnitude bits, mxa_scale_byte, mxa_pack
-// with mxa_inverse, mxa_store, the scale byte.  Every accumulator keeps the order over K of the kernels above (the split-K
+// the plain quantizer of mx.hip would have done it -- mxq_encode (mxquant.h), which both call, then mxa_store and the
+// scale byte.  Every accumulator keeps the order over K of the kernels above (the split-K
 // form: wave w the steps w, w + SK, ..., two in flight, wave 0 adds in wave order; the tiled form: the steps in order), so the
 // gate and up sums are slk_mx_gemm's float32 values bit for bit, and the codes are those of the three-step route
 // slk_mx_gemm to float32, slk_mx_glu to float32, slk_mx_quantize_act*.
@@ -259,7 +262,7 @@ __device__ __forceinline__ void glu_stage(float *__restrict__ tile, v4f g, v4f u
     for (int r = 0; r < 4; ++r) tile[(r0 + r) * GLU_LD + c] = mx_glu(bias ? g[r] + bg : g[r], bias ? u[r] + bu : u[r], p);
 }
 // The staged ROWS x 32 tile -> codes and scale bytes of hidden block `blk` of rows row0 .. (below `rows`), by one wave:
-// k_mx_quantize_act's body.  Returns whether a live block holds a NaN or an infinity.
+// k_mx_quantize_act's lane shape around the same mxq_encode.  Returns whether a live block holds a NaN or an infinity.
 template <int AF, int ROWS>
 __device__ __forceinline__ bool glu_quantize_tile(const float *__restrict__ tile, int lane, int row0, int rows, int N, int blk, bool blk_live,
                                                   uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs) {
@@ -272,15 +275,9 @@ __device__ __forceinline__ bool glu_quantize_tile(const float *__restrict__ tile
         float x[EPL];
 #pragma unroll
         for (int e = 0; e < EPL; ++e) x[e] = staged ? tile[r * GLU_LD + piece * EPL + e] : 0.0f;
-        int top = 0;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) top = max(top, (int)(__float_as_uint(x[e]) & 0x7fffffffu));
-        top = max(top, dpp_i<DPP_XOR1>(top));
-        if constexpr (LPB == 4) top = max(top, dpp_i<DPP_XOR2>(top));
+        unsigned eb, w[BYTES / 4];
+        const int top = mxq_encode<AF>(x, eb, w);
         bad |= live && top >= 0x7f800000;
-        const unsigned eb = mxa_scale_byte<AF>(top);
-        unsigned w[BYTES / 4];
-        mxa_pack<AF>(x, mxa_inverse(eb), w);
         if (live) {
             mxa_store<AF, EPL>(Hc + (size_t)m * mxa_byte_of<AF>((size_t)N) + (size_t)blk * (4 * mxa_bits<AF>()) + piece * BYTES, w);
             if (piece == 0) Hs[(size_t)m * (N / 32) + blk] = (uint8_t)eb;
@@ -530,15 +527,80 @@ __global__ __launch_bounds__(256) void k_mx_gemm_glu_experts_tiled(const uint8_t
 
 using namespace slk;
 
-// slk_mx_gemm (AF MXA_E4M3), _a4 (MXA_E2M1) and _a6 (MXA_E2M3) against an MXFP4 layer; _w6 (WF MXA_E2M3) against an MXFP6 one
-template <int AF, int WF = MXA_E2M1>
-static int mx_gemm(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
-                   const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
+// ---------------------------------------------------------------- the entries
+// f(MxPair<..>()) for an (a_fmt, w_fmt) that mx_check_pair has passed: the one place the two constants become template
+// arguments, in the manner of with_dtype.  INDEX is the pair's place in an entry's names: none, _a4, _a6, _w6, _w6a6.
+// (Every name SLK_RUN records is a literal: ProfScope may keep the pointer, and profiles/README.md reads them.)
+template <int A, int W, int I>
+struct MxPair {
+    static constexpr int AF = A, WF = W, INDEX = I;
+};
+template <class F>
+static int with_pair(int a_fmt, int w_fmt, F &&f) {
+    if (w_fmt == SLK_MX_W_FP6) return a_fmt == SLK_MX_ACT_FP6 ? f(MxPair<MXA_E2M3, MXA_E2M3, 4>()) : f(MxPair<MXA_E4M3, MXA_E2M3, 3>());
+    if (a_fmt == SLK_MX_ACT_FP4) return f(MxPair<MXA_E2M1, MXA_E2M1, 1>());
+    if (a_fmt == SLK_MX_ACT_FP6) return f(MxPair<MXA_E2M3, MXA_E2M1, 2>());
+    return f(MxPair<MXA_E4M3, MXA_E2M1, 0>());
+}
+static const char MX_W6_TAKES[] = "an MXFP6 layer takes MXFP8 (SLK_MX_ACT_FP8) or MXFP6 (SLK_MX_ACT_FP6) activations (a_fmt = %d)";
+static int mx_check_pair(int a_fmt, int w_fmt) {
+    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP4 || a_fmt == SLK_MX_ACT_FP6, "unknown a_fmt %d", a_fmt);
+    SLK_REQUIRE(w_fmt == SLK_MX_W_FP4 || w_fmt == SLK_MX_W_FP6, "unknown w_fmt %d", w_fmt);
+    SLK_REQUIRE(!(w_fmt == SLK_MX_W_FP6 && a_fmt == SLK_MX_ACT_FP4), MX_W6_TAKES, a_fmt);
+    return SLK_OK;
+}
+
+// What every product requires of its operands; `out` is Y or h_codes, and `out_name` says which in the text.  (The lists
+// below are functions because SLK_REQUIRE returns from the one it stands in: an entry returns what they return when it is not 0.)
+static int mx_check_operands(const void *a_codes, const void *a_scales, const void *w_codes, const void *w_scales, const void *out,
+                             const char *out_name, int M, int N, int K) {
     SLK_REQUIRE(M > 0 && N > 0, "M and N must be at least 1 (M = %d, N = %d)", M, N);
     SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);
-    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
     SLK_REQUIRE(a_codes && a_scales && w_codes && w_scales && out, "null pointer");
-    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(out), "a_codes, w_codes and out must be aligned to 16 bytes");
+    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(out), "a_codes, w_codes and %s must be aligned to 16 bytes", out_name);
+    return SLK_OK;
+}
+// ... what the fused gate/up products require on top, ahead of it: their rule for N has its own text and covers M ...
+static int mx_check_gated(int M, int N, const void *h_scales, const int *flag, float alpha, float limit, float shift, int interleaved) {
+    SLK_REQUIRE(M > 0 && N >= 32 && N % 32 == 0, "a block of h is 32 hidden columns: N must be a positive multiple of 32 (M = %d, N = %d)", M, N);
+    SLK_REQUIRE(N <= 0x3fffffff, "the layer has 2 N rows: N must be below 2^30 (N = %d)", N);
+    SLK_REQUIRE(h_scales, "null pointer");
+    SLK_REQUIRE(flag, "null flag");
+    SLK_REQUIRE(limit > 0.0f, "limit must be above 0, +inf meaning no clamp (limit = %g)", (double)limit);
+    SLK_REQUIRE(glu_finite(alpha) && glu_finite(shift), "alpha and shift must be finite (alpha = %g, shift = %g)", (double)alpha, (double)shift);
+    SLK_REQUIRE(interleaved == 0 || interleaved == 1, "interleaved must be 0 or 1 (got %d)", interleaved);
+    return SLK_OK;
+}
+// ... and the expert-grouped ones, behind it (M is positive by then)
+static int mx_check_experts(int E, int M, const int *offsets, const void *workspace, size_t ws_bytes) {
+    SLK_REQUIRE(offsets, "null offsets");
+    SLK_REQUIRE(workspace && (uintptr_t)workspace % sizeof(int) == 0, "the workspace must be non-null and aligned to 4 bytes");
+    SLK_REQUIRE(ws_bytes >= slk_mx_experts_workspace_bytes(E, M), "the workspace is too small: %zu bytes, slk_mx_experts_workspace_bytes(%d, %d) = %zu",
+                ws_bytes, E, M, slk_mx_experts_workspace_bytes(E, M));
+    SLK_REQUIRE(mxe_cap64(E, M) <= 65535, "M / 64 + E is above the 65535 row tiles of one launch (M = %d, E = %d)", M, E);
+    return SLK_OK;
+}
+
+// The prologue of both expert-grouped products: k_mx_expert_tiles on the stream, and what the two launches behind it need --
+// host-computable upper bounds of the tile counts as grid rows, and the two tables (their counts are ws[0] and ws[1]).
+struct ExpertGrid {
+    int rows16, rows64;
+    const int *t16, *t64;
+};
+static int mx_expert_prologue(const int *offsets, int E, int M, int *ws, int *flag, hipStream_t s, ExpertGrid &g) {
+    const int cap16 = (int)mxe_cap16(E, M), cap64 = (int)mxe_cap64(E, M);
+    // an expert of the split-K form has at most MXG_SPLIT_MAX_M / 16 tiles, so 4 E bounds the first launch as well
+    g = {cap16 < 4 * E ? cap16 : 4 * E, cap64, ws + MXE_HEAD, ws + MXE_HEAD + 3 * (size_t)cap16};
+    SLK_RUN("mx_expert_tiles", 0, 4.0 * (E + 1), s, (k_mx_expert_tiles<<<1, 256, 0, s>>>(offsets, E, M, ws, cap16, flag)));
+    return SLK_OK;
+}
+
+// slk_mx_gemm (P::AF MXA_E4M3), _a4 (MXA_E2M1) and _a6 (MXA_E2M3) against an MXFP4 layer; _w6 (P::WF MXA_E2M3) against an MXFP6 one
+template <class P>
+static int mx_gemm(P, const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                   const float *bias, int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
+    if (const int rc = mx_check_operands(a_codes, a_scales, w_codes, w_scales, out, "out", M, N, K)) return rc;
+    SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
     SLK_REQUIRE((M + 63) / 64 <= 65535, "M is above the 65535 row tiles of one launch (M = %d)", M);
     hipStream_t s = as_stream(stream);
     return with_dtype(out_dtype, [&](auto t) -> int {
@@ -546,109 +608,18 @@ static int mx_gemm(const char *name, const uint8_t *a_codes, const uint8_t *a_sc
         constexpr int OUT = decltype(t)::OUT;
         T *Y = static_cast<T *>(out);
         const double flops = 2.0 * M * N * K;
-        const double bytes = ((double)M * mxa_block_bytes<AF>() + (double)N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * N * sizeof(T);
+        const double bytes = ((double)M * mxa_block_bytes<P::AF>() + (double)N * mxa_block_bytes<P::WF>()) * K / 32.0 + (double)M * N * sizeof(T);
         if (M <= MXG_SPLIT_MAX_M) {
             const dim3 grid((N + 15) / 16, (M + 15) / 16);
             SLK_RUN(name, flops, bytes, s,
-                    (k_mx_gemm_splitk<OUT, AF, WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
+                    (k_mx_gemm_splitk<OUT, P::AF, P::WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
         } else {
             const dim3 grid((N + 63) / 64, (M + 63) / 64);
-            SLK_RUN(name, flops, bytes, s, (k_mx_gemm_tiled<OUT, AF, WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
+            SLK_RUN(name, flops, bytes, s,
+                    (k_mx_gemm_tiled<OUT, P::AF, P::WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, Y)));
         }
         return SLK_OK;
     });
-}
-
-// slk_mx_gemm_experts of one format pair: the prologue, the split-K product over the 16-row table and, where an expert can
-// have more than MXG_SPLIT_MAX_M rows at all, the tiled product over the 64-row table; in order on the stream
-template <int AF, int WF>
-static int mx_gemm_experts(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
-                           const float *bias, const int *offsets, int E, int M, int N, int K, int out_dtype, void *out, int *flag, int *ws,
-                           hipStream_t s) {
-    const int cap16 = (int)mxe_cap16(E, M), cap64 = (int)mxe_cap64(E, M);
-    // an expert of the split-K form has at most MXG_SPLIT_MAX_M / 16 tiles, so 4 E bounds the first launch as well
-    const int rows16 = cap16 < 4 * E ? cap16 : 4 * E, rows64 = cap64;
-    SLK_RUN("mx_expert_tiles", 0, 4.0 * (E + 1), s, (k_mx_expert_tiles<<<1, 256, 0, s>>>(offsets, E, M, ws, cap16, flag)));
-    const int *t16 = ws + MXE_HEAD, *t64 = ws + MXE_HEAD + 3 * (size_t)cap16;
-    return with_dtype(out_dtype, [&](auto t) -> int {
-        typedef typename decltype(t)::T T;
-        constexpr int OUT = decltype(t)::OUT;
-        T *Y = static_cast<T *>(out);
-        const double flops = 2.0 * M * N * K;
-        const double bytes = ((double)M * mxa_block_bytes<AF>() + (double)E * N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * N * sizeof(T);
-        const dim3 grid16((N + 15) / 16, rows16), grid64((N + 63) / 64, rows64);
-        SLK_RUN(name, flops, bytes, s,
-                (k_mx_gemm_experts_splitk<OUT, AF, WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, t16, N, K, Y)));
-        if (M > MXG_SPLIT_MAX_M)
-            SLK_RUN(name, 0, 0, s,
-                    (k_mx_gemm_experts_tiled<OUT, AF, WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, t64, N, K, Y)));
-        return SLK_OK;
-    });
-}
-
-// slk_mx_gemm_glu and slk_mx_gemm_glu_experts: what the two share of their argument lists
-#define SLK_GLU_REQUIRE()                                                                                                                     \
-    SLK_REQUIRE(M > 0 && N >= 32 && N % 32 == 0, "a block of h is 32 hidden columns: N must be a positive multiple of 32 (M = %d, N = %d)", M, N); \
-    SLK_REQUIRE(N <= 0x3fffffff, "the layer has 2 N rows: N must be below 2^30 (N = %d)", N);                                               \
-    SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);                        \
-    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP4 || a_fmt == SLK_MX_ACT_FP6, "unknown a_fmt %d", a_fmt);                   \
-    SLK_REQUIRE(w_fmt == SLK_MX_W_FP4 || w_fmt == SLK_MX_W_FP6, "unknown w_fmt %d", w_fmt);                                                  \
-    SLK_REQUIRE(!(w_fmt == SLK_MX_W_FP6 && a_fmt == SLK_MX_ACT_FP4),                                                                         \
-                "an MXFP6 layer takes MXFP8 (SLK_MX_ACT_FP8) or MXFP6 (SLK_MX_ACT_FP6) activations (a_fmt = %d)", a_fmt);                    \
-    SLK_REQUIRE(a_codes && a_scales && w_codes && w_scales && h_codes && h_scales, "null pointer");                                          \
-    SLK_REQUIRE(flag, "null flag");                                                                                                          \
-    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(h_codes), "a_codes, w_codes and h_codes must be aligned to 16 bytes"); \
-    SLK_REQUIRE(limit > 0.0f, "limit must be above 0, +inf meaning no clamp (limit = %g)", (double)limit);                                   \
-    SLK_REQUIRE(glu_finite(alpha) && glu_finite(shift), "alpha and shift must be finite (alpha = %g, shift = %g)", (double)alpha, (double)shift); \
-    SLK_REQUIRE(interleaved == 0 || interleaved == 1, "interleaved must be 0 or 1 (got %d)", interleaved)
-
-// the format pair of (a_fmt, w_fmt), checked, as template arguments: CALL(AF, WF, name suffix)
-#define SLK_GLU_PAIRS(CALL)                                          \
-    if (w_fmt == SLK_MX_W_FP6) {                                     \
-        if (a_fmt == SLK_MX_ACT_FP6) CALL(MXA_E2M3, MXA_E2M3, "_w6a6"); \
-        CALL(MXA_E4M3, MXA_E2M3, "_w6");                             \
-    }                                                                \
-    if (a_fmt == SLK_MX_ACT_FP4) CALL(MXA_E2M1, MXA_E2M1, "_a4");    \
-    if (a_fmt == SLK_MX_ACT_FP6) CALL(MXA_E2M3, MXA_E2M1, "_a6");    \
-    CALL(MXA_E4M3, MXA_E2M1, "")
-
-template <int AF, int WF>
-static int mx_gemm_glu(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
-                       const float *bias, int M, int N, int K, const GluParams p, uint8_t *h_codes, uint8_t *h_scales, int *flag, hipStream_t s) {
-    const double flops = 4.0 * M * N * K;
-    const double bytes = ((double)M * mxa_block_bytes<AF>() + 2.0 * N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * mxa_block_bytes<AF>() * N / 32.0;
-    if (M <= MXG_SPLIT_MAX_M) {
-        const dim3 grid(N / 32, (M + 15) / 16);
-        SLK_RUN(name, flops, bytes, s,
-                (k_mx_gemm_glu_splitk<AF, WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
-    } else {
-        const dim3 grid((N + 63) / 64, (M + 63) / 64);
-        SLK_RUN(name, flops, bytes, s,
-                (k_mx_gemm_glu_tiled<AF, WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
-    }
-    return SLK_OK;
-}
-
-// mx_gemm_experts' three launches with the fused tile bodies; flag[0] is the prologue's, flag[1] the non-finite rule's
-template <int AF, int WF>
-static int mx_gemm_glu_experts(const char *name, const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
-                               const float *bias, const int *offsets, int E, int M, int N, int K, const GluParams p, uint8_t *h_codes,
-                               uint8_t *h_scales, int *flag, int *ws, hipStream_t s) {
-    const int cap16 = (int)mxe_cap16(E, M), cap64 = (int)mxe_cap64(E, M);
-    const int rows16 = cap16 < 4 * E ? cap16 : 4 * E, rows64 = cap64;
-    SLK_RUN("mx_expert_tiles", 0, 4.0 * (E + 1), s, (k_mx_expert_tiles<<<1, 256, 0, s>>>(offsets, E, M, ws, cap16, flag)));
-    const int *t16 = ws + MXE_HEAD, *t64 = ws + MXE_HEAD + 3 * (size_t)cap16;
-    const double flops = 4.0 * M * N * K;
-    const double bytes = ((double)M * mxa_block_bytes<AF>() + 2.0 * E * N * mxa_block_bytes<WF>()) * K / 32.0 + (double)M * mxa_block_bytes<AF>() * N / 32.0;
-    const dim3 grid16(N / 32, rows16), grid64((N + 63) / 64, rows64);
-    SLK_RUN(name, flops, bytes, s,
-            (k_mx_gemm_glu_experts_splitk<AF, WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, t16, N, K, p, h_codes,
-                                                                                 h_scales, flag + 1)));
-    if (M > MXG_SPLIT_MAX_M)
-        SLK_RUN(name, 0, 0, s,
-                (k_mx_gemm_glu_experts_tiled<AF, WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, t64, N, K, p, h_codes,
-                                                                            h_scales, flag + 1)));
-    return SLK_OK;
 }
 
 extern "C" {
@@ -656,34 +627,62 @@ extern "C" {
 int slk_mx_gemm_glu(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias, int M,
                     int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift, int interleaved, uint8_t *h_codes,
                     uint8_t *h_scales, int *flag, slk_stream_t stream) {
-    SLK_GLU_REQUIRE();
+    static const char *const names[5] = {"mx_gemm_glu", "mx_gemm_glu_a4", "mx_gemm_glu_a6", "mx_gemm_glu_w6", "mx_gemm_glu_w6a6"};
+    if (const int rc = mx_check_gated(M, N, h_scales, flag, alpha, limit, shift, interleaved)) return rc;
+    if (const int rc = mx_check_operands(a_codes, a_scales, w_codes, w_scales, h_codes, "h_codes", M, N, K)) return rc;
+    if (const int rc = mx_check_pair(a_fmt, w_fmt)) return rc;
     SLK_REQUIRE((M + 63) / 64 <= 65535, "M is above the 65535 row tiles of one launch (M = %d)", M);
     SLK_REQUIRE(N / 32 <= 0x7fffffff / 64, "N is above the column tiles of one launch (N = %d)", N);
     hipStream_t s = as_stream(stream);
     const GluParams p = {alpha, limit, shift, interleaved};
-#define SLK_GLU_PAIR(AF, WF, SUFFIX) return mx_gemm_glu<AF, WF>("mx_gemm_glu" SUFFIX, a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag, s)
-    SLK_GLU_PAIRS(SLK_GLU_PAIR);
-#undef SLK_GLU_PAIR
+    return with_pair(a_fmt, w_fmt, [&](auto pair) -> int {
+        typedef decltype(pair) P;
+        const double flops = 4.0 * M * N * K;
+        const double bytes = ((double)M * mxa_block_bytes<P::AF>() + 2.0 * N * mxa_block_bytes<P::WF>()) * K / 32.0 + (double)M * mxa_block_bytes<P::AF>() * N / 32.0;
+        if (M <= MXG_SPLIT_MAX_M) {
+            const dim3 grid(N / 32, (M + 15) / 16);
+            SLK_RUN(names[P::INDEX], flops, bytes, s,
+                    (k_mx_gemm_glu_splitk<P::AF, P::WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
+        } else {
+            const dim3 grid((N + 63) / 64, (M + 63) / 64);
+            SLK_RUN(names[P::INDEX], flops, bytes, s,
+                    (k_mx_gemm_glu_tiled<P::AF, P::WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
+        }
+        return SLK_OK;
+    });
 }
 
+// slk_mx_gemm_experts' three launches with the fused tile bodies; flag[0] is the prologue's, flag[1] the non-finite rule's
 int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
                             const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift,
                             int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag, void *workspace, size_t ws_bytes,
                             slk_stream_t stream) {
+    static const char *const names[5] = {"mx_gemm_glu_experts", "mx_gemm_glu_experts_a4", "mx_gemm_glu_experts_a6", "mx_gemm_glu_experts_w6",
+                                         "mx_gemm_glu_experts_w6a6"};
     SLK_REQUIRE(E >= 1 && E <= MXE_MAX_EXPERTS, "E must be 1 .. %d experts (E = %d)", MXE_MAX_EXPERTS, E);
-    SLK_GLU_REQUIRE();
-    SLK_REQUIRE(offsets, "null offsets");
-    SLK_REQUIRE(workspace && (uintptr_t)workspace % sizeof(int) == 0, "the workspace must be non-null and aligned to 4 bytes");
-    SLK_REQUIRE(ws_bytes >= slk_mx_experts_workspace_bytes(E, M), "the workspace is too small: %zu bytes, slk_mx_experts_workspace_bytes(%d, %d) = %zu",
-                ws_bytes, E, M, slk_mx_experts_workspace_bytes(E, M));
-    SLK_REQUIRE(mxe_cap64(E, M) <= 65535, "M / 64 + E is above the 65535 row tiles of one launch (M = %d, E = %d)", M, E);
+    if (const int rc = mx_check_gated(M, N, h_scales, flag, alpha, limit, shift, interleaved)) return rc;
+    if (const int rc = mx_check_operands(a_codes, a_scales, w_codes, w_scales, h_codes, "h_codes", M, N, K)) return rc;
+    if (const int rc = mx_check_pair(a_fmt, w_fmt)) return rc;
+    if (const int rc = mx_check_experts(E, M, offsets, workspace, ws_bytes)) return rc;
     hipStream_t s = as_stream(stream);
     int *ws = static_cast<int *>(workspace);
     const GluParams p = {alpha, limit, shift, interleaved};
-#define SLK_GLU_PAIR(AF, WF, SUFFIX) \
-    return mx_gemm_glu_experts<AF, WF>("mx_gemm_glu_experts" SUFFIX, a_codes, a_scales, w_codes, w_scales, bias, offsets, E, M, N, K, p, h_codes, h_scales, flag, ws, s)
-    SLK_GLU_PAIRS(SLK_GLU_PAIR);
-#undef SLK_GLU_PAIR
+    ExpertGrid g;
+    if (const int rc = mx_expert_prologue(offsets, E, M, ws, flag, s, g)) return rc;
+    return with_pair(a_fmt, w_fmt, [&](auto pair) -> int {
+        typedef decltype(pair) P;
+        const double flops = 4.0 * M * N * K;
+        const double bytes = ((double)M * mxa_block_bytes<P::AF>() + 2.0 * E * N * mxa_block_bytes<P::WF>()) * K / 32.0 + (double)M * mxa_block_bytes<P::AF>() * N / 32.0;
+        const dim3 grid16(N / 32, g.rows16), grid64((N + 63) / 64, g.rows64);
+        SLK_RUN(names[P::INDEX], flops, bytes, s,
+                (k_mx_gemm_glu_experts_splitk<P::AF, P::WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, g.t16, N, K, p,
+                                                                                          h_codes, h_scales, flag + 1)));
+        if (M > MXG_SPLIT_MAX_M)
+            SLK_RUN(names[P::INDEX], 0, 0, s,
+                    (k_mx_gemm_glu_experts_tiled<P::AF, P::WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, g.t64, N, K, p,
+                                                                                     h_codes, h_scales, flag + 1)));
+        return SLK_OK;
+    });
 }
 
 size_t slk_mx_experts_workspace_bytes(int E, int M) {
@@ -691,60 +690,63 @@ size_t slk_mx_experts_workspace_bytes(int E, int M) {
     return sizeof(int) * (MXE_HEAD + 3 * (mxe_cap16(E, M) + mxe_cap64(E, M)));
 }
 
+// The prologue, the split-K product over the 16-row table and, where an expert can have more than MXG_SPLIT_MAX_M rows at
+// all, the tiled product over the 64-row table; in order on the stream
 int slk_mx_gemm_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
                         const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, int out_dtype, void *out, int *flag,
                         void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    static const char *const names[5] = {"mx_gemm_experts", "mx_gemm_experts_a4", "mx_gemm_experts_a6", "mx_gemm_experts_w6", "mx_gemm_experts_w6a6"};
     SLK_REQUIRE(E >= 1 && E <= MXE_MAX_EXPERTS, "E must be 1 .. %d experts (E = %d)", MXE_MAX_EXPERTS, E);
-    SLK_REQUIRE(M > 0 && N > 0, "M and N must be at least 1 (M = %d, N = %d)", M, N);
-    SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);
+    if (const int rc = mx_check_operands(a_codes, a_scales, w_codes, w_scales, out, "out", M, N, K)) return rc;
     SLK_REQUIRE(known_dtype(out_dtype), "unknown out_dtype %d", out_dtype);
-    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP4 || a_fmt == SLK_MX_ACT_FP6, "unknown a_fmt %d", a_fmt);
-    SLK_REQUIRE(w_fmt == SLK_MX_W_FP4 || w_fmt == SLK_MX_W_FP6, "unknown w_fmt %d", w_fmt);
-    SLK_REQUIRE(!(w_fmt == SLK_MX_W_FP6 && a_fmt == SLK_MX_ACT_FP4),
-                "an MXFP6 layer takes MXFP8 (SLK_MX_ACT_FP8) or MXFP6 (SLK_MX_ACT_FP6) activations (a_fmt = %d)", a_fmt);
-    SLK_REQUIRE(a_codes && a_scales && w_codes && w_scales && out, "null pointer");
-    SLK_REQUIRE(offsets, "null offsets");
+    if (const int rc = mx_check_pair(a_fmt, w_fmt)) return rc;
     SLK_REQUIRE(flag, "null flag");
-    SLK_REQUIRE(aligned16(a_codes) && aligned16(w_codes) && aligned16(out), "a_codes, w_codes and out must be aligned to 16 bytes");
-    SLK_REQUIRE(workspace && (uintptr_t)workspace % sizeof(int) == 0, "the workspace must be non-null and aligned to 4 bytes");
-    SLK_REQUIRE(ws_bytes >= slk_mx_experts_workspace_bytes(E, M), "the workspace is too small: %zu bytes, slk_mx_experts_workspace_bytes(%d, %d) = %zu",
-                ws_bytes, E, M, slk_mx_experts_workspace_bytes(E, M));
-    SLK_REQUIRE(mxe_cap64(E, M) <= 65535, "M / 64 + E is above the 65535 row tiles of one launch (M = %d, E = %d)", M, E);
+    if (const int rc = mx_check_experts(E, M, offsets, workspace, ws_bytes)) return rc;
     hipStream_t s = as_stream(stream);
     int *ws = static_cast<int *>(workspace);
-#define SLK_MXE_PAIR(AF, WF, NAME) return mx_gemm_experts<AF, WF>(NAME, a_codes, a_scales, w_codes, w_scales, bias, offsets, E, M, N, K, out_dtype, out, flag, ws, s)
-    if (w_fmt == SLK_MX_W_FP6) {
-        if (a_fmt == SLK_MX_ACT_FP6) SLK_MXE_PAIR(MXA_E2M3, MXA_E2M3, "mx_gemm_experts_w6a6");
-        SLK_MXE_PAIR(MXA_E4M3, MXA_E2M3, "mx_gemm_experts_w6");
-    }
-    if (a_fmt == SLK_MX_ACT_FP4) SLK_MXE_PAIR(MXA_E2M1, MXA_E2M1, "mx_gemm_experts_a4");
-    if (a_fmt == SLK_MX_ACT_FP6) SLK_MXE_PAIR(MXA_E2M3, MXA_E2M1, "mx_gemm_experts_a6");
-    SLK_MXE_PAIR(MXA_E4M3, MXA_E2M1, "mx_gemm_experts");
-#undef SLK_MXE_PAIR
+    ExpertGrid g;
+    if (const int rc = mx_expert_prologue(offsets, E, M, ws, flag, s, g)) return rc;
+    return with_pair(a_fmt, w_fmt, [&](auto pair) -> int {
+        typedef decltype(pair) P;
+        return with_dtype(out_dtype, [&](auto t) -> int {
+            typedef typename decltype(t)::T T;
+            constexpr int OUT = decltype(t)::OUT;
+            T *Y = static_cast<T *>(out);
+            const double flops = 2.0 * M * N * K;
+            const double bytes = ((double)M * mxa_block_bytes<P::AF>() + (double)E * N * mxa_block_bytes<P::WF>()) * K / 32.0 + (double)M * N * sizeof(T);
+            const dim3 grid16((N + 15) / 16, g.rows16), grid64((N + 63) / 64, g.rows64);
+            SLK_RUN(names[P::INDEX], flops, bytes, s,
+                    (k_mx_gemm_experts_splitk<OUT, P::AF, P::WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, g.t16, N, K, Y)));
+            if (M > MXG_SPLIT_MAX_M)
+                SLK_RUN(names[P::INDEX], 0, 0, s,
+                        (k_mx_gemm_experts_tiled<OUT, P::AF, P::WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, g.t64, N, K, Y)));
+            return SLK_OK;
+        });
+    });
 }
 
 int slk_mx_gemm(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
                 int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
-    return mx_gemm<MXA_E4M3>("mx_gemm", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
+    return mx_gemm(MxPair<MXA_E4M3, MXA_E2M1, 0>(), "mx_gemm", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
 }
 
 int slk_mx_gemm_a4(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
                    int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
-    return mx_gemm<MXA_E2M1>("mx_gemm_a4", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
+    return mx_gemm(MxPair<MXA_E2M1, MXA_E2M1, 1>(), "mx_gemm_a4", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
 }
 
 int slk_mx_gemm_a6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
                    int M, int N, int K, int out_dtype, void *out, slk_stream_t stream) {
-    return mx_gemm<MXA_E2M3>("mx_gemm_a6", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
+    return mx_gemm(MxPair<MXA_E2M3, MXA_E2M1, 2>(), "mx_gemm_a6", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
 }
 
 int slk_mx_gemm_w6(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
                    int M, int N, int K, int a_fmt, int out_dtype, void *out, slk_stream_t stream) {
-    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP6,
-                "an MXFP6 layer takes MXFP8 (SLK_MX_ACT_FP8) or MXFP6 (SLK_MX_ACT_FP6) activations (a_fmt = %d)", a_fmt);
-    if (a_fmt == SLK_MX_ACT_FP6)
-        return mx_gemm<MXA_E2M3, MXA_E2M3>("mx_gemm_w6a6", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
-    return mx_gemm<MXA_E4M3, MXA_E2M3>("mx_gemm_w6", a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
+    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP6, MX_W6_TAKES, a_fmt);  // (this entry's text for an unknown a_fmt as well)
+    return with_pair(a_fmt, SLK_MX_W_FP6, [&](auto pair) -> int {
+        const char *name = decltype(pair)::INDEX == 4 ? "mx_gemm_w6a6" : "mx_gemm_w6";
+        return mx_gemm(pair, name, a_codes, a_scales, w_codes, w_scales, bias, M, N, K, out_dtype, out, stream);
+    });
 }
 
 }  // extern "C"

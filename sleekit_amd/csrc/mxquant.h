@@ -1,5 +1,6 @@
 // What a kernel knows of an MX element format (include/sleekit_amd.h), whichever side of the product it is on: the element
-// encoders, roundings and decoders, the block scale, how one lane's codes are placed in words, stored and read back, and how
+// encoders, roundings and decoders, the block scale, how one lane's codes are placed in words, stored and read back, how 32
+// floats become a scale byte and those words (mxq_encode, the one block encoder of every quantizing kernel), and how
 // a layer's table indices map to codes.  Shared by the converters and the scale search of mx.hip, the product's fragments in
 // mxgemm.hip and the rotation's quantizing epilogue in hadamard.hip, so that all of them write and read the same bits.
 // Two roundings live here: *_code sends a tie to the even code and is the activations' rule (quantized on the fly, as the
@@ -187,6 +188,27 @@ __device__ __forceinline__ void mxa_pack(const float (&x)[N], float inv, unsigne
 // (mx.hip, k_mx_quantize_act).
 template <int FMT>
 __host__ __device__ constexpr int mxq_lanes() { return FMT == MXA_E2M3 ? 2 : 4; }
+
+// The block encoder, once: 32 floats -> one scale byte and each lane's code words.  x: this lane's N contiguous elements
+// of the block, whose 32 / N lanes are neighbours (N = 8: four lanes, two DPP steps; N = 16: two lanes, one).  eb: the
+// block's scale byte, the same in all of its lanes; w: this lane's words of the row's bit stream (mxa_pack under
+// mxa_inverse(eb)).  Returns the block's largest magnitude bits: a caller's non-finite rule is `>= 0x7f800000`, under its
+// own guard, as are its loads and stores.  Every lane of a block must call it.  The plain quantizer (mx.hip), the
+// rotation's epilogue (hadamard.hip) and the fused gate/up product's (mxgemm.hip) write the same bits because this is
+// the one place that makes them.
+template <int FMT, int N>
+__device__ __forceinline__ int mxq_encode(const float (&x)[N], unsigned &eb, unsigned (&w)[N * mxa_bits<FMT>() / 32]) {
+    static_assert(N == 8 || N == 16, "the maximum takes one or two DPP steps: two or four lanes a block");
+    static_assert(N * mxa_bits<FMT>() % 32 == 0, "a lane stores whole dwords: fewer lanes a block for this format");
+    int top = 0;
+#pragma unroll
+    for (int e = 0; e < N; ++e) top = max(top, (int)(__float_as_uint(x[e]) & 0x7fffffffu));
+    top = max(top, dpp_i<DPP_XOR1>(top));
+    if constexpr (N == 8) top = max(top, dpp_i<DPP_XOR2>(top));
+    eb = mxa_scale_byte<FMT>(top);
+    mxa_pack<FMT>(x, mxa_inverse(eb), w);
+    return top;
+}
 
 // One lane's words in memory: one, two or four of them move as one aligned vector, three (16 E2M3 codes: 12 bytes of a
 // row whose blocks are 24) as Codes12, three dwords, every one of them aligned.

@@ -104,6 +104,7 @@ everything runs on the GPU on the current stream, and there is no CPU fallback.
 """
 
 import collections
+import math
 
 import numpy as np
 import torch
@@ -347,14 +348,13 @@ def _torch_dtype(x):
 
 
 # An activation format as plain data: the bits of a code (a_codes is (M, K bits / 8)), its C constant, the C entries of its
-# plain quantizer, its de-quantizer and its product, and how the fused rotate-and-quantize entry is called: its name and
-# whether it takes the constant as its `fmt` argument.
-_Format = collections.namedtuple("_Format", "name bits c_fmt quantize_entry dequantize_entry gemm_entry rotate_entry rotate_takes_fmt")
+# plain quantizer and its de-quantizer, and how the fused rotate-and-quantize entry is called: its name and whether it takes
+# the constant as its `fmt` argument.  (The product's entry depends on the layer's format too: _GEMM below.)
+_Format = collections.namedtuple("_Format", "name bits c_fmt quantize_entry dequantize_entry rotate_entry rotate_takes_fmt")
 _FORMATS = {f.name: f for f in (
-    _Format("mxfp8", 8, _lib.MX_ACT_FP8, "slk_mx_quantize_act", "slk_mx_dequantize_act", "slk_mx_gemm", "slk_mx_rotate_quantize_act", True),
-    _Format("mxfp4", 4, _lib.MX_ACT_FP4, "slk_mx_quantize_act4", "slk_mx_dequantize", "slk_mx_gemm_a4", "slk_mx_rotate_quantize_act", True),
-    _Format("mxfp6_e2m3", 6, _lib.MX_ACT_FP6, "slk_mx_quantize_act6", "slk_mx_dequantize_act6", "slk_mx_gemm_a6", "slk_mx_rotate_quantize_act6",
-            False),
+    _Format("mxfp8", 8, _lib.MX_ACT_FP8, "slk_mx_quantize_act", "slk_mx_dequantize_act", "slk_mx_rotate_quantize_act", True),
+    _Format("mxfp4", 4, _lib.MX_ACT_FP4, "slk_mx_quantize_act4", "slk_mx_dequantize", "slk_mx_rotate_quantize_act", True),
+    _Format("mxfp6_e2m3", 6, _lib.MX_ACT_FP6, "slk_mx_quantize_act6", "slk_mx_dequantize_act6", "slk_mx_rotate_quantize_act6", False),
 )}
 _ACTIVATIONS = tuple(_FORMATS)
 _ACTIVATIONS_ARE = "activations must be " + ", ".join(f'"{name}"' for name in _ACTIVATIONS[:-1]) + f' or "{_ACTIVATIONS[-1]}"'
@@ -407,8 +407,17 @@ def _rotate_quantize_act(Xd, M, K, rotation, fmt):
     return codes, scales, flag
 
 
+# The quantizers' message, of x and of the hidden activations h of a gated MLP alike: h is the down layer's X.
+_H_FINITE = "activations must be finite: X holds a NaN or an infinity"
+
+
 def _raise_finite(flag):
-    _raise_flag(flag, "activations must be finite: X holds a NaN or an infinity")
+    _raise_flag(flag, _H_FINITE)
+
+
+def _quantize_x(Xd, M, K, rotation, fmt):
+    """_quantize_act of a contiguous device X (M, K), behind `rotation` where there is one (inside the quantizer)."""
+    return _rotate_quantize_act(Xd, M, K, rotation, fmt) if rotation is not None else _quantize_act(Xd, M, K, fmt)
 
 
 _MXFP6_TAKES = 'an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations'  # (the one weight format that refuses any)
@@ -419,14 +428,19 @@ def _check_pair(fmt, wf):
         raise ValueError(f'{_MXFP6_TAKES} (got "{fmt.name}")')
 
 
+# The dense product of each (activations, weights) pair: its C entry and whether that entry takes the activations' constant
+# as its `a_fmt` argument (the MXFP6 layer's one entry serves both of its pairs).
+_GEMM = {("mxfp8", "mxfp4"): ("slk_mx_gemm", False), ("mxfp4", "mxfp4"): ("slk_mx_gemm_a4", False),
+         ("mxfp6_e2m3", "mxfp4"): ("slk_mx_gemm_a6", False),
+         ("mxfp8", "mxfp6_e2m3"): ("slk_mx_gemm_w6", True), ("mxfp6_e2m3", "mxfp6_e2m3"): ("slk_mx_gemm_w6", True)}
+
+
 def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"], wf=_FP4):
     out = torch.empty((M, N), dtype=dtype, device=ac.device)
-    if wf is _FP6:
-        _lib.check(_lib.lib.slk_mx_gemm_w6(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, fmt.c_fmt,
-                                           _OUT[dtype], dev.ptr(out), dev.stream_handle()))
-        return out
-    _lib.check(getattr(_lib.lib, fmt.gemm_entry)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K,
-                                                 _OUT[dtype], dev.ptr(out), dev.stream_handle()))
+    entry, takes_fmt = _GEMM[fmt.name, wf.name]
+    which = (fmt.c_fmt,) if takes_fmt else ()
+    _lib.check(getattr(_lib.lib, entry)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, *which, _OUT[dtype],
+                                        dev.ptr(out), dev.stream_handle()))
     return out
 
 
@@ -446,13 +460,110 @@ def _weights(codes, scales, wf=_FP4):
     return N, K
 
 
-def _check_bias(bias, N):
-    if bias is not None and (not isinstance(bias, (np.ndarray, torch.Tensor)) or tuple(bias.shape) != (N,)):
-        raise ValueError(f"bias must be ({N},); got {tuple(getattr(bias, 'shape', ()))}")
+def _expert_weights(codes, scales, wf):
+    """(E, N, K) of stacked packed layers, codes (E, N, K bits / 8) and scales (E, N, K / 32), shapes and dtypes checked."""
+    for x, what in ((codes, "codes"), (scales, "scale bytes")):
+        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 3:
+            raise ValueError(f"{what} of stacked experts must be a 3-D NumPy array or torch tensor (experts, rows, bytes)")
+        if x.dtype not in (torch.uint8, np.uint8):
+            raise ValueError(f"{what} must be torch.uint8 (got {x.dtype})")
+    E, N, width = (int(v) for v in codes.shape)
+    if E < 1 or E > _lib.MX_MAX_EXPERTS or N < 1:
+        raise ValueError(f"codes must hold 1 .. {_lib.MX_MAX_EXPERTS} experts of at least one row (got {tuple(codes.shape)})")
+    K = _columns(width, wf.bits, "codes")
+    if tuple(scales.shape) != (E, N, K // BLOCK):
+        raise ValueError(f"scale bytes must be ({E}, {N}, {K // BLOCK}) for {E} ({N}, {K}) layers; got {tuple(scales.shape)}")
+    return E, N, K
 
 
-def _bias(bias):
-    return None if bias is None else dev.to_device(bias)
+def _check_bias(bias, shape):
+    """A bias of a layer (N,) or of a stack of layers (E, N), or None."""
+    if bias is not None and (not isinstance(bias, (np.ndarray, torch.Tensor)) or tuple(bias.shape) != shape):
+        raise ValueError(f"bias must be {shape}; got {tuple(getattr(bias, 'shape', ()))}")
+
+
+def _hidden(rows, what="the up layer"):
+    """N of an up layer of `rows` = 2 N rows: gate and up, and whole blocks of 32 hidden columns."""
+    if rows % 2 != 0:
+        raise ValueError(f"{what} holds gate and up: its row count must be even (got {rows})")
+    if rows // 2 < BLOCK or rows // 2 % BLOCK != 0:
+        raise ValueError(f"{what} must have 2 N rows with N a positive multiple of {BLOCK} (got {rows} rows)")
+    return rows // 2
+
+
+def _to_device(codes, scales, bias=None):
+    """One side of a product on the device: (codes, aligned for 16-byte loads, scale bytes, float32 bias or None)."""
+    return dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), None if bias is None else dev.to_device(bias)
+
+
+class _Layer(collections.namedtuple("_Layer", "codes scales bias wf E rows N K")):
+    """A packed layer as its caller gave it, checked (_layer): dense (E None) or a stack of E, `rows` rows of K columns in the
+    _Weights wf.  N is the width of what its product writes: rows, or for the up layer of a gated MLP the rows / 2 hidden columns."""
+
+    __slots__ = ()
+
+    def operands(self):
+        return _to_device(self.codes, self.scales, self.bias)
+
+    def has(self, role=""):
+        """The subject of a width mismatch: "the layer has", "the experts' layers have", with the layer's role in an MLP ("up ")."""
+        return f"the {role}layer has" if self.E is None else f"the experts' {role}layers have"
+
+
+def _layer(codes, scales, bias, wf, stacked=False, gated=False):
+    """The _Layer of (codes, scales, bias): shapes and dtypes of a dense layer or of a stack, of N rows or of 2 N (gate and up)."""
+    E, rows, K = _expert_weights(codes, scales, wf) if stacked else (None,) + _weights(codes, scales, wf)
+    N = rows if not gated else _hidden(rows, "every expert's up layer" if stacked else "the up layer")
+    _check_bias(bias, (rows,) if E is None else (E, rows))
+    return _Layer(codes, scales, bias, wf, E, rows, N, K)
+
+
+def _check_rotation(rotation, features, what, owner="the layer has"):
+    if rotation is not None:
+        from .rotation import Rotation
+
+        if not isinstance(rotation, Rotation):
+            raise ValueError(f"{what} must be a Rotation (got {type(rotation).__name__})")
+        if rotation.n != features:
+            raise ValueError(f"the {what} has {rotation.n} features but {owner} {features}")
+
+
+def _act_operands(a_codes, a_scales, fmt):
+    """(M, K) of activations given as codes in the _Format fmt, shapes and dtypes checked."""
+    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
+    K = _columns(width, fmt.bits, "a_codes")
+    _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
+    _check_scale_shape(a_scales, M, K, "activation scale bytes")
+    return M, K
+
+
+def _check_same_k(K, layer):
+    if layer.K != K:
+        raise ValueError(f"a_codes has {K} columns but {layer.has()} {layer.K}")
+
+
+def _float_rows(x, layer, role, dtype):
+    """x given as floats, for the K columns of `layer` (`role`: _Layer.has): (Xd (M, K) on the device, x's leading dimensions,
+    M, the result's dtype -- x's where `dtype` is None).  A dense layer takes x (..., K), a stack of experts x (M, K)."""
+    if layer.E is None:
+        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim < 1:
+            raise ValueError("x must be a NumPy array or torch tensor of at least one dimension")
+        if x.dtype not in _ACT:
+            raise ValueError(f"x must be {_ACT[0]}, torch.bfloat16 or torch.float16 (got {x.dtype})")
+    else:
+        _matrix(x, "x", _ACT)
+    x_dtype = _torch_dtype(x)
+    if dtype is None:
+        dtype = x_dtype
+    _out_dtype(dtype, x)
+    if x.shape[-1] != layer.K:
+        raise ValueError(f"x has {x.shape[-1]} columns but {layer.has(role)} {layer.K}")
+    lead = tuple(x.shape[:-1])
+    M = math.prod(lead)
+    if M < 1 or M >= 1 << 31:
+        raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
+    Xd = dev.to_device(x, x_dtype)
+    return Xd if layer.E is not None else Xd.reshape(M, layer.K), lead, M, dtype
 
 
 def _quantize(X, fmt):
@@ -516,16 +627,10 @@ def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, 
     fmt, wf = _activations(activations), _weight_format(weights)
     _check_pair(fmt, wf)
     _out_dtype(dtype, a_codes)
-    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    K = _columns(width, fmt.bits, "a_codes")
-    _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
-    _check_scale_shape(a_scales, M, K, "activation scale bytes")
-    N, Kw = _weights(codes, scales, wf)
-    if Kw != K:
-        raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
-    _check_bias(bias, N)
-    out = _gemm(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), dev.aligned(dev.to_device(codes, torch.uint8)),
-                dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt, wf)
+    M, K = _act_operands(a_codes, a_scales, fmt)
+    layer = _layer(codes, scales, bias, wf)
+    _check_same_k(K, layer)
+    out = _gemm(*_to_device(a_codes, a_scales)[:2], *layer.operands(), M, layer.N, K, dtype, fmt, wf)
     return dev.like_input(out, a_codes)
 
 
@@ -548,36 +653,13 @@ def linear_mxfp6(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
 def _linear(x, codes, scales, bias, dtype, activations, rotation, wf):
     fmt = _activations(activations)
     _check_pair(fmt, wf)
-    if rotation is not None:
-        from .rotation import Rotation
-
-        if not isinstance(rotation, Rotation):
-            raise ValueError(f"rotation must be a Rotation (got {type(rotation).__name__})")
-    if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim < 1:
-        raise ValueError("x must be a NumPy array or torch tensor of at least one dimension")
-    if x.dtype not in _ACT:
-        raise ValueError(f"x must be {_ACT[0]}, torch.bfloat16 or torch.float16 (got {x.dtype})")
-    if dtype is None:
-        dtype = _torch_dtype(x)
-    _out_dtype(dtype, x)
-    N, K = _weights(codes, scales, wf)
-    if x.shape[-1] != K:
-        raise ValueError(f"x has {x.shape[-1]} columns but the layer has {K}")
-    if rotation is not None and rotation.n != K:
-        raise ValueError(f"the rotation has {rotation.n} features but the layer has {K}")
-    _check_bias(bias, N)
-    lead = tuple(x.shape[:-1])
-    M = int(np.prod(lead, dtype=np.int64))
-    if M < 1 or M >= 1 << 31:
-        raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
-    Xd = dev.to_device(x, _torch_dtype(x)).reshape(M, K)
-    if rotation is not None:
-        ac, asc, flag = _rotate_quantize_act(Xd, M, K, rotation, fmt)
-    else:
-        ac, asc, flag = _quantize_act(Xd, M, K, fmt)
-    out = _gemm(ac, asc, dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, dtype, fmt, wf)
+    layer = _layer(codes, scales, bias, wf)
+    _check_rotation(rotation, layer.K, "rotation")
+    Xd, lead, M, dtype = _float_rows(x, layer, "", dtype)
+    ac, asc, flag = _quantize_x(Xd, M, layer.K, rotation, fmt)
+    out = _gemm(ac, asc, *layer.operands(), M, layer.N, layer.K, dtype, fmt, wf)
     _raise_finite(flag)
-    return dev.like_input(out.reshape(lead + (N,)), x)
+    return dev.like_input(out.reshape(lead + (layer.N,)), x)
 
 
 class _MXModule(torch.nn.Module):
@@ -618,6 +700,15 @@ class _MXModule(torch.nn.Module):
         self.activations = activations
 
 
+def _result_format(result):
+    """The _Weights of an MXResult, read off its widths: bits a code = 8 * codes width / (32 * scales width), 4 or 6."""
+    wide, blocks = int(result.codes.shape[-1]), int(result.scales.shape[-1])
+    by_bits = {wf.bits * BLOCK * blocks: wf for wf in _WEIGHTS.values()}
+    if result.codes.ndim != 2 or result.scales.ndim != 2 or blocks < 1 or 8 * wide not in by_bits:
+        raise ValueError(f"codes of {wide} bytes a row under {blocks} scale bytes are neither 4 nor 6 bits a weight")
+    return by_bits[8 * wide]
+
+
 class MXLinear(_MXModule):
     """A linear layer kept in its packed MX form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
     or None; forward(x) = linear_mxfp4(x, codes, scales, bias, activations=activations).  `activations` ("mxfp8", the
@@ -643,11 +734,7 @@ class MXLinear(_MXModule):
         bits a code = 8 * codes width / (32 * scales width), 4 or 6."""
         if not isinstance(layer, torch.nn.Linear):
             raise ValueError(f"MXLinear.from_result takes a torch.nn.Linear (got {type(layer).__name__})")
-        wide, blocks = int(result.codes.shape[-1]), int(result.scales.shape[-1])
-        by_bits = {wf.bits * BLOCK * blocks: wf for wf in _WEIGHTS.values()}
-        if result.codes.ndim != 2 or result.scales.ndim != 2 or blocks < 1 or 8 * wide not in by_bits:
-            raise ValueError(f"codes of {wide} bytes a row under {blocks} scale bytes are neither 4 nor 6 bits a weight")
-        wf = by_bits[8 * wide]
+        wf = _result_format(result)
         N, K = _weights(result.codes, result.scales, wf)
         if (N, K) != (layer.out_features, layer.in_features):
             raise ValueError(f"the result is of a ({N}, {K}) layer, not of this ({layer.out_features}, {layer.in_features}) one")
@@ -681,27 +768,6 @@ def _raise_flags(*checks):
     for v, (_, message) in zip(torch.cat([f.reshape(1).to(torch.int32) for f, _ in checks]).tolist(), checks):
         if v:
             raise ValueError(message)
-
-
-def _expert_weights(codes, scales, wf):
-    """(E, N, K) of stacked packed layers, codes (E, N, K bits / 8) and scales (E, N, K / 32), shapes and dtypes checked."""
-    for x, what in ((codes, "codes"), (scales, "scale bytes")):
-        if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim != 3:
-            raise ValueError(f"{what} of stacked experts must be a 3-D NumPy array or torch tensor (experts, rows, bytes)")
-        if x.dtype not in (torch.uint8, np.uint8):
-            raise ValueError(f"{what} must be torch.uint8 (got {x.dtype})")
-    E, N, width = (int(v) for v in codes.shape)
-    if E < 1 or E > _lib.MX_MAX_EXPERTS or N < 1:
-        raise ValueError(f"codes must hold 1 .. {_lib.MX_MAX_EXPERTS} experts of at least one row (got {tuple(codes.shape)})")
-    K = _columns(width, wf.bits, "codes")
-    if tuple(scales.shape) != (E, N, K // BLOCK):
-        raise ValueError(f"scale bytes must be ({E}, {N}, {K // BLOCK}) for {E} ({N}, {K}) layers; got {tuple(scales.shape)}")
-    return E, N, K
-
-
-def _check_expert_bias(bias, E, N):
-    if bias is not None and (not isinstance(bias, (np.ndarray, torch.Tensor)) or tuple(bias.shape) != (E, N)):
-        raise ValueError(f"bias must be ({E}, {N}); got {tuple(getattr(bias, 'shape', ()))}")
 
 
 def _check_offsets(offsets, E):
@@ -740,18 +806,12 @@ def matmul_mx_experts(a_codes, a_scales, codes, scales, offsets, bias=None, dtyp
     fmt, wf = _activations(activations), _weight_format(weights)
     _check_pair(fmt, wf)
     _out_dtype(dtype, a_codes)
-    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    K = _columns(width, fmt.bits, "a_codes")
-    _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
-    _check_scale_shape(a_scales, M, K, "activation scale bytes")
-    E, N, Kw = _expert_weights(codes, scales, wf)
-    if Kw != K:
-        raise ValueError(f"a_codes has {K} columns but the experts' layers have {Kw}")
-    _check_expert_bias(bias, E, N)
-    _check_offsets(offsets, E)
-    out, flag = _gemm_experts(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8),
-                              dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
-                              dev.to_device(offsets, torch.int32), E, M, N, K, dtype, fmt, wf)
+    M, K = _act_operands(a_codes, a_scales, fmt)
+    layer = _layer(codes, scales, bias, wf, stacked=True)
+    _check_same_k(K, layer)
+    _check_offsets(offsets, layer.E)
+    out, flag = _gemm_experts(*_to_device(a_codes, a_scales)[:2], *layer.operands(), dev.to_device(offsets, torch.int32), layer.E, M, layer.N, K,
+                              dtype, fmt, wf)
     _raise_flags((flag, _OFFSETS_RULE))
     return dev.like_input(out, a_codes)
 
@@ -759,30 +819,13 @@ def matmul_mx_experts(a_codes, a_scales, codes, scales, offsets, bias=None, dtyp
 def _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotation, wf, also=()):
     fmt = _activations(activations)
     _check_pair(fmt, wf)
-    if rotation is not None:
-        from .rotation import Rotation
-
-        if not isinstance(rotation, Rotation):
-            raise ValueError(f"rotation must be a Rotation (got {type(rotation).__name__})")
-    M, Kx = _matrix(x, "x", _ACT)
-    if dtype is None:
-        dtype = _torch_dtype(x)
-    _out_dtype(dtype, x)
-    E, N, K = _expert_weights(codes, scales, wf)
-    if Kx != K:
-        raise ValueError(f"x has {Kx} columns but the experts' layers have {K}")
-    if rotation is not None and rotation.n != K:
-        raise ValueError(f"the rotation has {rotation.n} features but the layers have {K}")
-    _check_expert_bias(bias, E, N)
-    _check_offsets(offsets, E)
-    Xd = dev.to_device(x, _torch_dtype(x))
-    if rotation is not None:
-        ac, asc, finite = _rotate_quantize_act(Xd, M, K, rotation, fmt)
-    else:
-        ac, asc, finite = _quantize_act(Xd, M, K, fmt)
-    out, flag = _gemm_experts(ac, asc, dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
-                              dev.to_device(offsets, torch.int32), E, M, N, K, dtype, fmt, wf)
-    _raise_flags(*also, (finite, "activations must be finite: X holds a NaN or an infinity"), (flag, _OFFSETS_RULE))
+    layer = _layer(codes, scales, bias, wf, stacked=True)
+    _check_rotation(rotation, layer.K, "rotation", "the layers have")
+    _check_offsets(offsets, layer.E)
+    Xd, _, M, dtype = _float_rows(x, layer, "", dtype)
+    ac, asc, finite = _quantize_x(Xd, M, layer.K, rotation, fmt)
+    out, flag = _gemm_experts(ac, asc, *layer.operands(), dev.to_device(offsets, torch.int32), layer.E, M, layer.N, layer.K, dtype, fmt, wf)
+    _raise_flags(*also, (finite, _H_FINITE), (flag, _OFFSETS_RULE))
     return dev.like_input(out, x)
 
 
@@ -882,16 +925,12 @@ class MXExperts(_MXModule):
         if not results:
             raise ValueError("MXExperts.from_results takes at least one MXResult")
         first = results[0]
-        wide, blocks = int(first.codes.shape[-1]), int(first.scales.shape[-1])
-        by_bits = {wf.bits * BLOCK * blocks: wf for wf in _WEIGHTS.values()}
-        if first.codes.ndim != 2 or first.scales.ndim != 2 or blocks < 1 or 8 * wide not in by_bits:
-            raise ValueError(f"codes of {wide} bytes a row under {blocks} scale bytes are neither 4 nor 6 bits a weight")
-        wf = by_bits[8 * wide]
+        wf = _result_format(first)
         N, K = _weights(first.codes, first.scales, wf)
         for e, r in enumerate(results):
             if tuple(r.codes.shape) != tuple(first.codes.shape) or tuple(r.scales.shape) != tuple(first.scales.shape):
                 raise ValueError(f"expert {e} is not a ({N}, {K}) layer of the first expert's format")
-        _check_expert_bias(biases, len(results), N)
+        _check_bias(biases, (len(results), N))
         if device is None:
             device = first.codes.device if isinstance(first.codes, torch.Tensor) else dev.require_gpu()
         self = cls(len(results), K, N, biases is not None, device, activations, wf.name)
@@ -963,7 +1002,6 @@ def quantize_experts(Ws, Hs, weights="mxfp4", act_order="diag", damp=0.01, scale
 #     mlp = MXGatedMLP.from_results(up_linear, up_result, down_linear, down_result);  y = mlp(x)
 # h_codes / h_scales are in the activations' own format, exactly as that format's quantizer writes them, and bit for bit
 # those of the three-step route matmul_mx(..., dtype=float32), glu(..., dtype=float32), quantize_mxfp8 / _mxfp4_act / _mxfp6_act.
-_H_FINITE = "activations must be finite: X holds a NaN or an infinity"  # (the quantizers' message: h is the down layer's X)
 _Gate = collections.namedtuple("_Gate", "alpha limit shift interleaved")
 _GATE_DEFAULT = _Gate(1.0, None, 0.0, False)
 
@@ -982,15 +1020,6 @@ def _gate(alpha, limit, shift, interleaved):
 
 def _gate_args(gate):
     return gate.alpha, float("inf") if gate.limit is None else gate.limit, gate.shift, int(gate.interleaved)
-
-
-def _hidden(rows, what="the up layer"):
-    """N of an up layer of `rows` = 2 N rows: gate and up, and whole blocks of 32 hidden columns."""
-    if rows % 2 != 0:
-        raise ValueError(f"{what} holds gate and up: its row count must be even (got {rows})")
-    if rows // 2 < BLOCK or rows // 2 % BLOCK != 0:
-        raise ValueError(f"{what} must have 2 N rows with N a positive multiple of {BLOCK} (got {rows} rows)")
-    return rows // 2
 
 
 def _glu(Yd, M, N, gate, dtype):
@@ -1034,7 +1063,7 @@ def _gemm_glu(ac, asc, wc, wsc, bias, M, N, K, fmt, wf, gate, fused=True, rotati
                                             *_gate_args(gate), dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
         return codes, scales, flag
     h = _glu(_gemm(ac, asc, wc, wsc, bias, M, 2 * N, K, torch.float32, fmt, wf), M, N, gate, torch.float32)
-    return _rotate_quantize_act(h, M, N, rotation, fmt) if rotation is not None else _quantize_act(h, M, N, fmt)
+    return _quantize_x(h, M, N, rotation, fmt)
 
 
 def _gemm_glu_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, fmt, wf, gate, fused=True, rotation=None):
@@ -1050,17 +1079,8 @@ def _gemm_glu_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, fmt, wf, gate
         return codes, scales, flags[0], flags[1]
     y, bad = _gemm_experts(ac, asc, wc, wsc, bias, offsets, E, M, 2 * N, K, torch.float32, fmt, wf)
     h = _glu(y, M, N, gate, torch.float32)
-    codes, scales, flag = _rotate_quantize_act(h, M, N, rotation, fmt) if rotation is not None else _quantize_act(h, M, N, fmt)
+    codes, scales, flag = _quantize_x(h, M, N, rotation, fmt)
     return codes, scales, bad, flag
-
-
-def _act_operands(a_codes, a_scales, fmt):
-    """(M, K) of quantized activations in the _Format fmt, shapes and dtypes checked."""
-    M, width = _matrix(a_codes, "a_codes", (torch.uint8, np.uint8))
-    K = _columns(width, fmt.bits, "a_codes")
-    _matrix(a_scales, "activation scale bytes", (torch.uint8, np.uint8))
-    _check_scale_shape(a_scales, M, K, "activation scale bytes")
-    return M, K
 
 
 def _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved, fused=True):
@@ -1069,13 +1089,9 @@ def _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights,
     _check_pair(fmt, wf)
     gate = _gate(alpha, limit, shift, interleaved)
     M, K = _act_operands(a_codes, a_scales, fmt)
-    rows, Kw = _weights(codes, scales, wf)
-    N = _hidden(rows)
-    if Kw != K:
-        raise ValueError(f"a_codes has {K} columns but the layer has {Kw}")
-    _check_bias(bias, 2 * N)
-    return _gemm_glu(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8), dev.aligned(dev.to_device(codes, torch.uint8)),
-                     dev.to_device(scales, torch.uint8), _bias(bias), M, N, K, fmt, wf, gate, fused)
+    up = _layer(codes, scales, bias, wf, gated=True)
+    _check_same_k(K, up)
+    return _gemm_glu(*_to_device(a_codes, a_scales)[:2], *up.operands(), M, up.N, K, fmt, wf, gate, fused)
 
 
 def matmul_mx_glu(a_codes, a_scales, codes, scales, bias=None, activations="mxfp8", weights="mxfp4", alpha=1.0, limit=None, shift=0.0,
@@ -1095,15 +1111,11 @@ def _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, acti
     _check_pair(fmt, wf)
     gate = _gate(alpha, limit, shift, interleaved)
     M, K = _act_operands(a_codes, a_scales, fmt)
-    E, rows, Kw = _expert_weights(codes, scales, wf)
-    N = _hidden(rows, "every expert's up layer")
-    if Kw != K:
-        raise ValueError(f"a_codes has {K} columns but the experts' layers have {Kw}")
-    _check_expert_bias(bias, E, 2 * N)
-    _check_offsets(offsets, E)
-    return _gemm_glu_experts(dev.aligned(dev.to_device(a_codes, torch.uint8)), dev.to_device(a_scales, torch.uint8),
-                             dev.aligned(dev.to_device(codes, torch.uint8)), dev.to_device(scales, torch.uint8), _bias(bias),
-                             dev.to_device(offsets, torch.int32), E, M, N, K, fmt, wf, gate, fused)
+    up = _layer(codes, scales, bias, wf, stacked=True, gated=True)
+    _check_same_k(K, up)
+    _check_offsets(offsets, up.E)
+    return _gemm_glu_experts(*_to_device(a_codes, a_scales)[:2], *up.operands(), dev.to_device(offsets, torch.int32), up.E, M, up.N, K, fmt, wf, gate,
+                             fused)
 
 
 def matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias=None, activations="mxfp8", weights="mxfp4", alpha=1.0, limit=None,
@@ -1116,14 +1128,15 @@ def matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias=None, 
     return dev.like_input(hc, a_codes), dev.like_input(hs, a_codes)
 
 
-def _check_rotation(rotation, features, what):
-    if rotation is not None:
-        from .rotation import Rotation
-
-        if not isinstance(rotation, Rotation):
-            raise ValueError(f"{what} must be a Rotation (got {type(rotation).__name__})")
-        if rotation.n != features:
-            raise ValueError(f"the {what} has {rotation.n} features but the layer has {features}")
+def _mlp_layers(up, down, wf_up, wf_down, stacked=False):
+    """The two _Layers of a gated MLP from (codes, scales, bias) each, the down layer over the up layer's hidden columns."""
+    up, down = _layer(*up, wf_up, stacked, gated=True), _layer(*down, wf_down, stacked)
+    if stacked and down.E != up.E:
+        raise ValueError(f"the up layers are of {up.E} experts but the down layers of {down.E}")
+    if down.K != up.N:
+        raise ValueError(f"the down layers have {down.K} columns but the up layers give {up.N} hidden columns" if stacked else
+                         f"the down layer has {down.K} columns but the up layer gives {up.N} hidden columns")
+    return up, down
 
 
 def _gated_mlp(x, up, down, dtype, activations, gate, rotation, down_rotation, fused, wf_up, wf_down):
@@ -1131,36 +1144,15 @@ def _gated_mlp(x, up, down, dtype, activations, gate, rotation, down_rotation, f
     fmt = _activations(activations)
     _check_pair(fmt, wf_up)
     _check_pair(fmt, wf_down)
-    if not isinstance(x, (np.ndarray, torch.Tensor)) or x.ndim < 1:
-        raise ValueError("x must be a NumPy array or torch tensor of at least one dimension")
-    if x.dtype not in _ACT:
-        raise ValueError(f"x must be {_ACT[0]}, torch.bfloat16 or torch.float16 (got {x.dtype})")
-    if dtype is None:
-        dtype = _torch_dtype(x)
-    _out_dtype(dtype, x)
-    rows, K = _weights(up[0], up[1], wf_up)
-    N = _hidden(rows)
-    Nd, Kd = _weights(down[0], down[1], wf_down)
-    if Kd != N:
-        raise ValueError(f"the down layer has {Kd} columns but the up layer gives {N} hidden columns")
-    if x.shape[-1] != K:
-        raise ValueError(f"x has {x.shape[-1]} columns but the up layer has {K}")
-    _check_rotation(rotation, K, "rotation")
-    _check_rotation(down_rotation, N, "down_rotation")
-    _check_bias(up[2], 2 * N)
-    _check_bias(down[2], Nd)
-    lead = tuple(x.shape[:-1])
-    M = int(np.prod(lead, dtype=np.int64))
-    if M < 1 or M >= 1 << 31:
-        raise ValueError(f"x must have 1 <= rows < 2^31 (got {tuple(x.shape)})")
-    Xd = dev.to_device(x, _torch_dtype(x)).reshape(M, K)
-    ac, asc, finite = _rotate_quantize_act(Xd, M, K, rotation, fmt) if rotation is not None else _quantize_act(Xd, M, K, fmt)
-    hc, hs, h_finite = _gemm_glu(ac, asc, dev.aligned(dev.to_device(up[0], torch.uint8)), dev.to_device(up[1], torch.uint8), _bias(up[2]), M, N, K,
-                                 fmt, wf_up, gate, fused, down_rotation)
-    out = _gemm(hc, hs, dev.aligned(dev.to_device(down[0], torch.uint8)), dev.to_device(down[1], torch.uint8), _bias(down[2]), M, Nd, N, dtype,
-                fmt, wf_down)
+    up, down = _mlp_layers(up, down, wf_up, wf_down)
+    _check_rotation(rotation, up.K, "rotation")
+    _check_rotation(down_rotation, up.N, "down_rotation")
+    Xd, lead, M, dtype = _float_rows(x, up, "up ", dtype)
+    ac, asc, finite = _quantize_x(Xd, M, up.K, rotation, fmt)
+    hc, hs, h_finite = _gemm_glu(ac, asc, *up.operands(), M, up.N, up.K, fmt, wf_up, gate, fused, down_rotation)
+    out = _gemm(hc, hs, *down.operands(), M, down.N, up.N, dtype, fmt, wf_down)
     _raise_flags((finite, _H_FINITE), (h_finite, _H_FINITE))
-    return dev.like_input(out.reshape(lead + (Nd,)), x)
+    return dev.like_input(out.reshape(lead + (down.N,)), x)
 
 
 def gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales, up_bias=None, down_bias=None, dtype=None, activations="mxfp8", weights="mxfp4",
@@ -1183,31 +1175,15 @@ def _gated_mlp_experts(x, up, down, offsets, dtype, activations, gate, rotation,
     fmt = _activations(activations)
     _check_pair(fmt, wf_up)
     _check_pair(fmt, wf_down)
-    M, Kx = _matrix(x, "x", _ACT)
-    if dtype is None:
-        dtype = _torch_dtype(x)
-    _out_dtype(dtype, x)
-    E, rows, K = _expert_weights(up[0], up[1], wf_up)
-    N = _hidden(rows, "every expert's up layer")
-    Ed, Nd, Kd = _expert_weights(down[0], down[1], wf_down)
-    if Ed != E:
-        raise ValueError(f"the up layers are of {E} experts but the down layers of {Ed}")
-    if Kd != N:
-        raise ValueError(f"the down layers have {Kd} columns but the up layers give {N} hidden columns")
-    if Kx != K:
-        raise ValueError(f"x has {Kx} columns but the experts' up layers have {K}")
-    _check_rotation(rotation, K, "rotation")
-    _check_rotation(down_rotation, N, "down_rotation")
-    _check_expert_bias(up[2], E, 2 * N)
-    _check_expert_bias(down[2], E, Nd)
-    _check_offsets(offsets, E)
-    Xd = dev.to_device(x, _torch_dtype(x))
+    up, down = _mlp_layers(up, down, wf_up, wf_down, stacked=True)
+    _check_rotation(rotation, up.K, "rotation")
+    _check_rotation(down_rotation, up.N, "down_rotation")
+    _check_offsets(offsets, up.E)
+    Xd, _, M, dtype = _float_rows(x, up, "up ", dtype)
     od = dev.to_device(offsets, torch.int32)
-    ac, asc, finite = _rotate_quantize_act(Xd, M, K, rotation, fmt) if rotation is not None else _quantize_act(Xd, M, K, fmt)
-    hc, hs, bad, h_finite = _gemm_glu_experts(ac, asc, dev.aligned(dev.to_device(up[0], torch.uint8)), dev.to_device(up[1], torch.uint8), _bias(up[2]),
-                                              od, E, M, N, K, fmt, wf_up, gate, fused, down_rotation)
-    out, _ = _gemm_experts(hc, hs, dev.aligned(dev.to_device(down[0], torch.uint8)), dev.to_device(down[1], torch.uint8), _bias(down[2]), od, E, M,
-                           Nd, N, dtype, fmt, wf_down)
+    ac, asc, finite = _quantize_x(Xd, M, up.K, rotation, fmt)
+    hc, hs, bad, h_finite = _gemm_glu_experts(ac, asc, *up.operands(), od, up.E, M, up.N, up.K, fmt, wf_up, gate, fused, down_rotation)
+    out, _ = _gemm_experts(hc, hs, *down.operands(), od, up.E, M, down.N, up.N, dtype, fmt, wf_down)
     _raise_flags(*also, (finite, _H_FINITE), (bad, _OFFSETS_RULE), (h_finite, _H_FINITE))
     return dev.like_input(out, x)
 

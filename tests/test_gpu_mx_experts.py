@@ -205,6 +205,29 @@ def test_invalid_offsets_raise_and_leave_no_tile(offsets):
     assert not mx.matmul_mx_experts(*ops, good).any()
 
 
+def test_two_raised_flags_give_the_first_message():
+    """E = 2, M = 4, K = 32, N = 16, MXFP8 on MXFP4.  A NaN in x with offsets that break the rule: the finite message, which
+    linear_mx_experts reads first.  A NaN in x with an expert id of E: the id message, which forward_tokens reads first.
+    (Invalid offsets are refused by the prologue before any address is made from them.)"""
+    from sleekit_amd import mx
+
+    E, M, N, K = 2, 4, 16, 32
+    _, _, codes, scales = tiny_operands(E, M, N, K)
+    x = torch.ones((M, K), device="cuda")
+    x[2, 5] = float("nan")
+    with pytest.raises(ValueError) as raised:
+        mx.linear_mx_experts(x, codes, scales, torch.tensor([0, 3, 2], dtype=torch.int32, device="cuda"))
+    assert str(raised.value) == mx._H_FINITE
+    mod = mx.MXExperts(E, K, N, bias=False).cuda()
+    ids = torch.tensor([[0], [1], [E], [0]], device="cuda")
+    with pytest.raises(ValueError) as raised:
+        mod.forward_tokens(x, ids)
+    assert str(raised.value) == mx._ids_message(E)
+    with pytest.raises(ValueError) as raised:   # ... and each of the two alone still has its own
+        mod.forward_tokens(x, ids.clamp(0, E - 1))
+    assert str(raised.value) == mx._H_FINITE
+
+
 # ---------------------------------------------------------------------------------------------------------------- 4. surface
 @pytest.mark.parametrize("activations,weights", PAIRS)
 def test_linear_is_quantizer_then_product(activations, weights):

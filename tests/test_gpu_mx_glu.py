@@ -436,3 +436,55 @@ def test_forward_tokens_against_a_loop_of_gated_mlps(gated):
         mlp.forward_tokens(x, beyond, gates)
     with pytest.raises(ValueError, match=r"offsets\[0\] == 0"):
         mlp(x[order // k], offsets.flip(0).contiguous())
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8. which message wins
+def tiny_mlp(mx, rng, E=2, K=32, N=32, Nd=16):
+    """MXExpertsMLP of E experts: up layers of 2 N = 64 rows, down layers 16 x 32, MXFP8 on MXFP4."""
+    up, down = mx.MXExperts(E, K, 2 * N).cuda(), mx.MXExperts(E, N, Nd).cuda()
+    for mod, rows, cols in ((up, 2 * N, K), (down, Nd, N)):
+        c, s = random_experts(rng, E, rows, cols, 118, 123, W4)
+        mod.codes.copy_(torch.from_numpy(c)), mod.scales.copy_(torch.from_numpy(s))
+    return mx.MXExpertsMLP(up, down)
+
+
+@pytest.mark.parametrize("fused", [True, False])
+def test_two_raised_flags_give_the_first_message(fused, monkeypatch):
+    """E = 2, M = 4, K = 32, N = 32.  (a) a NaN in x and offsets that break the rule: the finite message; (b) a NaN in x and an
+    expert id of E: the id message; (c) finite x against an up layer of scale bytes 254, so that h overflows: the finite message;
+    (d) valid x and invalid offsets: the offsets rule, and the result's buffer keeps its sentinel.  (Invalid offsets are refused
+    by the prologue before any address is made from them.)"""
+    from sleekit_amd import mx
+
+    E, M, K, N, Nd = 2, 4, 32, 32, 16
+    rng = np.random.default_rng(27)
+    mlp = tiny_mlp(mx, rng)
+    x = torch.from_numpy(block_gaussian(rng, M, K)).cuda()
+    nan = x.clone()
+    nan[1, 3] = float("nan")
+    bad_offsets = torch.tensor([0, 3, 2], dtype=torch.int32, device="cuda")
+
+    def message(call):
+        with pytest.raises(ValueError) as raised:
+            call()
+        return str(raised.value)
+
+    assert message(lambda: mlp(nan, bad_offsets, fused=fused)) == mx._H_FINITE                                           # (a)
+    assert message(lambda: mlp.forward_tokens(nan, torch.tensor([[0], [1], [E], [0]], device="cuda"), fused=fused)) == mx._ids_message(E)  # (b)
+    up = (mlp.up.codes[0], torch.full_like(mlp.up.scales[0], 254))                                                      # (c)
+    assert bool(torch.isfinite(x).all())
+    assert message(lambda: mx.gated_mlp_mx(100.0 * x, *up, mlp.down.codes[0], mlp.down.scales[0], fused=fused)) == mx._H_FINITE
+    # (d): every (M, Nd) float32 buffer the call allocates starts as sentinel bytes; the last of them is the result's
+    made, empty = [], torch.empty
+
+    def sentinel_empty(*args, **kw):
+        t = empty(*args, **kw)
+        if tuple(t.shape) == (M, Nd) and t.dtype == torch.float32:
+            t.view(torch.uint8).fill_(0x5A)
+            made.append(t)
+        return t
+
+    monkeypatch.setattr(torch, "empty", sentinel_empty)
+    assert message(lambda: mlp(x, bad_offsets, fused=fused)) == mx._OFFSETS_RULE
+    monkeypatch.undo()
+    assert made and bool((made[-1].view(torch.uint8) == 0x5A).all())

@@ -95,6 +95,31 @@ def test_argument_errors_do_not_touch_the_gpu():
     assert lib.slk_mx_dequantize_act(p, p, 4, 64, _lib.DTYPE_F16, p + 2, None, None) == _lib.E_ARG
 
 
+def test_every_requirement_of_the_dense_products_has_its_text():
+    """Each requirement of slk_mx_gemm, _a4, _a6 and _w6, tripped alone, with a word of its text in slk_last_error()."""
+    from sleekit_amd import _lib
+
+    lib, p, F32 = _lib.lib, 4096, _lib.DTYPE_F32
+    entries = [(getattr(lib, name), ()) for name in ("slk_mx_gemm", "slk_mx_gemm_a4", "slk_mx_gemm_a6")]
+    entries += [(lib.slk_mx_gemm_w6, (a_fmt,)) for a_fmt in (_lib.MX_ACT_FP8, _lib.MX_ACT_FP6)]
+    for entry, a_fmt in entries:
+        def call(a=p, asc=p, w=p, ws=p, M=4, N=4, K=64, out_dtype=F32, out=p):
+            return entry(a, asc, w, ws, None, M, N, K, *a_fmt, out_dtype, out, None)
+
+        for kw, word in ((dict(M=0), b"at least 1"), (dict(N=0), b"at least 1"), (dict(M=-1), b"at least 1"),
+                         (dict(K=0), b"multiple of 32"), (dict(K=16), b"multiple of 32"), (dict(K=48), b"multiple of 32"),
+                         (dict(out_dtype=7), b"out_dtype"),
+                         (dict(a=None), b"null pointer"), (dict(asc=None), b"null pointer"), (dict(w=None), b"null pointer"),
+                         (dict(ws=None), b"null pointer"), (dict(out=None), b"null pointer"),
+                         (dict(a=p + 8), b"aligned to 16"), (dict(w=p + 4), b"aligned to 16"), (dict(out=p + 2), b"aligned to 16"),
+                         (dict(M=65535 * 64 + 1), b"row tiles")):
+            assert call(**kw) == _lib.E_ARG, kw
+            assert word in lib.slk_last_error(), (kw, lib.slk_last_error())
+    for a_fmt in (_lib.MX_ACT_FP4, 3, -1):   # slk_mx_gemm_w6 has one text for every a_fmt it does not take
+        assert lib.slk_mx_gemm_w6(p, p, p, p, None, 4, 4, 64, a_fmt, F32, p, None) == _lib.E_ARG
+        assert b"MXFP6 layer takes" in lib.slk_last_error() and b"a_fmt = %d" % a_fmt in lib.slk_last_error()
+
+
 def test_python_refusals_come_before_the_device():
     """Shape and dtype errors are ValueError and need no GPU."""
     import pytest

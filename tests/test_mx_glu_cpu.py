@@ -91,6 +91,10 @@ def test_argument_errors_do_not_touch_the_gpu():
         refused(call(w_fmt=2), "w_fmt")
         refused(call(a_fmt=FP4, w_fmt=W6), "MXFP6 layer")
     refused(gemm(M=65535 * 64 + 1), "row tiles")
+    for call in (gemm, experts):
+        refused(call(N=1 << 30), "below 2^30")    # (which also bounds the column tiles of one launch: that text has no input of its own)
+        refused(call(N=-(1 << 30)), "multiple of 32")
+    refused(experts(M=64 * 65535, ws_bytes=1 << 30), "row tiles")
     refused(experts(offsets=None), "offsets")
     refused(experts(E=0), "experts")
     refused(experts(E=_lib.MX_MAX_EXPERTS + 1), "experts")
@@ -160,6 +164,90 @@ def test_python_refusals_come_before_the_device():
                  lambda: mx.MXExpertsMLP(mx.MXExperts(2, 64, 64), mx.MXExperts(3, 32, 8)), lambda: mx.MXExpertsMLP(mx.MXExperts(2, 64, 64), mx.MXExperts(2, 64, 8))):
         with pytest.raises(ValueError):
             make()
+
+
+def test_every_route_refuses_with_its_own_text():
+    """The checks the routes share -- activations as codes or as floats, the layer, its bias, the rotation, the offsets, the
+    format pair -- each reached through every public route that has it, one bad argument at a time, with that route's text."""
+    from sleekit_amd import mx
+    from sleekit_amd.rotation import Rotation
+
+    W6 = "mxfp6_e2m3"
+    x, x96 = np.zeros((4, 64), np.float32), np.zeros((4, 96), np.float32)
+    a8, a4, aE = np.zeros((4, 64), np.uint8), np.zeros((4, 32), np.uint8), np.full((4, 2), 127, np.uint8)
+    a96, aE96 = np.zeros((4, 96), np.uint8), np.full((4, 3), 127, np.uint8)
+    c, c6, s = np.zeros((8, 32), np.uint8), np.zeros((8, 48), np.uint8), np.full((8, 2), 127, np.uint8)
+    ec, ec6, es = np.zeros((2, 8, 32), np.uint8), np.zeros((2, 8, 48), np.uint8), np.full((2, 8, 2), 127, np.uint8)
+    up, ups = np.zeros((128, 32), np.uint8), np.full((128, 2), 127, np.uint8)        # N = 64 hidden columns; the down layer is (c, s)
+    eup, eups = np.zeros((2, 128, 32), np.uint8), np.full((2, 128, 2), 127, np.uint8)
+    off = np.array([0, 2, 4], np.int32)
+    rot128 = Rotation(128, device="cpu")
+    float_dtypes = "x must be torch.float32, torch.bfloat16 or torch.float16"
+    for call, text in (
+        # x given as floats: dtype, dimensions, width
+        (lambda: mx.linear_mxfp4(x.astype(np.float64), c, s), float_dtypes),
+        (lambda: mx.linear_mxfp6(x.astype(np.float64), c6, s), float_dtypes),
+        (lambda: mx.gated_mlp_mx(x.astype(np.float64), up, ups, c, s), float_dtypes),
+        (lambda: mx.linear_mx_experts(x.astype(np.float64), ec, es, off), r"x must be torch.float32 \(got float64\)"),
+        (lambda: mx.linear_mxfp4(np.zeros((), np.float32), c, s), "x must be a NumPy array or torch tensor of at least one dimension"),
+        (lambda: mx.linear_mxfp6(np.zeros((), np.float32), c6, s), "x must be a NumPy array or torch tensor of at least one dimension"),
+        (lambda: mx.gated_mlp_mx(np.zeros((), np.float32), up, ups, c, s), "x must be a NumPy array or torch tensor of at least one dimension"),
+        (lambda: mx.linear_mx_experts(x[0], ec, es, off), "x must be a 2-D NumPy array or torch tensor"),
+        (lambda: mx.linear_mxfp4(x96, c, s), "x has 96 columns but the layer has 64"),
+        (lambda: mx.linear_mxfp6(x96, c6, s), "x has 96 columns but the layer has 64"),
+        (lambda: mx.linear_mx_experts(x96, ec, es, off), "x has 96 columns but the experts' layers have 64"),
+        (lambda: mx.gated_mlp_mx(x96, up, ups, c, s), "x has 96 columns but the up layer has 64"),
+        # activations given as codes
+        (lambda: mx.matmul_mx(a8[0], aE, c, s), "a_codes must be a 2-D NumPy array or torch tensor"),
+        (lambda: mx.matmul_mx_experts(a8[0], aE, ec, es, off), "a_codes must be a 2-D NumPy array or torch tensor"),
+        (lambda: mx.matmul_mx(a8.astype(np.int32), aE, c, s), r"a_codes must be torch.uint8 \(got int32\)"),
+        (lambda: mx.matmul_mx_experts(a8.astype(np.int32), aE, ec, es, off), r"a_codes must be torch.uint8 \(got int32\)"),
+        (lambda: mx.matmul_mx(a8, aE[:, :1], c, s), r"activation scale bytes must be \(4, 2\)"),
+        (lambda: mx.matmul_mx_experts(a8, aE[:, :1], ec, es, off), r"activation scale bytes must be \(4, 2\)"),
+        (lambda: mx.matmul_mx(a96, aE96, c, s), "a_codes has 96 columns but the layer has 64"),
+        (lambda: mx.matmul_mx_experts(a96, aE96, ec, es, off), "a_codes has 96 columns but the experts' layers have 64"),
+        # the rotation: its type, and its size for `rotation` and for `down_rotation`
+        (lambda: mx.linear_mxfp4(x, c, s, rotation="hadamard"), r"rotation must be a Rotation \(got str\)"),
+        (lambda: mx.linear_mxfp6(x, c6, s, rotation="hadamard"), r"rotation must be a Rotation \(got str\)"),
+        (lambda: mx.linear_mx_experts(x, ec, es, off, rotation="hadamard"), r"rotation must be a Rotation \(got str\)"),
+        (lambda: mx.gated_mlp_mx(x, up, ups, c, s, rotation="hadamard"), r"^rotation must be a Rotation \(got str\)"),
+        (lambda: mx.gated_mlp_mx(x, up, ups, c, s, down_rotation="hadamard"), r"^down_rotation must be a Rotation \(got str\)"),
+        (lambda: mx.linear_mxfp4(x, c, s, rotation=rot128), "the rotation has 128 features but the layer has 64"),
+        (lambda: mx.linear_mxfp6(x, c6, s, rotation=rot128), "the rotation has 128 features but the layer has 64"),
+        (lambda: mx.linear_mx_experts(x, ec, es, off, rotation=rot128), "the rotation has 128 features but the layers have 64"),
+        (lambda: mx.gated_mlp_mx(x, up, ups, c, s, rotation=rot128), "the rotation has 128 features but the layer has 64"),
+        (lambda: mx.gated_mlp_mx(x, up, ups, c, s, down_rotation=rot128), "the down_rotation has 128 features but the layer has 64"),
+        # the bias
+        (lambda: mx.matmul_mx(a8, aE, c, s, bias=np.zeros(7, np.float32)), r"bias must be \(8,\); got \(7,\)"),
+        (lambda: mx.linear_mxfp4(x, c, s, bias=np.zeros(7, np.float32)), r"bias must be \(8,\); got \(7,\)"),
+        (lambda: mx.linear_mxfp6(x, c6, s, bias=np.zeros((1, 8), np.float32)), r"bias must be \(8,\); got \(1, 8\)"),
+        (lambda: mx.matmul_mx_experts(a8, aE, ec, es, off, bias=np.zeros(8, np.float32)), r"bias must be \(2, 8\); got \(8,\)"),
+        (lambda: mx.linear_mx_experts(x, ec, es, off, bias=np.zeros((2, 7), np.float32)), r"bias must be \(2, 8\); got \(2, 7\)"),
+        (lambda: mx.gated_mlp_mx(x, up, ups, c, s, up_bias=np.zeros(64, np.float32)), r"bias must be \(128,\); got \(64,\)"),
+        (lambda: mx.gated_mlp_mx(x, up, ups, c, s, down_bias=np.zeros(9, np.float32)), r"bias must be \(8,\); got \(9,\)"),
+        (lambda: mx.matmul_mx_glu_experts(a8, aE, eup, eups, off, bias=np.zeros((2, 64), np.float32)), r"bias must be \(2, 128\); got \(2, 64\)"),
+        # the offsets: dtype and length
+        (lambda: mx.matmul_mx_experts(a8, aE, ec, es, off.astype(np.int64)), r"offsets must be int32 \(3,\).*got int64 \(3,\)"),
+        (lambda: mx.linear_mx_experts(x, ec, es, off.astype(np.int64)), r"offsets must be int32 \(3,\).*got int64 \(3,\)"),
+        (lambda: mx.matmul_mx_experts(a8, aE, ec, es, off[:2]), r"offsets must be int32 \(3,\).*got int32 \(2,\)"),
+        (lambda: mx.linear_mx_experts(x, ec, es, off[:2]), r"offsets must be int32 \(3,\).*got int32 \(2,\)"),
+        # a dense layer where a stack belongs, and the reverse
+        (lambda: mx.matmul_mx_experts(a8, aE, c, s, off), "codes of stacked experts must be a 3-D"),
+        (lambda: mx.linear_mx_experts(x, c, s, off), "codes of stacked experts must be a 3-D"),
+        (lambda: mx.matmul_mx(a8, aE, ec, es), "codes must be a 2-D NumPy array or torch tensor"),
+        (lambda: mx.linear_mxfp4(x, ec, es), "codes must be a 2-D NumPy array or torch tensor"),
+        (lambda: mx.linear_mxfp6(x, ec6, es), "codes must be a 2-D NumPy array or torch tensor"),
+        (lambda: mx.gated_mlp_mx(x, eup, eups, c, s), "codes must be a 2-D NumPy array or torch tensor"),
+        (lambda: mx.gated_mlp_mx(x, up, ups, ec, es), "codes must be a 2-D NumPy array or torch tensor"),
+        # the refused pair
+        (lambda: mx.matmul_mx(a4, aE, c6, s, activations="mxfp4", weights=W6), 'an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations \\(got "mxfp4"\\)'),
+        (lambda: mx.matmul_mx_experts(a4, aE, ec6, es, off, activations="mxfp4", weights=W6), 'an MXFP6 layer takes .* \\(got "mxfp4"\\)'),
+        (lambda: mx.linear_mxfp6(x, c6, s, activations="mxfp4"), 'an MXFP6 layer takes .* \\(got "mxfp4"\\)'),
+        (lambda: mx.linear_mx_experts(x, ec6, es, off, activations="mxfp4", weights=W6), 'an MXFP6 layer takes .* \\(got "mxfp4"\\)'),
+        (lambda: mx.gated_mlp_mx(x, np.zeros((128, 48), np.uint8), ups, c6, s, activations="mxfp4", weights=W6), 'an MXFP6 layer takes .* \\(got "mxfp4"\\)'),
+    ):
+        with pytest.raises(ValueError, match=text):
+            call()
 
 
 def test_model_is_silu_times_up_and_the_gpt_oss_formula():

@@ -19,7 +19,8 @@ Every side runs on preallocated outputs and is timed with device events (median 
   fused   rows x n = 4096 x 4096, block 4096, bfloat16 x, for the three formats:
           (two) slk_hadamard_rows to float32 + slk_mx_quantize_act / _act6 / _act4
           (one) slk_mx_rotate_quantize_act / _act6
-          with the bytes each must move as a share of HBM.
+          with the bytes each must move as a share of HBM; with --parent-lib also the fused kernel of this library and of
+          that one alternating, each side twice, as in the quantize rows.
   quantize  4096 x 11008 bfloat16: each plain quantizer (slk_mx_quantize_act, _act6, _act4) and each activation
           de-quantizer (slk_mx_dequantize_act, _act6, to bfloat16) alone, this library and --parent-lib (required) alternating,
           each side twice; the spread is the difference of the parent's own two medians.
@@ -176,7 +177,7 @@ def quantize_rows(M, K, reps, parent):
                   flush=True)
 
 
-def fused_rows(rows, n, block, reps):
+def fused_rows(rows, n, block, reps, parent=None):
     s = dev.stream_handle
     gen = torch.Generator(device="cuda").manual_seed(rows + n)
     x = torch.randn((rows, n), device="cuda", generator=gen).to(torch.bfloat16)
@@ -198,16 +199,16 @@ def fused_rows(rows, n, block, reps):
             _lib.check(quantize(dev.ptr(yf), _lib.DTYPE_F32, rows, n, dev.ptr(c), dev.ptr(sc), dev.ptr(flag), s()))
         return run
 
-    def one(fmt):
+    def one(fmt, lib=L):
         def run():
             if fmt == "mxfp6_e2m3":
-                _lib.check(L.slk_mx_rotate_quantize_act6(dev.ptr(x), _lib.DTYPE_BF16, rows, n, block, dev.ptr(rot.signs), dev.ptr(c6), dev.ptr(sc),
+                _lib.check(lib.slk_mx_rotate_quantize_act6(dev.ptr(x), _lib.DTYPE_BF16, rows, n, block, dev.ptr(rot.signs), dev.ptr(c6), dev.ptr(sc),
                                                          dev.ptr(flag), s()))
             else:
                 fp4 = fmt == "mxfp4"
-                _lib.check(L.slk_mx_rotate_quantize_act(dev.ptr(x), _lib.DTYPE_BF16, rows, n, block, dev.ptr(rot.signs),
-                                                        _lib.MX_ACT_FP4 if fp4 else _lib.MX_ACT_FP8, dev.ptr(c4 if fp4 else c8), dev.ptr(sc),
-                                                        dev.ptr(flag), s()))
+                _lib.check(lib.slk_mx_rotate_quantize_act(dev.ptr(x), _lib.DTYPE_BF16, rows, n, block, dev.ptr(rot.signs),
+                                                          _lib.MX_ACT_FP4 if fp4 else _lib.MX_ACT_FP8, dev.ptr(c4 if fp4 else c8), dev.ptr(sc),
+                                                          dev.ptr(flag), s()))
         return run
 
     for fmt, bits in (("mxfp8", 8), ("mxfp6_e2m3", 6), ("mxfp4", 4)):
@@ -222,6 +223,10 @@ def fused_rows(rows, n, block, reps):
                               **stats(t_one), repeat_us=round(t_one2[0], 1), bytes=b_one, share_of_hbm=round(b_one / HBM * 1e6 / t_one[0], 3),
                               two_over_one=round(t_two[0] / t_one[0], 2),
                               median_below_two_steps_min=bool(max(t_one[0], t_one2[0]) < min(t_two[1], t_two2[1])))), flush=True)
+        if parent is not None:  # the fused kernel alone, this library and the parent's alternating, each side twice
+            this, there, this2, there2 = timed([one(fmt), one(fmt, parent)] * 2, reps)
+            print(json.dumps(dict(bench="fused", shape=f"{rows}x{n}", block=block, fmt=fmt, side="fused against the parent's",
+                                  **against_parent((this, this2), (there, there2)))), flush=True)
 
 
 def main():
@@ -240,7 +245,7 @@ def main():
                 linear_rows(N, K, M, args.reps, parent)
                 torch.cuda.empty_cache()
     if args.only in (None, "fused"):
-        fused_rows(4096, 4096, 4096, args.reps)
+        fused_rows(4096, 4096, 4096, args.reps, parent)
     if args.only == "quantize" or (args.only is None and parent is not None):
         assert parent is not None, "--only quantize compares against --parent-lib"
         quantize_rows(4096, 11008, args.reps, parent)
