@@ -177,6 +177,42 @@ int slk_hessian_patch_dead(float *H, float *W, int R, int n, void *workspace, si
 int slk_hessian_accumulate(float *H, float *mean, const float *X, int n, int T,
                            long long count_before, void *workspace, size_t ws_bytes, slk_stream_t stream);
 
+/* a1, for a mixture of experts: E running statistics in one call, the host reading nothing.
+ *   - X: M x n float32, rows sorted by expert; offsets: E + 1 int32 in DEVICE memory under the rule of slk_mx_gemm_experts
+ *     (offsets[0] == 0, non-decreasing, offsets[E] == M); H: E x n x n; mean: E x n; counts: E int64 in DEVICE memory,
+ *     read and written, >= 0; flag: one int in device memory.
+ *   - An expert e with T_e = offsets[e + 1] - offsets[e] > 0 rows: H[e] and mean[e] become what slk_hessian_accumulate(H[e],
+ *     mean[e], X + offsets[e] n, n, T_e, counts[e], ...) makes them, bit for bit on any data -- the same kernel bodies run
+ *     the same steps, with f = (float)((double)c / c') and cnt = (float)c' formed on the device -- and counts[e] becomes
+ *     counts[e] + T_e.  An expert without rows: no byte of H[e], mean[e] or counts[e] is read or written.
+ *   - A one-workgroup prologue checks the offsets rule before any address is made from an offset: broken, flag[0] = 1 and H,
+ *     mean and counts stay unwritten; kept, flag[0] = 0.  Everything runs in order on the caller's stream.
+ *   - Two paths, as in the single call: the float32 MFMA chain at every n; the bfloat16 x 3 path when n % 128 == 0 and the
+ *     workspace has slk_hessian_experts_workspace_bytes(E, n, M) bytes.  The grouped entry never chunks: its bfloat16 path
+ *     equals the single call whose workspace holds all T_e tokens; with less room, a NULL workspace or M / 32 + E above
+ *     65535 it takes the float32 path.
+ *   - slk_hessian_experts_workspace_bytes(E, n, M) = align_up(32 (1 + E), 256) + (n % 128 == 0 ? 6 n 32 (M / 32 + min(E, M))
+ *     : 0): the table of the prologue (8 ints of head, 8 ints an expert: first row, rows, first 32-token slab, f, cnt), then
+ *     the planes of every expert's tokens padded to 32.  0 for E, n or M < 1.
+ * SLK_E_ARG, before any launch, slk_last_error() naming the offender: E < 1 or E > SLK_MX_MAX_EXPERTS, n or M < 1, a NULL
+ *   pointer other than the workspace, a workspace off 16-byte alignment, a non-NULL workspace below the table's 32 (1 + E)
+ *   bytes.
+ *
+ * slk_hessian_accumulate_experts_mx: the same statistics of MX-coded rows -- a_codes / a_scales, M rows as the activation
+ *   quantizers and slk_mx_gemm_glu* write them, a_fmt SLK_MX_ACT_FP8, _FP4 or _FP6, n % 32 == 0, a_codes aligned to 16 bytes
+ *   -- that is of x = value(code) 2^(b - 127), with the same per-expert running-mean arithmetic, prologue, table and
+ *   empty-expert rule.  Every such x is a bfloat16 exactly, so X^T X is one bfloat16 MFMA pass with exact products and
+ *   float32 sums, at every n.  Exactness is promised for scale bytes 10 .. 245 (every E4M3 value 2^-9 2^(b - 127) .. 448
+ *   2^(b - 127) is then a normal bfloat16; the 4- and 6-bit formats lie inside that) and no further.  flag is TWO ints:
+ *   flag[0] the offsets rule's, flag[1] = 1 when a scale byte of a row is 255 (E8M0's NaN, as slk_mx_dequantize_act
+ *   raises it).  The workspace holds the table only: slk_hessian_experts_workspace_bytes(E, 32, M) bytes suffice.        */
+size_t slk_hessian_experts_workspace_bytes(int E, int n, int M);
+int slk_hessian_accumulate_experts(float *H, float *mean, const float *X, const int *offsets, int E, int n, int M,
+                                   long long *counts, int *flag, void *workspace, size_t ws_bytes, slk_stream_t stream);
+int slk_hessian_accumulate_experts_mx(float *H, float *mean, const uint8_t *a_codes, const uint8_t *a_scales, int a_fmt,
+                                      const int *offsets, int E, int n, int M, long long *counts, int *flag, void *workspace,
+                                      size_t ws_bytes, slk_stream_t stream);
+
 /* a4  column statistics for the err / sqerr orders  (sleekit/obq.py:60-69)
  *     miss[j] = sum over rows, in row order, of |q(W) - W| (squared == 0) or its square; for n == 1 in NumPy's pairwise
  *     order over the R rows, which is how NumPy reduces an (R, 1) array along axis 0 (the grouped forms likewise). */

@@ -1,7 +1,7 @@
 """sleekit_amd: MI355X-native GPTQ/OBQ layer quantization behind the sleekit function surface.
 
     from sleekit_amd import obq, scaling, codebook, groups, packing, mx, rotation, Sleekit, MXLinear, MXExperts, PackedLinear
-    from sleekit_amd import MXGatedMLP, MXExpertsMLP
+    from sleekit_amd import MXGatedMLP, MXExpertsMLP, ExpertStatistics
     from sleekit_amd import Rotation, RotatedLinear
 
 mirrors `sleekit.obq`, `sleekit.scaling`, `sleekit.codebook` and `sleekit.Sleekit` of
@@ -22,8 +22,8 @@ _SUBMODULES = ("codebook", "obq", "scaling", "statistics", "engine", "dist", "sy
 def __getattr__(name):
     if name in _SUBMODULES:
         return importlib.import_module(f"{__name__}.{name}")
-    if name == "Sleekit":
-        return importlib.import_module(f"{__name__}.statistics").Sleekit
+    if name in ("Sleekit", "ExpertStatistics"):
+        return getattr(importlib.import_module(f"{__name__}.statistics"), name)
     if name in ("MXLinear", "MXExperts", "MXGatedMLP", "MXExpertsMLP"):
         return getattr(importlib.import_module(f"{__name__}.mx"), name)
     if name == "PackedLinear":

@@ -47,6 +47,9 @@ PROTOTYPES = {
     "slk_hessian_strip_mean": (c_int, [P, P, c_int, P, P]),
     "slk_hessian_patch_dead": (c_int, [P, P, c_int, c_int, P, c_size_t, P]),
     "slk_hessian_accumulate": (c_int, [P, P, P, c_int, c_int, c_longlong, P, c_size_t, P]),
+    "slk_hessian_experts_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "slk_hessian_accumulate_experts": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "slk_hessian_accumulate_experts_mx": (c_int, [P, P, P, P, c_int, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_codebook_stats_workspace_bytes": (c_size_t, []),
     "slk_codebook_stats": (c_int, [P, c_size_t, c_int, c_double, c_double, P, c_int, P, P, P, P, c_size_t, P]),
     "slk_sort_workspace_bytes": (c_size_t, [c_size_t]),

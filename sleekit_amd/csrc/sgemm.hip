@@ -1,6 +1,8 @@
 // float32 MFMA products on the path:
 //   a11  channelwise_error (sleekit/obq.py:89-95): row_err = rowsum(((W-Q) @ H) * (W-Q))
 //   a1   Sleekit.add_batch (sleekit/statistics.py:76-87): H = H f + X^T X / c'
+//        and, for the E experts of a mixture in one call, slk_hessian_accumulate_experts (float rows) and
+//        slk_hessian_accumulate_experts_mx (MX-coded rows: one bfloat16 MFMA pass over the decoded codes)
 // Both are dense contractions on v_mfma_f32_32x32x2_f32 through mfma32.h.
 #include <stdlib.h>
 
@@ -8,6 +10,7 @@
 
 #include "mfma32.h"
 #include "mfma_bf16x3.h"
+#include "mxquant.h"
 
 namespace slk {
 
@@ -435,12 +438,20 @@ __global__ __launch_bounds__(256) void k_error_reduce(const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------ Hessian accumulation
-// Lower tiles of X^T X, mirrored on store so H stays exactly symmetric.
-__global__ __launch_bounds__(256) void k_hessian_tiles(float *__restrict__ H, const float *__restrict__ X, int n, int T,
-                                                       float factor, float count, int vec_ok) {
-    __shared__ Tile128Smem sm;
-    const int bi = blockIdx.y, bj = blockIdx.x;
-    if (bj > bi) return;
+// The bodies of the four kernels are functions of (operand, row count, tile, factor, count): the single-layer kernels call
+// them with their arguments, the expert-grouped ones (further down) with an expert's slice and the factor and count the
+// prologue formed for it -- the same steps in the same order, so an expert's statistics are the single call's bit for bit.
+//
+// One entry of the running update, mirrored: H[i][j] = H[j][i] = fl(fl(H[i][j] f) + fl(v / cnt)).
+__device__ __forceinline__ void hessian_store(float *__restrict__ H, int n, int i, int j, float v, float factor, float count) {
+    const float h = H[(size_t)i * n + j] * factor + v / count;
+    H[(size_t)i * n + j] = h;
+    if (i != j) H[(size_t)j * n + i] = h;
+}
+
+// Lower tile (bi, bj) of X^T X, mirrored on store so H stays exactly symmetric.
+__device__ __forceinline__ void hessian_tile_f32(Tile128Smem &sm, float *__restrict__ H, const float *__restrict__ X, int n, int T,
+                                                 int bi, int bj, float factor, float count, int vec_ok) {
     const int i0 = bi * T32, j0 = bj * T32;
     const int t = threadIdx.x;
     Acc128 acc;
@@ -467,26 +478,23 @@ __global__ __launch_bounds__(256) void k_hessian_tiles(float *__restrict__ H, co
     }
     tile128_foreach(acc, [&](int r, int c, float v) {
         const int i = i0 + r, j = j0 + c;
-        if (i < n && j < n && (bi != bj || j <= i)) {
-            const float h = H[(size_t)i * n + j] * factor + v / count;
-            H[(size_t)i * n + j] = h;
-            if (i != j) H[(size_t)j * n + i] = h;
-        }
+        if (i < n && j < n && (bi != bj || j <= i)) hessian_store(H, n, i, j, v, factor, count);
     });
+}
+__global__ __launch_bounds__(256) void k_hessian_tiles(float *__restrict__ H, const float *__restrict__ X, int n, int T,
+                                                       float factor, float count, int vec_ok) {
+    __shared__ Tile128Smem sm;
+    if (blockIdx.x > blockIdx.y) return;
+    hessian_tile_f32(sm, H, X, n, T, blockIdx.y, blockIdx.x, factor, count, vec_ok);
 }
 
 // X (T x n, tokens x features) -> the three bfloat16 pieces of its TRANSPOSE in the GEMM's slab order: slab
 // (128-feature block ib, 32-token step ks) is [feature in block][32 tokens], contiguous; tokens beyond T are
 // zero.  One workgroup per slab: 32 coalesced rows of 128 floats in, through LDS, 8 KB per plane out.
-__global__ __launch_bounds__(256) void k_split3_transposed(PtrTable xs, int n, int T, int t_first, int t_count,
-                                                           unsigned short *__restrict__ out, size_t plane, int swz,
-                                                           const int *__restrict__ skip_if_symmetric) {
-    __shared__ float tile[32][T32 + 1];
-    // blockIdx.z: the layer of a stack (its own X, flag and planes)
-    const float *__restrict__ X = xs.p[blockIdx.z];
-    out += (size_t)blockIdx.z * 3 * plane;
-    if (skip_if_symmetric && skip_if_symmetric[blockIdx.z] > 0) return;  // (the layer error: a symmetric H is split as it stands)
-    const int ib = blockIdx.x, ks = blockIdx.y;
+typedef float Split3Tile[32][T32 + 1];
+// slab (ib, ks) of X's planes, `ksteps` slabs a feature block
+__device__ __forceinline__ void split3_transposed_slab(Split3Tile &tile, const float *__restrict__ X, int n, int T, int t_first, int t_count,
+                                                       unsigned short *__restrict__ out, size_t plane, int swz, int ib, int ks, int ksteps) {
     const int t = threadIdx.x;
     for (int e = t; e < 32 * T32; e += 256) {
         const int tt = e >> 7, ii = e & 127;
@@ -498,7 +506,7 @@ __global__ __launch_bounds__(256) void k_split3_transposed(PtrTable xs, int n, i
     unsigned w[3][8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) split3_pair(tile[half + 2 * e][ii], tile[half + 2 * e + 1][ii], w[0][e], w[1][e], w[2][e]);
-    const size_t slab = ((size_t)ib * gridDim.y + ks) * 4096 + (size_t)ii * 32;
+    const size_t slab = ((size_t)ib * ksteps + ks) * 4096 + (size_t)ii * 32;
     const int c0 = (t & 1) * 2;  // this thread's two 16-byte chunks of the row
     const int p0 = swz ? swizzled_chunk(ii, c0) : c0, p1 = swz ? swizzled_chunk(ii, c0 + 1) : c0 + 1;
 #pragma unroll
@@ -508,16 +516,25 @@ __global__ __launch_bounds__(256) void k_split3_transposed(PtrTable xs, int n, i
         *reinterpret_cast<uint4v_t *>(o + p1 * 8) = (uint4v_t){w[p][4], w[p][5], w[p][6], w[p][7]};
     }
 }
+__global__ __launch_bounds__(256) void k_split3_transposed(PtrTable xs, int n, int T, int t_first, int t_count,
+                                                           unsigned short *__restrict__ out, size_t plane, int swz,
+                                                           const int *__restrict__ skip_if_symmetric) {
+    __shared__ Split3Tile tile;
+    // blockIdx.z: the layer of a stack (its own X, flag and planes)
+    if (skip_if_symmetric && skip_if_symmetric[blockIdx.z] > 0) return;  // (the layer error: a symmetric H is split as it stands)
+    split3_transposed_slab(tile, xs.p[blockIdx.z], n, T, t_first, t_count, out + (size_t)blockIdx.z * 3 * plane, plane, swz, blockIdx.x, blockIdx.y,
+                           gridDim.y);
+}
 
 // Lower tiles of X^T X on the bfloat16 MFMA (mfma_bf16x3.h), from the planes of k_split3_transposed; same
-// epilogue as k_hessian_tiles.  Tiles of the lower triangle in an XCD-aware order (see k_syrk_triangle).
+// epilogue as k_hessian_tiles.  Tiles of the lower triangle in an XCD-aware order (see k_syrk_triangle): `block` of the
+// launch's 8 * ceil(total / 8) workgroups.
 template <bool DMA>
-__global__ __launch_bounds__(256) void k_hessian_tiles_bf16(float *__restrict__ H, const unsigned short *__restrict__ Xp, int n,
-                                                            int ksteps, size_t plane, float factor, float count) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+__device__ __forceinline__ void hessian_tile_bf16(unsigned char *smem_raw, float *__restrict__ H, const unsigned short *__restrict__ Xp, int n,
+                                                  int ksteps, size_t plane, int block, float factor, float count) {
     TileBf16Smem &sm = *reinterpret_cast<TileBf16Smem *>(smem_raw);
     const int m = n / T32, total = m * (m + 1) / 2, per_xcd = (total + 7) / 8;
-    const int lin = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int lin = (block & 7) * per_xcd + (block >> 3);
     if (lin >= total) return;
     int bi = (int)((sqrtf(8.0f * (float)lin + 1.0f) - 1.0f) * 0.5f);
     while (bi * (bi + 1) / 2 > lin) --bi;
@@ -553,12 +570,14 @@ __global__ __launch_bounds__(256) void k_hessian_tiles_bf16(float *__restrict__ 
     // tail as it is)
     tile128_foreach(acc, [&](int r, int c, float v) {
         const int i = i0 + r, j = j0 + c;
-        if (bi != bj || j <= i) {
-            const float h = H[(size_t)i * n + j] * factor + v / count;
-            H[(size_t)i * n + j] = h;
-            if (i != j) H[(size_t)j * n + i] = h;
-        }
+        if (bi != bj || j <= i) hessian_store(H, n, i, j, v, factor, count);
     });
+}
+template <bool DMA>
+__global__ __launch_bounds__(256) void k_hessian_tiles_bf16(float *__restrict__ H, const unsigned short *__restrict__ Xp, int n,
+                                                            int ksteps, size_t plane, float factor, float count) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    hessian_tile_bf16<DMA>(smem_raw, H, Xp, n, ksteps, plane, blockIdx.x, factor, count);
 }
 
 // mean[j] = mean[j] * factor + (sum over the T tokens of X[t][j]) / count  (statistics.py:76-87).
@@ -566,21 +585,23 @@ __global__ __launch_bounds__(256) void k_hessian_tiles_bf16(float *__restrict__ 
 // running sums (128-byte row segments, loads independent of one another), then a fixed-order reduction through LDS.
 // (One thread per feature walking all T tokens, the first version, took 470 us for 2048 x 4096: longer than the
 // Hessian update itself.)
-__global__ __launch_bounds__(256) void k_mean_update(float *__restrict__ mean, const float *__restrict__ X, int n, int T,
-                                                     float factor, float count) {
-    __shared__ float part[8][33];
+// x(t, j): element j of token t -- a float row's, or a coded row's value (the expert-grouped statistics over MX codes)
+typedef float MeanPart[8][33];
+template <class LoadX>
+__device__ __forceinline__ void mean_update_block(MeanPart &part, float *__restrict__ mean, int n, int T, int block, float factor, float count,
+                                                  LoadX x) {
     const int f = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int j = blockIdx.x * 32 + f;
+    const int j = block * 32 + f;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
     if (j < n) {
         int t = g;
         for (; t + 24 < T; t += 32) {
-            s0 = s0 + X[(size_t)t * n + j];
-            s1 = s1 + X[(size_t)(t + 8) * n + j];
-            s2 = s2 + X[(size_t)(t + 16) * n + j];
-            s3 = s3 + X[(size_t)(t + 24) * n + j];
+            s0 = s0 + x(t, j);
+            s1 = s1 + x(t + 8, j);
+            s2 = s2 + x(t + 16, j);
+            s3 = s3 + x(t + 24, j);
         }
-        for (; t < T; t += 8) s0 = s0 + X[(size_t)t * n + j];
+        for (; t < T; t += 8) s0 = s0 + x(t, j);
     }
     part[g][f] = (s0 + s1) + (s2 + s3);
     __syncthreads();
@@ -590,6 +611,258 @@ __global__ __launch_bounds__(256) void k_mean_update(float *__restrict__ mean, c
         for (int q = 1; q < 8; ++q) s = s + part[q][f];
         mean[j] = mean[j] * factor + s / count;
     }
+}
+__global__ __launch_bounds__(256) void k_mean_update(float *__restrict__ mean, const float *__restrict__ X, int n, int T,
+                                                     float factor, float count) {
+    __shared__ MeanPart part;
+    mean_update_block(part, mean, n, T, blockIdx.x, factor, count, [&](int t, int j) { return X[(size_t)t * n + j]; });
+}
+
+// ------------------------------------------------------------------ expert-grouped Hessian accumulation
+// slk_hessian_accumulate_experts / _experts_mx: E running statistics, rows sorted by expert, `offsets` and `counts` in device
+// memory.  k_expert_stats, one workgroup, runs first on the stream: it checks the offsets rule of slk_mx_gemm_experts before
+// any address is made from an offset, sets flag[0], advances counts[e] of the experts that have rows (no other entry of
+// counts is touched) and, given a workspace, writes one entry an expert.  The kernels behind it are the single-layer bodies
+// above over grids with an expert axis; a workgroup of an expert without rows returns at once.
+//
+// The workspace, as ints: [0] the 32-token slabs of all experts' planes, [1] .. [7] unused; from [8] E entries of 8 ints
+// (first row, rows, first slab, f's bits, cnt's bits, 3 unused).  Without a workspace the kernels form the same five values
+// from flag[0], offsets and the advanced counts: c' = counts[e], c = c' - rows.
+constexpr int XS_HEAD = 8, XS_ENTRY = 8;
+struct ExpertRows {
+    int first, rows, slab;  // rows == 0: nothing to do (no rows, or offsets that break the rule)
+    float f, cnt;
+};
+__device__ __forceinline__ void expert_factor(long long before, int rows, float &f, float &cnt) {
+    const long long after = before + rows;
+    f = (float)((double)before / (double)after);
+    cnt = (float)after;
+}
+__device__ __forceinline__ ExpertRows expert_rows(const int *__restrict__ table, const int *__restrict__ offsets,
+                                                  const long long *__restrict__ counts, const int *__restrict__ flag, int e) {
+    ExpertRows x = {0, 0, 0, 0.0f, 0.0f};
+    if (table) {
+        const int *entry = table + XS_HEAD + XS_ENTRY * (size_t)e;
+        x.first = entry[0], x.rows = entry[1], x.slab = entry[2], x.f = __int_as_float(entry[3]), x.cnt = __int_as_float(entry[4]);
+    } else if (flag[0] == 0) {  // (the prologue has checked the rule: the offsets are addresses now)
+        x.first = offsets[e], x.rows = offsets[e + 1] - x.first;
+        if (x.rows > 0) expert_factor(counts[e] - x.rows, x.rows, x.f, x.cnt);
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(256) void k_expert_stats(const int *__restrict__ offsets, int E, int M, long long *__restrict__ counts,
+                                                      int *__restrict__ table, int *__restrict__ flag, int flags) {
+    __shared__ int scan[256];
+    __shared__ int base;
+    const int t = threadIdx.x;
+    int bad = 0;
+    for (int e = t; e < E; e += 256) {
+        const int o0 = offsets[e], o1 = offsets[e + 1];
+        bad |= o1 < o0 || (e == 0 && o0 != 0) || (e == E - 1 && o1 != M);
+    }
+    bad = __syncthreads_or(bad);
+    if (t < flags) flag[t] = t == 0 && bad ? 1 : 0;
+    if (t == 0) base = 0;
+    for (int e0 = 0; e0 < E; e0 += 256) {  // 256 experts a round, each thread its expert's slabs behind an exclusive scan
+        const int e = e0 + t;
+        const int o0 = !bad && e < E ? offsets[e] : 0, rows = !bad && e < E ? offsets[e + 1] - o0 : 0, slabs = (rows + 31) / 32;
+        scan[t] = slabs;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {  // (inclusive, Hillis-Steele)
+            const int a = t >= d ? scan[t - d] : 0;
+            __syncthreads();
+            scan[t] += a;
+            __syncthreads();
+        }
+        float f = 0.0f, cnt = 0.0f;
+        if (rows > 0) {
+            const long long before = counts[e];
+            expert_factor(before, rows, f, cnt);
+            counts[e] = before + rows;
+        }
+        if (table && e < E) {
+            int *entry = table + XS_HEAD + XS_ENTRY * (size_t)e;
+            entry[0] = o0, entry[1] = rows, entry[2] = base + scan[t] - slabs, entry[3] = __float_as_int(f), entry[4] = __float_as_int(cnt);
+        }
+        __syncthreads();
+        if (t == 255) base += scan[255];
+        __syncthreads();
+    }
+    if (table && t == 0) table[0] = base;
+}
+
+#define SLK_EXPERT_ARGS const int *__restrict__ table, const int *__restrict__ offsets, const long long *__restrict__ counts, const int *__restrict__ flag
+
+// grid (feature blocks of 32, experts)
+__global__ __launch_bounds__(256) void k_mean_update_experts(float *__restrict__ mean, const float *__restrict__ X, int n, SLK_EXPERT_ARGS) {
+    __shared__ MeanPart part;
+    const ExpertRows x = expert_rows(table, offsets, counts, flag, blockIdx.y);
+    if (x.rows == 0) return;
+    const float *__restrict__ Xe = X + (size_t)x.first * n;
+    mean_update_block(part, mean + (size_t)blockIdx.y * n, n, x.rows, blockIdx.x, x.f, x.cnt, [&](int t, int j) { return Xe[(size_t)t * n + j]; });
+}
+// grid (tile columns, tile rows, experts)
+__global__ __launch_bounds__(256, 4) void k_hessian_tiles_experts(float *__restrict__ H, const float *__restrict__ X, int n, SLK_EXPERT_ARGS) {
+    __shared__ Tile128Smem sm;
+    if (blockIdx.x > blockIdx.y) return;
+    const ExpertRows x = expert_rows(table, offsets, counts, flag, blockIdx.z);
+    if (x.rows == 0) return;
+    const float *__restrict__ Xe = X + (size_t)x.first * n;
+    hessian_tile_f32(sm, H + (size_t)blockIdx.z * n * n, Xe, n, x.rows, blockIdx.y, blockIdx.x, x.f, x.cnt, n % 4 == 0 && (uintptr_t)Xe % 16 == 0);
+}
+// The bfloat16 x 3 path (a table is there): expert e's planes are 3 x (n / 128) x its slabs x 4096 values from its first slab
+// on, as the single call lays out one chunk that holds all its tokens.
+__device__ __forceinline__ int expert_of_slab(const int *__restrict__ table, int E, int slab) {
+    int lo = 0, hi = E - 1;  // the last expert whose first slab is <= slab (those without rows share their successor's)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[XS_HEAD + XS_ENTRY * (size_t)mid + 2] <= slab) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// grid (feature blocks of 128, an upper bound of the slabs)
+__global__ __launch_bounds__(256) void k_split3_transposed_experts(const float *__restrict__ X, int n, int E, const int *__restrict__ table,
+                                                                   unsigned short *__restrict__ planes, int swz) {
+    __shared__ Split3Tile tile;
+    if ((int)blockIdx.y >= table[0]) return;
+    const ExpertRows x = expert_rows(table, nullptr, nullptr, nullptr, expert_of_slab(table, E, blockIdx.y));
+    const int ksteps = (x.rows + 31) / 32, m = n / T32;
+    split3_transposed_slab(tile, X + (size_t)x.first * n, n, x.rows, 0, x.rows, planes + (size_t)3 * m * 4096 * x.slab, (size_t)n * ksteps * 32, swz,
+                           blockIdx.x, blockIdx.y - x.slab, ksteps);
+}
+// grid (8 * ceil(lower tiles / 8), experts)
+template <bool DMA>
+__global__ __launch_bounds__(256) void k_hessian_tiles_bf16_experts(float *__restrict__ H, const unsigned short *__restrict__ planes, int n,
+                                                                    const int *__restrict__ table) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const ExpertRows x = expert_rows(table, nullptr, nullptr, nullptr, blockIdx.y);
+    if (x.rows == 0) return;
+    const int ksteps = (x.rows + 31) / 32;
+    hessian_tile_bf16<DMA>(smem_raw, H + (size_t)blockIdx.y * n * n, planes + (size_t)3 * (n / T32) * 4096 * x.slab, n, ksteps,
+                           (size_t)n * ksteps * 32, blockIdx.x, x.f, x.cnt);
+}
+
+// ... and over MX-coded rows (a_codes / a_scales as the activation quantizers write them): x = value(code) 2^(b - 127) has
+// at most 4 significant bits, so it is a bfloat16 exactly (scale bytes 10 .. 245 keep every E4M3 value normal, 2^-9 2^(b - 127)
+// .. 448 2^(b - 127); results are promised exact inside that range only) and X^T X is ONE bfloat16 MFMA pass with exact
+// products and float32 sums.  The block scales lie along the features, not along the summed tokens, so the block-scaled
+// MFMA is no use; v_mfma_f32_32x32x16_bf16 is.  A workgroup decodes 32 tokens x 128 features of each operand into a
+// [token][feature] image in LDS, and both operands are COLUMN reads of it: ds_read_b64_tr_b16.  No software pipelining yet.
+//
+// Byte offset of 16-byte chunk ch (8 features) of token row `row` in an image of 256-byte rows; the XOR keeps the
+// transposed reads off one another's banks (stores and reads go through it alike).
+__device__ __forceinline__ int mxs_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
+
+typedef short bf16x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+// the 32x32x16 operand of 32 features from feature f0 of the image, tokens k0 .. k0 + 15: lane l holds feature f0 + (l & 31),
+// tokens k0 + 8 (l >> 5) + 0 .. 7.  Every lane of the wave must call it (the gather crosses lanes).
+__device__ __forceinline__ bf16x8_t mxs_operand(const unsigned char *img, int f0, int k0) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    const int ch = (f0 + 16 * (g & 1)) / 8 + (p >> 1), row = k0 + 8 * (g >> 1) + q;
+    typedef __attribute__((address_space(3))) bf16x4_t *lds_ptr;
+    const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + mxs_off(row, ch) + 8 * (p & 1)));
+    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(img + mxs_off(row + 4, ch) + 8 * (p & 1)));
+    union {
+        bf16x4_t h[2];
+        bf16x8_t v;
+    } u;
+    u.h[0] = lo, u.h[1] = hi;
+    return u.v;
+}
+// One coded element: its code's unit of whole dwords, then the code
+template <int FMT>
+__device__ __forceinline__ float mxs_value(const uint8_t *__restrict__ codes, const uint8_t *__restrict__ scales, int n, size_t row, int j, bool &bad) {
+    constexpr int UNIT = FMT == MXA_E2M3 ? 16 : FMT == MXA_E2M1 ? 8 : 4;
+    unsigned w[UNIT * mxa_bits<FMT>() / 32];
+    mxa_load<FMT, UNIT>(codes + mxa_byte_of<FMT>(row * n + (j & ~(UNIT - 1))), w);
+    unsigned c = 0u;
+#pragma unroll
+    for (int e = 0; e < UNIT; ++e)
+        if ((j & (UNIT - 1)) == e) c = mxa_code_at<FMT>(w, e);
+    const unsigned b = scales[row * (n / 32) + j / 32];
+    bad |= b == 255u;
+    return mxa_value<FMT>(c) * e8m0_value(b);
+}
+// grid (feature blocks of 32, experts)
+template <int FMT>
+__global__ __launch_bounds__(256) void k_mean_update_experts_mx(float *__restrict__ mean, const uint8_t *__restrict__ codes,
+                                                                const uint8_t *__restrict__ scales, int n, SLK_EXPERT_ARGS, int *__restrict__ nan_flag) {
+    __shared__ MeanPart part;
+    const ExpertRows x = expert_rows(table, offsets, counts, flag, blockIdx.y);
+    if (x.rows == 0) return;
+    bool bad = false;
+    mean_update_block(part, mean + (size_t)blockIdx.y * n, n, x.rows, blockIdx.x, x.f, x.cnt,
+                      [&](int t, int j) { return mxs_value<FMT>(codes, scales, n, (size_t)x.first + t, j, bad); });
+    if (bad) *nan_flag = 1;
+}
+// grid (tile columns, tile rows, experts); 4 waves, each 64 x 64 of the 128 x 128 tile
+template <int FMT>
+__global__ __launch_bounds__(256) void k_hessian_tiles_experts_mx(float *__restrict__ H, const uint8_t *__restrict__ codes,
+                                                                  const uint8_t *__restrict__ scales, int n, SLK_EXPERT_ARGS) {
+    __shared__ __attribute__((aligned(16))) unsigned char img[2][32 * 256];
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    if (bj > bi) return;
+    const ExpertRows x = expert_rows(table, offsets, counts, flag, blockIdx.z);
+    if (x.rows == 0) return;
+    H += (size_t)blockIdx.z * n * n;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int i0 = bi * T32, j0 = bj * T32, wi = 64 * (wave >> 1), wj = 64 * (wave & 1);
+    float16_t acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    const int tok = t >> 3, fc = (t & 7) * 16;  // this thread stages 16 features (half a block) of one token, per operand
+    for (int k0 = 0; k0 < x.rows; k0 += 32) {
+        __syncthreads();
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            const int feature = (side ? j0 : i0) + fc;
+            unsigned short v[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) v[e] = 0;
+            if (k0 + tok < x.rows && feature < n) {  // (n is a multiple of 32: 16 features are inside or outside together)
+                const size_t row = (size_t)x.first + k0 + tok;
+                unsigned w[(16 * mxa_bits<FMT>() + 31) / 32];
+                mxa_load<FMT, 16>(codes + mxa_byte_of<FMT>(row * n + feature), w);
+                const float sc = e8m0_value(scales[row * (n / 32) + feature / 32]);  // (byte 255: NaNs; the mean's kernel raises the flag)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) v[e] = pk_bf16(mxa_value<FMT>(mxa_code_at<FMT>(w, e)) * sc);
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                uint4v_t pack;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pack[e] = (unsigned)v[8 * c + 2 * e] | ((unsigned)v[8 * c + 2 * e + 1] << 16);
+                *reinterpret_cast<uint4v_t *>(img[side] + mxs_off(tok, fc / 8 + c)) = pack;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ks = 0; ks < 32; ks += 16) {
+            bf16x8_t a[2], b[2];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) a[s] = mxs_operand(img[0], wi + 32 * s, ks), b[s] = mxs_operand(img[1], wj + 32 * s, ks);
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int u = 0; u < 2; ++u) acc[s][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], b[u], acc[s][u], 0, 0, 0);
+        }
+    }
+    // D of the MFMA: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int i = i0 + wi + 32 * s + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), j = j0 + wj + 32 * u + (lane & 31);
+                if (i < n && j < n && (bi != bj || j <= i)) hessian_store(H, n, i, j, acc[s][u][r], x.f, x.cnt);
+            }
 }
 
 }  // namespace slk
@@ -770,6 +1043,99 @@ int slk_hessian_accumulate(float *H, float *mean, const float *X, int n, int T, 
     SLK_RUN("hessian_syrk", (double)T * n * (n + 1), 4.0 * T * n + 8.0 * n * n, s,
             k_hessian_tiles<<<grid, 256, 0, s>>>(H, X, n, T, factor, count, n % 4 == 0 && (uintptr_t)X % 16 == 0));
     return SLK_OK;
+}
+
+// Bytes of the table, and the 32-token slabs the planes of all experts can take: every expert with rows pads to 32
+static inline size_t xs_table_bytes(int E) { return sizeof(int) * (XS_HEAD + (size_t)XS_ENTRY * E); }
+static inline size_t xs_slab_cap(int E, int M) { return (size_t)M / 32 + (size_t)(E < M ? E : M); }
+
+size_t slk_hessian_experts_workspace_bytes(int E, int n, int M) {
+    if (E < 1 || n < 1 || M < 1) return 0;
+    return align_up(xs_table_bytes(E), 256) + (n % T32 == 0 ? (size_t)6 * n * 32 * xs_slab_cap(E, M) : 0);
+}
+
+static int xs_check(int E, int n, int M, const void *H, const void *mean, const void *offsets, const void *counts, const void *flag,
+                    const void *workspace, size_t ws_bytes) {
+    SLK_REQUIRE(E >= 1 && E <= SLK_MX_MAX_EXPERTS, "E must be 1 .. %d experts (E = %d)", SLK_MX_MAX_EXPERTS, E);
+    SLK_REQUIRE(n >= 1 && M >= 1, "n and M must be at least 1 (n = %d, M = %d)", n, M);
+    SLK_REQUIRE(H && mean, "null H or mean");
+    SLK_REQUIRE(offsets, "null offsets");
+    SLK_REQUIRE(counts, "null counts");
+    SLK_REQUIRE(flag, "null flag");
+    SLK_REQUIRE((uintptr_t)workspace % 16 == 0, "the workspace must be aligned to 16 bytes");
+    SLK_REQUIRE(!workspace || ws_bytes >= xs_table_bytes(E), "the workspace is too small for the table of %d experts: %zu bytes, at least %zu",
+                E, ws_bytes, xs_table_bytes(E));
+    SLK_REQUIRE((n + T32 - 1) / T32 <= 65535, "n is above the 65535 tile rows of one launch (n = %d)", n);
+    return SLK_OK;
+}
+
+int slk_hessian_accumulate_experts(float *H, float *mean, const float *X, const int *offsets, int E, int n, int M, long long *counts,
+                                   int *flag, void *workspace, size_t ws_bytes, slk_stream_t stream) {
+    if (const int rc = xs_check(E, n, M, H, mean, offsets, counts, flag, workspace, ws_bytes)) return rc;
+    SLK_REQUIRE(X, "null X");
+    hipStream_t s = as_stream(stream);
+    int *table = static_cast<int *>(workspace);
+    const int nt = (n + T32 - 1) / T32;
+    SLK_RUN("expert_stats", 0, 4.0 * (E + 1) + 16.0 * E, s, k_expert_stats<<<1, 256, 0, s>>>(offsets, E, M, counts, table, flag, 1));
+    SLK_RUN("mean_update_experts", 0, 4.0 * M * n, s,
+            k_mean_update_experts<<<dim3((n + 31) / 32, E), 256, 0, s>>>(mean, X, n, table, offsets, counts, flag));
+    // bfloat16 x 3 path: whole tiles of features, and room for the planes of every expert's tokens padded to 32; no chunks
+    Arena ws(workspace, ws_bytes);
+    ws.take<int>(XS_HEAD + (size_t)XS_ENTRY * E);
+    const size_t slabs = xs_slab_cap(E, M);
+    // (its split is one launch over the slabs: past 65535 of them, 2 M tokens, the float32 chain as well)
+    unsigned short *planes =
+        n % T32 == 0 && slabs <= 65535 && !opt(OPT_NO_BF16_HESSIAN) ? ws.take<unsigned short>((size_t)3 * n * 32 * slabs) : nullptr;
+    if (planes) {
+        SLK_LDS_OPT_IN(k_hessian_tiles_bf16_experts<false>, sizeof(TileBf16Smem));
+        SLK_LDS_OPT_IN(k_hessian_tiles_bf16_experts<true>, sizeof(TileBf16DmaSmem));
+        const int dma = !opt(OPT_NO_BF16_DMA);
+        const int m = n / T32, total = m * (m + 1) / 2;
+        SLK_RUN("hessian_split_experts", 0, 10.0 * M * n, s,
+                k_split3_transposed_experts<<<dim3(m, (unsigned)slabs), 256, 0, s>>>(X, n, E, table, planes, dma));
+        if (dma)
+            SLK_RUN("hessian_syrk_bf16_experts", 6.0 * M * n * (n + (double)T32), 6.0 * M * n + 8.0 * n * n * E, s,
+                    k_hessian_tiles_bf16_experts<true><<<dim3(8 * ((total + 7) / 8), E), 256, sizeof(TileBf16DmaSmem), s>>>(H, planes, n, table));
+        else
+            SLK_RUN("hessian_syrk_bf16_experts", 6.0 * M * n * (n + (double)T32), 6.0 * M * n + 8.0 * n * n * E, s,
+                    k_hessian_tiles_bf16_experts<false><<<dim3(8 * ((total + 7) / 8), E), 256, sizeof(TileBf16Smem), s>>>(H, planes, n, table));
+        return SLK_OK;
+    }
+    SLK_RUN("hessian_syrk_experts", (double)M * n * (n + 1), 4.0 * M * n + 8.0 * n * n * E, s,
+            k_hessian_tiles_experts<<<dim3(nt, nt, E), 256, 0, s>>>(H, X, n, table, offsets, counts, flag));
+    return SLK_OK;
+}
+
+}  // extern "C"
+
+template <int FMT>
+static int hessian_experts_mx(float *H, float *mean, const uint8_t *a_codes, const uint8_t *a_scales, const int *offsets, int E, int n, int M,
+                              long long *counts, int *flag, int *table, hipStream_t s) {
+    const int nt = (n + T32 - 1) / T32;
+    const double coded = (double)M * n / 32.0 * mxa_block_bytes<FMT>();
+    SLK_RUN("expert_stats", 0, 4.0 * (E + 1) + 16.0 * E, s, k_expert_stats<<<1, 256, 0, s>>>(offsets, E, M, counts, table, flag, 2));
+    SLK_RUN("mean_update_experts_mx", 0, coded, s,
+            k_mean_update_experts_mx<FMT><<<dim3(n / 32, E), 256, 0, s>>>(mean, a_codes, a_scales, n, table, offsets, counts, flag, flag + 1));
+    SLK_RUN("hessian_syrk_experts_mx", (double)M * n * (n + 1), coded * nt + 8.0 * n * n * E, s,
+            k_hessian_tiles_experts_mx<FMT><<<dim3(nt, nt, E), 256, 0, s>>>(H, a_codes, a_scales, n, table, offsets, counts, flag));
+    return SLK_OK;
+}
+
+extern "C" {
+
+int slk_hessian_accumulate_experts_mx(float *H, float *mean, const uint8_t *a_codes, const uint8_t *a_scales, int a_fmt, const int *offsets,
+                                      int E, int n, int M, long long *counts, int *flag, void *workspace, size_t ws_bytes,
+                                      slk_stream_t stream) {
+    if (const int rc = xs_check(E, n, M, H, mean, offsets, counts, flag, workspace, ws_bytes)) return rc;
+    SLK_REQUIRE(n % 32 == 0, "MX blocks are 32 columns: n must be a positive multiple of 32 (n = %d)", n);
+    SLK_REQUIRE(a_codes && a_scales, "null a_codes or a_scales");
+    SLK_REQUIRE(aligned16(a_codes), "a_codes must be aligned to 16 bytes");
+    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP4 || a_fmt == SLK_MX_ACT_FP6, "unknown a_fmt %d", a_fmt);
+    hipStream_t s = as_stream(stream);
+    int *table = static_cast<int *>(workspace);
+    if (a_fmt == SLK_MX_ACT_FP4) return hessian_experts_mx<MXA_E2M1>(H, mean, a_codes, a_scales, offsets, E, n, M, counts, flag, table, s);
+    if (a_fmt == SLK_MX_ACT_FP6) return hessian_experts_mx<MXA_E2M3>(H, mean, a_codes, a_scales, offsets, E, n, M, counts, flag, table, s);
+    return hessian_experts_mx<MXA_E4M3>(H, mean, a_codes, a_scales, offsets, E, n, M, counts, flag, table, s);
 }
 
 }  // extern "C"

@@ -13,10 +13,17 @@ What each piece maps to:
   pipeline (`engine.quantize_layer`) and the bias correction `bias += ((W - Q) * mean).sum(1)`, all on device
   tensors -- the reference goes through `.numpy()` for every one of them (statistics.py:162-166).
 * the three presets (statistics.py:107-144) are rows of `_PRESETS`.
+
+`ExpertStatistics` is the same running mean and Hessian for the E experts of a mixture-of-experts layer, one grouped call
+a batch (`slk_hessian_accumulate_experts`, or `slk_hessian_accumulate_experts_mx` for rows that exist as MX codes only):
+
+    up = ExpertStatistics(E, K);  up.add_tokens(x, expert_ids)            # (T, K) rows, (T, k) routing
+    results = mx.quantize_experts(Ws, up.hessians())
 """
 
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -280,3 +287,106 @@ class Sleekit:
     def free(self):
         self.layer = self.mean = self.hessian = None
         self.count = 0
+
+
+class ExpertStatistics:
+    """Running statistics of the inputs of E experts of one shape: `hessian` (E, n, n), `mean` (E, n) float32 and `counts` (E,)
+    int64, all on the device.  A batch is one grouped call whatever the routing: each expert's statistics are bit for bit
+    what `Sleekit.add_batch` makes of that expert's rows, an expert without rows is not touched, and the host reads neither
+    the routing nor the counts.  E = 1 with offsets [0, M] is the dense case: a single layer's statistics, also from codes."""
+
+    def __init__(self, num_experts, features, device=None):
+        if isinstance(num_experts, bool) or not isinstance(num_experts, int) or not 1 <= num_experts <= _lib.MX_MAX_EXPERTS:
+            raise ValueError(f"num_experts must be 1 .. {_lib.MX_MAX_EXPERTS} (got {num_experts!r})")
+        if isinstance(features, bool) or not isinstance(features, int) or features < 1:
+            raise ValueError(f"features must be a positive int (got {features!r})")
+        self.device = torch.device(device) if device is not None else dev.require_gpu()
+        if self.device.type != "cuda":
+            raise RuntimeError("sleekit_amd.ExpertStatistics accumulates on the GPU")
+        self.num_experts, self.features = num_experts, features
+        self.hessian = torch.zeros((num_experts, features, features), dtype=torch.float32, device=self.device)
+        self.mean = torch.zeros((num_experts, features), dtype=torch.float32, device=self.device)
+        self.counts = torch.zeros(num_experts, dtype=torch.int64, device=self.device)
+
+    def _offsets(self, offsets):
+        from . import mx
+
+        mx._check_offsets(offsets, self.num_experts)
+        return dev.to_device(offsets, torch.int32)
+
+    def _workspace(self, features, rows):
+        return dev.scratch(_lib.lib.slk_hessian_experts_workspace_bytes(self.num_experts, features, rows), "expert_stats")
+
+    def _add_rows(self, rows, offsets, also=()):
+        """`rows` (M, n) float32 on the device, sorted by expert under the device `offsets`; the flags are read once, after the launches."""
+        from . import mx
+
+        M = rows.shape[0]
+        flag = torch.empty(1, dtype=torch.int32, device=rows.device)
+        ws, ws_bytes = self._workspace(self.features, M)
+        _lib.check(_lib.lib.slk_hessian_accumulate_experts(dev.ptr(self.hessian), dev.ptr(self.mean), dev.ptr(rows), dev.ptr(offsets),
+                                                            self.num_experts, self.features, M, dev.ptr(self.counts), dev.ptr(flag),
+                                                            dev.ptr(ws), ws_bytes, dev.stream_handle()))
+        mx._raise_flags(*also, (flag, mx._OFFSETS_RULE))
+
+    def _rows(self, x, what):
+        from . import mx
+
+        M, n = mx._matrix(x, what, mx._ACT)
+        if n != self.features:
+            raise ValueError(f"{what} has {n} columns but the statistics are of {self.features} features")
+        return dev.to_device(x, mx._torch_dtype(x)).float().contiguous()
+
+    def add_batch(self, x_sorted, offsets):
+        """One batch of rows already sorted by expert: x_sorted (M, n) float32, bfloat16 or float16 (converted to float32 as
+        Sleekit.add_batch converts), offsets int32 (E + 1,) as mx.matmul_mx_experts takes them.  Offsets that break the rule
+        change nothing and are a ValueError, raised after the launches by one read of the call's flag."""
+        rows = self._rows(x_sorted, "x_sorted")
+        self._add_rows(rows, self._offsets(offsets))
+
+    def add_tokens(self, x, expert_ids):
+        """One batch of routed tokens: x (T, n) and expert_ids (T,) or (T, k), sorted by mx.sort_by_expert's rule on the
+        device; a token counts once for each expert it goes to.  Ids outside 0 .. E - 1 are a ValueError (read with the
+        call's flag), and nothing is accumulated then: the grouped call is given offsets that break the rule."""
+        from . import mx
+
+        rows = self._rows(x, "x")
+        T = rows.shape[0]
+        if not isinstance(expert_ids, (np.ndarray, torch.Tensor)) or expert_ids.ndim not in (1, 2) or expert_ids.shape[0] != T or \
+                (expert_ids.ndim == 2 and expert_ids.shape[1] < 1):
+            raise ValueError(f"expert_ids must be ({T},) or ({T}, k) for x of {T} rows; got {tuple(getattr(expert_ids, 'shape', ()))}")
+        k = 1 if expert_ids.ndim == 1 else int(expert_ids.shape[1])
+        order, offsets, bad = mx._sorted_by_expert(mx._expert_ids(expert_ids, self.num_experts), self.num_experts)
+        offsets = offsets - bad  # (bad ids: offsets[0] == -1 breaks the rule on the device, so nothing is accumulated)
+        self._add_rows(rows[order // k], offsets, ((bad, mx._ids_message(self.num_experts)),))
+
+    def add_codes(self, a_codes, a_scales, offsets, activations="mxfp8"):
+        """One batch of rows that exist as MX codes, sorted by expert: a_codes / a_scales as the activation quantizers and
+        mx.matmul_mx_glu* write them, in the format `activations`.  The statistics are those of the de-quantized rows; the
+        product is one bfloat16 MFMA pass (every such value is a bfloat16 exactly).  An E8M0 NaN (scale byte 255) is a
+        ValueError."""
+        from . import mx
+
+        fmt = mx._activations(activations)
+        M, n = mx._act_operands(a_codes, a_scales, fmt)
+        if n != self.features:
+            raise ValueError(f"a_codes has {n} columns but the statistics are of {self.features} features")
+        offsets = self._offsets(offsets)
+        ac, asc = (dev.aligned(dev.to_device(t, torch.uint8)) for t in (a_codes, a_scales))
+        flag = torch.empty(2, dtype=torch.int32, device=ac.device)
+        ws, ws_bytes = self._workspace(32, M)
+        _lib.check(_lib.lib.slk_hessian_accumulate_experts_mx(dev.ptr(self.hessian), dev.ptr(self.mean), dev.ptr(ac), dev.ptr(asc), fmt.c_fmt,
+                                                               dev.ptr(offsets), self.num_experts, n, M, dev.ptr(self.counts), dev.ptr(flag),
+                                                               dev.ptr(ws), ws_bytes, dev.stream_handle()))
+        mx._raise_flags((flag[0], mx._OFFSETS_RULE), (flag[1], "a scale byte of the activations is 255: E8M0's NaN"))
+
+    def hessians(self, fill_unseen=True):
+        """The (E, n, n) Hessians, what mx.quantize_experts takes.  fill_unseen: an expert that has seen no token gets the
+        identity (GPTQ under H = I is round-to-nearest) in place of its zero matrix -- torch ops on the device, no host read."""
+        if not fill_unseen:
+            return self.hessian
+        eye = torch.eye(self.features, dtype=torch.float32, device=self.device)
+        return torch.where((self.counts == 0)[:, None, None], eye, self.hessian)
+
+    def free(self):
+        self.hessian = self.mean = self.counts = None
