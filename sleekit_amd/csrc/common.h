@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/sleekit_amd.h"
 
 namespace slk {
@@ -309,6 +311,24 @@ static inline int with_dtype(int dtype, F &&f) {
     if (dtype == SLK_DTYPE_BF16) return f(PkOut<PK_BF16>());
     if (dtype == SLK_DTYPE_F16) return f(PkOut<PK_F16>());
     return f(PkOut<PK_F32>());
+}
+
+// f(std::true_type()) or f(std::false_type()): the one place OPT_NO_BF16_DMA becomes a type -- true: the bfloat16 x 3
+// GEMMs bring their operands to LDS by global_load_lds (mfma_bf16x3.h), false: staged through registers.
+//   return with_bf16_staging([&](auto dma) -> int { SLK_RUN(..., kernel<dma.value><<<...>>>(...)); return SLK_OK; });
+template <class F>
+static inline int with_bf16_staging(F &&f) {
+    if (opt(OPT_NO_BF16_DMA)) return f(std::false_type());
+    return f(std::true_type());
+}
+
+// Entry `lin` of the lower triangle listed row by row, (0, 0), (1, 0), (1, 1), (2, 0), ... -> (bi, bj <= bi): the float32
+// guess of the row, corrected either way.
+__device__ __forceinline__ void lower_tile(int lin, int &bi, int &bj) {
+    bi = (int)((sqrtf(8.0f * (float)lin + 1.0f) - 1.0f) * 0.5f);
+    while (bi * (bi + 1) / 2 > lin) --bi;
+    while ((bi + 1) * (bi + 2) / 2 <= lin) ++bi;
+    bj = lin - bi * (bi + 1) / 2;
 }
 
 // Broadcast lane `src` (wave-uniform index) of a double to the whole wave through SGPRs.

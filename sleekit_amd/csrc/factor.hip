@@ -1087,10 +1087,9 @@ __global__ __launch_bounds__(256) void k_syrk_triangle(double *__restrict__ A, i
     const int total = m * (m + 1) / 2, per_xcd = (total + 7) / 8;
     const int lin = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if (lin >= total) return;
-    int row = (int)((sqrtf(8.0f * (float)lin + 1.0f) - 1.0f) * 0.5f);
-    while (row * (row + 1) / 2 > lin) --row;
-    while ((row + 1) * (row + 2) / 2 <= lin) ++row;
-    const int bi = t0 + row, bj = t0 + lin - row * (row + 1) / 2;
+    int bi, bj;
+    lower_tile(lin, bi, bj);
+    bi += t0, bj += t0;
     Acc64 acc;
     acc.zero();
     const int t = threadIdx.x;

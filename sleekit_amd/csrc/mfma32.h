@@ -49,6 +49,14 @@ struct Acc128 {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) c[i][j][r] = 0.0f;
     }
+    __device__ __forceinline__ void scale(float f) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) c[i][j][r] = c[i][j][r] * f;
+    }
 };
 
 // 8 consecutive floats from p (16-byte aligned when VEC), as two 16-byte loads.
@@ -123,19 +131,26 @@ __device__ __forceinline__ void tile128_mac(Acc128 &acc, Tile128Smem &sm, int k_
     }
 }
 
+// Where the accumulators lie in the tile (the D map above): register r of c[i][j] is (tile128_row(i, r), tile128_col(j)),
+// so c[i][0][r] and c[i][1][r] are two elements of one row, and the 32 lanes with the same lane >> 5 hold that row's others.
+__device__ __forceinline__ int tile128_row(int i, int r) {
+    const int lane = threadIdx.x & 63, wr = threadIdx.x >> 7;
+    return wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+}
+__device__ __forceinline__ int tile128_col(int j) {
+    const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
+    return wc * 64 + j * 32 + (lane & 31);
+}
+
 // f(row, col, value) for every accumulator element of this thread (tile-local coordinates).
 template <class F>
 __device__ __forceinline__ void tile128_foreach(const Acc128 &acc, F f) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                f(wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), wc * 64 + j * 32 + (lane & 31),
-                  acc.c[i][j][r]);
+            for (int r = 0; r < 16; ++r) f(tile128_row(i, r), tile128_col(j), acc.c[i][j][r]);
 }
 
 }  // namespace slk

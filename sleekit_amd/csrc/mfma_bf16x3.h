@@ -19,6 +19,8 @@
 //   D: as v_mfma_f32_32x32x2_f32 (mfma32.h)
 #pragma once
 
+#include <type_traits>
+
 #include "mfma32.h"
 
 namespace slk {
@@ -48,15 +50,42 @@ __device__ __forceinline__ void split3_pair(float x, float y, unsigned &w1, unsi
     w3 = __builtin_bit_cast(unsigned, (bf16x2_t){x3, y3});
 }
 
-// acc += A(128 x K) * Bt(128 x K)^T from operands split beforehand (k_split3 in sgemm.hip): plane p of A is a row-major
-// bfloat16 image A_p[row][k], likewise Bt_p[col][k].  The loop then has no vector arithmetic at all: six
-// 16-byte loads per operand and round, twelve LDS writes, the reads and the MFMAs.
-// la(k0, v) / lb(k0, v): v[p][h] = 16 bytes h of plane p of this thread's row (threadIdx.x >> 1), k = k0 + 16 (threadIdx.x & 1) + 8 h ...
-template <class LA, class LB>
-__device__ __forceinline__ void tile128_mac_planes(Acc128 &acc, TileBf16Smem &sm, int k_begin, int k_end, LA la, LB lb) {
+// The six piece products of one 32 x 32 block over 16 k, smallest terms first (pieces 3·1, 2·2, 1·3, 2·1, 1·2, 1·1):
+// both stagings below issue exactly this on the same accumulators in the same K order, so they agree bit for bit.
+__device__ __forceinline__ void mfma_bf16x3(float16_t &acc, const bf16x8_t (&a)[3], const bf16x8_t (&b)[3]) {
+    float16_t c = acc;
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
+    acc = c;
+}
+
+// acc += A(128 x K) * Bt(128 x K)^T from operands split beforehand (k_split3 in sgemm.hip): plane p of A is a
+// bfloat16 image A_p[row][k] in slabs, likewise Bt_p[col][k].  Both stagings take the operands the same way:
+// a_slabs / b_slabs: this tile's slab of K-step 0 in plane 0 -- 128 rows x 32 k, 4096 elements; consecutive K-steps are
+// 4096 elements apart, the planes a_plane / b_plane.
+//
+// Staged through registers.  The loop has no vector arithmetic at all: six 16-byte loads per operand and round,
+// twelve LDS writes, the reads and the MFMAs.
+__device__ __forceinline__ void tile128_mac_bf16_staged(Acc128 &acc, TileBf16Smem &sm, int k_begin, int k_end,
+                                                        const unsigned short *__restrict__ a_slabs, size_t a_plane,
+                                                        const unsigned short *__restrict__ b_slabs, size_t b_plane) {
     const int t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6;
     const int wr = wave >> 1, wc = wave & 1;
+    // v[p][h] = 16 bytes h of plane p of this thread's row (t >> 1) of the slab, k = k0 + 16 (t & 1) + 8 h ...
+    auto load = [&](const unsigned short *slabs, size_t plane, int k0, uint4v_t(&v)[3][2]) {
+        const unsigned short *q = slabs + (size_t)(k0 >> 5) * 4096 + (size_t)t * 16;
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) v[p][h] = *reinterpret_cast<const uint4v_t *>(q + p * plane + 8 * h);
+    };
+    auto la = [&](int k0, uint4v_t(&v)[3][2]) { load(a_slabs, a_plane, k0, v); };
+    auto lb = [&](int k0, uint4v_t(&v)[3][2]) { load(b_slabs, b_plane, k0, v); };
     // A round's MFMAs last ~0.7 us, less than a trip to memory: the loads run TWO rounds ahead, in two register
     // sets used in turn.  Rounds go in pairs and every load is issued unconditionally (clamped to the last
     // round), so that the compiler can count what is in flight (s_waitcnt vmcnt(12), not 0).
@@ -92,20 +121,10 @@ __device__ __forceinline__ void tile128_mac_planes(Acc128 &acc, TileBf16Smem &sm
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float16_t c = acc.c[i][j];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[j][0], c, 0, 0, 0);
-                    acc.c[i][j] = c;
-                }
+                for (int j = 0; j < 2; ++j) mfma_bf16x3(acc.c[i][j], a[i], b[j]);
         }
     };
-    // pairs of rounds; an odd count runs its last round once more with a zero weight?  No: every caller's depth
-    // is a multiple of 64 or ends on a pair boundary -- handled by the single-round tail below.
+    // pairs of rounds, then the single round an odd count leaves
     int k0 = k_begin;
     for (; k0 + 2 * KB16 <= k_end; k0 += 2 * KB16) {
         __syncthreads();
@@ -153,10 +172,9 @@ __device__ __forceinline__ int swizzled_chunk(int row, int c) { return c ^ ((row
 #ifndef SLK_BF16_COPY_AFTER_HALF
 #define SLK_BF16_COPY_AFTER_HALF 1
 #endif
-// a_slabs / b_slabs: this tile's slab of K-step 0 in plane 0 (consecutive steps 4096 elements apart, planes *_plane apart).
-__device__ __forceinline__ void tile128_mac_dma(Acc128 &acc, TileBf16DmaSmem &sm, int k_begin, int k_end,
-                                                const unsigned short *__restrict__ a_slabs, size_t a_plane,
-                                                const unsigned short *__restrict__ b_slabs, size_t b_plane) {
+__device__ __forceinline__ void tile128_mac_bf16_dma(Acc128 &acc, TileBf16DmaSmem &sm, int k_begin, int k_end,
+                                                    const unsigned short *__restrict__ a_slabs, size_t a_plane,
+                                                    const unsigned short *__restrict__ b_slabs, size_t b_plane) {
     const int t = threadIdx.x;
     const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wr = wave >> 1, wc = wave & 1;
@@ -208,18 +226,21 @@ __device__ __forceinline__ void tile128_mac_dma(Acc128 &acc, TileBf16DmaSmem &sm
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    float16_t c = acc.c[i][j];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i][2], b[s][j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i][1], b[s][j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i][0], b[s][j][2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i][1], b[s][j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i][0], b[s][j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s][i][0], b[s][j][0], c, 0, 0, 0);
-                    acc.c[i][j] = c;
-                }
+                for (int j = 0; j < 2; ++j) mfma_bf16x3(acc.c[i][j], a[s][i], b[s][j]);
         }
     }
+}
+
+// The one entry: DMA chooses the staging, smem_raw is the workgroup's sizeof(TileBf16<DMA>) bytes of LDS (16-byte aligned).
+template <bool DMA>
+using TileBf16 = std::conditional_t<DMA, TileBf16DmaSmem, TileBf16Smem>;
+template <bool DMA>
+__device__ __forceinline__ void tile128_mac_bf16(Acc128 &acc, unsigned char *smem_raw, int k_begin, int k_end,
+                                                 const unsigned short *__restrict__ a_slabs, size_t a_plane,
+                                                 const unsigned short *__restrict__ b_slabs, size_t b_plane) {
+    TileBf16<DMA> &sm = *reinterpret_cast<TileBf16<DMA> *>(smem_raw);
+    if constexpr (DMA) tile128_mac_bf16_dma(acc, sm, k_begin, k_end, a_slabs, a_plane, b_slabs, b_plane);
+    else tile128_mac_bf16_staged(acc, sm, k_begin, k_end, a_slabs, a_plane, b_slabs, b_plane);
 }
 
 }  // namespace slk

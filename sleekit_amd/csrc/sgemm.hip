@@ -21,6 +21,61 @@ namespace slk {
 // second kernel adds the tiles left to right, so results are run-to-run identical.
 using HPtrs = PtrTable;  // the Hessians of a batch of layers stacked by rows
 
+// The epilogue of both error kernels, for the tile at (r0, j0): rowpart[wc][row] = the sum over column wave wc's 64 columns
+// of acc * (W - Q); G, when given, receives acc.  The order of additions per row is fixed: 0 + acc d for column block 0,
+// then block 1, then the lane tree xor 16 ... xor 1 (and row_sums_store adds the two column waves).  GUARD: the columns at
+// or past n count for nothing (n % 128 != 0).
+// The 32 differences W - Q of a half of the sub-tile are fetched TOGETHER -- rows beyond R (GUARD: columns beyond n) read the
+// last one and count for nothing --, then the sixteen row sums go down the lane tree side by side.  Row by row -- four loads,
+// a wait, five dependent shuffles each -- the tail of a tile was 32 trips to memory one behind the other.
+template <bool GUARD>
+__device__ __forceinline__ void row_sums(const Acc128 &acc, const float *__restrict__ W, const float *__restrict__ Q,
+                                         float *__restrict__ G, int R, int n, int r0, int j0, float (&rowpart)[2][T32]) {
+    const int wc = (threadIdx.x >> 6) & 1;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float dd[16][2], sv[16];
+        // (plain loops over tile128_row: handed out through a lambda that captures W, Q and G, the compiler no longer
+        // proves the store to G apart from the loads behind it and waits for every pair of loads on its own)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = tile128_row(i, r);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int col = j0 + tile128_col(j);
+                const bool live = r0 + row < R && (!GUARD || col < n);
+                const size_t o = (size_t)min(r0 + row, R - 1) * n + (GUARD ? min(col, n - 1) : col);
+                dd[r][j] = W[o] - Q[o];
+                if (G && live) G[o] = acc.c[i][j][r];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float sacc = 0.0f;
+            if (r0 + tile128_row(i, r) < R) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    if (!GUARD || j0 + tile128_col(j) < n) sacc = sacc + acc.c[i][j][r] * dd[r][j];
+            }
+            sv[r] = sacc;
+        }
+#pragma unroll
+        for (int m = 16; m >= 1; m >>= 1)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sv[r] = sv[r] + __shfl_xor(sv[r], m, 64);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if ((threadIdx.x & 31) == 0) rowpart[wc][tile128_row(i, r)] = sv[r];
+    }
+}
+// ... and the tile's row sums to their slot of the scratch
+__device__ __forceinline__ void row_sums_store(const float (&rowpart)[2][T32], float *__restrict__ partial, int R, int r0, int p_stride,
+                                               int slot) {
+    __syncthreads();
+    if (threadIdx.x < T32 && r0 + threadIdx.x < R)
+        partial[(size_t)(r0 + threadIdx.x) * p_stride + slot] = rowpart[0][threadIdx.x] + rowpart[1][threadIdx.x];
+}
+
 __global__ __launch_bounds__(256) void k_error_tiles(const float *__restrict__ W, const float *__restrict__ Q,
                                                      const HPtrs hs, int R, int n,
                                                      float *__restrict__ G, float *__restrict__ partial,
@@ -61,13 +116,14 @@ __global__ __launch_bounds__(256) void k_error_tiles(const float *__restrict__ W
     const int ksplit = sym ? j0 : 0;  // [0, ksplit) counted twice
     const int a_row = r0 + (t >> 1), a_k = (t & 1) * 8;  // A: D = W - Q, K contiguous
     const int b_k = t >> 4, b_col = j0 + (t & 15) * 8;   // B: H, columns contiguous
-    auto twice = [&]() {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc.c[i][j][r] = acc.c[i][j][r] * 2.0f;
+    // the rows under the band, twice, then the band -- over whichever pair of loaders applies
+    auto product = [&](auto la, auto lb) {
+        if (ksplit > 0) {
+            tile128_mac<true, true>(acc, sm, 0, ksplit, la, lb);
+            acc.scale(2.0f);
+            __syncthreads();
+        }
+        tile128_mac<true, true>(acc, sm, ksplit, kend, la, lb);
     };
     if (vec_ok && r0 + T32 <= R && j0 + T32 <= n && kfull == n) {
         // interior tile: unconditional 16-byte loads
@@ -81,13 +137,8 @@ __global__ __launch_bounds__(256) void k_error_tiles(const float *__restrict__ W
             for (int e = 0; e < 8; ++e) v[e] = w[e] - q[e];
         };
         auto lb = [&](int k0, float(&v)[8]) { load8<true>(ph + (size_t)k0 * n, v); };
-        if (ksplit > 0) {
-            tile128_mac<true, true>(acc, sm, 0, ksplit, la, lb);
-            twice();
-            __syncthreads();
-        }
-        tile128_mac<true, true>(acc, sm, ksplit, kend, la, lb);
-    } else if (ksplit > 0) {
+        product(la, lb);
+    } else {
         const bool row_ok = a_row < R;
         const size_t arow = (size_t)min(a_row, R - 1) * n;
         auto la = [&](int k0, float(&v)[8]) {
@@ -102,56 +153,10 @@ __global__ __launch_bounds__(256) void k_error_tiles(const float *__restrict__ W
             const int k = k0 + b_k;
             load8_guarded(H + (size_t)min(k, n - 1) * n + min(b_col, n - 1), n - 1 - b_col, k < n, v);
         };
-        tile128_mac<true, true>(acc, sm, 0, ksplit, la, lb);
-        twice();
-        __syncthreads();
-        tile128_mac<true, true>(acc, sm, ksplit, kend, la, lb);
-    } else {
-        const bool row_ok = a_row < R;
-        const size_t arow = (size_t)min(a_row, R - 1) * n;
-        tile128_mac<true, true>(
-            acc, sm, 0, kend,
-            [&](int k0, float(&v)[8]) {
-                const int k = min(k0 + a_k, n - 1), last = n - 1 - (k0 + a_k);
-                float w[8], q[8];
-                load8_guarded(W + arow + k, last, row_ok, w);
-                load8_guarded(Q + arow + k, last, row_ok, q);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = w[e] - q[e];
-            },
-            [&](int k0, float(&v)[8]) {
-                const int k = k0 + b_k;
-                load8_guarded(H + (size_t)min(k, n - 1) * n + min(b_col, n - 1), n - 1 - b_col, k < n, v);
-            });
+        product(la, lb);
     }
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            float s = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int col = j0 + wc * 64 + j * 32 + (lane & 31);
-                const float v = acc.c[i][j][r];
-                if (r0 + row < R && col < n) {
-                    const size_t o = (size_t)(r0 + row) * n + col;
-                    if (G) G[o] = v;
-                    s = s + v * (W[o] - Q[o]);
-                }
-            }
-            // reduce over the 32 lanes that share this row
-#pragma unroll
-            for (int m = 16; m >= 1; m >>= 1) s = s + __shfl_xor(s, m, 64);
-            if ((lane & 31) == 0) rowpart[wc][row] = s;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < T32 && r0 + threadIdx.x < R)
-        partial[(size_t)(r0 + threadIdx.x) * p_stride + tile_x] = rowpart[0][threadIdx.x] + rowpart[1][threadIdx.x];
+    row_sums<true>(acc, W, Q, G, R, n, r0, j0, rowpart);
+    row_sums_store(rowpart, partial, R, r0, p_stride, tile_x);
 }
 
 // x (or x - y when y is given), rows x n row-major -> its three bfloat16 pieces in the GEMM's own order:
@@ -163,7 +168,7 @@ __global__ __launch_bounds__(256) void k_error_tiles(const float *__restrict__ W
 // would otherwise be split once per tile that uses it (32 times at n = 4096).
 // blockIdx.y: the layer of a stack (its own x, flag and planes: out + blockIdx.y * 3 * plane); one launch for a round's
 // Hessians -- eight 4 MB matrices split one by one are eight launches of 17 us each, bound by nothing but their number.
-// swz: the 16-byte chunks of a row swizzled for global_load_lds (tile128_mac_dma).
+// swz: the 16-byte chunks of a row swizzled for global_load_lds (tile128_mac_bf16<true>).
 __global__ __launch_bounds__(256) void k_split3(PtrTable xs, const float *__restrict__ y, int rows, int n,
                                                 unsigned short *__restrict__ out, size_t plane,
                                                 const int *__restrict__ sym_flag, int swz, int band_only, int average) {
@@ -202,7 +207,7 @@ __global__ __launch_bounds__(256) void k_split3(PtrTable xs, const float *__rest
         split3_pair(v[2], v[3], w[0][1], w[1][1], w[2][1]);
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
-            // (swz: the 16-byte chunk moves inside its row, see tile128_mac_dma)
+            // (swz: the 16-byte chunk moves inside its row, see swizzled_chunk)
             const size_t eo = swz ? (e & ~(size_t)31) + (size_t)(swizzled_chunk(r, k4 >> 3) * 8 + (k4 & 7)) : e;
             unsigned *o = reinterpret_cast<unsigned *>(out + (size_t)p * plane + eo);
             o[0] = w[p][0];
@@ -222,9 +227,7 @@ __global__ __launch_bounds__(256) void k_error_tiles_bf16(const float *__restric
                                                           float *__restrict__ partial, int n_tiles,
                                                           const int *__restrict__ sym_flag, int p_stride, int cb, int rpl,
                                                           float *__restrict__ G, int asym_mode) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    TileBf16Smem &sm = *reinterpret_cast<TileBf16Smem *>(smem_raw);
-    TileBf16DmaSmem &smd = *reinterpret_cast<TileBf16DmaSmem *>(smem_raw);  // DMA: operands copied to LDS by the loads themselves
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];  // TileBf16<DMA>
     __shared__ float rowpart[2][T32];
     // XCD-aware tile order, column-major inside the XCD.  Workgroup i runs on XCD i % 8 (own L2).  XCD x takes
     // the row tiles [x rpx, (x + 1) rpx) (rpx = 4 for a 4096-row layer) and walks the column tiles in the order
@@ -275,100 +278,41 @@ __global__ __launch_bounds__(256) void k_error_tiles_bf16(const float *__restric
     const bool full_k = G != nullptr || (sym_flag[layer] <= 0 && asym_mode != 2);  // (2: the planes hold (H + H^T) / 2)
     if (sym_flag[layer] <= 0 && !asym_mode) return;
     Hp += (size_t)layer * 3 * n * n;
-    const int t = threadIdx.x;
     Acc128 acc;
     acc.zero();
-    // slab (row block, k step) of a plane: 128 x 32 bfloat16, this thread's 32 bytes at (t >> 1, 16 (t & 1))
     const int ksteps = n / 32;
     const size_t d_plane = (size_t)n_rt * T32 * n, h_plane = (size_t)n * n;
-    const unsigned short *pd = Dp + (size_t)tile_y * ksteps * 4096 + (size_t)t * 16;
-    const unsigned short *ph = Hp + (size_t)tile_x * ksteps * 4096 + (size_t)t * 16;
-    auto la = [&](int k0, uint4v_t(&v)[3][2]) {
-        const unsigned short *q = pd + (size_t)(k0 >> 5) * 4096;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) v[p][h] = *reinterpret_cast<const uint4v_t *>(q + p * d_plane + 8 * h);
-    };
-    auto lb = [&](int k0, uint4v_t(&v)[3][2]) {
-        const unsigned short *q = ph + (size_t)(k0 >> 5) * 4096;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) v[p][h] = *reinterpret_cast<const uint4v_t *>(q + p * h_plane + 8 * h);
-    };
+    const unsigned short *a_slabs = Dp + (size_t)tile_y * ksteps * 4096, *b_slabs = Hp + (size_t)tile_x * ksteps * 4096;
+    auto product = [&](int k_begin, int k_end) { tile128_mac_bf16<DMA>(acc, smem_raw, k_begin, k_end, a_slabs, d_plane, b_slabs, h_plane); };
     // sum_k D_k H_kj over all k == 2 * sum_{k < j0} + the 128-wide diagonal band (see k_error_tiles)
     const int k_lo = blk_lo * T32, k_below = min(blk_hi * T32, j0);  // [k_lo, k_below) lies under the band: twice
-    const unsigned short *a_slabs = Dp + (size_t)tile_y * ksteps * 4096, *b_slabs = Hp + (size_t)tile_x * ksteps * 4096;
     if (full_k) {
         // the product itself is wanted (local search: G = (W - Q) H, obq.py:231), or H is not symmetric: every k, nothing
         // counted twice
-        if (DMA)
-            tile128_mac_dma(acc, smd, 0, n, a_slabs, d_plane, b_slabs, h_plane);
-        else
-            tile128_mac_planes(acc, sm, 0, n, la, lb);
+        product(0, n);
     } else if (k_below > k_lo) {
-        if (DMA)
-            tile128_mac_dma(acc, smd, k_lo, k_below, a_slabs, d_plane, b_slabs, h_plane);
-        else
-            tile128_mac_planes(acc, sm, k_lo, k_below, la, lb);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc.c[i][j][r] = acc.c[i][j][r] * 2.0f;
+        product(k_lo, k_below);
+        acc.scale(2.0f);
         __syncthreads();
     }
-    if (!full_k && blk_hi == tile_x + 1) {
-        if (DMA)
-            tile128_mac_dma(acc, smd, j0, j0 + T32, a_slabs, d_plane, b_slabs, h_plane);
-        else
-            tile128_mac_planes(acc, sm, j0, j0 + T32, la, lb);
-    }
+    if (!full_k && blk_hi == tile_x + 1) product(j0, j0 + T32);
+    row_sums<false>(acc, W, Q, G, R, n, r0, j0, rowpart);
+    row_sums_store(rowpart, partial, R, r0, p_stride, p_slot);
+}
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    // (epilogue: the 32 differences W - Q of a half of the sub-tile are fetched TOGETHER -- rows beyond R read the last row
-    // and count for nothing --, then the sixteen row sums go down the lane tree side by side.  Row by row -- four loads,
-    // a wait, five dependent shuffles each -- the tail of a tile was 32 trips to memory one behind the other.)
+// H[i][j .. j + 3] of an n x n matrix, zeros beyond it; vec: one 16-byte load where all four are inside
+__device__ __forceinline__ float4_t load4_inside(const float *__restrict__ H, int n, bool vec, int i, int j) {
+    float4_t v = (float4_t){0.0f, 0.0f, 0.0f, 0.0f};
+    if (i < n) {
+        if (vec && j + 3 < n) {
+            v = *reinterpret_cast<const float4_t *>(H + (size_t)i * n + j);
+        } else {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float dd[16][2], sv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            const bool live = r0 + row < R;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const size_t o = (size_t)min(r0 + row, R - 1) * n + j0 + wc * 64 + j * 32 + (lane & 31);
-                dd[r][j] = W[o] - Q[o];
-                if (G && live) G[o] = acc.c[i][j][r];
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            float sacc = 0.0f;
-            if (r0 + row < R) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) sacc = sacc + acc.c[i][j][r] * dd[r][j];
-            }
-            sv[r] = sacc;
-        }
-#pragma unroll
-        for (int m = 16; m >= 1; m >>= 1)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] = sv[r] + __shfl_xor(sv[r], m, 64);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if ((lane & 31) == 0) rowpart[wc][row] = sv[r];
+            for (int e = 0; e < 4; ++e)
+                if (j + e < n) v[e] = H[(size_t)i * n + j + e];
         }
     }
-    __syncthreads();
-    if (threadIdx.x < T32 && r0 + threadIdx.x < R)
-        partial[(size_t)(r0 + threadIdx.x) * p_stride + p_slot] = rowpart[0][threadIdx.x] + rowpart[1][threadIdx.x];
+    return v;
 }
 
 // flag[0] = 1 iff H is bit-wise symmetric (flag must be preset to 1).  One workgroup per pair of mirrored
@@ -378,48 +322,27 @@ __global__ __launch_bounds__(256) void k_symmetry_flag(PtrTable hs, int n, int *
     __shared__ float tile[64][65];
     const float *__restrict__ H = hs.p[blockIdx.y];  // blockIdx.y: the layer of a stack, with a flag of its own
     flag += blockIdx.y;
-    // pair index -> (bi >= bj)
-    int bi = (int)((sqrtf(8.0f * (float)blockIdx.x + 1.0f) - 1.0f) * 0.5f);
-    while ((bi + 1) * (bi + 2) / 2 <= (int)blockIdx.x) ++bi;
-    while (bi * (bi + 1) / 2 > (int)blockIdx.x) --bi;
-    const int bj = (int)blockIdx.x - bi * (bi + 1) / 2;
+    int bi, bj;  // pair index -> (bi >= bj)
+    lower_tile(blockIdx.x, bi, bj);
     const int t = threadIdx.x, c4 = (t & 15) * 4, r_first = t >> 4;  // 16 threads x 16 bytes per row, 16 rows per pass
     const bool vec = n % 4 == 0 && (uintptr_t)H % 16 == 0;
     bool ok = true;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const int r = r_first + 16 * p, i = bi * 64 + r, j = bj * 64 + c4;
-        float4_t v = (float4_t){0.0f, 0.0f, 0.0f, 0.0f};
-        if (i < n) {
-            if (vec && j + 3 < n) {
-                v = *reinterpret_cast<const float4_t *>(H + (size_t)i * n + j);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j + e < n) v[e] = H[(size_t)i * n + j + e];
-            }
-        }
+        const int r = r_first + 16 * p;
+        const float4_t v = load4_inside(H, n, vec, bi * 64 + r, bj * 64 + c4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) tile[r][c4 + e] = v[e];
     }
     __syncthreads();
-    {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int r = r_first + 16 * p, i = bj * 64 + r, j = bi * 64 + c4;  // the mirrored tile, read row-wise
-            if (i >= n) continue;
-            float4_t v = (float4_t){0.0f, 0.0f, 0.0f, 0.0f};
-            if (vec && j + 3 < n) {
-                v = *reinterpret_cast<const float4_t *>(H + (size_t)i * n + j);
-            } else {
+    for (int p = 0; p < 4; ++p) {
+        const int r = r_first + 16 * p, i = bj * 64 + r, j = bi * 64 + c4;  // the mirrored tile, read row-wise
+        if (i >= n) continue;
+        const float4_t v = load4_inside(H, n, vec, i, j);
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j + e < n) v[e] = H[(size_t)i * n + j + e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (j + e < n) ok = ok && (__float_as_int(v[e]) == __float_as_int(tile[c4 + e][r]));
-        }
+        for (int e = 0; e < 4; ++e)
+            if (j + e < n) ok = ok && (__float_as_int(v[e]) == __float_as_int(tile[c4 + e][r]));
     }
     if (!ok) flag[0] = 0;
 }
@@ -447,6 +370,18 @@ __device__ __forceinline__ void hessian_store(float *__restrict__ H, int n, int 
     const float h = H[(size_t)i * n + j] * factor + v / count;
     H[(size_t)i * n + j] = h;
     if (i != j) H[(size_t)j * n + i] = h;
+}
+// ... and the lower tile (bi, bj) of them from its accumulators: inside the matrix, and on a diagonal tile at or under the
+// diagonal only (the mirror writes the rest).
+// (The 64 read-modify-writes of a thread come out as 64 load -> wait -> store round trips one behind the other; fetching
+// the old values first was measured on the bfloat16 kernel: 310 against 300 us per 2048 tokens -- 256 VGPRs, and two
+// workgroups per CU hide the tail as it is.)
+__device__ __forceinline__ void hessian_store_tile(const Acc128 &acc, float *__restrict__ H, int n, int bi, int bj, float factor,
+                                                   float count) {
+    tile128_foreach(acc, [&](int r, int c, float v) {
+        const int i = bi * T32 + r, j = bj * T32 + c;
+        if (i < n && j < n && (bi != bj || j <= i)) hessian_store(H, n, i, j, v, factor, count);
+    });
 }
 
 // Lower tile (bi, bj) of X^T X, mirrored on store so H stays exactly symmetric.
@@ -476,6 +411,8 @@ __device__ __forceinline__ void hessian_tile_f32(Tile128Smem &sm, float *__restr
                 load8_guarded(X + (size_t)min(k, T - 1) * n + min(b_col, n - 1), n - 1 - b_col, k < T, v);
             });
     }
+    // (hessian_store_tile written out: through the shared function k_hessian_tiles_experts compiled to another epilogue and
+    // was measured 1.8 % slower where an expert has a hundred rows -- DESIGN.md section 29)
     tile128_foreach(acc, [&](int r, int c, float v) {
         const int i = i0 + r, j = j0 + c;
         if (i < n && j < n && (bi != bj || j <= i)) hessian_store(H, n, i, j, v, factor, count);
@@ -532,46 +469,15 @@ __global__ __launch_bounds__(256) void k_split3_transposed(PtrTable xs, int n, i
 template <bool DMA>
 __device__ __forceinline__ void hessian_tile_bf16(unsigned char *smem_raw, float *__restrict__ H, const unsigned short *__restrict__ Xp, int n,
                                                   int ksteps, size_t plane, int block, float factor, float count) {
-    TileBf16Smem &sm = *reinterpret_cast<TileBf16Smem *>(smem_raw);
     const int m = n / T32, total = m * (m + 1) / 2, per_xcd = (total + 7) / 8;
     const int lin = (block & 7) * per_xcd + (block >> 3);
     if (lin >= total) return;
-    int bi = (int)((sqrtf(8.0f * (float)lin + 1.0f) - 1.0f) * 0.5f);
-    while (bi * (bi + 1) / 2 > lin) --bi;
-    while ((bi + 1) * (bi + 2) / 2 <= lin) ++bi;
-    const int bj = lin - bi * (bi + 1) / 2;
-    const int t = threadIdx.x;
+    int bi, bj;
+    lower_tile(lin, bi, bj);
     Acc128 acc;
     acc.zero();
-    const unsigned short *pa = Xp + (size_t)bi * ksteps * 4096 + (size_t)t * 16;
-    const unsigned short *pb = Xp + (size_t)bj * ksteps * 4096 + (size_t)t * 16;
-    auto la = [&](int k0, uint4v_t(&v)[3][2]) {
-        const unsigned short *q = pa + (size_t)(k0 >> 5) * 4096;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) v[p][h] = *reinterpret_cast<const uint4v_t *>(q + p * plane + 8 * h);
-    };
-    auto lb = [&](int k0, uint4v_t(&v)[3][2]) {
-        const unsigned short *q = pb + (size_t)(k0 >> 5) * 4096;
-#pragma unroll
-        for (int p = 0; p < 3; ++p)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) v[p][h] = *reinterpret_cast<const uint4v_t *>(q + p * plane + 8 * h);
-    };
-    if (DMA)
-        tile128_mac_dma(acc, *reinterpret_cast<TileBf16DmaSmem *>(smem_raw), 0, ksteps * 32, Xp + (size_t)bi * ksteps * 4096, plane,
-                        Xp + (size_t)bj * ksteps * 4096, plane);
-    else
-        tile128_mac_planes(acc, sm, 0, ksteps * 32, la, lb);
-    const int i0 = bi * T32, j0 = bj * T32;
-    // (the 64 read-modify-writes of a thread come out as 64 load -> wait -> store round trips one behind the other; fetching
-    // the old values first was measured: 310 against 300 us per 2048 tokens -- 256 VGPRs, and two workgroups per CU hide the
-    // tail as it is)
-    tile128_foreach(acc, [&](int r, int c, float v) {
-        const int i = i0 + r, j = j0 + c;
-        if (bi != bj || j <= i) hessian_store(H, n, i, j, v, factor, count);
-    });
+    tile128_mac_bf16<DMA>(acc, smem_raw, 0, ksteps * 32, Xp + (size_t)bi * ksteps * 4096, plane, Xp + (size_t)bj * ksteps * 4096, plane);
+    hessian_store_tile(acc, H, n, bi, bj, factor, count);
 }
 template <bool DMA>
 __global__ __launch_bounds__(256) void k_hessian_tiles_bf16(float *__restrict__ H, const unsigned short *__restrict__ Xp, int n,
@@ -633,7 +539,8 @@ struct ExpertRows {
     int first, rows, slab;  // rows == 0: nothing to do (no rows, or offsets that break the rule)
     float f, cnt;
 };
-__device__ __forceinline__ void expert_factor(long long before, int rows, float &f, float &cnt) {
+// `rows` tokens on top of `before`: H = H f + X^T X / cnt (slk_hessian_accumulate on the host, the prologue on the device)
+__host__ __device__ __forceinline__ void expert_factor(long long before, int rows, float &f, float &cnt) {
     const long long after = before + rows;
     f = (float)((double)before / (double)after);
     cnt = (float)after;
@@ -755,7 +662,6 @@ __global__ __launch_bounds__(256) void k_hessian_tiles_bf16_experts(float *__res
 __device__ __forceinline__ int mxs_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
 typedef short bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 // the 32x32x16 operand of 32 features from feature f0 of the image, tokens k0 .. k0 + 15: lane l holds feature f0 + (l & 31),
 // tokens k0 + 8 (l >> 5) + 0 .. 7.  Every lane of the wave must call it (the gather crosses lanes).
 __device__ __forceinline__ bf16x8_t mxs_operand(const unsigned char *img, int f0, int k0) {
@@ -807,15 +713,10 @@ __global__ __launch_bounds__(256) void k_hessian_tiles_experts_mx(float *__restr
     const ExpertRows x = expert_rows(table, offsets, counts, flag, blockIdx.z);
     if (x.rows == 0) return;
     H += (size_t)blockIdx.z * n * n;
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int t = threadIdx.x, wave = t >> 6;
     const int i0 = bi * T32, j0 = bj * T32, wi = 64 * (wave >> 1), wj = 64 * (wave & 1);
-    float16_t acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    Acc128 acc;
+    acc.zero();
     const int tok = t >> 3, fc = (t & 7) * 16;  // this thread stages 16 features (half a block) of one token, per operand
     for (int k0 = 0; k0 < x.rows; k0 += 32) {
         __syncthreads();
@@ -850,19 +751,10 @@ __global__ __launch_bounds__(256) void k_hessian_tiles_experts_mx(float *__restr
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int u = 0; u < 2; ++u) acc[s][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], b[u], acc[s][u], 0, 0, 0);
+                for (int u = 0; u < 2; ++u) acc.c[s][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], b[u], acc.c[s][u], 0, 0, 0);
         }
     }
-    // D of the MFMA: column lane & 31, row (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = i0 + wi + 32 * s + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), j = j0 + wj + 32 * u + (lane & 31);
-                if (i < n && j < n && (bi != bj || j <= i)) hessian_store(H, n, i, j, acc[s][u][r], x.f, x.cnt);
-            }
+    hessian_store_tile(acc, H, n, bi, bj, x.f, x.cnt);
 }
 
 }  // namespace slk
@@ -871,10 +763,19 @@ using namespace slk;
 
 extern "C" {
 
-static PtrTable one_ptr(const float *p) {
+static PtrTable ptr_table(const float *const *ps, int count) {
     PtrTable t;
-    for (int b = 0; b < 64; ++b) t.p[b] = b == 0 ? p : nullptr;
+    for (int b = 0; b < 64; ++b) t.p[b] = b < count ? ps[b] : nullptr;
     return t;
+}
+static PtrTable one_ptr(const float *p) { return ptr_table(&p, 1); }
+
+// flag[b] = 1 iff the n x n matrix hs.p[b] is bit-wise symmetric, b < batch
+static int symmetry_flags(const PtrTable &hs, int batch, int n, int *flag, hipStream_t s) {
+    const int t64 = (n + 63) / 64;
+    SLK_RUN("set_flag", 0, 4, s, k_set_flag<<<1, 64, 0, s>>>(flag, 1, batch));
+    SLK_RUN("symmetry_check", 0, 4.0 * n * n * batch, s, k_symmetry_flag<<<dim3(t64 * (t64 + 1) / 2, batch), 256, 0, s>>>(hs, n, flag));
+    return SLK_OK;
 }
 
 static int row_errors_impl(const float *W, const float *Q, const float *const *Hs, int batch, int rpl, int n, float *row_err,
@@ -906,17 +807,14 @@ static int row_errors_impl(const float *W, const float *Q, const float *const *H
     if (cb > 0) zero_async(partial, (size_t)R * n_slots * sizeof(float), s);  // the float32 kernel fills n_tiles slots only
     dim3 grid(8 * ((n_tiles * n_rt + 7) / 8));  // a multiple of the 8 XCDs: see the tile order in the kernel
     bool aligned = ((uintptr_t)W | (uintptr_t)Q) % 16 == 0;
-    HPtrs hp;
-    for (int b = 0; b < 64; ++b) hp.p[b] = b < batch ? Hs[b] : nullptr;
+    const HPtrs hp = ptr_table(Hs, batch);
     for (int b = 0; b < batch; ++b) aligned = aligned && (uintptr_t)Hs[b] % 16 == 0;
     const int vec_ok = n % 4 == 0 && aligned;
     const bool try_sym = !opt(OPT_NO_SYM_ERROR);  // (with G too: the bfloat16 kernel needs H symmetric)
     if (try_sym && sym_known) {
         sym = const_cast<int *>(sym_known);  // verdicts computed elsewhere (slk_symmetry_flag), read only from here on
     } else if (try_sym) {
-        SLK_RUN("set_flag", 0, 4, s, k_set_flag<<<1, 64, 0, s>>>(sym, 1, batch));
-        const int t64 = (n + 63) / 64;
-        SLK_RUN("symmetry_check", 0, 4.0 * n * n * batch, s, k_symmetry_flag<<<dim3(t64 * (t64 + 1) / 2, batch), 256, 0, s>>>(hp, n, sym));
+        if (const int rc = symmetry_flags(hp, batch, n, sym, s)) return rc;
     }
     // the bfloat16 x 3 kernel when the shape allows (16-byte loads, whole tiles of columns).  Its operands are split into
     // planes first, 10 bytes of traffic per element of H and layer; until the end of round 2 a batch with fewer than 1024
@@ -944,9 +842,7 @@ static int row_errors_impl(const float *W, const float *Q, const float *const *H
     };
     // algorithmic flops: the definition (2 R n^2) whichever way they are obtained
     if (bf16_ok) {
-        SLK_LDS_OPT_IN(k_error_tiles_bf16<false>, sizeof(TileBf16Smem));
-        SLK_LDS_OPT_IN(k_error_tiles_bf16<true>, sizeof(TileBf16DmaSmem));
-        const int dma = !opt(OPT_NO_BF16_DMA);  // operands to LDS by global_load_lds (swizzled planes)
+        const int dma = !opt(OPT_NO_BF16_DMA);  // operands to LDS by global_load_lds: swizzled planes
         SLK_RUN("error_split", 0, 14.0 * R * n, s,
                 k_split3<<<2048, 256, 0, s>>>(one_ptr(W), Q, R, n, Dp, d_plane, batch == 1 && !asym_mode ? sym : nullptr, dma, 0, 0));
         {
@@ -962,14 +858,15 @@ static int row_errors_impl(const float *W, const float *Q, const float *const *H
         // flops as executed: six bfloat16 products per float32 product, over k <= j only (the definition of the
         // layer error, SURVEY.md 8d, counts 2 R n^2 float32 flops: a third of this, twice over)
         const int wgs = cb > 0 ? n_rt * n_slots : 8 * ((n_rt + 7) / 8) * ((n_tiles + 7) / 8 * 8);  // see the tile order in the kernel
-        if (dma)
+        const int rc = with_bf16_staging([&](auto staging) -> int {
+            constexpr bool DMA = decltype(staging)::value;
+            SLK_LDS_OPT_IN(k_error_tiles_bf16<DMA>, sizeof(TileBf16<DMA>));
             SLK_RUN_W("error_gemm_bf16", 6.0 * R * n * (n + (double)T32), 6.0 * R * n + 3.0 * n * n * batch, cb > 0 ? wgs : n_rt * n_tiles, s,
-                      k_error_tiles_bf16<true><<<wgs, 256, sizeof(TileBf16DmaSmem), s>>>(W, Q, Dp, Hp, R, n, partial, n_tiles, sym, n_slots,
-                                                                                         cb, rpl, G, asym_mode));
-        else
-            SLK_RUN_W("error_gemm_bf16", 6.0 * R * n * (n + (double)T32), 6.0 * R * n + 3.0 * n * n * batch, cb > 0 ? wgs : n_rt * n_tiles, s,
-                      k_error_tiles_bf16<false><<<wgs, 256, sizeof(TileBf16Smem), s>>>(W, Q, Dp, Hp, R, n, partial, n_tiles, sym, n_slots,
-                                                                                        cb, rpl, G, asym_mode));
+                      k_error_tiles_bf16<DMA><<<wgs, 256, sizeof(TileBf16<DMA>), s>>>(W, Q, Dp, Hp, R, n, partial, n_tiles, sym, n_slots, cb,
+                                                                                      rpl, G, asym_mode));
+            return SLK_OK;
+        });
+        if (rc) return rc;
         if (!asym_mode) SLK_RUN("error_gemm_f32", 0, 0, s, f32_all(sym, 1));
     } else {
         SLK_RUN("error_gemm", 2.0 * R * n * n, 8.0 * R * n + 4.0 * n * n * batch + (G ? 4.0 * R * n : 0.0), s,
@@ -996,19 +893,14 @@ int slk_row_errors_batch(const float *W, const float *Q, const float *const *H, 
 
 int slk_symmetry_flag(const float *H, int n, int *flag, slk_stream_t stream) {
     SLK_REQUIRE(H && flag && n > 0, "bad arguments");
-    hipStream_t s = as_stream(stream);
-    const int t64 = (n + 63) / 64;
-    SLK_RUN("set_flag", 0, 4, s, k_set_flag<<<1, 64, 0, s>>>(flag, 1, 1));
-    SLK_RUN("symmetry_check", 0, 4.0 * n * n, s, k_symmetry_flag<<<t64 * (t64 + 1) / 2, 256, 0, s>>>(one_ptr(H), n, flag));
-    return SLK_OK;
+    return symmetry_flags(one_ptr(H), 1, n, flag, as_stream(stream));
 }
 
 int slk_hessian_accumulate(float *H, float *mean, const float *X, int n, int T, long long count_before,
                            void *workspace, size_t ws_bytes, slk_stream_t stream) {
     SLK_REQUIRE(H && mean && X && n > 0 && T > 0 && count_before >= 0, "bad arguments");
-    const long long after = count_before + T;
-    const float factor = (float)((double)count_before / (double)after);
-    const float count = (float)after;
+    float factor, count;
+    expert_factor(count_before, T, factor, count);
     hipStream_t s = as_stream(stream);
     const int nt = (n + T32 - 1) / T32;
     SLK_RUN("mean_update", 0, 4.0 * T * n, s, k_mean_update<<<(n + 31) / 32, 256, 0, s>>>(mean, X, n, T, factor, count));
@@ -1016,8 +908,6 @@ int slk_hessian_accumulate(float *H, float *mean, const float *X, int n, int T, 
     Arena ws(workspace, ws_bytes);
     const size_t room = workspace && ws_bytes > 4096 ? (ws_bytes - 4096) / ((size_t)6 * n) / 32 * 32 : 0;  // tokens per chunk
     if (n % T32 == 0 && room >= 32 && !opt(OPT_NO_BF16_HESSIAN)) {
-        SLK_LDS_OPT_IN(k_hessian_tiles_bf16<false>, sizeof(TileBf16Smem));
-        SLK_LDS_OPT_IN(k_hessian_tiles_bf16<true>, sizeof(TileBf16DmaSmem));
         const int dma = !opt(OPT_NO_BF16_DMA);
         const int chunk = (int)(room < (size_t)((T + 31) / 32 * 32) ? room : (size_t)((T + 31) / 32 * 32));
         unsigned short *Xp = ws.take<unsigned short>((size_t)3 * n * chunk);
@@ -1028,14 +918,15 @@ int slk_hessian_accumulate(float *H, float *mean, const float *X, int n, int T, 
             SLK_RUN("hessian_split", 0, 10.0 * cnt * n, s,
                     k_split3_transposed<<<dim3(m, ksteps), 256, 0, s>>>(one_ptr(X), n, T, t0, cnt, Xp, plane, dma, nullptr));
             // the running-mean factor applies once per batch: later chunks add to what the first one scaled
-            if (dma)
+            const int rc = with_bf16_staging([&](auto staging) -> int {
+                constexpr bool DMA = decltype(staging)::value;
+                SLK_LDS_OPT_IN(k_hessian_tiles_bf16<DMA>, sizeof(TileBf16<DMA>));
                 SLK_RUN("hessian_syrk_bf16", 6.0 * cnt * n * (n + (double)T32), 6.0 * cnt * n + 8.0 * n * n, s,
-                        k_hessian_tiles_bf16<true><<<8 * ((total + 7) / 8), 256, sizeof(TileBf16DmaSmem), s>>>(
+                        k_hessian_tiles_bf16<DMA><<<8 * ((total + 7) / 8), 256, sizeof(TileBf16<DMA>), s>>>(
                             H, Xp, n, ksteps, plane, t0 == 0 ? factor : 1.0f, count));
-            else
-                SLK_RUN("hessian_syrk_bf16", 6.0 * cnt * n * (n + (double)T32), 6.0 * cnt * n + 8.0 * n * n, s,
-                        k_hessian_tiles_bf16<false><<<8 * ((total + 7) / 8), 256, sizeof(TileBf16Smem), s>>>(
-                            H, Xp, n, ksteps, plane, t0 == 0 ? factor : 1.0f, count));
+                return SLK_OK;
+            });
+            if (rc) return rc;
         }
         return SLK_OK;
     }
@@ -1087,19 +978,17 @@ int slk_hessian_accumulate_experts(float *H, float *mean, const float *X, const 
     unsigned short *planes =
         n % T32 == 0 && slabs <= 65535 && !opt(OPT_NO_BF16_HESSIAN) ? ws.take<unsigned short>((size_t)3 * n * 32 * slabs) : nullptr;
     if (planes) {
-        SLK_LDS_OPT_IN(k_hessian_tiles_bf16_experts<false>, sizeof(TileBf16Smem));
-        SLK_LDS_OPT_IN(k_hessian_tiles_bf16_experts<true>, sizeof(TileBf16DmaSmem));
         const int dma = !opt(OPT_NO_BF16_DMA);
         const int m = n / T32, total = m * (m + 1) / 2;
         SLK_RUN("hessian_split_experts", 0, 10.0 * M * n, s,
                 k_split3_transposed_experts<<<dim3(m, (unsigned)slabs), 256, 0, s>>>(X, n, E, table, planes, dma));
-        if (dma)
+        return with_bf16_staging([&](auto staging) -> int {
+            constexpr bool DMA = decltype(staging)::value;
+            SLK_LDS_OPT_IN(k_hessian_tiles_bf16_experts<DMA>, sizeof(TileBf16<DMA>));
             SLK_RUN("hessian_syrk_bf16_experts", 6.0 * M * n * (n + (double)T32), 6.0 * M * n + 8.0 * n * n * E, s,
-                    k_hessian_tiles_bf16_experts<true><<<dim3(8 * ((total + 7) / 8), E), 256, sizeof(TileBf16DmaSmem), s>>>(H, planes, n, table));
-        else
-            SLK_RUN("hessian_syrk_bf16_experts", 6.0 * M * n * (n + (double)T32), 6.0 * M * n + 8.0 * n * n * E, s,
-                    k_hessian_tiles_bf16_experts<false><<<dim3(8 * ((total + 7) / 8), E), 256, sizeof(TileBf16Smem), s>>>(H, planes, n, table));
-        return SLK_OK;
+                    k_hessian_tiles_bf16_experts<DMA><<<dim3(8 * ((total + 7) / 8), E), 256, sizeof(TileBf16<DMA>), s>>>(H, planes, n, table));
+            return SLK_OK;
+        });
     }
     SLK_RUN("hessian_syrk_experts", (double)M * n * (n + 1), 4.0 * M * n + 8.0 * n * n * E, s,
             k_hessian_tiles_experts<<<dim3(nt, nt, E), 256, 0, s>>>(H, X, n, table, offsets, counts, flag));
