@@ -91,7 +91,8 @@ typedef void *slk_stream_t;
  * activations: slk_mx_quantize_act6, slk_mx_dequantize_act6, slk_mx_gemm_a6 and slk_mx_rotate_quantize_act6 (likewise), then MXFP6
  * (E2M3) layers: slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6 and slk_mx_gemm_w6 (likewise), then the expert-grouped
  * product: slk_mx_experts_workspace_bytes and slk_mx_gemm_experts (likewise), then the gated MLP: slk_mx_glu, slk_mx_gemm_glu
- * and slk_mx_gemm_glu_experts (likewise). */
+ * and slk_mx_gemm_glu_experts (likewise), then the weight-only products of an MX layer against 16-bit activations:
+ * slk_mx_gemm_a16 and slk_mx_gemm_experts_a16 (likewise). */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -751,6 +752,41 @@ int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, con
                             const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha,
                             float limit, float shift, int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag,
                             void *workspace, size_t ws_bytes, slk_stream_t stream);
+
+/* A stored MX layer against 16-bit activations, weight-only (W4A16, W6A16): the layer as slk_mx_pack / slk_mx_pack6 left it,
+ * de-quantized inside a bfloat16 / float16 MFMA GEMM (v_mfma_f32_16x16x32_bf16 / _f16).  No de-quantized weight is written
+ * to memory, nothing quantizes the activations, and the dense call is one launch without a workspace.
+ * slk_mx_gemm_a16: out[m][n] = sum_k Xc[m][k] Wc[n][k] (+ bias[n]) for a layer of N rows (output features) and K columns:
+ *   - Wc is what the layer's de-quantizer writes in the compute type, slk_mx_dequantize (w_fmt SLK_MX_W_FP4, E2M1; w_codes
+ *     N x K / 2) or slk_mx_dequantize_act6 (SLK_MX_W_FP6, E2M3; w_codes N x 3 K / 4) with out_dtype = compute_dtype:
+ *     value(code) 2^(b - 127) in float32, b the block's byte of w_scales (N x K / 32), rounded once to nearest even;
+ *   - Xc is X (M x K row-major, `x_dtype`: float32, bfloat16 or float16) rounded to nearest even to the compute type through
+ *     float32 (the identity when it has it);
+ *   - compute_dtype is SLK_DTYPE_BF16 or SLK_DTYPE_F16; the products are exact in float32, the sums float32 inside the MFMA
+ *     over K in a fixed order (no atomics: a repeated call gives the same bits); the float32 bias (N, may be NULL) is added
+ *     in float32 and the result rounded once to `out_dtype` (M x N row-major).
+ *   Exactness.  The operand contract is promised where every non-zero Wc is a NORMAL number of the compute type: scale bytes
+ *   10 .. 245 for bfloat16 (as slk_hessian_accumulate_experts_mx words it), 116 .. 140 for float16.  Outside these ranges Wc
+ *   is still the de-quantizer's value for every scale byte -- the float32 product rounded to nearest even: a subnormal, a
+ *   zero or an infinity of the compute type -- and what a subnormal operand then contributes is the MFMA's own treatment of
+ *   subnormals, which this library does not examine.  (One bit of Wc differs from the de-quantizer's and no sum can show it:
+ *   the E2M1 code 0x8 is -0 where the de-quantizer writes +0.)  Scale byte 255 is not looked for: its block's products are
+ *   NaN, as in slk_mx_gemm.  X is not looked at for NaN or infinity either: they propagate as in any GEMM.
+ *   Up to M = 64 a workgroup is one 16 x 16 tile of out whose 8 waves share K (the layer is read once per 16 rows); above, a
+ *   workgroup is a 64 x 64 tile that de-quantizes its weights into LDS -- the switch of slk_mx_gemm.
+ * slk_mx_gemm_experts_a16: the same over the E layers of a mixture-of-experts layer, rows sorted by expert, under
+ *   slk_mx_gemm_experts' rules word for word: w_codes / w_scales / bias E layers one after the other, offsets (DEVICE, E + 1
+ *   ints) and their rule, flag (DEVICE int, written by the call; 1 and out untouched where the rule breaks), an expert
+ *   without rows, the workspace of slk_mx_experts_workspace_bytes(E, M) and its layout, three launches in order on `stream`.
+ *   Each expert's rows are BIT FOR BIT slk_mx_gemm_a16 on that slice of X with that expert's layer and bias.
+ * SLK_E_ARG, before any launch, slk_last_error() naming the offender: M or N < 1, K % 32 != 0 or K < 32, a NULL X, w_codes,
+ *   w_scales or out, an unknown x_dtype, out_dtype or w_fmt, compute_dtype not BF16 or F16, X, w_codes or out off 16-byte
+ *   alignment, ceil(M / 64) above the 65535 row tiles of one launch; for the experts what slk_mx_gemm_experts refuses. */
+int slk_mx_gemm_a16(const void *X, int x_dtype, const uint8_t *w_codes, const uint8_t *w_scales, int w_fmt, const float *bias,
+                    int M, int N, int K, int compute_dtype, int out_dtype, void *out, slk_stream_t stream);
+int slk_mx_gemm_experts_a16(const void *X, int x_dtype, const uint8_t *w_codes, const uint8_t *w_scales, int w_fmt,
+                            const float *bias, const int *offsets, int E, int M, int N, int K, int compute_dtype, int out_dtype,
+                            void *out, int *flag, void *workspace, size_t ws_bytes, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -28,6 +28,7 @@
 // The stored forms feed the instruction with plain loads (16 bytes a piece; three of 8 for E2M3): no shuffle, no pre-swizzle, no LDS.
 // D: lane l holds column l & 15, rows 4 (l >> 4) + 0 .. 3.
 #include "common.h"
+#include "mxexperts.h"
 #include "mxglu.h"
 #include "mxquant.h"
 
@@ -163,10 +164,9 @@ __device__ __forceinline__ void store_tile(v4f acc, const float *__restrict__ bi
 // Few rows (M <= MXG_SPLIT_MAX_M): the weights are read once and the time is their bandwidth, so a workgroup is one
 // 16 x 16 tile of Y and its SK waves share K: wave w takes the 128-steps w, w + SK, ..., in this order, and wave 0 adds
 // the SK partial tiles in wave order.  Both orders are fixed, so a result does not depend on timing.
-constexpr int MXG_SK = 8;
-constexpr int MXG_SPLIT_MAX_M = 64;
-// (The body is shared with the expert-grouped kernel below: row0 / rows are the tile's first row and the row bound of the
-// matrix -- or of the expert --, n0 the tile's first column.)
+// (MXG_SK and MXG_SPLIT_MAX_M are mxexperts.h's: mxgemm_a16.hip switches forms where this file does.  The body is shared
+// with the expert-grouped kernel below: row0 / rows are the tile's first row and the row bound of the matrix -- or of the
+// expert --, n0 the tile's first column.)
 template <int OUT, int AF, int WF>
 __device__ __forceinline__ void mx_gemm_splitk_tile(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                     const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
@@ -464,21 +464,8 @@ __global__ __launch_bounds__(256) void k_mx_expert_tiles(const int *__restrict__
     if (t < 2) ws[t] = base[t];
 }
 
-// One row tile of one expert: the dense kernels' bodies on that expert's layer, bias and row bound.
-template <int WF>
-struct ExpertTile {
-    const uint8_t *Wc, *Ws;
-    const float *bias;
-    int row0, rows;
-    __device__ __forceinline__ ExpertTile(const int *__restrict__ table, const uint8_t *__restrict__ w_codes,
-                                          const uint8_t *__restrict__ w_scales, const float *__restrict__ b, int N, int K) {
-        const int *entry = table + 3 * (size_t)blockIdx.y;
-        const size_t e = (size_t)entry[0], blocks = (size_t)N * (K / 32);
-        Wc = w_codes + e * blocks * (4 * mxa_bits<WF>()), Ws = w_scales + e * blocks;  // 16 or 24 bytes of codes a block
-        bias = b ? b + e * N : nullptr;
-        row0 = entry[1], rows = entry[2];
-    }
-};
+// One row tile of one expert is an ExpertTile (mxexperts.h): the dense kernels' bodies on that expert's layer, bias and
+// row bound.
 template <int OUT, int AF, int WF>
 __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_experts_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                                         const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
@@ -571,8 +558,8 @@ static int mx_check_gated(int M, int N, const void *h_scales, const int *flag, f
     SLK_REQUIRE(interleaved == 0 || interleaved == 1, "interleaved must be 0 or 1 (got %d)", interleaved);
     return SLK_OK;
 }
-// ... and the expert-grouped ones, behind it (M is positive by then)
-static int mx_check_experts(int E, int M, const int *offsets, const void *workspace, size_t ws_bytes) {
+// ... and the expert-grouped ones, behind it (M is positive by then; mxexperts.h: mxgemm_a16.hip's entry asks the same)
+int slk::mx_check_experts(int E, int M, const int *offsets, const void *workspace, size_t ws_bytes) {
     SLK_REQUIRE(offsets, "null offsets");
     SLK_REQUIRE(workspace && (uintptr_t)workspace % sizeof(int) == 0, "the workspace must be non-null and aligned to 4 bytes");
     SLK_REQUIRE(ws_bytes >= slk_mx_experts_workspace_bytes(E, M), "the workspace is too small: %zu bytes, slk_mx_experts_workspace_bytes(%d, %d) = %zu",
@@ -583,11 +570,7 @@ static int mx_check_experts(int E, int M, const int *offsets, const void *worksp
 
 // The prologue of both expert-grouped products: k_mx_expert_tiles on the stream, and what the two launches behind it need --
 // host-computable upper bounds of the tile counts as grid rows, and the two tables (their counts are ws[0] and ws[1]).
-struct ExpertGrid {
-    int rows16, rows64;
-    const int *t16, *t64;
-};
-static int mx_expert_prologue(const int *offsets, int E, int M, int *ws, int *flag, hipStream_t s, ExpertGrid &g) {
+int slk::mx_expert_prologue(const int *offsets, int E, int M, int *ws, int *flag, hipStream_t s, ExpertGrid &g) {
     const int cap16 = (int)mxe_cap16(E, M), cap64 = (int)mxe_cap64(E, M);
     // an expert of the split-K form has at most MXG_SPLIT_MAX_M / 16 tiles, so 4 E bounds the first launch as well
     g = {cap16 < 4 * E ? cap16 : 4 * E, cap64, ws + MXE_HEAD, ws + MXE_HEAD + 3 * (size_t)cap16};

@@ -82,6 +82,15 @@ Known answers: indices 0, 1, 30, 31, 32, 61, 62 are codes 3f 3e 21 00 01 1e 1f; 
     res = quantize_mxfp6(W, H, nb_ls_moves=10);  y = linear_mxfp6(x, res.codes, res.scales, bias, activations="mxfp6_e2m3")
     layer = MXLinear.from_result(nn_linear, res)          # the format is read off the widths of res.codes and res.scales
 
+WEIGHT-ONLY (W4A16, W6A16).  `activations="bfloat16"` or "float16" (linear_mxfp4, linear_mxfp6, linear_mx_experts, MXLinear,
+MXExperts; both weight formats) quantizes nothing: the layer is de-quantized inside a bfloat16 / float16 MFMA GEMM
+(slk_mx_gemm_a16) and x, rounded to that type where it is float32, meets dequantize_mxfp4 / _mxfp6(codes, scales, dtype=that
+type) bit for bit.  One launch, no flag, no wait for the stream; a NaN or an infinity in x propagates as in any GEMM.  The
+operand contract is promised where every non-zero weight is a normal number of the type: scale bytes 10 .. 245 for bfloat16,
+116 .. 140 for float16.  `rotation=R` is the call on R.apply(x, dtype=that type).  matmul_mx* and the gated MLP take coded
+activations only and refuse the two names.
+    y = linear_mxfp4(x, res.codes, res.scales, bias, activations="bfloat16");  layer = MXLinear.from_result(nn_linear, res, "bfloat16")
+
 EXPERTS.  A mixture-of-experts layer is E packed layers of one shape, stacked: codes (E, N, K bits / 8), scales (E, N, K / 32),
 bias (E, N).  One call multiplies every row with the layer of its expert (slk_mx_gemm_experts): the rows are sorted by expert
 and `offsets`, int32 (E + 1,) on the device, says where each expert's rows begin -- offsets[0] == 0, never decreasing,
@@ -356,14 +365,30 @@ _FORMATS = {f.name: f for f in (
     _Format("mxfp4", 4, _lib.MX_ACT_FP4, "slk_mx_quantize_act4", "slk_mx_dequantize", "slk_mx_rotate_quantize_act", True),
     _Format("mxfp6_e2m3", 6, _lib.MX_ACT_FP6, "slk_mx_quantize_act6", "slk_mx_dequantize_act6", "slk_mx_rotate_quantize_act6", False),
 )}
-_ACTIVATIONS = tuple(_FORMATS)
+# The 16-bit activations of the weight-only mode (module docstring, W4A16 / W6A16) are no coded format: x itself, rounded to
+# `dtype` inside the product, which de-quantizes the layer to that type (slk_mx_gemm_a16).  Both weight formats take both.
+_Half = collections.namedtuple("_Half", "name dtype")
+_HALVES = {h.name: h for h in (_Half("bfloat16", torch.bfloat16), _Half("float16", torch.float16))}
+_ACTIVATIONS = tuple(_FORMATS) + tuple(_HALVES)
 _ACTIVATIONS_ARE = "activations must be " + ", ".join(f'"{name}"' for name in _ACTIVATIONS[:-1]) + f' or "{_ACTIVATIONS[-1]}"'
+# What refuses a 16-bit name where only coded activations make sense (each text names the way that does exist)
+_CODES_ONLY = ('16-bit activations are not codes: matmul_mx* multiply activations that exist as MX codes; for "bfloat16" or "float16" '
+               "call linear_mxfp4, linear_mxfp6 or linear_mx_experts on x itself")
+_GATED_CODES_ONLY = ('a gated MLP writes its hidden activations as MX codes: 16-bit activations ("bfloat16", "float16") through the gated '
+                     "epilogue are not supported; use \"mxfp8\", \"mxfp4\" or \"mxfp6_e2m3\", or run the layers as MXLinear / MXExperts")
+_STATS_CODES_ONLY = ('add_codes takes rows that exist as MX codes ("mxfp8", "mxfp4" or "mxfp6_e2m3"): 16-bit rows go to add / add_tokens '
+                     "as they are")
 
 
-def _activations(activations):
-    """The _Format of an `activations` value.  (The bare "mxfp6" names two element formats and is refused.)"""
-    if not isinstance(activations, str) or activations not in _FORMATS:
+def _activations(activations, coded=None):
+    """The _Format of an `activations` value, or the _Half of a 16-bit one.  (The bare "mxfp6" names two element formats and is
+    refused.)  coded: the caller takes coded activations only, and this is its text for a 16-bit name."""
+    if not isinstance(activations, str) or activations not in _ACTIVATIONS:
         raise ValueError(f"{_ACTIVATIONS_ARE} (got {activations!r})")
+    if activations in _HALVES:
+        if coded is not None:
+            raise ValueError(f'{coded} (got "{activations}")')
+        return _HALVES[activations]
     return _FORMATS[activations]
 
 
@@ -424,7 +449,7 @@ _MXFP6_TAKES = 'an MXFP6 layer takes "mxfp8" or "mxfp6_e2m3" activations'  # (th
 
 
 def _check_pair(fmt, wf):
-    if fmt.name not in wf.activations:
+    if fmt.name not in wf.activations and fmt.name not in _HALVES:
         raise ValueError(f'{_MXFP6_TAKES} (got "{fmt.name}")')
 
 
@@ -441,6 +466,20 @@ def _gemm(ac, asc, wc, wsc, bias, M, N, K, dtype, fmt=_FORMATS["mxfp8"], wf=_FP4
     which = (fmt.c_fmt,) if takes_fmt else ()
     _lib.check(getattr(_lib.lib, entry)(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, *which, _OUT[dtype],
                                         dev.ptr(out), dev.stream_handle()))
+    return out
+
+
+def _rotated_x(Xd, rotation, half):
+    """What the weight-only product reads: x, or behind a rotation x R in the compute type (slk_hadamard_rows writing it)."""
+    return Xd if rotation is None else rotation.apply(Xd, dtype=half.dtype)
+
+
+def _gemm_a16(Xd, wc, wsc, bias, M, N, K, dtype, half, wf):
+    """out (M, N) of a contiguous device x (M, K) against a packed layer, weight-only: one launch, no flag, nothing to wait for."""
+    Xd = dev.aligned(Xd)
+    out = torch.empty((M, N), dtype=dtype, device=Xd.device)
+    _lib.check(_lib.lib.slk_mx_gemm_a16(dev.ptr(Xd), _OUT[Xd.dtype], dev.ptr(wc), dev.ptr(wsc), wf.c_fmt, dev.ptr(bias), M, N, K,
+                                        _OUT[half.dtype], _OUT[dtype], dev.ptr(out), dev.stream_handle()))
     return out
 
 
@@ -624,7 +663,7 @@ def matmul_mx(a_codes, a_scales, codes, scales, bias=None, dtype=torch.float32, 
     -- or, with activations="mxfp4", MXFP4 activations (M, K / 2), or, with "mxfp6_e2m3", MXFP6 ones (M, 3 K / 4) -- against
     an MXFP4 layer (N, K), float32 sums in a fixed order, the result rounded once to `dtype`.  weights="mxfp6_e2m3": against
     an MXFP6 layer, codes (N, 3 K / 4), with "mxfp8" or "mxfp6_e2m3" activations."""
-    fmt, wf = _activations(activations), _weight_format(weights)
+    fmt, wf = _activations(activations, _CODES_ONLY), _weight_format(weights)
     _check_pair(fmt, wf)
     _out_dtype(dtype, a_codes)
     M, K = _act_operands(a_codes, a_scales, fmt)
@@ -640,13 +679,17 @@ def linear_mxfp4(x, codes, scales, bias=None, dtype=None, activations="mxfp8", r
     quantize_mxfp6_act, the W4A6 path), multiplied with the layer (N, K) as
     in matmul_mx and the float32 bias (N,) added; the result is (..., N) in `dtype`, or in x's dtype when `dtype` is None.
     rotation (a rotation.Rotation over K features): x R is quantized instead of x, the rotation running inside the
-    quantizer -- bit for bit linear_mxfp4(rotation.apply(x, dtype=torch.float32), ...) with the same `dtype` result."""
+    quantizer -- bit for bit linear_mxfp4(rotation.apply(x, dtype=torch.float32), ...) with the same `dtype` result.
+    activations="bfloat16" or "float16": weight-only (module docstring) -- nothing is quantized, the layer is de-quantized
+    inside a 16-bit MFMA GEMM, one launch; a non-finite x is not refused; rotation= is then the call on
+    rotation.apply(x, dtype=that type)."""
     return _linear(x, codes, scales, bias, dtype, activations, rotation, _FP4)
 
 
 def linear_mxfp6(x, codes, scales, bias=None, dtype=None, activations="mxfp8", rotation=None):
     """linear_mxfp4 with a packed MXFP6 weight, codes (N, 3 K / 4): W6A8 with activations="mxfp8", W6A6 with "mxfp6_e2m3"
-    ("mxfp4": ValueError).  The activation quantizers, the fused rotation and the result's dtype are linear_mxfp4's."""
+    ("mxfp4": ValueError), W6A16 with "bfloat16" or "float16".  The activation quantizers, the fused rotation, the
+    weight-only mode and the result's dtype are linear_mxfp4's."""
     return _linear(x, codes, scales, bias, dtype, activations, rotation, _FP6)
 
 
@@ -656,9 +699,12 @@ def _linear(x, codes, scales, bias, dtype, activations, rotation, wf):
     layer = _layer(codes, scales, bias, wf)
     _check_rotation(rotation, layer.K, "rotation")
     Xd, lead, M, dtype = _float_rows(x, layer, "", dtype)
-    ac, asc, flag = _quantize_x(Xd, M, layer.K, rotation, fmt)
-    out = _gemm(ac, asc, *layer.operands(), M, layer.N, layer.K, dtype, fmt, wf)
-    _raise_finite(flag)
+    if isinstance(fmt, _Half):
+        out = _gemm_a16(_rotated_x(Xd, rotation, fmt), *layer.operands(), M, layer.N, layer.K, dtype, fmt, wf)
+    else:
+        ac, asc, flag = _quantize_x(Xd, M, layer.K, rotation, fmt)
+        out = _gemm(ac, asc, *layer.operands(), M, layer.N, layer.K, dtype, fmt, wf)
+        _raise_finite(flag)
     return dev.like_input(out.reshape(lead + (layer.N,)), x)
 
 
@@ -693,7 +739,7 @@ class _MXModule(torch.nn.Module):
             state_dict = {k: v for k, v in state_dict.items() if k != key}  # (the base class knows no such key)
         if weights != self.weights:  # (the buffers have the module's shape: another format is never read into them)
             error_msgs.append(f"{key}: the state is of an {weights!r} layer, this module holds {self.weights!r} weights")
-        elif activations not in _WEIGHTS[self.weights].activations:
+        elif activations not in _WEIGHTS[self.weights].activations and activations not in _HALVES:
             error_msgs.append(f"{key}: {_MXFP6_TAKES} (got {activations!r})")
             activations = self.activations
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
@@ -712,7 +758,7 @@ def _result_format(result):
 class MXLinear(_MXModule):
     """A linear layer kept in its packed MX form: buffers `codes` (N, K / 2), `scales` (N, K / 32) and `bias` (N,) float32
     or None; forward(x) = linear_mxfp4(x, codes, scales, bias, activations=activations).  `activations` ("mxfp8", the
-    default, "mxfp4" or "mxfp6_e2m3") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8".
+    default, "mxfp4", "mxfp6_e2m3", or weight-only "bfloat16" / "float16") is plain extra state: a state_dict saved before it existed has none, loads unchanged and means "mxfp8".
     weights="mxfp6_e2m3": an MXFP6 layer, `codes` (N, 3 K / 4), forward through linear_mxfp6; it refuses "mxfp4" activations.
     `weights` is extra state too, written only when it is not "mxfp4"; a state of the other weight format is an error."""
 
@@ -787,6 +833,18 @@ def _gemm_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, dtype, fmt, wf):
     return out, flag
 
 
+def _gemm_experts_a16(Xd, wc, wsc, bias, offsets, E, M, N, K, dtype, half, wf):
+    """_gemm_experts for 16-bit activations (slk_mx_gemm_experts_a16): the same workspace, the same flag."""
+    Xd = dev.aligned(Xd)
+    out = torch.empty((M, N), dtype=dtype, device=Xd.device)
+    flag = torch.empty(1, dtype=torch.int32, device=Xd.device)
+    ws, ws_bytes = dev.scratch(_lib.lib.slk_mx_experts_workspace_bytes(E, M), "mx_experts")
+    _lib.check(_lib.lib.slk_mx_gemm_experts_a16(dev.ptr(Xd), _OUT[Xd.dtype], dev.ptr(wc), dev.ptr(wsc), wf.c_fmt, dev.ptr(bias), dev.ptr(offsets),
+                                                E, M, N, K, _OUT[half.dtype], _OUT[dtype], dev.ptr(out), dev.ptr(flag), dev.ptr(ws), ws_bytes,
+                                                dev.stream_handle()))
+    return out, flag
+
+
 def _expert_tile_tables(E, M):
     """The two tile tables the last grouped product of (E, M) on this stream left in its workspace, as NumPy arrays (tiles, 3)
     of (expert, first row, row bound): 16-row tiles, then 64-row tiles (tests/test_gpu_mx_experts.py holds them to a model)."""
@@ -803,7 +861,7 @@ def matmul_mx_experts(a_codes, a_scales, codes, scales, offsets, bias=None, dtyp
     offsets is int32 (E + 1,) and stays on the device; it must start at 0, never decrease and end at M (an expert may have
     no rows).  The rule is checked on the device: where it does not hold nothing is computed and a ValueError is raised --
     after the launches, by one read of the call's flag (which waits for the stream)."""
-    fmt, wf = _activations(activations), _weight_format(weights)
+    fmt, wf = _activations(activations, _CODES_ONLY), _weight_format(weights)
     _check_pair(fmt, wf)
     _out_dtype(dtype, a_codes)
     M, K = _act_operands(a_codes, a_scales, fmt)
@@ -823,8 +881,13 @@ def _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotatio
     _check_rotation(rotation, layer.K, "rotation", "the layers have")
     _check_offsets(offsets, layer.E)
     Xd, _, M, dtype = _float_rows(x, layer, "", dtype)
-    ac, asc, finite = _quantize_x(Xd, M, layer.K, rotation, fmt)
-    out, flag = _gemm_experts(ac, asc, *layer.operands(), dev.to_device(offsets, torch.int32), layer.E, M, layer.N, layer.K, dtype, fmt, wf)
+    od = dev.to_device(offsets, torch.int32)
+    if isinstance(fmt, _Half):
+        finite = None
+        out, flag = _gemm_experts_a16(_rotated_x(Xd, rotation, fmt), *layer.operands(), od, layer.E, M, layer.N, layer.K, dtype, fmt, wf)
+    else:
+        ac, asc, finite = _quantize_x(Xd, M, layer.K, rotation, fmt)
+        out, flag = _gemm_experts(ac, asc, *layer.operands(), od, layer.E, M, layer.N, layer.K, dtype, fmt, wf)
     _raise_flags(*also, (finite, _H_FINITE), (flag, _OFFSETS_RULE))
     return dev.like_input(out, x)
 
@@ -835,7 +898,8 @@ def linear_mx_experts(x, codes, scales, offsets, bias=None, dtype=None, activati
     `rotation`, of the fused rotate-and-quantize kernel), then multiplied by one grouped product; (M, N) in `dtype`, or in
     x's dtype when `dtype` is None.  The two flags -- finite activations, the offsets rule -- are read together after the
     launches: one wait for the stream a call.  With rotation= the result is the call on rotation.apply(x,
-    dtype=torch.float32) bit for bit."""
+    dtype=torch.float32) bit for bit.  activations="bfloat16" or "float16": weight-only as in linear_mxfp4 -- no quantizer, the
+    offsets flag alone is read, and rotation= is the call on rotation.apply(x, dtype=that type)."""
     return _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotation, _weight_format(weights))
 
 
@@ -1085,7 +1149,7 @@ def _gemm_glu_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, fmt, wf, gate
 
 def _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved, fused=True):
     """matmul_mx_glu before its flag is read: (h_codes, h_scales, flag), device tensors."""
-    fmt, wf = _activations(activations), _weight_format(weights)
+    fmt, wf = _activations(activations, _GATED_CODES_ONLY), _weight_format(weights)
     _check_pair(fmt, wf)
     gate = _gate(alpha, limit, shift, interleaved)
     M, K = _act_operands(a_codes, a_scales, fmt)
@@ -1107,7 +1171,7 @@ def matmul_mx_glu(a_codes, a_scales, codes, scales, bias=None, activations="mxfp
 
 def _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, activations, weights, alpha, limit, shift, interleaved, fused=True):
     """matmul_mx_glu_experts before its flags are read: (h_codes, h_scales, offsets flag, finite flag), device tensors."""
-    fmt, wf = _activations(activations), _weight_format(weights)
+    fmt, wf = _activations(activations, _GATED_CODES_ONLY), _weight_format(weights)
     _check_pair(fmt, wf)
     gate = _gate(alpha, limit, shift, interleaved)
     M, K = _act_operands(a_codes, a_scales, fmt)
@@ -1141,7 +1205,7 @@ def _mlp_layers(up, down, wf_up, wf_down, stacked=False):
 
 def _gated_mlp(x, up, down, dtype, activations, gate, rotation, down_rotation, fused, wf_up, wf_down):
     """gated_mlp_mx on up = (codes, scales, bias) and down = the same, each layer in its own weight format."""
-    fmt = _activations(activations)
+    fmt = _activations(activations, _GATED_CODES_ONLY)
     _check_pair(fmt, wf_up)
     _check_pair(fmt, wf_down)
     up, down = _mlp_layers(up, down, wf_up, wf_down)
@@ -1172,7 +1236,7 @@ def gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales, up_bias=None, 
 
 
 def _gated_mlp_experts(x, up, down, offsets, dtype, activations, gate, rotation, down_rotation, fused, wf_up, wf_down, also=()):
-    fmt = _activations(activations)
+    fmt = _activations(activations, _GATED_CODES_ONLY)
     _check_pair(fmt, wf_up)
     _check_pair(fmt, wf_down)
     up, down = _mlp_layers(up, down, wf_up, wf_down, stacked=True)
@@ -1201,6 +1265,7 @@ class _GatedModule(torch.nn.Module):
         N = _hidden(up.out_features)
         if down.in_features != N:
             raise ValueError(f"the down layer has {down.in_features} columns but the up layer gives {N} hidden columns")
+        _activations(up.activations, _GATED_CODES_ONLY), _activations(down.activations, _GATED_CODES_ONLY)
         if up.activations != down.activations:
             raise ValueError(f"up and down must take the same activations: h is written in x's format (got {up.activations!r} and {down.activations!r})")
         self.up, self.down = up, down

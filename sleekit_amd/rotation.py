@@ -201,7 +201,7 @@ class RotatedLinear(torch.nn.Module):
     def from_result(cls, layer, result, codebook=None, fused=False, activations="mxfp8", **kw):
         """The module of a torch.nn.Linear and the result of Sleekit(layer).quantize_packed / quantize_mxfp4 / quantize_mxfp6 (rotation=):
         MXLinear.from_result(layer, result) inside when the result carries `codes`, else PackedLinear.from_result(layer,
-        result, codebook, **kw).  fused and activations ("mxfp8" | "mxfp4" | "mxfp6_e2m3") are the MXLinear's (class docstring, mx.MXLinear)."""
+        result, codebook, **kw).  fused and activations ("mxfp8" | "mxfp4" | "mxfp6_e2m3" | "bfloat16" | "float16") are the MXLinear's (class docstring, mx.MXLinear)."""
         rotation = getattr(result, "rotation", None)
         if rotation is None:
             raise ValueError("the result carries no rotation: it was not quantized with rotation=")
@@ -218,9 +218,16 @@ class RotatedLinear(torch.nn.Module):
         return cls(inner, rotation, fused)
 
     def forward(self, x):
-        if self.fused:
+        if self.fused or self._weight_only():
             return self.inner(x, rotation=self.rotation)
         return self.inner(self.rotation.apply(x))
+
+    def _weight_only(self):
+        """An MXLinear with 16-bit activations inside: it has no quantizer to fuse the rotation into, and rotates x itself --
+        the transform writing the compute type, then the product -- so both values of `fused` are that one route."""
+        from .mx import _HALVES, MXLinear
+
+        return isinstance(self.inner, MXLinear) and self.inner.activations in _HALVES
 
     def extra_repr(self):
         return f"features={self.signs.numel()}, block={self.block}" + (", fused=True" if self.fused else "")

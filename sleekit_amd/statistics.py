@@ -367,7 +367,7 @@ class ExpertStatistics:
         ValueError."""
         from . import mx
 
-        fmt = mx._activations(activations)
+        fmt = mx._activations(activations, mx._STATS_CODES_ONLY)
         M, n = mx._act_operands(a_codes, a_scales, fmt)
         if n != self.features:
             raise ValueError(f"a_codes has {n} columns but the statistics are of {self.features} features")
