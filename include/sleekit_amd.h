@@ -92,7 +92,8 @@ typedef void *slk_stream_t;
  * (E2M3) layers: slk_mx_scale_search6, slk_mx_pack6, slk_mx_unpack6 and slk_mx_gemm_w6 (likewise), then the expert-grouped
  * product: slk_mx_experts_workspace_bytes and slk_mx_gemm_experts (likewise), then the gated MLP: slk_mx_glu, slk_mx_gemm_glu
  * and slk_mx_gemm_glu_experts (likewise), then the weight-only products of an MX layer against 16-bit activations:
- * slk_mx_gemm_a16 and slk_mx_gemm_experts_a16 (likewise). */
+ * slk_mx_gemm_a16 and slk_mx_gemm_experts_a16 (likewise), then the gated MLP's product in front of a rotated down layer:
+ * slk_mx_gemm_glu_rot and slk_mx_gemm_glu_experts_rot (likewise). */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -739,10 +740,23 @@ int slk_mx_gemm_experts(const uint8_t *a_codes, const uint8_t *a_scales, const u
  *   caller.  Offsets that break the rule leave h_codes and h_scales untouched.  Each expert's rows are bit for bit
  *   slk_mx_gemm_glu of that slice.
  *
+ * slk_mx_gemm_glu_rot, slk_mx_gemm_glu_experts_rot: slk_mx_gemm_glu / _experts for a down layer that sits behind a block
+ *   Hadamard rotation of the N hidden columns, R = diag(s) blockdiag(H_block) / sqrt(block) of slk_hadamard_rows, with a block
+ *   of 2, 4, 8, 16 or 32: a block of R then lies inside one MX block of h, and the product's epilogue rotates each row's block
+ *   before it quantizes it, still in one launch.  signs: N float32 of +-1, DEVICE, aligned to 16 bytes, or NULL for all +1; the
+ *   expert form shares the one rotation among all experts.  h_codes, h_scales and the flag(s) are bit for bit those of
+ *   slk_mx_gemm* to float32, slk_mx_glu to float32 and slk_mx_rotate_quantize_act / _act6 with that block and those signs:
+ *   steps 1 to 3 of slk_hadamard_rows (transposed == 0) on the float32 h -- v = s h; the butterflies for h = 1, 2, ...,
+ *   block / 2 in that order, lower + upper and lower - upper; y = v c, c the float32 rounding of 1 / sqrt((double)block) -- with
+ *   no rounding in between, then the quantizer of a_fmt.  The flags are those of the plain entries: a NaN or an infinity
+ *   anywhere in a block of h reaches its whole Hadamard block and raises the non-finite flag (the outputs are then not
+ *   meaningful, as for the quantizers).  Blocks above 32 are not taken here: a caller runs the three entries named above.
+ *
  * SLK_E_ARG, before any launch: M < 1, N no positive multiple of 32 (slk_mx_glu: N < 1), K as in slk_mx_gemm, a NULL pointer
  *   other than bias, an unknown dtype, a_fmt or w_fmt, the refused pair, Y, H, a_codes, w_codes or h_codes off 16-byte
  *   alignment, limit not above 0 (a NaN included), alpha or shift not finite, interleaved not 0 or 1, and for the experts
- *   what slk_mx_gemm_experts refuses.                                                                                   */
+ *   what slk_mx_gemm_experts refuses; for the _rot entries also a block that is no power of two in 2 .. 32 and signs off
+ *   16-byte alignment.                                                                                                 */
 int slk_mx_glu(const void *Y, int x_dtype, int M, int N, float alpha, float limit, float shift, int interleaved, int out_dtype,
                void *H, slk_stream_t stream);
 int slk_mx_gemm_glu(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
@@ -752,6 +766,14 @@ int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, con
                             const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha,
                             float limit, float shift, int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag,
                             void *workspace, size_t ws_bytes, slk_stream_t stream);
+int slk_mx_gemm_glu_rot(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                        const float *bias, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift,
+                        int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag, int block, const float *signs,
+                        slk_stream_t stream);
+int slk_mx_gemm_glu_experts_rot(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                                const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha,
+                                float limit, float shift, int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag,
+                                void *workspace, size_t ws_bytes, int block, const float *signs, slk_stream_t stream);
 
 /* A stored MX layer against 16-bit activations, weight-only (W4A16, W6A16): the layer as slk_mx_pack / slk_mx_pack6 left it,
  * de-quantized inside a bfloat16 / float16 MFMA GEMM (v_mfma_f32_16x16x32_bf16 / _f16).  No de-quantized weight is written

@@ -145,6 +145,12 @@ PROTOTYPES = {
     "slk_mx_gemm_glu_experts": (
         c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, P, P, P, P, c_size_t, P],
     ),
+    "slk_mx_gemm_glu_rot": (
+        c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, P, P, P, c_int, P, P],
+    ),
+    "slk_mx_gemm_glu_experts_rot": (
+        c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, P, P, P, P, c_size_t, c_int, P, P],
+    ),
     "slk_mx_gemm_a16": (c_int, [P, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "slk_mx_gemm_experts_a16": (
         c_int, [P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P],

@@ -14,6 +14,7 @@
 // chunks-per-row is a multiple of block / 16, whatever the row.  The butterfly fixes which two values meet in each addition,
 // so none of this shows in the result.
 #include "common.h"
+#include "hadamard.h"
 #include "mxquant.h"
 
 #include <math.h>
@@ -44,46 +45,6 @@ template <class T>
 struct alignas(16) HdPiece {
     T e[16 / sizeof(T)];
 };
-
-// the value lane (l ^ D) holds, for a 32-bit word
-template <int D>
-__device__ __forceinline__ int hd_xor_word(int x, int lane) {
-    if constexpr (D == 1) return dpp_i<DPP_XOR1>(x);
-    else if constexpr (D == 2) return dpp_i<DPP_XOR2>(x);
-    else if constexpr (D == 4) return dpp_i<0x1B>(dpp_i<DPP_HALF_MIRROR>(x));  // (i ^ 7) ^ 3
-    else if constexpr (D == 8) return dpp_i<0x128>(x);                          // row_ror:8 of a row of 16
-    else if constexpr (D == 16) {
-        // rows 1 and 3 of the first operand change places with rows 0 and 2 of the second: [0] = rows 0 0 2 2, [1] = 1 1 3 3
-        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
-        return (int)((lane & 16) ? r[0] : r[1]);
-    } else {
-        // the upper half of the first operand changes places with the lower half of the second: [0] = lower lower, [1] = upper upper
-        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
-        return (int)((lane & 32) ? r[0] : r[1]);
-    }
-}
-template <int D>
-__device__ __forceinline__ float hd_xor(float x, int lane) { return __int_as_float(hd_xor_word<D>(__float_as_int(x), lane)); }
-template <int D>
-__device__ __forceinline__ double hd_xor(double x, int lane) {
-    const long long b = __double_as_longlong(x);
-    const unsigned lo = (unsigned)hd_xor_word<D>((int)(b & 0xffffffffLL), lane);
-    const unsigned hi = (unsigned)hd_xor_word<D>((int)(b >> 32), lane);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// one stage between lanes: the lower element takes lower + upper, the upper one lower - upper.  (Written as p + (-v) under a
-// per-lane sign mask instead of the select, an earlier form of this kernel took 162 to 210 registers instead of 64 to 113
-// and ran 8 to 14 % slower at 4096 rows: DESIGN.md section 16.)
-template <int D, class C>
-__device__ __forceinline__ void hd_lane_stage(C (&v)[HD_CHUNK], int lane) {
-    const bool upper = lane & D;
-#pragma unroll
-    for (int e = 0; e < HD_CHUNK; ++e) {
-        const C p = hd_xor<D>(v[e], lane);
-        v[e] = upper ? p - v[e] : v[e] + p;
-    }
-}
 
 // Where a lane's chunk lies: chunks are numbered through the whole matrix, one trip, the grid covers every chunk.
 struct HdChunk {
@@ -147,19 +108,7 @@ template <class C>
 __device__ __forceinline__ void hd_butterfly(C (&v)[HD_CHUNK], int lb, int t, C (*xch)[HD_THREADS]) {
     const int lane = t & 63;
     // strides 1 .. 8
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (lb > k) {
-            const int h = 1 << k;
-#pragma unroll
-            for (int i = 0; i < HD_CHUNK; ++i)
-                if ((i & h) == 0) {
-                    const C a = v[i], b = v[i + h];
-                    v[i] = a + b;
-                    v[i + h] = a - b;
-                }
-        }
-    }
+    hd_register_stages(v, lb);
     // strides 16 .. 512: lanes of one wave (lb is uniform, and so is every branch here)
     if (lb > 4) hd_lane_stage<1>(v, lane);
     if (lb > 5) hd_lane_stage<2>(v, lane);

@@ -28,9 +28,12 @@
 // The stored forms feed the instruction with plain loads (16 bytes a piece; three of 8 for E2M3): no shuffle, no pre-swizzle, no LDS.
 // D: lane l holds column l & 15, rows 4 (l >> 4) + 0 .. 3.
 #include "common.h"
+#include "hadamard.h"
 #include "mxexperts.h"
 #include "mxglu.h"
 #include "mxquant.h"
+
+#include <math.h>
 
 namespace slk {
 
@@ -252,7 +255,18 @@ __global__ __launch_bounds__(256) void k_mx_gemm_tiled(const uint8_t *__restrict
 // not the packer's (contiguous elements a lane), so the float32 tile of h goes through LDS: rows of GLU_LD = 36 floats (the
 // pad keeps a row on 16 bytes for the re-read in 16-byte pieces; a 32-lane group's dword stores fall on 32 distinct banks:
 // lanes of q = 0 on 0 .. 15, of q = 1 on 4 * 36 % 32 + 0 .. 15), re-read in the quantizer's lane shape, mxq_lanes lanes a block.
+//
+// The rotating form (slk_mx_gemm_glu_rot, _experts_rot): the down layer sits behind a block Hadamard rotation of at most 32
+// hidden columns, which then lies inside the staged block of its row.  Between the re-read and the encoder a lane runs steps
+// 1 to 3 of slk_hadamard_rows' contract on its EPL elements -- v = s h, the butterflies (hadamard.h: strides below EPL in
+// registers, the rest lane distances 1 and 2 inside a quad, DPP), y = v c -- in k_hadamard_quantize's operations, so the codes
+// are those of slk_mx_rotate_quantize_act* on the float32 h.  ROT is a template argument: the plain form compiles as before.
 constexpr int GLU_LD = 36;
+struct GluRot {
+    const float *signs;  // N of +-1 on 16 bytes, or null: all +1
+    int lb;              // the block is 2^lb, 1 .. 5
+    float c;             // 1 / sqrt(block), rounded once from double
+};
 
 // One MFMA tile of gate and up sums -> h in the staged tile: rows r0 .. r0 + 3, column c.
 __device__ __forceinline__ void glu_stage(float *__restrict__ tile, v4f g, v4f u, const float *__restrict__ bias, int gate, int up, int r0,
@@ -263,11 +277,27 @@ __device__ __forceinline__ void glu_stage(float *__restrict__ tile, v4f g, v4f u
 }
 // The staged ROWS x 32 tile -> codes and scale bytes of hidden block `blk` of rows row0 .. (below `rows`), by one wave:
 // k_mx_quantize_act's lane shape around the same mxq_encode.  Returns whether a live block holds a NaN or an infinity.
-template <int AF, int ROWS>
+// ROT: the block is rotated first; the signs of a lane's columns are the same in every row.  The stages between lanes run
+// with every lane of the wave active, outside `staged` and `live`: a lane that stages nothing carries zeros through them.
+template <int AF, int ROWS, bool ROT>
 __device__ __forceinline__ bool glu_quantize_tile(const float *__restrict__ tile, int lane, int row0, int rows, int N, int blk, bool blk_live,
-                                                  uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs) {
+                                                  uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, const GluRot rot) {
     constexpr int LPB = mxq_lanes<AF>(), EPL = 32 / LPB, BYTES = EPL * mxa_bits<AF>() / 8;
     bool bad = false;
+    float s[EPL];
+    if constexpr (ROT) {
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) s[e] = 1.0f;
+        if (rot.signs && blk_live) {  // (a block past the end has no signs; uniform over the wave)
+            const v4f *sp = reinterpret_cast<const v4f *>(rot.signs + (size_t)32 * blk + (lane % LPB) * EPL);
+#pragma unroll
+            for (int p = 0; p < EPL / 4; ++p) {
+                const v4f four = sp[p];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s[4 * p + e] = four[e];
+            }
+        }
+    }
 #pragma unroll
     for (int i0 = 0; i0 < ROWS * LPB; i0 += 64) {  // (every lane of a block takes the round: 64 is a multiple of LPB)
         const int i = i0 + lane, r = i / LPB, piece = i % LPB, m = row0 + r;
@@ -275,6 +305,13 @@ __device__ __forceinline__ bool glu_quantize_tile(const float *__restrict__ tile
         float x[EPL];
 #pragma unroll
         for (int e = 0; e < EPL; ++e) x[e] = staged ? tile[r * GLU_LD + piece * EPL + e] : 0.0f;
+        if constexpr (ROT) {
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) x[e] = s[e] * x[e];
+            hd_quad_butterfly(x, rot.lb, lane);
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) x[e] = x[e] * rot.c;
+        }
         unsigned eb, w[BYTES / 4];
         const int top = mxq_encode<AF>(x, eb, w);
         bad |= live && top >= 0x7f800000;
@@ -288,12 +325,12 @@ __device__ __forceinline__ bool glu_quantize_tile(const float *__restrict__ tile
 
 // Few rows: a workgroup is 16 rows x one block of 32 hidden columns -- four accumulators a wave, gate and up times two
 // 16-column tiles -- and each A fragment meets four B fragments.  (row0 / rows as in mx_gemm_splitk_tile; blk the block.)
-template <int AF, int WF>
+template <int AF, int WF, bool ROT = false>
 __device__ __forceinline__ void mx_gemm_glu_splitk_tile(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                         const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                         const float *__restrict__ bias, int row0, int rows, int blk, int N, int K,
                                                         const GluParams p, uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs,
-                                                        int *__restrict__ flag) {
+                                                        int *__restrict__ flag, const GluRot rot = GluRot()) {
     __shared__ v4f part[MXG_SK - 1][4][64];
     __shared__ float tile[16 * GLU_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -335,7 +372,7 @@ __device__ __forceinline__ void mx_gemm_glu_splitk_tile(const uint8_t *__restric
         for (int t = 0; t < 2; ++t) glu_stage(tile, acc[2 * t], acc[2 * t + 1], bias, wrow[2 * t], wrow[2 * t + 1], 4 * q, 16 * t + (lane & 15), p);
     }
     __syncthreads();
-    if (wave == 0 && glu_quantize_tile<AF, 16>(tile, lane, row0, rows, N, blk, true, Hc, Hs)) *flag = 1;
+    if (wave == 0 && glu_quantize_tile<AF, 16, ROT>(tile, lane, row0, rows, N, blk, true, Hc, Hs, rot)) *flag = 1;
 }
 template <int AF, int WF>
 __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_glu_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
@@ -344,16 +381,24 @@ __global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_glu_splitk(const uint8_
                                                                     uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag) {
     mx_gemm_glu_splitk_tile<AF, WF>(Ac, As, Wc, Ws, bias, blockIdx.y * 16, M, blockIdx.x, N, K, p, Hc, Hs, flag);
 }
+template <int AF, int WF>
+__global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_glu_rot_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                        const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                        const float *__restrict__ bias, int M, int N, int K, const GluParams p,
+                                                                        uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag,
+                                                                        const GluRot rot) {
+    mx_gemm_glu_splitk_tile<AF, WF, true>(Ac, As, Wc, Ws, bias, blockIdx.y * 16, M, blockIdx.x, N, K, p, Hc, Hs, flag, rot);
+}
 
 // Many rows: a wave keeps its 32 x 32 tile of h, one block a row, as eight accumulators -- gate and up times 2 x 2 -- and the
 // four waves of a workgroup cover 64 x 64.  N % 32 == 0, so a wave's block is whole or past the end; a wave past the end
 // loads zeros, stores nothing and keeps the barrier.
-template <int AF, int WF>
+template <int AF, int WF, bool ROT = false>
 __device__ __forceinline__ void mx_gemm_glu_tiled_tile(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
                                                        const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
                                                        const float *__restrict__ bias, int row0, int rows, int col0, int N, int K,
                                                        const GluParams p, uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs,
-                                                       int *__restrict__ flag) {
+                                                       int *__restrict__ flag, const GluRot rot = GluRot()) {
     __shared__ float tile[4][32 * GLU_LD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bpr = K / 32, steps = (bpr + 3) / 4;
@@ -395,7 +440,7 @@ __device__ __forceinline__ void mx_gemm_glu_tiled_tile(const uint8_t *__restrict
         for (int j = 0; j < 2; ++j)
             glu_stage(tile[wave], acc[0][i][j], acc[1][i][j], blk_live ? bias : nullptr, wrow[0][j], wrow[1][j], 16 * i + 4 * q, 16 * j + (lane & 15), p);
     __syncthreads();
-    if (glu_quantize_tile<AF, 32>(tile[wave], lane, m0, rows, N, n0 / 32, blk_live, Hc, Hs)) *flag = 1;
+    if (glu_quantize_tile<AF, 32, ROT>(tile[wave], lane, m0, rows, N, n0 / 32, blk_live, Hc, Hs, rot)) *flag = 1;
 }
 template <int AF, int WF>
 __global__ __launch_bounds__(256) void k_mx_gemm_glu_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
@@ -403,6 +448,14 @@ __global__ __launch_bounds__(256) void k_mx_gemm_glu_tiled(const uint8_t *__rest
                                                            const float *__restrict__ bias, int M, int N, int K, const GluParams p,
                                                            uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag) {
     mx_gemm_glu_tiled_tile<AF, WF>(Ac, As, Wc, Ws, bias, blockIdx.y * 64, M, blockIdx.x * 64, N, K, p, Hc, Hs, flag);
+}
+template <int AF, int WF>
+__global__ __launch_bounds__(256) void k_mx_gemm_glu_rot_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                               const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                               const float *__restrict__ bias, int M, int N, int K, const GluParams p,
+                                                               uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag,
+                                                               const GluRot rot) {
+    mx_gemm_glu_tiled_tile<AF, WF, true>(Ac, As, Wc, Ws, bias, blockIdx.y * 64, M, blockIdx.x * 64, N, K, p, Hc, Hs, flag, rot);
 }
 
 // ---------------------------------------------------------------- a mixture-of-experts layer in one call
@@ -509,6 +562,29 @@ __global__ __launch_bounds__(256) void k_mx_gemm_glu_experts_tiled(const uint8_t
     const ExpertTile<WF> x(table, Wc, Ws, bias, 2 * N, K);
     mx_gemm_glu_tiled_tile<AF, WF>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x * 64, N, K, p, Hc, Hs, flag);
 }
+// ... and of its rotating form: one rotation of the N hidden columns, shared by all experts
+template <int AF, int WF>
+__global__ __launch_bounds__(64 * MXG_SK) void k_mx_gemm_glu_rot_experts_splitk(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                                const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                                const float *__restrict__ bias, const int *__restrict__ count,
+                                                                                const int *__restrict__ table, int N, int K, const GluParams p,
+                                                                                uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs,
+                                                                                int *__restrict__ flag, const GluRot rot) {
+    if ((int)blockIdx.y >= *count) return;
+    const ExpertTile<WF> x(table, Wc, Ws, bias, 2 * N, K);
+    mx_gemm_glu_splitk_tile<AF, WF, true>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x, N, K, p, Hc, Hs, flag, rot);
+}
+template <int AF, int WF>
+__global__ __launch_bounds__(256) void k_mx_gemm_glu_rot_experts_tiled(const uint8_t *__restrict__ Ac, const uint8_t *__restrict__ As,
+                                                                       const uint8_t *__restrict__ Wc, const uint8_t *__restrict__ Ws,
+                                                                       const float *__restrict__ bias, const int *__restrict__ count,
+                                                                       const int *__restrict__ table, int N, int K, const GluParams p,
+                                                                       uint8_t *__restrict__ Hc, uint8_t *__restrict__ Hs, int *__restrict__ flag,
+                                                                       const GluRot rot) {
+    if ((int)blockIdx.y >= *count) return;
+    const ExpertTile<WF> x(table, Wc, Ws, bias, 2 * N, K);
+    mx_gemm_glu_tiled_tile<AF, WF, true>(Ac, As, x.Wc, x.Ws, x.bias, x.row0, x.rows, blockIdx.x * 64, N, K, p, Hc, Hs, flag, rot);
+}
 
 }  // namespace slk
 
@@ -605,17 +681,31 @@ static int mx_gemm(P, const char *name, const uint8_t *a_codes, const uint8_t *a
     });
 }
 
-extern "C" {
+// ... and the rotating ones, last: the block of the rotation and its signs (N % 32 == 0 by then, so the block divides N)
+static int mx_check_rot(int block, const float *signs, GluRot &rot) {
+    SLK_REQUIRE(block >= 2 && block <= 32 && (block & (block - 1)) == 0,
+                "block must be a power of two in 2..32: a Hadamard block of h lies inside one MX block (got %d)", block);
+    SLK_REQUIRE(aligned16(signs), "signs must be aligned to 16 bytes");
+    int lb = 0;
+    while ((1 << lb) < block) ++lb;
+    rot = {signs, lb, (float)(1.0 / sqrt((double)block))};
+    return SLK_OK;
+}
 
-int slk_mx_gemm_glu(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias, int M,
-                    int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift, int interleaved, uint8_t *h_codes,
-                    uint8_t *h_scales, int *flag, slk_stream_t stream) {
-    static const char *const names[5] = {"mx_gemm_glu", "mx_gemm_glu_a4", "mx_gemm_glu_a6", "mx_gemm_glu_w6", "mx_gemm_glu_w6a6"};
+// slk_mx_gemm_glu (ROT false; block and signs unused) and slk_mx_gemm_glu_rot
+template <bool ROT>
+static int mx_gemm_glu(const char *const (&names)[5], const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                       const float *bias, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift, int interleaved,
+                       uint8_t *h_codes, uint8_t *h_scales, int *flag, int block, const float *signs, slk_stream_t stream) {
     if (const int rc = mx_check_gated(M, N, h_scales, flag, alpha, limit, shift, interleaved)) return rc;
     if (const int rc = mx_check_operands(a_codes, a_scales, w_codes, w_scales, h_codes, "h_codes", M, N, K)) return rc;
     if (const int rc = mx_check_pair(a_fmt, w_fmt)) return rc;
     SLK_REQUIRE((M + 63) / 64 <= 65535, "M is above the 65535 row tiles of one launch (M = %d)", M);
     SLK_REQUIRE(N / 32 <= 0x7fffffff / 64, "N is above the column tiles of one launch (N = %d)", N);
+    GluRot rot = {};
+    if constexpr (ROT) {
+        if (const int rc = mx_check_rot(block, signs, rot)) return rc;
+    }
     hipStream_t s = as_stream(stream);
     const GluParams p = {alpha, limit, shift, interleaved};
     return with_pair(a_fmt, w_fmt, [&](auto pair) -> int {
@@ -624,29 +714,41 @@ int slk_mx_gemm_glu(const uint8_t *a_codes, const uint8_t *a_scales, const uint8
         const double bytes = ((double)M * mxa_block_bytes<P::AF>() + 2.0 * N * mxa_block_bytes<P::WF>()) * K / 32.0 + (double)M * mxa_block_bytes<P::AF>() * N / 32.0;
         if (M <= MXG_SPLIT_MAX_M) {
             const dim3 grid(N / 32, (M + 15) / 16);
-            SLK_RUN(names[P::INDEX], flops, bytes, s,
-                    (k_mx_gemm_glu_splitk<P::AF, P::WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
+            if constexpr (ROT)
+                SLK_RUN(names[P::INDEX], flops, bytes, s,
+                        (k_mx_gemm_glu_rot_splitk<P::AF, P::WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag, rot)));
+            else
+                SLK_RUN(names[P::INDEX], flops, bytes, s,
+                        (k_mx_gemm_glu_splitk<P::AF, P::WF><<<grid, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
         } else {
             const dim3 grid((N + 63) / 64, (M + 63) / 64);
-            SLK_RUN(names[P::INDEX], flops, bytes, s,
-                    (k_mx_gemm_glu_tiled<P::AF, P::WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
+            if constexpr (ROT)
+                SLK_RUN(names[P::INDEX], flops, bytes, s,
+                        (k_mx_gemm_glu_rot_tiled<P::AF, P::WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag, rot)));
+            else
+                SLK_RUN(names[P::INDEX], flops, bytes, s,
+                        (k_mx_gemm_glu_tiled<P::AF, P::WF><<<grid, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, M, N, K, p, h_codes, h_scales, flag)));
         }
         return SLK_OK;
     });
 }
 
-// slk_mx_gemm_experts' three launches with the fused tile bodies; flag[0] is the prologue's, flag[1] the non-finite rule's
-int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
-                            const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift,
-                            int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag, void *workspace, size_t ws_bytes,
-                            slk_stream_t stream) {
-    static const char *const names[5] = {"mx_gemm_glu_experts", "mx_gemm_glu_experts_a4", "mx_gemm_glu_experts_a6", "mx_gemm_glu_experts_w6",
-                                         "mx_gemm_glu_experts_w6a6"};
+// slk_mx_gemm_experts' three launches with the fused tile bodies; flag[0] is the prologue's, flag[1] the non-finite rule's.
+// slk_mx_gemm_glu_experts (ROT false) and slk_mx_gemm_glu_experts_rot
+template <bool ROT>
+static int mx_gemm_glu_experts(const char *const (&names)[5], const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes,
+                               const uint8_t *w_scales, const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt,
+                               float alpha, float limit, float shift, int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag,
+                               void *workspace, size_t ws_bytes, int block, const float *signs, slk_stream_t stream) {
     SLK_REQUIRE(E >= 1 && E <= MXE_MAX_EXPERTS, "E must be 1 .. %d experts (E = %d)", MXE_MAX_EXPERTS, E);
     if (const int rc = mx_check_gated(M, N, h_scales, flag, alpha, limit, shift, interleaved)) return rc;
     if (const int rc = mx_check_operands(a_codes, a_scales, w_codes, w_scales, h_codes, "h_codes", M, N, K)) return rc;
     if (const int rc = mx_check_pair(a_fmt, w_fmt)) return rc;
     if (const int rc = mx_check_experts(E, M, offsets, workspace, ws_bytes)) return rc;
+    GluRot rot = {};
+    if constexpr (ROT) {
+        if (const int rc = mx_check_rot(block, signs, rot)) return rc;
+    }
     hipStream_t s = as_stream(stream);
     int *ws = static_cast<int *>(workspace);
     const GluParams p = {alpha, limit, shift, interleaved};
@@ -657,15 +759,64 @@ int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, con
         const double flops = 4.0 * M * N * K;
         const double bytes = ((double)M * mxa_block_bytes<P::AF>() + 2.0 * E * N * mxa_block_bytes<P::WF>()) * K / 32.0 + (double)M * mxa_block_bytes<P::AF>() * N / 32.0;
         const dim3 grid16(N / 32, g.rows16), grid64((N + 63) / 64, g.rows64);
-        SLK_RUN(names[P::INDEX], flops, bytes, s,
-                (k_mx_gemm_glu_experts_splitk<P::AF, P::WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, g.t16, N, K, p,
-                                                                                          h_codes, h_scales, flag + 1)));
-        if (M > MXG_SPLIT_MAX_M)
-            SLK_RUN(names[P::INDEX], 0, 0, s,
-                    (k_mx_gemm_glu_experts_tiled<P::AF, P::WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, g.t64, N, K, p,
-                                                                                     h_codes, h_scales, flag + 1)));
+        if constexpr (ROT)
+            SLK_RUN(names[P::INDEX], flops, bytes, s,
+                    (k_mx_gemm_glu_rot_experts_splitk<P::AF, P::WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, g.t16, N, K,
+                                                                                                  p, h_codes, h_scales, flag + 1, rot)));
+        else
+            SLK_RUN(names[P::INDEX], flops, bytes, s,
+                    (k_mx_gemm_glu_experts_splitk<P::AF, P::WF><<<grid16, 64 * MXG_SK, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws, g.t16, N, K, p,
+                                                                                              h_codes, h_scales, flag + 1)));
+        if (M > MXG_SPLIT_MAX_M) {
+            if constexpr (ROT)
+                SLK_RUN(names[P::INDEX], 0, 0, s,
+                        (k_mx_gemm_glu_rot_experts_tiled<P::AF, P::WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, g.t64, N, K,
+                                                                                             p, h_codes, h_scales, flag + 1, rot)));
+            else
+                SLK_RUN(names[P::INDEX], 0, 0, s,
+                        (k_mx_gemm_glu_experts_tiled<P::AF, P::WF><<<grid64, 256, 0, s>>>(a_codes, a_scales, w_codes, w_scales, bias, ws + 1, g.t64, N, K, p,
+                                                                                         h_codes, h_scales, flag + 1)));
+        }
         return SLK_OK;
     });
+}
+
+extern "C" {
+
+int slk_mx_gemm_glu(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias, int M,
+                    int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift, int interleaved, uint8_t *h_codes,
+                    uint8_t *h_scales, int *flag, slk_stream_t stream) {
+    static const char *const names[5] = {"mx_gemm_glu", "mx_gemm_glu_a4", "mx_gemm_glu_a6", "mx_gemm_glu_w6", "mx_gemm_glu_w6a6"};
+    return mx_gemm_glu<false>(names, a_codes, a_scales, w_codes, w_scales, bias, M, N, K, a_fmt, w_fmt, alpha, limit, shift, interleaved, h_codes,
+                              h_scales, flag, 0, nullptr, stream);
+}
+
+int slk_mx_gemm_glu_rot(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias, int M,
+                        int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift, int interleaved, uint8_t *h_codes,
+                        uint8_t *h_scales, int *flag, int block, const float *signs, slk_stream_t stream) {
+    static const char *const names[5] = {"mx_gemm_glu_rot", "mx_gemm_glu_rot_a4", "mx_gemm_glu_rot_a6", "mx_gemm_glu_rot_w6", "mx_gemm_glu_rot_w6a6"};
+    return mx_gemm_glu<true>(names, a_codes, a_scales, w_codes, w_scales, bias, M, N, K, a_fmt, w_fmt, alpha, limit, shift, interleaved, h_codes,
+                             h_scales, flag, block, signs, stream);
+}
+
+int slk_mx_gemm_glu_experts(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales, const float *bias,
+                            const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit, float shift,
+                            int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag, void *workspace, size_t ws_bytes,
+                            slk_stream_t stream) {
+    static const char *const names[5] = {"mx_gemm_glu_experts", "mx_gemm_glu_experts_a4", "mx_gemm_glu_experts_a6", "mx_gemm_glu_experts_w6",
+                                         "mx_gemm_glu_experts_w6a6"};
+    return mx_gemm_glu_experts<false>(names, a_codes, a_scales, w_codes, w_scales, bias, offsets, E, M, N, K, a_fmt, w_fmt, alpha, limit, shift,
+                                      interleaved, h_codes, h_scales, flag, workspace, ws_bytes, 0, nullptr, stream);
+}
+
+int slk_mx_gemm_glu_experts_rot(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *w_codes, const uint8_t *w_scales,
+                                const float *bias, const int *offsets, int E, int M, int N, int K, int a_fmt, int w_fmt, float alpha, float limit,
+                                float shift, int interleaved, uint8_t *h_codes, uint8_t *h_scales, int *flag, void *workspace, size_t ws_bytes,
+                                int block, const float *signs, slk_stream_t stream) {
+    static const char *const names[5] = {"mx_gemm_glu_experts_rot", "mx_gemm_glu_experts_rot_a4", "mx_gemm_glu_experts_rot_a6",
+                                         "mx_gemm_glu_experts_rot_w6", "mx_gemm_glu_experts_rot_w6a6"};
+    return mx_gemm_glu_experts<true>(names, a_codes, a_scales, w_codes, w_scales, bias, offsets, E, M, N, K, a_fmt, w_fmt, alpha, limit, shift,
+                                     interleaved, h_codes, h_scales, flag, workspace, ws_bytes, block, signs, stream);
 }
 
 size_t slk_mx_experts_workspace_bytes(int E, int M) {

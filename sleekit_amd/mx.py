@@ -107,6 +107,9 @@ at the end of this file has the gate, the two layouts and the calls.
     h_codes, h_scales = matmul_mx_glu(a_codes, a_scales, up_codes, up_scales, up_bias)      # (M, N bits / 8), (M, N / 32)
     y = gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales);  y = MXGatedMLP(up, down)(x)
     y = MXExpertsMLP(up_experts, down_experts).forward_tokens(x, expert_ids, gates)
+A down layer quantized behind a rotation of the hidden features (down_rotation=; matmul_mx_glu(rotation=)) keeps the three
+launches when the rotation's block is at most 32: the product rotates each MX block of h before it quantizes it
+(slk_mx_gemm_glu_rot).  A larger block takes the elementwise route between the two products, with the same bits.
 
 Same conventions as the rest of the package: NumPy in gives NumPy out, device tensors in give device tensors out,
 everything runs on the GPU on the current stream, and there is no CPU fallback.
@@ -418,13 +421,17 @@ def _quantize_act6(Xd, M, K):
     return _quantize_act(Xd, M, K, _FORMATS["mxfp6_e2m3"])
 
 
+def _rot_signs(rotation, device):
+    """The rotation's signs on `device`, aligned: what the rotating entries take beside rotation.block."""
+    return dev.aligned(rotation.signs if rotation.signs.device == device else rotation.signs.to(device))
+
+
 def _rotate_quantize_act(Xd, M, K, rotation, fmt):
     """_quantize_act of (X R) without X R in memory: the transform's float32 value goes into the quantizer."""
     if isinstance(fmt, bool):
         fmt = _FORMATS["mxfp4" if fmt else "mxfp8"]
     Xd = dev.aligned(Xd)
-    signs = rotation.signs if rotation.signs.device == Xd.device else rotation.signs.to(Xd.device)
-    signs = dev.aligned(signs)
+    signs = _rot_signs(rotation, Xd.device)
     codes, scales, flag = _act_outputs(Xd, M, K, fmt)
     which = (fmt.c_fmt,) if fmt.rotate_takes_fmt else ()
     _lib.check(getattr(_lib.lib, fmt.rotate_entry)(dev.ptr(Xd), _OUT[Xd.dtype], M, K, rotation.block, dev.ptr(signs), *which, dev.ptr(codes),
@@ -1066,6 +1073,8 @@ def quantize_experts(Ws, Hs, weights="mxfp4", act_order="diag", damp=0.01, scale
 #     mlp = MXGatedMLP.from_results(up_linear, up_result, down_linear, down_result);  y = mlp(x)
 # h_codes / h_scales are in the activations' own format, exactly as that format's quantizer writes them, and bit for bit
 # those of the three-step route matmul_mx(..., dtype=float32), glu(..., dtype=float32), quantize_mxfp8 / _mxfp4_act / _mxfp6_act.
+# With rotation=R (matmul_mx_glu*) or down_rotation=R (the MLP calls), R a Rotation of the N hidden features, they are those of
+# R.apply(glu(...), dtype=float32) and that quantizer: inside the product's epilogue for a block of at most 32, by those steps above it.
 _Gate = collections.namedtuple("_Gate", "alpha limit shift interleaved")
 _GATE_DEFAULT = _Gate(1.0, None, 0.0, False)
 
@@ -1116,15 +1125,24 @@ def glu(y, alpha=1.0, limit=None, shift=0.0, interleaved=False, dtype=None):
     return dev.like_input(out.reshape(lead + (N,)), y)
 
 
+_GLU_ROT_MAX_BLOCK = BLOCK  # the fused product rotates h inside the MX block it stages: Hadamard blocks of 2 .. 32 hidden columns
+
+
 def _gemm_glu(ac, asc, wc, wsc, bias, M, N, K, fmt, wf, gate, fused=True, rotation=None):
-    """(h_codes, h_scales, flag) of device operands: the fused product, or (fused=False, or with a `rotation` of the N hidden
-    features, which spans more than a tile) the three-step route -- the product to float32, slk_mx_glu to float32, the plain
-    or the rotating quantizer.  The caller reads the flag (_H_FINITE) once everything that follows has been launched."""
-    if fused and rotation is None:
+    """(h_codes, h_scales, flag) of device operands: the fused product -- with a `rotation` of the N hidden features whose
+    block is at most 32, its rotating form (slk_mx_gemm_glu_rot) --, or (fused=False, or a rotation of a larger block, which
+    spans more than the product stages of a row) the three-step route -- the product to float32, slk_mx_glu to float32, the
+    plain or the rotating quantizer.  The caller reads the flag (_H_FINITE) once everything that follows has been launched."""
+    if fused and (rotation is None or rotation.block <= _GLU_ROT_MAX_BLOCK):
         codes, scales, _ = _act_outputs(ac, M, N, fmt)
         flag = torch.zeros(1, dtype=torch.int32, device=ac.device)
-        _lib.check(_lib.lib.slk_mx_gemm_glu(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, fmt.c_fmt, wf.c_fmt,
-                                            *_gate_args(gate), dev.ptr(codes), dev.ptr(scales), dev.ptr(flag), dev.stream_handle()))
+        args = (dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), M, N, K, fmt.c_fmt, wf.c_fmt, *_gate_args(gate), dev.ptr(codes),
+                dev.ptr(scales), dev.ptr(flag))
+        if rotation is None:
+            _lib.check(_lib.lib.slk_mx_gemm_glu(*args, dev.stream_handle()))
+        else:
+            signs = _rot_signs(rotation, ac.device)
+            _lib.check(_lib.lib.slk_mx_gemm_glu_rot(*args, rotation.block, dev.ptr(signs), dev.stream_handle()))
         return codes, scales, flag
     h = _glu(_gemm(ac, asc, wc, wsc, bias, M, 2 * N, K, torch.float32, fmt, wf), M, N, gate, torch.float32)
     return _quantize_x(h, M, N, rotation, fmt)
@@ -1133,13 +1151,17 @@ def _gemm_glu(ac, asc, wc, wsc, bias, M, N, K, fmt, wf, gate, fused=True, rotati
 def _gemm_glu_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, fmt, wf, gate, fused=True, rotation=None):
     """(h_codes, h_scales, offsets flag, finite flag): _gemm_glu over rows sorted by expert.  (Unfused under invalid offsets,
     the product writes nothing and the next two steps run on an unwritten matrix: the offsets flag is the one to read first.)"""
-    if fused and rotation is None:
+    if fused and (rotation is None or rotation.block <= _GLU_ROT_MAX_BLOCK):
         codes, scales, _ = _act_outputs(ac, M, N, fmt)
         flags = torch.zeros(2, dtype=torch.int32, device=ac.device)
         ws, ws_bytes = dev.scratch(_lib.lib.slk_mx_experts_workspace_bytes(E, M), "mx_experts")
-        _lib.check(_lib.lib.slk_mx_gemm_glu_experts(dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), dev.ptr(offsets), E, M, N, K,
-                                                    fmt.c_fmt, wf.c_fmt, *_gate_args(gate), dev.ptr(codes), dev.ptr(scales), dev.ptr(flags),
-                                                    dev.ptr(ws), ws_bytes, dev.stream_handle()))
+        args = (dev.ptr(ac), dev.ptr(asc), dev.ptr(wc), dev.ptr(wsc), dev.ptr(bias), dev.ptr(offsets), E, M, N, K, fmt.c_fmt, wf.c_fmt,
+                *_gate_args(gate), dev.ptr(codes), dev.ptr(scales), dev.ptr(flags), dev.ptr(ws), ws_bytes)
+        if rotation is None:
+            _lib.check(_lib.lib.slk_mx_gemm_glu_experts(*args, dev.stream_handle()))
+        else:
+            signs = _rot_signs(rotation, ac.device)
+            _lib.check(_lib.lib.slk_mx_gemm_glu_experts_rot(*args, rotation.block, dev.ptr(signs), dev.stream_handle()))
         return codes, scales, flags[0], flags[1]
     y, bad = _gemm_experts(ac, asc, wc, wsc, bias, offsets, E, M, 2 * N, K, torch.float32, fmt, wf)
     h = _glu(y, M, N, gate, torch.float32)
@@ -1147,7 +1169,7 @@ def _gemm_glu_experts(ac, asc, wc, wsc, bias, offsets, E, M, N, K, fmt, wf, gate
     return codes, scales, bad, flag
 
 
-def _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved, fused=True):
+def _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved, fused=True, rotation=None):
     """matmul_mx_glu before its flag is read: (h_codes, h_scales, flag), device tensors."""
     fmt, wf = _activations(activations, _GATED_CODES_ONLY), _weight_format(weights)
     _check_pair(fmt, wf)
@@ -1155,21 +1177,26 @@ def _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights,
     M, K = _act_operands(a_codes, a_scales, fmt)
     up = _layer(codes, scales, bias, wf, gated=True)
     _check_same_k(K, up)
-    return _gemm_glu(*_to_device(a_codes, a_scales)[:2], *up.operands(), M, up.N, K, fmt, wf, gate, fused)
+    _check_rotation(rotation, up.N, "rotation", "the up layer gives")
+    return _gemm_glu(*_to_device(a_codes, a_scales)[:2], *up.operands(), M, up.N, K, fmt, wf, gate, fused, rotation)
 
 
 def matmul_mx_glu(a_codes, a_scales, codes, scales, bias=None, activations="mxfp8", weights="mxfp4", alpha=1.0, limit=None, shift=0.0,
-                  interleaved=False):
+                  interleaved=False, rotation=None):
     """(h_codes (M, N bits / 8), h_scales (M, N / 32)): quantized activations (M, K) against an up layer of 2 N rows (codes
     (2 N, K bits / 8), scales (2 N, K / 32), bias (2 N,) float32), the gate applied to the float32 sums, and h quantized to
     the activations' own format -- one launch, and the bits of matmul_mx(dtype=float32), glu(dtype=float32) and that format's
-    quantizer.  N must be a multiple of 32.  A NaN or an infinity in h: ValueError, as from the quantizers."""
-    hc, hs, flag = _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved)
+    quantizer.  N must be a multiple of 32.  A NaN or an infinity in h: ValueError, as from the quantizers.
+    rotation (a rotation.Rotation over the N hidden features): h R is quantized instead of h, for a down layer quantized
+    behind R -- the bits of rotation.apply(glu(...), dtype=float32) and that format's quantizer.  With a block of at most 32
+    the product's epilogue rotates h itself (slk_mx_gemm_glu_rot), still one launch; a larger block takes the three steps."""
+    hc, hs, flag = _matmul_mx_glu(a_codes, a_scales, codes, scales, bias, activations, weights, alpha, limit, shift, interleaved, rotation=rotation)
     _raise_flags((flag, _H_FINITE))
     return dev.like_input(hc, a_codes), dev.like_input(hs, a_codes)
 
 
-def _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, activations, weights, alpha, limit, shift, interleaved, fused=True):
+def _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, activations, weights, alpha, limit, shift, interleaved, fused=True,
+                           rotation=None):
     """matmul_mx_glu_experts before its flags are read: (h_codes, h_scales, offsets flag, finite flag), device tensors."""
     fmt, wf = _activations(activations, _GATED_CODES_ONLY), _weight_format(weights)
     _check_pair(fmt, wf)
@@ -1178,16 +1205,19 @@ def _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, acti
     up = _layer(codes, scales, bias, wf, stacked=True, gated=True)
     _check_same_k(K, up)
     _check_offsets(offsets, up.E)
+    _check_rotation(rotation, up.N, "rotation", "the up layers give")
     return _gemm_glu_experts(*_to_device(a_codes, a_scales)[:2], *up.operands(), dev.to_device(offsets, torch.int32), up.E, M, up.N, K, fmt, wf, gate,
-                             fused)
+                             fused, rotation)
 
 
 def matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias=None, activations="mxfp8", weights="mxfp4", alpha=1.0, limit=None,
-                          shift=0.0, interleaved=False):
+                          shift=0.0, interleaved=False, rotation=None):
     """matmul_mx_glu for a stack of E experts in one call (slk_mx_gemm_glu_experts): rows sorted by expert under `offsets`
     (matmul_mx_experts' rule and its ValueError), codes (E, 2 N, K bits / 8), scales (E, 2 N, K / 32), bias (E, 2 N).  Each
-    expert's rows are bit for bit matmul_mx_glu of that slice.  Offsets that break the rule leave nothing computed."""
-    hc, hs, bad, flag = _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, activations, weights, alpha, limit, shift, interleaved)
+    expert's rows are bit for bit matmul_mx_glu of that slice.  Offsets that break the rule leave nothing computed.
+    rotation: as in matmul_mx_glu, one Rotation of the N hidden features shared by all experts (slk_mx_gemm_glu_experts_rot)."""
+    hc, hs, bad, flag = _matmul_mx_glu_experts(a_codes, a_scales, codes, scales, offsets, bias, activations, weights, alpha, limit, shift, interleaved,
+                                               rotation=rotation)
     _raise_flags((bad, _OFFSETS_RULE), (flag, _H_FINITE))
     return dev.like_input(hc, a_codes), dev.like_input(hs, a_codes)
 
@@ -1226,9 +1256,10 @@ def gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales, up_bias=None, 
     (2 N, K), up_bias (2 N,)), and matmul_mx runs the down layer (Nd, N) on them, + down_bias (Nd,): (..., Nd) in `dtype`, or
     in x's dtype when it is None.  The flags of x and of h are read together after the launches: one wait for the stream.
     fused=False runs the three-step route between the products instead -- the up product to float32, glu to float32, the plain
-    quantizer -- with the same bits.  That route is also the one taken when the down layer sits behind a rotation
-    (down_rotation, a Rotation over the N hidden features): a Hadamard block of h spans more than one tile of the product, so
-    the fused product is not asked to rotate h, and glu's float32 h feeds the fused rotate-and-quantize kernel instead."""
+    quantizer -- with the same bits.  When the down layer sits behind a rotation (down_rotation, a Rotation over the N hidden
+    features) of a block of at most 32, the fused product rotates each MX block of h before it quantizes it
+    (matmul_mx_glu(rotation=)): still three launches.  A larger Hadamard block spans more of a row than the product stages, so
+    that case takes the three-step route, glu's float32 h feeding the fused rotate-and-quantize kernel -- the same bits."""
     wf = _weight_format(weights)
     gate = _gate(alpha, limit, shift, interleaved)
     return _gated_mlp(x, (up_codes, up_scales, up_bias), (down_codes, down_scales, down_bias), dtype, activations, gate, rotation, down_rotation,

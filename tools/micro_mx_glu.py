@@ -2,6 +2,7 @@
 """The fused gated MX MLP against the five-step route it replaces, on the MI355X.
 
     python tools/micro_mx_glu.py [--reps 20] [--models gpt-oss,llama-7b] [--m 1,16,256,4096] [--t 16,64,8192] [--e 32,128] [--pair a8w4]
+                                 [--down-block 32]
 
 A gated MLP down(act(gate(x)) * up(x)): gpt-oss (K = 2880, N = 2880 hidden columns, gate and up interleaved, alpha = 1.702,
 limit = 7, shift = 1), dense at M rows and as E experts with T tokens routed uniformly to k = 4 experts each (M = 4 T sorted
@@ -16,6 +17,11 @@ one process, and the five-step route is in the rotation twice: the difference of
 
 (b) rounds the hidden activations twice (to bfloat16, then onto the MX grid), so its result is not (a)'s bit for bit; (a) and
 (c) are checked to agree before anything is timed.  One JSON line per row.
+
+--down-block B puts the down layer behind a Rotation of the N hidden features with that block (down_rotation=).  Up to 32 the
+fused product rotates h in its epilogue (slk_mx_gemm_glu_rot), and (c), fused=False, is the route such a call took before
+that kernel: the up product to float32, slk_mx_glu, the rotating quantizer.  The rows then time (a) against (c), with (c) in
+the rotation twice for the spread; (b) has no rotation to compare and is left out.
 """
 
 import argparse
@@ -30,6 +36,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from sleekit_amd import mx  # noqa: E402
+from sleekit_amd.rotation import Rotation  # noqa: E402
 
 K_TOP = 4
 MODELS = {"gpt-oss": dict(K=2880, N=2880, out=2880, gate=dict(alpha=1.702, limit=7.0, shift=1.0, interleaved=True)),
@@ -79,7 +86,16 @@ def report(what, M, pair, ts, flops, **more):
                           faster=bool(a[0] + spread < min(b[0], b2[0])), tflops=round(flops / a[0] * 1e-6, 1))), flush=True)
 
 
-def dense(name, M, pair, reps):
+def report_rotated(what, M, pair, block, ts, flops, **more):
+    (a, c, c2) = ts
+    spread = abs(c[0] - c2[0])
+    us = lambda t: [round(v, 1) for v in t]  # noqa: E731
+    print(json.dumps(dict(model=what, M=M, pair=pair, down_block=block, **more, fused_us=us(a), unfused_us=us(c), unfused_again_us=us(c2),
+                          spread_us=round(spread, 1), unfused_over_fused=round(min(c[0], c2[0]) / a[0], 2),
+                          faster=bool(a[0] + spread < min(c[0], c2[0])), tflops=round(flops / a[0] * 1e-6, 1))), flush=True)
+
+
+def dense(name, M, pair, reps, block=0):
     spec, act = MODELS[name], PAIRS[pair]
     K, N, out, gate = spec["K"], spec["N"], spec["out"], spec["gate"]
     gen = torch.Generator(device="cuda").manual_seed(M + K + N)
@@ -97,11 +113,17 @@ def dense(name, M, pair, reps):
         y = mx.linear_mxfp4(x, uc, us, activations=act)
         return mx.linear_mxfp4(torch_gate(y, **gate), dc, ds, activations=act)
 
+    if block:
+        kw["down_rotation"] = Rotation(N, block=block, seed=1)
     assert torch.equal(fused().view(torch.int16), unfused().view(torch.int16)), "fused and unfused disagree"
-    report(name, M, pair, timed([fused, five_step, unfused, five_step], reps), 2.0 * M * K * 2 * N + 2.0 * M * N * out)
+    flops = 2.0 * M * K * 2 * N + 2.0 * M * N * out
+    if block:
+        report_rotated(name, M, pair, block, timed([fused, unfused, unfused], reps), flops)
+    else:
+        report(name, M, pair, timed([fused, five_step, unfused, five_step], reps), flops)
 
 
-def experts(name, E, T, pair, reps, layers):
+def experts(name, E, T, pair, reps, layers, block=0):
     spec, act = MODELS[name], PAIRS[pair]
     K, N, out, gate = spec["K"], spec["N"], spec["out"], spec["gate"]
     M = K_TOP * T
@@ -112,20 +134,24 @@ def experts(name, E, T, pair, reps, layers):
     up, down = mx.MXExperts(E, K, 2 * N, bias=False, device="cuda", activations=act), mx.MXExperts(E, N, out, bias=False, device="cuda", activations=act)
     up.codes, up.scales, down.codes, down.scales = uc, us, dc, ds
     mlp = mx.MXExpertsMLP(up, down, **gate)
+    rot = Rotation(N, block=block, seed=1) if block else None
 
     def fused():
-        return mlp(x, offsets)
+        return mlp(x, offsets, down_rotation=rot)
 
     def unfused():
-        return mlp(x, offsets, fused=False)
+        return mlp(x, offsets, fused=False, down_rotation=rot)
 
     def five_step():
         y = mx.linear_mx_experts(x, uc, us, offsets, activations=act)
         return mx.linear_mx_experts(torch_gate(y, **gate), dc, ds, offsets, activations=act)
 
     assert torch.equal(fused().view(torch.int16), unfused().view(torch.int16)), "fused and unfused disagree"
-    report(name, M, pair, timed([fused, five_step, unfused, five_step], reps), 2.0 * M * K * 2 * N + 2.0 * M * N * out, E=E, T=T,
-           largest_expert=int(counts.max()))
+    flops, more = 2.0 * M * K * 2 * N + 2.0 * M * N * out, dict(E=E, T=T, largest_expert=int(counts.max()))
+    if block:
+        report_rotated(name, M, pair, block, timed([fused, unfused, unfused], reps), flops, **more)
+    else:
+        report(name, M, pair, timed([fused, five_step, unfused, five_step], reps), flops, **more)
 
 
 def main():
@@ -136,13 +162,14 @@ def main():
     ap.add_argument("--t", default="16,64,8192")
     ap.add_argument("--e", default="32,128")
     ap.add_argument("--pair", default="a8w4")
+    ap.add_argument("--down-block", type=int, default=0, help="the block of a down rotation (0: none)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "micro_mx_glu measures the MI355X; there is no CPU path"
     torch.cuda.set_device(0)
     ints = lambda s: [int(v) for v in s.split(",") if v]  # noqa: E731
     for name in args.models.split(","):
         for M in ints(args.m):
-            dense(name, M, args.pair, args.reps)
+            dense(name, M, args.pair, args.reps, args.down_block)
         torch.cuda.empty_cache()
     if "gpt-oss" in args.models.split(","):
         spec = MODELS["gpt-oss"]
@@ -150,7 +177,7 @@ def main():
             gen = torch.Generator(device="cuda").manual_seed(E)
             layers = layer((E,), 2 * spec["N"], spec["K"], gen), layer((E,), spec["out"], spec["N"], gen)
             for T in ints(args.t):
-                experts("gpt-oss", E, T, args.pair, args.reps, layers)
+                experts("gpt-oss", E, T, args.pair, args.reps, layers, args.down_block)
             del layers
             torch.cuda.empty_cache()
 
