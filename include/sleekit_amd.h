@@ -93,7 +93,8 @@ typedef void *slk_stream_t;
  * product: slk_mx_experts_workspace_bytes and slk_mx_gemm_experts (likewise), then the gated MLP: slk_mx_glu, slk_mx_gemm_glu
  * and slk_mx_gemm_glu_experts (likewise), then the weight-only products of an MX layer against 16-bit activations:
  * slk_mx_gemm_a16 and slk_mx_gemm_experts_a16 (likewise), then the gated MLP's product in front of a rotated down layer:
- * slk_mx_gemm_glu_rot and slk_mx_gemm_glu_experts_rot (likewise). */
+ * slk_mx_gemm_glu_rot and slk_mx_gemm_glu_experts_rot (likewise), then MoE routing: slk_moe_topk, slk_moe_sort_workspace_bytes,
+ * slk_moe_sort, slk_mx_quantize_act_rows and slk_moe_combine (likewise). */
 int slk_abi_version(void);
 const char *slk_last_error(void);
 /* Run-time switches between code paths that give the same results (the tests hold them to that) or that shape a
@@ -809,6 +810,66 @@ int slk_mx_gemm_a16(const void *X, int x_dtype, const uint8_t *w_codes, const ui
 int slk_mx_gemm_experts_a16(const void *X, int x_dtype, const uint8_t *w_codes, const uint8_t *w_scales, int w_fmt,
                             const float *bias, const int *offsets, int E, int M, int N, int K, int compute_dtype, int out_dtype,
                             void *out, int *flag, void *workspace, size_t ws_bytes, slk_stream_t stream);
+
+/* MoE routing: from router logits to the combined output around the grouped products above, every step a launch on `stream`
+ * -- top-k gates, the stable sort by expert, the activation quantizer behind a row map, the gate-weighted sum.  T tokens take
+ * k experts of E each: n = T k routed rows, entry t k + j the j-th choice of token t.  All pointers are DEVICE pointers; the
+ * host reads nothing.  Two rules hold for every kernel: no workgroup waits for another (order comes from the launches alone),
+ * and no address is made from an index read from device memory before it has been checked against its range -- a bad index
+ * raises the call's flag, and neither reads nor writes anything.  Every flag is zeroed by its call, as slk_mx_quantize_act's.
+ *
+ * slk_moe_topk: logits (T x E; float32, bfloat16 or float16 by `dtype`, converted to float32, which is exact) -> expert_ids
+ *   (int32 T x k) and gates (float32 T x k).
+ *   - selection: column j is the j-th largest logit of the token; expert a ranks before expert b when v[a] > v[b], or when
+ *     v[a] == v[b] and a < b: +0 and -0 tie, and of equal values the lower index wins.
+ *   - gates, all float32, every operation rounded once, nothing contracted: m = the token's largest logit, e = expf(v - m),
+ *     g = e / s (the IEEE quotient).  SLK_MOE_GATE_SELECTED: s is the sum of the k selected e's -- a softmax over the selected
+ *     logits (gpt-oss; also Mixtral's and Qwen3's softmax, top-k, renormalise, the same function) -- as the tree
+ *     ((e0 + e1) + (e2 + e3)) + ((e4 + e5) + (e6 + e7)) + the same of e8 .. e15, an absent e being +0.  SLK_MOE_GATE_ALL: s is
+ *     the sum over all E experts, the selected probabilities left as they are: with a[l] = e[l] + e[l + 64] + e[l + 128] + ...
+ *     from left to right for l = 0 .. 63, r[i] that tree over a[16 i] .. a[16 i + 15], s = (r[0] + r[1]) + (r[2] + r[3]).
+ *   - flag[0] = 1 when a token's row holds a NaN or +inf, or fewer than k of its logits are above -inf (-inf is otherwise
+ *     legal: it masks an expert).  Whatever the logits, the ids written lie in 0 .. E - 1 and are distinct within a token; a
+ *     flagged token's gates are 0.
+ *   One wave a token, the token's logits in registers, no LDS, no barrier.
+ * slk_moe_sort: the stable counting sort of n int32 expert ids.  order[p] (int32 n) is the entry t k + j that is p-th in
+ *   sorted order -- ids ascending, equal ids in their original order --, pos (int32 n) its inverse, pos[order[p]] == p, and
+ *   offsets (int32 E + 1) where each expert's rows begin: the rule of slk_mx_gemm_experts, offsets[0] == 0, offsets[e] <=
+ *   offsets[e + 1], offsets[E] == n.  An id outside 0 .. E - 1 raises flag[0] and is clamped into the range for the sort, so
+ *   the outputs obey the rule whatever the ids.  The result does not depend on timing (counts are integer atomics in LDS,
+ *   whose sums commute; no place comes from an atomic's return value): a repeated call gives the same bits.  n <= 1024 is one
+ *   launch of one workgroup and needs no workspace (NULL, 0 are taken); above, three launches -- counts per chunk of 2048
+ *   entries (from 2^21 entries up: of ceil(n / 1024) rounded up to 64), their scan in expert-major order, the placement -- and
+ *   slk_moe_sort_workspace_bytes(n, E) = 4 E chunks bytes, aligned to 4.  slk_moe_sort_workspace_bytes is 0 for n <= 1024 and
+ *   for sizes the sort refuses.
+ * slk_mx_quantize_act_rows: slk_mx_quantize_act (a_fmt SLK_MX_ACT_FP8), _act4 (_FP4) or _act6 (_FP6) behind a row map: row i
+ *   of a_codes / a_scales, i < M, is the quantization of row rows[i] / div of X (T x K): BIT FOR BIT what that entry writes
+ *   for the gathered matrix, which is never in memory.  The route calls it with rows = order, div = k, M = n.  flag is TWO
+ *   ints: flag[0] = 1 for a NaN or an infinity in a row that is mapped (rows that are not are not read); flag[1] = 1 for a
+ *   source row outside 0 .. T - 1, whose blocks are encoded from zeros and load nothing.
+ * slk_moe_combine: out[t][c] = sum_j gates[t][j] * Y[pos[t k + j]][c] for Y (n x N, y_dtype) and out (T x N, out_dtype): Y
+ *   converted to float32, each product rounded, then each add rounded, in the order j = 0, 1, ..., k - 1 starting from the
+ *   first term itself, the sum rounded once to out_dtype (to nearest even).  gates == NULL means ones, and no multiply.  A
+ *   pos outside 0 .. n - 1 raises flag[0] and its term is left out.  No atomics: a repeated call gives the same bits.  Where
+ *   N is a multiple of a 16-byte piece of Y (4 float32, 8 of a 16-bit type) a thread moves such a piece; otherwise rows do
+ *   not start on 16-byte boundaries and every column goes alone.
+ * SLK_E_ARG, before any launch, slk_last_error() naming the offender: a NULL pointer other than combine's gates and a sort's
+ *   unneeded workspace; logits off its element's alignment, X, a_codes, Y or out off 16 bytes, any other pointer off 4; E < 1
+ *   or E > SLK_MX_MAX_EXPERTS; k < 1, k > E or k > SLK_MOE_MAX_K (slk_moe_topk; slk_moe_combine takes any k >= 1); an unknown
+ *   dtype, gating or a_fmt; T, N, M or n < 1; K % 32 != 0 or K < 32; div < 1; a workspace below
+ *   slk_moe_sort_workspace_bytes(n, E); n = T k (M for the quantizer) above 2^24.                                       */
+#define SLK_MOE_GATE_SELECTED 0
+#define SLK_MOE_GATE_ALL 1
+#define SLK_MOE_MAX_K 16
+int slk_moe_topk(const void *logits, int dtype, int T, int E, int k, int gating, int *expert_ids, float *gates, int *flag,
+                 slk_stream_t stream);
+size_t slk_moe_sort_workspace_bytes(int n, int E);
+int slk_moe_sort(const int *expert_ids, int n, int E, int *order, int *pos, int *offsets, int *flag, void *workspace,
+                 size_t ws_bytes, slk_stream_t stream);
+int slk_mx_quantize_act_rows(const void *X, int x_dtype, int T, int K, const int *rows, int div, int M, int a_fmt,
+                             uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream);
+int slk_moe_combine(const void *Y, int y_dtype, const int *pos, const float *gates, int T, int k, int N, void *out,
+                    int out_dtype, int *flag, slk_stream_t stream);
 
 /* a11 channelwise_error  (sleekit/obq.py:89-95): row_err[r] = (W-Q)[r] H (W-Q)[r]^T.
  *     G (may be NULL): the R x n product (W - Q) @ H, reused by the local search. */

@@ -3,6 +3,7 @@
     from sleekit_amd import obq, scaling, codebook, groups, packing, mx, rotation, Sleekit, MXLinear, MXExperts, PackedLinear
     from sleekit_amd import MXGatedMLP, MXExpertsMLP, ExpertStatistics
     from sleekit_amd import Rotation, RotatedLinear
+    from sleekit_amd import routing, route_topk, sort_experts
 
 mirrors `sleekit.obq`, `sleekit.scaling`, `sleekit.codebook` and `sleekit.Sleekit` of
 Coloquinte/sleekit for the hot path.  Submodules are imported lazily
@@ -16,7 +17,7 @@ import importlib
 # queue count to the process environment: the GPU is shared, and more queues per process than the machine allows are not
 # ours to take.)
 
-_SUBMODULES = ("codebook", "obq", "scaling", "statistics", "engine", "dist", "synth", "groups", "packing", "mx", "rotation", "_lib", "_device")
+_SUBMODULES = ("codebook", "obq", "scaling", "statistics", "engine", "dist", "synth", "groups", "packing", "mx", "rotation", "routing", "_lib", "_device")
 
 
 def __getattr__(name):
@@ -26,6 +27,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f"{__name__}.statistics"), name)
     if name in ("MXLinear", "MXExperts", "MXGatedMLP", "MXExpertsMLP"):
         return getattr(importlib.import_module(f"{__name__}.mx"), name)
+    if name in ("route_topk", "sort_experts", "Routing"):
+        return getattr(importlib.import_module(f"{__name__}.routing"), name)
     if name == "PackedLinear":
         return importlib.import_module(f"{__name__}.packing").PackedLinear
     if name in ("Rotation", "RotatedLinear"):

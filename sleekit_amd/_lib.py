@@ -28,6 +28,8 @@ MX_ACT_FP8, MX_ACT_FP4 = 0, 1  # slk_mx_rotate_quantize_act `fmt`
 MX_ACT_FP6 = 2  # slk_mx_gemm_w6 `a_fmt` (beside MX_ACT_FP8)
 MX_W_FP4, MX_W_FP6 = 0, 1  # slk_mx_gemm_experts `w_fmt`
 MX_MAX_EXPERTS = 1024
+MOE_GATE_SELECTED, MOE_GATE_ALL = 0, 1  # slk_moe_topk `gating`
+MOE_MAX_K = 16
 ORDER_NONE, ORDER_DIAG, ORDER_ERR, ORDER_SQERR, ORDER_KEYS = 0, 1, 2, 3, 4
 ORDER_MODES = {"none": ORDER_NONE, "diag": ORDER_DIAG, "err": ORDER_ERR, "sqerr": ORDER_SQERR}
 
@@ -155,6 +157,11 @@ PROTOTYPES = {
     "slk_mx_gemm_experts_a16": (
         c_int, [P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P],
     ),
+    "slk_moe_topk": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "slk_moe_sort_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "slk_moe_sort": (c_int, [P, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    "slk_mx_quantize_act_rows": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P]),
+    "slk_moe_combine": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P, c_int, P, P]),
     "slk_row_errors": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_row_errors_batch": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "slk_symmetry_flag": (c_int, [P, c_int, P, P]),

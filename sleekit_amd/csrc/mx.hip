@@ -3,7 +3,7 @@
 // share one power-of-two scale (an E8M0 byte); the elements are E2M1 codes, two a byte (MXFP4), E2M3 codes, a row as a
 // stream of 6-bit codes (MXFP6), or E4M3 codes, one a byte (MXFP8).
 //   a layer:      slk_mx_scale_search, slk_mx_pack, slk_mx_unpack (E2M1); slk_mx_scale_search6, _pack6, _unpack6 (E2M3)
-//   activations:  slk_mx_quantize_act (E4M3), _act4 (E2M1), _act6 (E2M3)
+//   activations:  slk_mx_quantize_act (E4M3), _act4 (E2M1), _act6 (E2M3); slk_mx_quantize_act_rows: the three behind a row map
 //   either, back: slk_mx_dequantize (E2M1), slk_mx_dequantize_act (E4M3), _act6 (E2M3): one kernel, whatever wrote the codes
 //   between two layers of a gated MLP: slk_mx_glu, the gate (mxglu.h) over a (M, 2 N) matrix, elementwise
 //
@@ -234,6 +234,55 @@ __global__ __launch_bounds__(256) void k_mx_quantize_act(const T *__restrict__ X
     if (bad) *flag = 1;
 }
 
+// The plain quantizer behind a row map: row m of the output is the quantization of row rows[m] / div of X (tokens x K), so a
+// mixture-of-experts layer quantizes its routed rows straight from x and the gathered matrix is never in memory.  The lane
+// shape, the encoder and the stores are k_mx_quantize_act's, so the bits are those of that kernel on the gathered matrix.
+// The map is read from device memory: a source row outside 0 .. tokens - 1 raises flag[1], loads nothing and is encoded as
+// a block of zeros; flag[0] is the non-finite flag, as above.
+template <class T, int FMT, int LPB>
+__global__ __launch_bounds__(256) void k_mx_quantize_act_rows(const T *__restrict__ X, int tokens, int bpr, const int *__restrict__ rows,
+                                                              int div, size_t blocks, uint8_t *__restrict__ codes, uint8_t *__restrict__ E,
+                                                              int *__restrict__ flag) {
+    constexpr int EPL = 32 / LPB, BYTES = EPL * mxa_bits<FMT>() / 8;
+    constexpr int PER = 16 / (int)sizeof(T), PIECES = EPL / PER;
+    typedef T V __attribute__((ext_vector_type(PER)));
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    const size_t units = LPB * blocks, rounds = (units + threads - 1) / threads;
+    const V *src = reinterpret_cast<const V *>(X);
+    bool bad = false, off = false;
+    for (size_t r = 0; r < rounds; ++r) {
+        const size_t i = r * threads + gid;
+        const bool live = i < units;
+        float x[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) x[e] = 0.0f;
+        if (live) {
+            const size_t b = i / LPB, m = b / (size_t)bpr, kb = b - m * (size_t)bpr;
+            const int row = rows[m];
+            const unsigned from = (unsigned)max(row, 0) / (unsigned)div;
+            if (row < 0 || from >= (unsigned)tokens) {
+                off = true;
+            } else {
+                const size_t at = (((size_t)from * bpr + kb) * LPB + i % LPB) * PIECES;
+#pragma unroll
+                for (int p = 0; p < PIECES; ++p) {
+                    const V v = src[at + p];
+#pragma unroll
+                    for (int e = 0; e < PER; ++e) x[p * PER + e] = act_f32<T>(v[e]);
+                }
+            }
+        }
+        unsigned eb, w[BYTES / 4];
+        bad |= mxq_encode<FMT>(x, eb, w) >= 0x7f800000;
+        if (live) {
+            mxa_store<FMT, EPL>(codes + BYTES * i, w);
+            if (i % LPB == 0) E[i / LPB] = (uint8_t)eb;
+        }
+    }
+    if (bad) flag[0] = 1;
+    if (off) flag[1] = 1;
+}
+
 // ---------------------------------------------------------------- the gate, elementwise
 // H (M, N) = mx_glu(gate, up) of Y (M, 2 N): VEC hidden columns a thread (4 where N % 4 == 0, so that every piece is one
 // aligned vector: 16 bytes of float32, 8 of a 16-bit type), a unit a step, a whole grid apart.  Not interleaved, a thread reads
@@ -400,6 +449,23 @@ static int mx_quantize_act(const char *name, const void *X, int x_dtype, int M, 
     });
 }
 
+// slk_mx_quantize_act_rows in one element format (the checks are the entry's)
+template <int FMT>
+static int mx_quantize_act_rows(const void *X, int x_dtype, int T, int K, const int *rows, int div, int M, uint8_t *a_codes, uint8_t *a_scales,
+                                int *flag, hipStream_t s) {
+    const size_t blocks = (size_t)M * (K / 32);
+    zero_async(flag, 2 * sizeof(int), s);
+    constexpr int LPB = mxq_lanes<FMT>();
+    const int grid = mx_grid(LPB * blocks, 1);
+    return with_dtype(x_dtype, [&](auto t) -> int {
+        typedef typename decltype(t)::T Tx;
+        const double bytes = (mxa_block_bytes<FMT>() + 32.0 * sizeof(Tx)) * blocks + 4.0 * M;
+        SLK_RUN("mx_quantize_act_rows", 0, bytes, s,
+                (k_mx_quantize_act_rows<Tx, FMT, LPB><<<grid, 256, 0, s>>>(static_cast<const Tx *>(X), T, K / 32, rows, div, blocks, a_codes, a_scales, flag)));
+        return SLK_OK;
+    });
+}
+
 // slk_mx_dequantize (MXA_E2M1), slk_mx_dequantize_act (MXA_E4M3) and _act6 (MXA_E2M3)
 template <int FMT>
 static int mx_dequantize(const char *name, const uint8_t *codes, const uint8_t *scales, int M, int K, int out_dtype, void *out, int *flag,
@@ -487,6 +553,23 @@ int slk_mx_quantize_act4(const void *X, int x_dtype, int M, int K, uint8_t *a_co
 
 int slk_mx_quantize_act6(const void *X, int x_dtype, int M, int K, uint8_t *a_codes, uint8_t *a_scales, int *flag, slk_stream_t stream) {
     return mx_quantize_act<MXA_E2M3>("mx_quantize_act6", X, x_dtype, M, K, a_codes, a_scales, flag, stream);
+}
+
+int slk_mx_quantize_act_rows(const void *X, int x_dtype, int T, int K, const int *rows, int div, int M, int a_fmt, uint8_t *a_codes,
+                             uint8_t *a_scales, int *flag, slk_stream_t stream) {
+    SLK_REQUIRE(T > 0 && M > 0, "T and M must be at least 1 (T = %d, M = %d)", T, M);
+    SLK_REQUIRE(M <= 1 << 24, "M is above the 2^24 routed rows of one call (got %d)", M);
+    SLK_REQUIRE(K >= 32 && K % 32 == 0, "MX blocks are 32 columns: K must be a positive multiple of 32 (K = %d)", K);
+    SLK_REQUIRE(div >= 1, "div must be at least 1 (got %d)", div);
+    SLK_REQUIRE(known_dtype(x_dtype), "unknown x_dtype %d", x_dtype);
+    SLK_REQUIRE(a_fmt == SLK_MX_ACT_FP8 || a_fmt == SLK_MX_ACT_FP4 || a_fmt == SLK_MX_ACT_FP6, "unknown a_fmt %d", a_fmt);
+    SLK_REQUIRE(X && rows && a_codes && a_scales && flag, "null pointer");
+    SLK_REQUIRE(aligned16(X) && aligned16(a_codes), "X and a_codes must be aligned to 16 bytes");
+    SLK_REQUIRE((uintptr_t)rows % 4 == 0 && (uintptr_t)flag % 4 == 0, "rows and flag must be aligned to 4 bytes");
+    hipStream_t s = as_stream(stream);
+    if (a_fmt == SLK_MX_ACT_FP4) return mx_quantize_act_rows<MXA_E2M1>(X, x_dtype, T, K, rows, div, M, a_codes, a_scales, flag, s);
+    if (a_fmt == SLK_MX_ACT_FP6) return mx_quantize_act_rows<MXA_E2M3>(X, x_dtype, T, K, rows, div, M, a_codes, a_scales, flag, s);
+    return mx_quantize_act_rows<MXA_E4M3>(X, x_dtype, T, K, rows, div, M, a_codes, a_scales, flag, s);
 }
 
 int slk_mx_dequantize(const uint8_t *codes, const uint8_t *scales, int R, int n, int out_dtype, void *out, int *flag,

@@ -100,6 +100,8 @@ rows are bit for bit matmul_mx of that slice.  Every format pair of matmul_mx is
     experts = MXExperts.from_results(results, biases)          # buffers codes, scales, bias
     y = experts.forward_tokens(x, expert_ids, gates)           # x (T, K), expert_ids and gates (T, k) -> (T, N)
     order, offsets = sort_by_expert(expert_ids, E);  Y = linear_mx_experts(x[order // k], codes, scales, offsets, bias)
+    y = experts.forward_logits(x, logits, k)                   # from router logits (T, E): top-k gates, sort, row-mapped quantizer,
+                                                               # product and combine in HIP (sleekit_amd.routing), forward_tokens' bits
 
 GATED MLP.  down(act(gate(x)) * up(x)) in three launches: the up layer holds gate and up (2 N rows), and the fused product
 (slk_mx_gemm_glu) applies the gate in float32 and writes h as the down layer's a_codes / a_scales -- the section "gated MLP"
@@ -124,6 +126,7 @@ import torch
 from . import _device as dev
 from . import _lib
 from . import groups
+from . import routing
 from .codebook import Codebook
 
 BLOCK = 32
@@ -813,14 +816,7 @@ _OFFSETS_RULE = ("offsets must start at 0, never decrease and end at the number 
                  "offsets[0] == 0, offsets[e] <= offsets[e + 1], offsets[E] == M")
 
 
-def _raise_flags(*checks):
-    """(device flag or None, message) pairs read in ONE device -> host transfer, the first raised flag's message raised."""
-    checks = [(f, m) for f, m in checks if f is not None]
-    if not checks:
-        return
-    for v, (_, message) in zip(torch.cat([f.reshape(1).to(torch.int32) for f, _ in checks]).tolist(), checks):
-        if v:
-            raise ValueError(message)
+_raise_flags = routing._raise_flags  # (device flag or None, message) pairs read in ONE device -> host transfer
 
 
 def _check_offsets(offsets, E):
@@ -881,7 +877,36 @@ def matmul_mx_experts(a_codes, a_scales, codes, scales, offsets, bias=None, dtyp
     return dev.like_input(out, a_codes)
 
 
-def _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotation, wf, also=()):
+def _gathered(Xd, routed):
+    """The routed rows x[order // k] of a device x (T, K) in memory, by one torch index: what the paths without a row-mapped
+    quantizer read (a rotation, 16-bit activations).  (order is slk_moe_sort's: a permutation of 0 .. T k - 1, every place of
+    which was checked against n before it was written.)"""
+    order, k = routed
+    return Xd[torch.div(order, k, rounding_mode="floor").long()]
+
+
+def _quantize_routed(Xd, T, K, routed, rotation, fmt):
+    """_quantize_x of the routed rows x[order // k], routed = (order, k): (a_codes, a_scales, finite flag, row-map flag).
+    Without a rotation the quantizer reads x through the row map (slk_mx_quantize_act_rows) and the routed rows are never in
+    memory; with one they are gathered first and the row-map flag is None."""
+    if rotation is None:
+        ac, asc, flags = routing._quantize_rows(Xd, T, K, routed[0], routed[1], routed[0].numel(), fmt.c_fmt, fmt.bits)
+        return ac, asc, flags[0], flags[1]
+    return (*_quantize_x(_gathered(Xd, routed), routed[0].numel(), K, rotation, fmt), None)
+
+
+def _settle(checks, deferred, out, x):
+    """How a grouped call ends: its flags read now and the result handed back the way x came in, or (deferred, a list) its
+    checks appended for the caller to read with its own, and the device result."""
+    if deferred is not None:
+        deferred.extend(checks)
+        return out
+    _raise_flags(*checks)
+    return dev.like_input(out, x)
+
+
+def _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotation, wf, also=(), routed=None, deferred=None):
+    """routed = (order, k): x is (T, K) and the rows that are multiplied are x[order // k] (forward_logits)."""
     fmt = _activations(activations)
     _check_pair(fmt, wf)
     layer = _layer(codes, scales, bias, wf, stacked=True)
@@ -889,14 +914,19 @@ def _linear_experts(x, codes, scales, offsets, bias, dtype, activations, rotatio
     _check_offsets(offsets, layer.E)
     Xd, _, M, dtype = _float_rows(x, layer, "", dtype)
     od = dev.to_device(offsets, torch.int32)
+    off = None
     if isinstance(fmt, _Half):
         finite = None
+        if routed is not None:
+            Xd, M = _gathered(Xd, routed), routed[0].numel()
         out, flag = _gemm_experts_a16(_rotated_x(Xd, rotation, fmt), *layer.operands(), od, layer.E, M, layer.N, layer.K, dtype, fmt, wf)
     else:
-        ac, asc, finite = _quantize_x(Xd, M, layer.K, rotation, fmt)
+        if routed is None:
+            ac, asc, finite = _quantize_x(Xd, M, layer.K, rotation, fmt)
+        else:
+            (ac, asc, finite, off), M = _quantize_routed(Xd, M, layer.K, routed, rotation, fmt), routed[0].numel()
         out, flag = _gemm_experts(ac, asc, *layer.operands(), od, layer.E, M, layer.N, layer.K, dtype, fmt, wf)
-    _raise_flags(*also, (finite, _H_FINITE), (flag, _OFFSETS_RULE))
-    return dev.like_input(out, x)
+    return _settle((*also, (off, routing.ROWS_MESSAGE), (finite, _H_FINITE), (flag, _OFFSETS_RULE)), deferred, out, x)
 
 
 def linear_mx_experts(x, codes, scales, offsets, bias=None, dtype=None, activations="mxfp8", weights="mxfp4", rotation=None):
@@ -929,8 +959,7 @@ def _expert_ids(expert_ids, E):
     return dev.to_device(expert_ids, torch.int64).reshape(-1)
 
 
-def _ids_message(E):
-    return f"expert ids must lie in 0 .. {E - 1}"
+_ids_message = routing.ids_message
 
 
 def sort_by_expert(expert_ids, E):
@@ -967,6 +996,24 @@ def _route_tokens(x, expert_ids, gates, num_experts, out_features, run):
     for j in range(1, k):
         total = total + (y[:, j] if g is None else y[:, j] * g[:, j:j + 1])
     return dev.like_input(total.to(_torch_dtype(x)), x)
+
+
+def _route_logits(x, logits, k, gating, num_experts, out_features, run):
+    """What MXExperts.forward_logits and MXExpertsMLP.forward_logits share, every step a HIP launch (sleekit_amd.routing):
+    top-k ids and gates of the logits, the counting sort of the T k ids, run(Xd, (order, k), offsets, checks) -- a grouped
+    layer or MLP that reads x (T, K) through the row map, appends its own flags to `checks` and returns the device result
+    (T k, N) in x's dtype --, and the combine.  Every flag of the call is read together after the last launch: one wait."""
+    T, _ = _matrix(x, "x", _ACT)
+    _out_dtype(_torch_dtype(x), x)
+    _, E, l_dtype = routing._check_logits(logits, k, gating, T, num_experts)
+    k = int(k)
+    ids, gates, bad_logits = routing._topk(dev.to_device(logits, l_dtype), T, E, k, gating)
+    order, pos, offsets, bad_ids = routing._sort(ids.reshape(-1), T * k, E)
+    checks = [(bad_logits, routing.LOGITS_MESSAGE), (bad_ids, _ids_message(E))]
+    y = run(dev.to_device(x, _torch_dtype(x)), (order, k), offsets, checks)
+    out, bad_pos = routing._combine(y, pos, gates, T, k, out_features, _torch_dtype(x))
+    _raise_flags(*checks, (bad_pos, routing.POS_MESSAGE))
+    return dev.like_input(out, x)
 
 
 class MXExperts(_MXModule):
@@ -1025,6 +1072,22 @@ class MXExperts(_MXModule):
             return _linear_experts(rows, self.codes, self.scales, offsets, self.bias, None, self.activations, rotation, _WEIGHTS[self.weights], also=also)
 
         return _route_tokens(x, expert_ids, gates, self.num_experts, self.out_features, run)
+
+    def forward_logits(self, x, logits, k, gating="selected", rotation=None):
+        """x (T, K) and router logits (T, E) -> (T, N) in x's dtype: the whole route in hand-written kernels -- top-k ids and
+        gates (routing.route_topk's: `gating` "selected" or "all"), the counting sort by expert, the activation quantizer
+        reading x through the row map order // k (no (T k, K) float matrix is in memory), the grouped product, and the
+        gate-weighted float32 sum in the order j = 0, 1, ..., k - 1 (no atomics).  The bits are those of
+        forward_tokens(x, r.expert_ids, r.gates) for r = routing.route_topk(logits, k, gating).  Every flag of the call
+        -- logits, ids, row map, finite activations, offsets, combine -- is read together after the last launch: one wait for
+        the stream.  With rotation=, or with activations="bfloat16" / "float16", there is no row-mapped quantizer: those paths
+        gather x[order // k] with one torch index, as forward_tokens does, and only the rest is new; rotation= is the call
+        on rotation.apply(x) as in forward_tokens."""
+        def run(Xd, routed, offsets, checks):
+            return _linear_experts(Xd, self.codes, self.scales, offsets, self.bias, None, self.activations, rotation, _WEIGHTS[self.weights],
+                                   routed=routed, deferred=checks)
+
+        return _route_logits(x, logits, k, gating, self.num_experts, self.out_features, run)
 
     def extra_repr(self):
         return (f"num_experts={self.num_experts}, in_features={self.in_features}, out_features={self.out_features}, "
@@ -1266,7 +1329,9 @@ def gated_mlp_mx(x, up_codes, up_scales, down_codes, down_scales, up_bias=None, 
                       fused, wf, wf)
 
 
-def _gated_mlp_experts(x, up, down, offsets, dtype, activations, gate, rotation, down_rotation, fused, wf_up, wf_down, also=()):
+def _gated_mlp_experts(x, up, down, offsets, dtype, activations, gate, rotation, down_rotation, fused, wf_up, wf_down, also=(), routed=None,
+                       deferred=None):
+    """routed, deferred: as in _linear_experts."""
     fmt = _activations(activations, _GATED_CODES_ONLY)
     _check_pair(fmt, wf_up)
     _check_pair(fmt, wf_down)
@@ -1276,11 +1341,14 @@ def _gated_mlp_experts(x, up, down, offsets, dtype, activations, gate, rotation,
     _check_offsets(offsets, up.E)
     Xd, _, M, dtype = _float_rows(x, up, "up ", dtype)
     od = dev.to_device(offsets, torch.int32)
-    ac, asc, finite = _quantize_x(Xd, M, up.K, rotation, fmt)
+    off = None
+    if routed is None:
+        ac, asc, finite = _quantize_x(Xd, M, up.K, rotation, fmt)
+    else:
+        (ac, asc, finite, off), M = _quantize_routed(Xd, M, up.K, routed, rotation, fmt), routed[0].numel()
     hc, hs, bad, h_finite = _gemm_glu_experts(ac, asc, *up.operands(), od, up.E, M, up.N, up.K, fmt, wf_up, gate, fused, down_rotation)
     out, _ = _gemm_experts(hc, hs, *down.operands(), od, up.E, M, down.N, up.N, dtype, fmt, wf_down)
-    _raise_flags(*also, (finite, _H_FINITE), (bad, _OFFSETS_RULE), (h_finite, _H_FINITE))
-    return dev.like_input(out, x)
+    return _settle((*also, (off, routing.ROWS_MESSAGE), (finite, _H_FINITE), (bad, _OFFSETS_RULE), (h_finite, _H_FINITE)), deferred, out, x)
 
 
 class _GatedModule(torch.nn.Module):
@@ -1376,10 +1444,10 @@ class MXExpertsMLP(_GatedModule):
         return cls(MXExperts.from_results(up_results, up_biases, activations, device), MXExperts.from_results(down_results, down_biases, activations, device),
                    alpha, limit, shift, interleaved)
 
-    def _run(self, x, offsets, rotation, fused, down_rotation, also=()):
+    def _run(self, x, offsets, rotation, fused, down_rotation, also=(), routed=None, deferred=None):
         return _gated_mlp_experts(x, (self.up.codes, self.up.scales, self.up.bias), (self.down.codes, self.down.scales, self.down.bias), offsets, None,
                                   self.activations, self.gate, rotation, down_rotation, fused, _WEIGHTS[self.up.weights], _WEIGHTS[self.down.weights],
-                                  also)
+                                  also, routed, deferred)
 
     def forward(self, x, offsets, rotation=None, fused=True, down_rotation=None):
         return self._run(x, offsets, rotation, fused, down_rotation)
@@ -1389,3 +1457,12 @@ class MXExpertsMLP(_GatedModule):
         expert_ids[t][j] (x[t]), the routing, the gather back and the ordered float32 sum of MXExperts.forward_tokens."""
         return _route_tokens(x, expert_ids, gates, self.num_experts, self.out_features,
                              lambda rows, offsets, also: self._run(rows, offsets, rotation, fused, down_rotation, also))
+
+    def forward_logits(self, x, logits, k, gating="selected", rotation=None, fused=True, down_rotation=None):
+        """x (T, K) and router logits (T, E) -> (T, Nd) in x's dtype: MXExperts.forward_logits with the gated MLP of every
+        expert in place of its layer -- top-k, sort, the quantizer reading x through the row map, the fused grouped product,
+        the grouped down product, the combine --, the bits of forward_tokens(x, r.expert_ids, r.gates, ...) for r =
+        routing.route_topk(logits, k, gating), one wait for the stream.  `fused` and `down_rotation` as in forward; with
+        rotation= there is no row-mapped quantizer and x[order // k] is gathered with one torch index, as forward_tokens does."""
+        return _route_logits(x, logits, k, gating, self.num_experts, self.out_features,
+                             lambda Xd, routed, offsets, checks: self._run(Xd, offsets, rotation, fused, down_rotation, (), routed, checks))
